@@ -12,14 +12,17 @@ timed region.  At N GPUs every rank renders its own keyframe of the shared
 model and the 40 B/surfel gradients are exchanged over RCCL (weak scaling:
 value = n_gpus * N / step time).
 
-    python bench.py                       # 1 GPU, 20 steps, 3 warm-up
+    python bench.py                       # 1 GPU, 20 steps, 3 warm-up: the headline alone
+    python bench.py --full                # + per-kernel HIP events, roofline, extras, CPU baselines
+    python bench.py --dump-outputs DIR    # + the last timed step's results as DIR/<name>.npy
     python bench.py --gpus 8              # starts 8 ranks itself (torch.distributed.run, RCCL over xGMI)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3     # the driver's form
 
 Rank 0 prints ONE JSON line.  This file is the headline: scene, timed loop, per-kernel HIP events; the roofline
-object, the replayed counters and the CPU baseline leg live in bench_support.py, the secondary measurements
-(`extras`) in bench_extras.py.
+object, the replayed counters, the CPU baseline leg and the output dump live in bench_support.py, the secondary
+measurements (`extras`) in bench_extras.py.  A plain run sets up, warms up, times the steps and prints the line; whatever
+else it measures (per-kernel events, roofline, extras, CPU baselines) runs with --full only.
 """
 from __future__ import annotations
 
@@ -39,7 +42,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from bench_support import cpu_baselines, kernel_table, log, roofline_block
+from bench_support import cpu_baselines, dump_outputs, kernel_table, log, roofline_block
 
 
 def main(extras_only=None):
@@ -50,6 +53,11 @@ def main(extras_only=None):
     ap.add_argument("--n", type=int, default=500_000, help="surfels (BASELINE config 3: 500k)")
     ap.add_argument("--height", type=int, default=64)
     ap.add_argument("--width", type=int, default=2048)
+    ap.add_argument("--full", action="store_true", help="also the per-kernel HIP-event pass and roofline, bench_extras.py's "
+                    "secondary measurements and the CPU baselines (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the parameters (and, engine mode, loss and allmap) the "
+                    "last timed step left as DIR/<name>.npy (without SLS_DETERMINISTIC: from an un-timed replay of the "
+                    "same steps with integer-atomic gradient sums, see bench_support.dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip bench_extras.py's secondary measurements")
     ap.add_argument("--no-timing", action="store_true", help="do not record per-kernel HIP events")
@@ -224,14 +232,15 @@ def main(extras_only=None):
     log(f"scene ready; dp_mode={dp_mode} calibration={dp_cal}")
     window = cams if n_kf > 1 else [cam]
     model, engine = fresh(full_sort=args.full_sort, dp_mode=dp_mode)
-    timing = not args.no_timing and not extras_only
+    timing = args.full and not args.no_timing and not extras_only
     # events around the dominant kernel only, and around one launch in eight of it (mode 4): the kernel is timed
     # live inside the timed region, and the iteration — host-bound at this size — pays for 1/8 of an event pair
     n_iters = args.steps * ips
     dt, step = run(model, engine, window, args.warmup * ips, n_iters, pick=pick_rank,
                    after_warmup=(lambda: lib.sls_timing_enable(4)) if timing else None)
     if engine is not None and status_read is False:
-        assert not engine._read_status()["overflow"], "instance buffers overflowed during the timed region"
+        engine.last = engine._read_status()          # (the last iteration's status: --dump-outputs writes its loss)
+        assert not engine.last["overflow"], "instance buffers overflowed during the timed region"
 
     def collect():
         ns = lib.sls_timing_slots()
@@ -244,6 +253,10 @@ def main(extras_only=None):
     kernels, live, comm = {}, {}, None
     if timing:
         live = collect()                     # the dominant kernel, measured inside the timed region
+    if args.dump_outputs:                    # (before the per-kernel pass steps the model on; enable(1) drops replay events)
+        dump_outputs(args.dump_outputs, rank, model, engine, H, W, lambda: fresh(full_sort=args.full_sort, dp_mode=dp_mode),
+                     lambda m, e: run(m, e, window, args.warmup * ips, n_iters, pick=pick_rank), status_read is False)
+    if timing:
         lib.sls_timing_enable(1)             # every launch, in an extra un-timed pass of the same steps
         if engine is not None and world > 1:
             engine.comm_events = []
@@ -295,19 +308,22 @@ def main(extras_only=None):
                 delta.index_add_(0, start + cons, -torch.ones_like(start, dtype=torch.int32))
                 touched = int(torch.unique(st.vals[:st.R][torch.cumsum(delta[:st.R], 0) > 0]).numel())
             return st.R, int(cons.sum().item()), touched
-    per_kf = [workload(c) for c in window]
-    wts = kf_p if n_kf > 1 else np.array([1.0])
-    R, R_eff, N_touched = (int(round(float(np.dot(wts, [w[k] for w in per_kf])))) for k in range(3))
+    R = R_eff = N_touched = None
+    if args.full:           # (they feed the roofline and the per-kernel table)
+        per_kf = [workload(c) for c in window]
+        wts = kf_p if n_kf > 1 else np.array([1.0])
+        R, R_eff, N_touched = (int(round(float(np.dot(wts, [w[k] for w in per_kf])))) for k in range(3))
     tw, th = _abi.tile_size()
     P = H * W
     ms_per_step, ms_per_iter = dt / args.steps * 1e3, dt / n_iters * 1e3
     value = world * N * ips / (dt / args.steps) / 1e6
     roofline = roofline_block(kernels, live, N, R, R_eff, P, N_touched, H, W) if kernels else None
     breakdown = kernel_table(kernels, n_iters, N, R, R_eff, P, N_touched)
-    log("per-kernel pass done")
+    if timing:
+        log("per-kernel pass done")
 
     extras = None
-    if world == 1 and engine is not None and (extras_only or not args.no_extras):
+    if world == 1 and engine is not None and (extras_only or (args.full and not args.no_extras)):
         import bench_extras
         ctx = SimpleNamespace(args=args, dev=dev, lib=lib, scene=scene, poses=poses, depth=depth, valid=valid, cfg=cfg,
                               cams=cams, window=window, kf_p=kf_p, n_kf=n_kf, pick_rank=pick_rank, N=N, H=H, W=W, ips=ips,
@@ -317,9 +333,9 @@ def main(extras_only=None):
             print(json.dumps(extras), file=result_out, flush=True)
             return
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baselines(scene, poses, depth, valid, cfg, N, H, W, (tw, th))
-    log("cpu baseline done")
+        log("cpu baseline done")
 
     out = {
         "metric": "fwd+bwd Msplats/s", "value": round(value, 3), "unit": "Msplats/s", "n_gpus": world,
@@ -342,7 +358,9 @@ def main(extras_only=None):
                                    "iterations old (verified exact), else sorted from scratch"
                                    if (engine is not None and engine.reuse_depth_order and status_read is not False)
                                    else "sorted from scratch"),
-                   "repeated_iterations": dict(engine.stats) if engine is not None else None},
+                   "repeated_iterations": dict(engine.stats) if engine is not None else None,
+                   "gradient_sums": "integer atomics (SLS_DETERMINISTIC)" if os.environ.get("SLS_DETERMINISTIC", "0")
+                   in ("1", "2") else "float atomics"},
         "rccl_ranks": world if backend == "nccl" else 0, "collective_backend": backend,
         "dp_mode": (comm["mode"] if comm else dp_mode), "dp_overlap": None,
         "dp_calibration_ms": dp_cal,

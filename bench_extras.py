@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench_extras.py — the secondary measurements behind bench.py's `extras` (1 GPU; the headline stays the driver's
-command).  Called by bench.py unless --no-extras; `python bench_extras.py [names...]` runs them alone and prints one JSON
+command).  Called by bench.py --full unless --no-extras; `python bench_extras.py [names...]` runs them alone and prints one JSON
 object.  Every figure is a whole mapping iteration (or what its key says) on the bench's scene and keyframe sampling
 unless stated otherwise.
 

@@ -182,6 +182,56 @@ def kernel_table(kernels, n_iters, N, R, R_eff, P, N_touched):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, rank, model, engine, H, W, fresh, run, async_status):
+    """--dump-outputs: what the last timed step left to its caller, as <path>/<name>.npy — the four raw parameter
+    tensors after its Adam update (xyz, scaling, rotation, opacity: float32) and, in engine mode, that iteration's loss
+    (pixel term, regulariser: float64) and rendered maps (allmap, 7 x H x W float32; planes 5-6 are zeros, see
+    MappingEngine.allmap).  Above DUMP_BYTES in all, every array keeps the same fraction of its rows (the parameters:
+    one seeded sample of surfels for all four) or pixels (allmap), so that two runs of one size stay comparable.
+    Unless SLS_DETERMINISTIC is set, the timed steps sum the gradient records with float atomics, whose order changes
+    from run to run, and Adam (eps 1e-15) turns a sign flipped by it into a whole step: no two runs end on the same
+    model.  Then the outputs come from an un-timed replay, on every rank, of the same steps (same scene, keyframe draws
+    and step calls, `fresh()` + `run()`) on a fresh model with integer-atomic sums: the same outputs every run.  The
+    timed steps and the headline figures are those of a plain run."""
+    det = os.environ.get("SLS_DETERMINISTIC")
+    if det not in ("1", "2"):
+        os.environ["SLS_DETERMINISTIC"] = "1"            # (read when an engine is built and by every staged backward)
+        try:
+            model, engine = fresh()
+            run(model, engine)
+            if engine is not None and async_status:
+                engine.last = engine._read_status()
+        finally:
+            if det is None:
+                del os.environ["SLS_DETERMINISTIC"]
+            else:
+                os.environ["SLS_DETERMINISTIC"] = det
+        log("replayed the timed steps with integer-atomic gradient sums for --dump-outputs")
+    if rank != 0:
+        return
+    par = {k: getattr(model, "_" + k).detach().cpu().numpy() for k in ("xyz", "scaling", "rotation", "opacity")}
+    extra = {}
+    if engine is not None and engine.last is not None:
+        extra["loss"] = np.array([engine.last["loss_pixel"], engine.last["loss_reg"]], dtype=np.float64)
+        extra["allmap"] = engine.allmap(H, W).cpu().numpy()
+    total = sum(a.nbytes for a in (*par.values(), *extra.values()))
+    if total > DUMP_BYTES:
+        rng = np.random.default_rng(0)
+        n = len(par["xyz"])
+        rows = np.sort(rng.choice(n, size=int(n * DUMP_BYTES / total * 0.99), replace=False))
+        par = {k: a[rows] for k, a in par.items()}
+        if "allmap" in extra:
+            px = np.sort(rng.choice(H * W, size=int(H * W * DUMP_BYTES / total * 0.99), replace=False))
+            extra["allmap"] = extra["allmap"].reshape(7, H * W)[:, px]
+    os.makedirs(path, exist_ok=True)
+    for name, a in {**par, **extra}.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step written to {path} ({', '.join(par) + (', ' if extra else '') + ', '.join(extra)})")
+
+
 def cpu_baselines(scene, poses, depth, valid, cfg, N, H, W, tile):
     """The CPU legs (rank 0, 1 GPU only).  Primary = the baseline BASELINE.json names: the pure-PyTorch tile
     rasterizer (oracle/torch_tiles.py), one WHOLE mapping iteration (activations, render, render() post-processing

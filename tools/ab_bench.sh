@@ -13,7 +13,7 @@ for shape in ${SHAPES:-"500000,64,2048"}; do
   for rep in $(seq ${REPS:-2}); do
     for v in "$@"; do
       cp gpurun_tmp_$v.so splat_loam_amd/libsls_hip.so
-      timeout 200 python bench.py --no-cpu-baseline --no-extras --n $n --height $h --width $w 2>/dev/null | python -c "
+      timeout 200 python bench.py --full --no-cpu-baseline --no-extras --n $n --height $h --width $w 2>/dev/null | python -c "
 import json, os, sys
 d = json.loads(sys.stdin.read()); sel = os.environ.get('KERNELS', '')
 print('$n ${h}x$w [$v]', d['value'], d['config']['ms_per_iteration'], {k: v['avg_us'] for k, v in d['kernels'].items() if sel in k})" || echo "$n [$v] FAILED"
