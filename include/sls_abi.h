@@ -158,8 +158,8 @@ int sls_forward_stage1(const SlsCamera *cam, int N,
  * per pixel block the compact list of the (list position, surfel) pairs that reached one of
  * its pixels; with it sls_backward walks exactly those, 64 per round, instead of re-deriving
  * them with a box test over the tile's whole list (the name is round 2's, when the hand-over
- * was a bit mask per 64 list entries).  *block_masks_shape (may be null): which pixel-block shape wrote it
- * (0: none, 2: 4x4, 3: 8x2) — hand it to sls_backward together with the buffer. */
+ * was a bit mask per 64 list entries).  *block_masks_shape (may be null): the producer's tag of the hand-over
+ * (0: none, 3: the 8x2 pixel blocks' compact lists) — hand it to sls_backward together with the buffer. */
 size_t sls_sort_scratch_bytes(uint64_t R);
 size_t sls_block_mask_bytes(uint64_t R, int H, int W);
 int sls_forward_stage2(const SlsCamera *cam, int N, uint64_t R,
@@ -178,8 +178,8 @@ int sls_forward_stage2(const SlsCamera *cam, int N, uint64_t R,
 /* ---- backward ----------------------------------------------------------
  * vals_sorted (+ vals_stride: 1 or 2, as stage 2 returned them)/ranges/rec/pix_* are the forward's buffers
  * (never allmap: the caller may have overwritten it in place).  block_masks + block_masks_shape: the forward's
- * hand-over and the block shape that wrote it; the compact lists are walked only if that shape is the backward
- * kernel's own (otherwise, or with null / 0, the backward culls the tile's list itself).  grec: N*16 floats of
+ * hand-over and its producer's tag; the compact lists are walked only for tag 3 (otherwise, or with null / 0, the
+ * backward culls the tile's list itself).  grec: N*16 floats of
  * scratch (zeroed by the call).  Outputs: dL/dmeans3D (N*3), dL/dscales (N*2),
  * dL/drotations (N*4, w.r.t. the normalised quaternion as passed in),
  * dL/dopacities (N). */
@@ -582,11 +582,10 @@ int sls_timing_collect(double *total_ms_host, int64_t *counts_host);
  * load balance across tiles.  Pass nulls to switch it off (the default). */
 int sls_debug_wave_cycles(uint32_t *fwd_cycles, uint32_t *bwd_cycles);
 
-/* Tuning/diagnostic: choose the tile kernels' pixel-block shape: 2 = 4x4, 3 = 8x2 (the default);
- * negative = keep.  Both produce the same results; the tests run both.  Like sls_timing_* and
- * sls_debug_wave_cycles this is a PROCESS-wide diagnostic switch (torch runs backward nodes on its autograd
- * device thread, which must see what the calling thread chose); the data path itself keeps no mutable state. */
-int sls_debug_variant(int fwd_variant, int bwd_variant);
+/* Kept for binary compatibility: the tile kernels' pixel-block shape, forward and backward.  3 (8x2 blocks) is the
+ * only one; it and negative values are accepted and change nothing, anything else (2, the removed 4x4 blocks,
+ * included) returns SLS_E_ARG.  Sets no state. */
+int sls_debug_variant(int fwd, int bwd);
 
 /* Device self-test of the wave64 primitives (DPP reduction, ballot ranking).
  * Returns 0 if they behave as the kernels assume.  Synchronises. */

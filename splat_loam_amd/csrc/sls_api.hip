@@ -20,6 +20,15 @@ void set_error(const char *fmt, ...)
     va_end(ap);
 }
 
+// Diagnostic switches are per PROCESS (sls_common.hpp: DebugState): torch runs a backward node on its autograd
+// device thread, not on the thread that called sls_debug_wave_cycles, so per-thread state would silently not reach
+// sls_backward under loss.backward().  They are tuning aids only: the data path keeps no mutable state of its own.
+DebugState &debug_state()
+{
+    static DebugState s;
+    return s;
+}
+
 // ---------------------------------------------------------------------------
 // per-kernel timing (HIP events on the launch stream)
 // ---------------------------------------------------------------------------
@@ -420,13 +429,11 @@ int sls_debug_wave_cycles(uint32_t *fwd_cycles, uint32_t *bwd_cycles)
     return SLS_OK;
 }
 
-int sls_debug_variant(int fwd_variant, int bwd_variant)
+int sls_debug_variant(int fwd, int bwd)
 {
-    SLS_REQUIRE((fwd_variant < 0 || fwd_variant == 2 || fwd_variant == 3) &&
-                    (bwd_variant < 0 || bwd_variant == 2 || bwd_variant == 3),
-                "variants: 2 = 4x4 pixel blocks, 3 = 8x2 pixel blocks (negative: leave as it is)");
-    if (fwd_variant >= 0) debug_state().fwd_variant = fwd_variant;
-    if (bwd_variant >= 0) debug_state().bwd_variant = bwd_variant;
+    // (kept for binary compatibility: the 8x2 pixel blocks are the only tile kernels, so there is nothing to set)
+    SLS_REQUIRE((fwd < 0 || fwd == 3) && (bwd < 0 || bwd == 3),
+                "tile-kernel variant: only 3 (8x2 pixel blocks) exists; the 4x4 variant 2 was removed (negative: no change)");
     return SLS_OK;
 }
 

@@ -41,11 +41,10 @@ enum TimerSlot {
     T_RENDER_FWD, T_GREC_MEMSET, T_RENDER_BWD, T_PREPROCESS_BWD, T_ADAM, T_KNN, T_CONSUMER, T_RESORT, T_BIN_COUNT, T_BIN_DIRECT,
     T_COUNT
 };
-// Debug / tuning switches (sls_debug_variant, sls_debug_wave_cycles, sls_timing_*): ONE set per process, relaxed
-// atomics — a backward reached through torch autograd runs on the autograd engine's device thread and must see
-// what the Python thread chose.  Diagnostics only; the data path itself keeps no mutable state.
+// Debug / tuning switches (sls_debug_wave_cycles, sls_timing_*): ONE set per process, relaxed atomics — a backward
+// reached through torch autograd runs on the autograd engine's device thread and must see what the Python thread
+// chose.  Diagnostics only; the data path itself keeps no mutable state.
 struct DebugState {
-    std::atomic<int> fwd_variant{3}, bwd_variant{3};           // 2: 4x4 pixel blocks, 3: 8x2 (default)
     std::atomic<uint32_t *> dbg_fwd_cycles{nullptr}, dbg_bwd_cycles{nullptr};
 };
 DebugState &debug_state();

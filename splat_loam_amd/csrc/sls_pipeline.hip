@@ -207,8 +207,7 @@ int sls_forward_stage2(const SlsCamera *cam, int N, uint64_t R, const float *rec
     // With the surfels' block boxes the tile sort delivers (surfel, block mask) pairs in list order and the forward
     // runs its dense rounds — the kernels of sls_mapping_step, under the same long-list rule (R is exact here)
     const uint2 *bmask = nullptr;
-    const bool default_kernels = debug_state().fwd_variant == 3;
-    const uint32_t *boxes = (default_kernels && !keys64_out) ? block_box : nullptr;
+    const uint32_t *boxes = keys64_out ? nullptr : block_box;
     int rc;
     if (!keys64_out && R > 0 && bin_direct_possible(dc, N, (uint32_t)R)) {
         // direct binning (sls_sort.hip), as in sls_mapping_step; the records are gathered from rect / block_box
@@ -230,7 +229,7 @@ int sls_forward_stage2(const SlsCamera *cam, int N, uint64_t R, const float *rec
     const uint32_t *sorted_vals = *sorted_in_tmp ? vals_tmp : vals;
     *sorted_list = bmask ? (const uint32_t *)bmask : sorted_vals;
     *sorted_stride = bmask ? 2 : 1;
-    if (block_masks_shape) *block_masks_shape = block_masks ? (int)debug_state().fwd_variant : 0;
+    if (block_masks_shape) *block_masks_shape = block_masks ? 3 : 0;
     return launch_render_fwd(dc, ranges, sorted_vals, rec, col_cs, row_cs, allmap, pix_state, pix_contrib,
                              tile_consumed, st, false, block_masks, (cam->flags & SLS_CAM_LEAN_ALLMAP) != 0, nullptr, bmask,
                              true);       // (+ the backward's launch order into the hand-over buffer)
@@ -338,8 +337,8 @@ int sls_forward_ws(const SlsCamera *cam, int N, const float *means3D, const floa
     const int H = cam->H, W = cam->W;
     const DevCam dc = make_devcam(*cam);
     const uint32_t cap = (uint32_t)R_capacity;
-    if (!bin_direct_possible(dc, N, cap) || debug_state().fwd_variant != 3 || debug_state().bwd_variant != 3) {
-        set_error("sls_forward_ws serves what the direct binning serves (<= 512 tiles, D10 off, default tile kernels): use the staged forward");
+    if (!bin_direct_possible(dc, N, cap)) {
+        set_error("sls_forward_ws serves what the direct binning serves (<= 512 tiles, D10 off): use the staged forward");
         return SLS_E_UNSUPPORTED;
     }
     const MapWs w = carve(N, H, W, R_capacity, workspace, false);
@@ -355,8 +354,7 @@ int sls_forward_ws(const SlsCamera *cam, int N, const float *means3D, const floa
     uint32_t *okeys, *ovals, *n_dev;
     uint32_t *order = depth_order ? depth_order : w.order;
     depth_order_key_buffers(N, w.order_scratch, order, &okeys, &ovals, &n_dev);
-    constexpr bool no_merge = false;
-    const bool merged_sort = reuse_rounds >= 1 && !no_merge;
+    const bool merged_sort = reuse_rounds >= 1;
     DirectBin db = make_direct_bin(dc, N, w.sort_scratch, (uint2 *)w.serec, reuse_rounds >= 1, true);
     // (as in sls_mapping_step: the direct binning reads the emission records only)
     int rc = launch_preprocess_fwd(dc, 0, 0.0f, 0.0f, nullptr, N, means3D, scales, rotations, opacities, w.rec, radii,
@@ -381,7 +379,7 @@ int sls_forward_ws(const SlsCamera *cam, int N, const float *means3D, const floa
     // a forward nobody differentiates (render() under no_grad: Mapper.densify, the tracker) writes no hand-over; one
     // that is leaves the backward its blocks' compact lists and their costs (sorted into the camera's launch order by
     // passengers of the backward's last kernel, for the camera's NEXT backward: as sls_mapping_step does)
-    *block_masks_shape = want_backward ? (int)debug_state().fwd_variant : 0;
+    *block_masks_shape = want_backward ? 3 : 0;
     return launch_render_fwd(dc, w.ranges, list, w.rec, col_cs, row_cs, allmap, w.pix_state, w.pix_contrib, nullptr, st,
                              true, want_backward ? w.block_masks : nullptr, (cam->flags & SLS_CAM_LEAN_ALLMAP) != 0,
                              want_backward ? w.block_cost : nullptr, bmask, false);
@@ -411,12 +409,10 @@ int sls_backward_ws(const SlsCamera *cam, int N, const float *means3D, const flo
     // the blocks most expensive first per XCD, in the order this camera's PREVIOUS backward left in the caller's buffer
     // (its tag word says whether one has: a first visit walks the natural order)
     const int T = dc.GX * dc.GY;
-    const bool order_bwd = block_order != nullptr && block_masks_shape == 3 && debug_state().bwd_variant == 3 &&
-                           T % 32 == 0 && kTileW == 16 && kTileH == 16;
-    // (a tile-kernel variant switched between forward and backward — sls_debug_variant — is no lost gradient: the launcher
-    //  walks the forward's compact lists only when block_masks_shape names the backward's own shape, otherwise the
-    //  backward culls the tiles' lists itself; the kernel's tag check is a last guard against a FOREIGN buffer, which the
-    //  workspace lease rules out on this path)
+    const bool order_bwd = block_order != nullptr && block_masks_shape == 3 && T % 32 == 0 && kTileW == 16 && kTileH == 16;
+    // (the launcher walks the forward's compact lists only when block_masks_shape is 3, otherwise the backward culls the
+    //  tiles' lists itself; the kernel's tag check is a last guard against a FOREIGN buffer, which the workspace lease
+    //  rules out on this path)
     int rc = launch_render_bwd(dc, w.ranges, sorted_list, w.rec, col_cs, row_cs, w.pix_state, w.pix_contrib, dL_dallmap,
                                w.grec, st, block_masks_shape ? w.block_masks : nullptr,
                                (cam->flags & SLS_CAM_LEAN_ALLMAP) != 0, w.touched, nullptr, nullptr, nullptr,
@@ -491,22 +487,19 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
     if (allmap_out) *allmap_out = w.allmap;
     uint8_t *touched = w.touched;   // (the backward tile kernel marks the surfels it reaches)
     const bool det = cfg->deterministic != 0;
-    // one launch with predicted scales (cfg->deterministic = 2) where the default tile kernels hand compact lists over
-    const bool det_one = cfg->deterministic == 2 && cfg->det_prev != nullptr && debug_state().bwd_variant == 3 &&
-                         debug_state().fwd_variant == 3;
+    // one launch with predicted scales (cfg->deterministic = 2) on the forward's compact lists
+    const bool det_one = cfg->deterministic == 2 && cfg->det_prev != nullptr;
     SLS_REQUIRE(cfg->deterministic >= 0 && cfg->deterministic <= 2, "deterministic: 0 off, 1 two launches, 2 one launch with predicted scales");
     SLS_REQUIRE(cfg->deterministic != 2 || cfg->det_prev, "deterministic = 2 needs the keyframe's det_prev buffer");
-    // With the default backward kernel and depth_ratio = 0 the consumer's second kernel is folded into the
+    // With depth_ratio = 0 the consumer's second kernel is folded into the
     // backward tile kernel: every pixel block computes its dL/dallmap from kernel B's planes itself ...
-    const bool fuse_c = debug_state().bwd_variant == 3 && cfg->depth_ratio == 0.0f;
+    const bool fuse_c = cfg->depth_ratio == 0.0f;
     // ... and with the keyframe's launch-order buffer kernel B's work too
-    constexpr bool no_fused_b = false;
-    const bool fuse_b = fuse_c && cfg->block_order != nullptr && !no_fused_b;
+    const bool fuse_b = fuse_c && cfg->block_order != nullptr;
     // the backward's blocks are launched most expensive first (cost recorded by the forward, sorted per XCD by eight
     // passenger workgroups — of the consumer's launch, or with fuse_b of the previous iteration's last launch): 8x2
     // kernels, XCD-interleaved tile mapping (T % 32 == 0)
-    const bool order_bwd = debug_state().bwd_variant == 3 && debug_state().fwd_variant == 3 &&
-                           (dc.GX * dc.GY) % 32 == 0 && kTileW == 16 && kTileH == 16;
+    const bool order_bwd = (dc.GX * dc.GY) % 32 == 0 && kTileW == 16 && kTileH == 16;
     // cfg->phase: 0 = the whole iteration; 1 = up to the tile backward (+ the early gradient bitmap); 2 = the rest
     auto front = [&]() -> int {
         // (the status block is zeroed by thread 0 of preprocess_fwd, the iteration's first kernel)
@@ -525,15 +518,13 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
         depth_order_key_buffers(N, w.order_scratch, order, &okeys, &ovals, &n_dev);
         // Repairing the previous order: its first step (sorting windows of the old order by the new keys) rides in the
         // preprocess launch — it needs nothing the preprocess produces
-        constexpr bool no_merge = false;
-        const bool merged_sort = cfg->reuse_depth_order >= 1 && !no_merge;
+        const bool merged_sort = cfg->reuse_depth_order >= 1;
         // Direct binning (sls_sort.hip) where it applies: no unsorted instance array, no scan of tiles_touched; the preprocess
         // then leaves the emission records in the form its first kernel gathers (rectangle + block box)
         const bool direct = bin_direct_possible(dc, N, cap);
         // (the staged API scans the count table's rows with a launch of its own instead)
-        constexpr bool no_coarse = false;
         DirectBin db;
-        if (direct) db = make_direct_bin(dc, N, w.sort_scratch, (uint2 *)w.serec, cfg->reuse_depth_order >= 1, !no_coarse);
+        if (direct) db = make_direct_bin(dc, N, w.sort_scratch, (uint2 *)w.serec, cfg->reuse_depth_order >= 1, true);
         // (the direct binning reads the emission records only — not the rectangles, the tile counts, the depths or the
         //  block boxes as arrays of their own; a repair whose window sort rides in the preprocess launch computes its
         //  keys itself: 32 bytes per surfel that are not written)
@@ -555,19 +546,17 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
         if (rc) return rc;
         int in_tmp = 0;
         const uint2 *bmask = nullptr;
-        // (pairs instead of values only if both tile kernels are the default 8x2 ones: no other reads them)
-        const bool pairs_ok = debug_state().fwd_variant == 3 && debug_state().bwd_variant == 3;
         if (direct) {
             rc = launch_bin_direct(dc, N, cap, db, handoff.counted != 0, order, w.erec, nullptr, nullptr, w.sort_scratch, w.vals,
                                    w.ranges, &status_dev->R, &status_dev->overflow, handoff.resort_windows,
-                                   handoff.resort_edges, pairs_ok ? &bmask : nullptr, cfg->block_masks, st);
+                                   handoff.resort_edges, &bmask, cfg->block_masks, st);
         } else {
             rc = launch_bin_sort(dc, N, &status_dev->R, cap, order, w.rect, w.tiles, dc.tile_cull ? w.tmask : nullptr,
                                  (dc.GX < 65536 && dc.GY < 65536) ? w.erec : nullptr, w.depth,
                                  w.offsets, w.tkeys, w.vals,
                                  w.tkeys_tmp, w.vals_tmp, w.sort_scratch, w.sort_scratch_bytes, &in_tmp, w.ranges, nullptr,
                                  &status_dev->overflow, st, &handoff, &status_dev->R,
-                                 pairs_ok ? w.sbox : nullptr, &bmask, cfg->block_masks);
+                                 w.sbox, &bmask, cfg->block_masks);
         }
         if (rc) return rc;
         // (with the pairs the plain value arrays are not written: the list IS the pairs, two words apart)
@@ -596,7 +585,7 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
         rc = launch_render_bwd(dc, w.ranges, sorted_vals, w.rec, col_cs, row_cs, w.pix_state, w.pix_contrib, w.dL_dallmap,
                                w.grec, st, w.block_masks, cfg->depth_ratio == 0.0f, touched,    // the consumer's dL/d(median, distortion) are 0 then
                                fuse_c ? &cargs : nullptr, (det && !det_one) ? w.det_max : nullptr, det ? w.det_acc : nullptr, block_order,
-                               vals_stride, (int)debug_state().fwd_variant, false,
+                               vals_stride, 3, false,
                                det_one ? cfg->det_prev : nullptr, w.det_gex, &status_dev->overflow, fuse_b,
                                (fuse_b && order_bwd) ? block_order_tag(dc.GX * dc.GY) : 0u);
         if (rc) return rc;

@@ -1,7 +1,7 @@
-// sls_render_block.hip — tile kernels, "pixel block x surfel slot" variant.
-// SURVEY.md §8a rows A6/A7; maths in DESIGN.md §2; same inputs, outputs and
-// per-pixel state as the kernels of sls_render.hip (the variants are
-// interchangeable: forward of one, backward of the other).
+// sls_render_block.hip — the tile kernels (A6 forward blend, A7 backward; SURVEY.md §8a, maths in DESIGN.md §2)
+// and their launchers: one wave per 8x2 pixel block x 4 list entries per step.  (The kernels keep their block shape
+// as template parameters, BW x BH; 8x2 is the one instantiated.)  No MFMA: there is no dense contraction here
+// (BASELINE.json north_star).
 //
 // Why: with one pixel per lane a wave evaluates ONE surfel per ~110-instruction
 // step and the kernel time is the serial instruction stream of the longest
@@ -13,7 +13,7 @@
 // mask), which costs ~35 instructions per step, so
 //   * the serial chain per wave is ~4x shorter and there are 4x more waves
 //     (8 per SIMD): the SIMDs stay busy and the image rows balance;
-//   * the support-box cull works on 4x4 pixels instead of 8x8, so far fewer
+//   * the support-box cull works on 16 pixels instead of 8x8, so far fewer
 //     lanes evaluate a surfel that cannot touch them;
 //   * backward: the 16 gradient fields are reduced over the 16 pixels of a slot
 //     with ONE reduce-scatter per step (4 surfels) instead of one per surfel,
@@ -25,49 +25,6 @@
 #include "sls_consumer_dev.hpp"
 
 namespace sls {
-
-#ifdef SLS_TRACE
-// Experiment build only (make FAST='$(COMMON) -munsafe-fp-atomics -DSLS_TRACE'; read back with sls_debug_wave_cycles, profiles/r03l_wave_trace*.txt): every wave of
-// the tile kernels records when it ran (100 MHz wall clock), where (HW_ID) and how many rounds / steps it did.
-__device__ uint32_t g_trace[2][8192 * 4];
-// forward: shader clocks a wave spent waiting for the staged records (+ LDS store) / in cull + compaction / in the
-// steps / at the round's end
-__device__ uint32_t g_trace_phase[8192 * 4];
-__device__ uint32_t g_trace_phase_b[8192 * 4];    // backward: wait for the staged records + store / list / steps / (unused)
-// marks: wall-clock offsets (10 ns units) from the wave's start at up to four points of its life, taken when the
-// value passed (the result of the loads the point waits for) is in a register
-__device__ uint32_t g_trace_mark[2][8192 * 4];
-#define SLS_MARK(kern_, k_, v_) { asm volatile("" :: "v"(v_)); const uint32_t m_ = (uint32_t)(wall_clock64() - trace_t0); \
-                                  if (threadIdx.x == 0 && blockIdx.x < 8192) g_trace_mark[kern_][4 * blockIdx.x + (k_)] = m_; }
-#define SLS_PHASE_DECL() uint64_t ph_t = clock64(); uint32_t ph_acc[4] = { 0, 0, 0, 0 }
-#define SLS_PHASE(k_) { const uint64_t now_ = clock64(); ph_acc[k_] += (uint32_t)(now_ - ph_t); ph_t = now_; }
-#define SLS_PHASE_RESET() ph_t = clock64()
-#define SLS_PHASE_END() if (threadIdx.x == 0 && blockIdx.x < 8192) { for (int k_ = 0; k_ < 4; ++k_) g_trace_phase[4 * blockIdx.x + k_] = ph_acc[k_]; }
-#define SLS_PHASE_END_B() if (threadIdx.x == 0 && blockIdx.x < 8192) { for (int k_ = 0; k_ < 4; ++k_) g_trace_phase_b[4 * blockIdx.x + k_] = ph_acc[k_]; }
-#define SLS_TRACE_BEGIN() const uint64_t trace_t0 = wall_clock64(); uint32_t trace_rounds = 0, trace_steps = 0, trace_sparse = 0
-#define SLS_TRACE_ACTIVE(m_) { const int na_ = __builtin_popcountll((m_) & 0x1111111111111111ull); trace_sparse += (na_ <= 1 ? 1u : 0u) + (na_ <= 2 ? 1u << 10 : 0u) + (na_ <= 4 ? 1u << 20 : 0u); }
-#define SLS_TRACE_ROUND() ++trace_rounds
-#define SLS_TRACE_STEP() ++trace_steps
-#define SLS_TRACE_END(k_)                                                                                 \
-    if (threadIdx.x == 0 && blockIdx.x < 8192) {                                                          \
-        uint32_t *t = g_trace[k_] + 4 * blockIdx.x;                                                       \
-        t[0] = (uint32_t)trace_t0; t[1] = (uint32_t)wall_clock64();                                       \
-        t[2] = (k_) == 0 ? trace_sparse : __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));       \
-        t[3] = (trace_rounds << 16) | (trace_steps & 0xFFFFu);                                            \
-    }
-#else
-#define SLS_MARK(kern_, k_, v_)
-#define SLS_TRACE_BEGIN()
-#define SLS_TRACE_ACTIVE(m_)
-#define SLS_TRACE_ROUND()
-#define SLS_TRACE_STEP()
-#define SLS_TRACE_END(k_)
-#define SLS_PHASE_DECL()
-#define SLS_PHASE(k_)
-#define SLS_PHASE_RESET()
-#define SLS_PHASE_END()
-#define SLS_PHASE_END_B()
-#endif
 
 template <int CTRL>
 __device__ __forceinline__ float dppq(float v)
@@ -215,7 +172,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
     __shared__ uint32_t s_flag[65];
     uint32_t ccnt = 0;                            // entries of this block's compact list so far
     const uint64_t t_start = DBG ? clock64() : 0;
-    SLS_TRACE_BEGIN();
     const int lane = threadIdx.x, slot = lane & 3, p = lane >> 2;
     const int T = cam.GX * cam.GY;
     int tile, sub;
@@ -252,8 +208,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
     const BlockCone cone = make_block_cone(cam, (float)x0 + 0.5f * (float)(BW - 1), (float)y0 + 0.5f * (float)(BH - 1),
                                            0.5f * (float)(BW - 1), 0.5f * (float)(BH - 1));
     const int nr = (n + 63) / 64;
-    SLS_MARK(0, 0, n);
-    SLS_MARK(0, 1, d2);
     if (lane < kRec4) s_rec[64 * kRec4 + lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     SLS_STAGE_DECL
     if (nr > 0 && !wave_done) {
@@ -266,17 +220,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
     uint2 *const clist = blk_mask ? reinterpret_cast<uint2 *>(blk_mask + block_list_entries_word(T, kPerTile))
                                         + ((size_t)range.x * kPerTile + (size_t)sub * (size_t)n) : nullptr;
     uint32_t my_idx_next = (blk_mask && nr > 0 && !wave_done) ? vals[range.x + (uint32_t)min(lane, n - 1)] : 0u;
-    SLS_PHASE_DECL();
     for (int r = 0; r < nr && !wave_done; ++r) {
         float bcx, bcy, bhx, bhy;
         if (!block_active_box<BW, BH>(wave_ballot(!done), x0, y0, bcx, bcy, bhx, bhy)) break;
-        SLS_PHASE_RESET();
-        SLS_TRACE_ROUND();
-        SLS_TRACE_ACTIVE(wave_ballot(!done));
         if (blk_mask) s_flag[lane] = 0u;   // entries of this round that reach at least one pixel of the block
         // single wave: LDS operations complete in program order, no barrier needed
         SLS_WSTAGE_STORE()
-        if (r == 0) SLS_MARK(0, 2, sp4.x);
         const uint32_t my_idx = my_idx_next;
         if (r + 1 < nr) {
             SLS_WSTAGE_LOAD_REC()
@@ -285,7 +234,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
         }
         const int cnt = min(64, n - r * 64);
         __builtin_amdgcn_wave_barrier();
-        SLS_PHASE(0);
         bool pass = false;
         if (lane < cnt) {
             const float4 c4 = s_rec[lane * kRec4 + 4];
@@ -301,7 +249,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
         if (pass) s_list[__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = (uint32_t)lane;
         if (lane < 3) s_list[npass + lane] = 64u;          // pad to a multiple of four with the empty record
         __builtin_amdgcn_wave_barrier();
-        SLS_PHASE(1);
         if (DBG) { st_staged += (uint32_t)cnt; st_pass += (uint32_t)npass; }
         for (int k = 0; k < npass; k += 4) {
             const int j = (int)s_list[k + slot];
@@ -320,12 +267,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
                     st_geom += (gb & (0x1111111111111111ull << q)) ? 1u : 0u;
                 }
             }
-#ifdef SLS_FWD_SKIP_DEAD
-            // (a step none of whose 64 (pixel, entry) pairs is live: measured rare enough that testing for it — a
-            //  ballot of mask logic costs two half-rate VALU instructions — does not pay; kept as a build switch)
-            if (!wave_ballot(live)) continue;
-#endif
-            SLS_TRACE_STEP();
             // alpha of the lanes that take part (0: the entry passes through, f = 1)
             const float a = live ? e.alpha : 0.0f;
             const float f = 1.0f - a;
@@ -383,7 +324,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
             }
             if (wave_done) break;
         }
-        SLS_PHASE(2);
         if (blk_mask) {
             __builtin_amdgcn_wave_barrier();
             const bool fl = s_flag[lane] != 0u;
@@ -392,10 +332,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
                         make_uint2((uint32_t)(r * 64 + lane), my_idx);
             ccnt += (uint32_t)__builtin_popcountll(rmask);
         }
-        SLS_PHASE(3);
     }
 
-    SLS_MARK(0, 3, Tr);
     // combine the four slots of a pixel
     D = quad_sum(D); const float N0 = quad_sum(N01.x), N1 = quad_sum(N01.y); N2 = quad_sum(N2);
     M1 = quad_sum(M1); M2 = quad_sum(M2);
@@ -425,8 +363,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
         for (int off = 32; off > 0; off >>= 1) c = max(c, (uint32_t)__shfl_down(c, off, 64));
         if (lane == 0) atomicMax(&tile_consumed[tile], c);
     }
-    SLS_TRACE_END(0);
-    SLS_PHASE_END();
     if (DBG && lane == 0) {
         dbg_cycles[tile * kPerTile + sub] = (uint32_t)(clock64() - t_start);
         uint32_t *st = dbg_cycles + (size_t)T * kPerTile;
@@ -468,7 +404,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
     __shared__ uint32_t s_qpos[kQueueCap], s_qidx[kQueueCap];   // queued survivors: list position, surfel
     __shared__ uint32_t s_rpos[2][64];            // list positions of the entries of the current / the next round
     const uint64_t t_start = DBG ? clock64() : 0;
-    SLS_TRACE_BEGIN();
     const int lane = threadIdx.x, slot = lane & 3, p = lane >> 2;
     const int T = cam.GX * cam.GY;
     int tile, sub;
@@ -535,13 +470,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
     __shared__ uint32_t s_ridx[2][64];            // surfels of the entries of the current / the next round
     if (blk_mask && n > 0 && !wave_done) s_ridx[0][lane] = bmask[range.x + (uint32_t)min(lane, n - 1)].x;
     int cur = 0, cur_k = min(n, 64);
-    SLS_PHASE_DECL();
     while (cur_k > 0 && !wave_done) {
         float bcx, bcy, bhx, bhy;
         if (!block_active_box<BW, BH>(wave_ballot(!done), x0, y0, bcx, bcy, bhx, bhy)) break;
-        SLS_PHASE_RESET();
-        SLS_TRACE_ROUND();
-        SLS_TRACE_ACTIVE(wave_ballot(!done));
         if (blk_mask) s_flag[lane] = 0u;   // entries of this round that reach at least one pixel of the block
         // single wave: LDS operations complete in program order, no barrier needed
         SLS_WSTAGE_STORE()
@@ -584,7 +515,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
         }
         const int cnt = cur_k;
         __builtin_amdgcn_wave_barrier();
-        SLS_PHASE(0);
         bool pass = false;
         if (lane < cnt) {
             const float4 c4 = s_rec[lane * kRec4 + 4];
@@ -600,7 +530,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
         if (pass) s_list[__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = (uint32_t)lane | (s_rpos[cur][lane] << 7);
         if (lane < 3) s_list[npass + lane] = 64u;          // pad to a multiple of four with the empty record
         __builtin_amdgcn_wave_barrier();
-        SLS_PHASE(1);
         if (DBG) { st_staged += (uint32_t)cnt; st_pass += (uint32_t)npass; }
         for (int k = 0; k < npass; k += 4) {
             const uint32_t lv = s_list[k + slot];
@@ -620,7 +549,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
                     st_geom += (gb & (0x1111111111111111ull << q)) ? 1u : 0u;
                 }
             }
-            SLS_TRACE_STEP();
             // alpha of the lanes that take part (0: the entry passes through, f = 1)
             const float a = live ? e.alpha : 0.0f;
             const float f = 1.0f - a;
@@ -688,7 +616,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
             }
             if (wave_done) break;
         }
-        SLS_PHASE(2);
         if (blk_mask) {
             __builtin_amdgcn_wave_barrier();
             const bool fl = lane < cnt && s_flag[lane] != 0u;
@@ -698,7 +625,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
             ccnt += (uint32_t)__builtin_popcountll(rmask);
         }
         cur = nb; cur_k = nk;
-        SLS_PHASE(3);
     }
 #undef SLS_SCAN_POS
 #undef SLS_SCAN_LOAD
@@ -732,8 +658,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
         for (int off = 32; off > 0; off >>= 1) c = max(c, (uint32_t)__shfl_down(c, off, 64));
         if (lane == 0) atomicMax(&tile_consumed[tile], c);
     }
-    SLS_TRACE_END(0);
-    SLS_PHASE_END();
     if (DBG && lane == 0) {
         dbg_cycles[tile * kPerTile + sub] = (uint32_t)(clock64() - t_start);
         uint32_t *st = dbg_cycles + (size_t)T * kPerTile;
@@ -777,24 +701,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
 //            fixed-point value reaches 2^50 — the prediction was off by more than 2^22 — sets bit 3 of the iteration's
 //            overflow word: the iteration is void and the caller repeats it with the two launches above.
 // Same kernel otherwise: the result does not depend on the order of the blocks or of the atomics.
-// SLS_ABL_EXTRA (experiment builds only, tools/build_variant.sh ... -DSLS_ABL_EXTRA=k): behind the engine's tile backward a
-// SECOND launch of the same kernel, timed in a slot of its own ("knn" in bench.py's kernel table), with one ingredient
-// changed — k = 1: no atomics (what they cost), k = 2: unchanged, its gradient records into a scratch copy (the control:
-// the production launch's time under the same bracketing).  The iteration's results are not touched.
-#ifdef SLS_ABL_EXTRA
-#define SLS_ABL_PARAM , int abl
-#define SLS_ABL_ARG(v_) , v_
-#else
-#define SLS_ABL_PARAM
-#define SLS_ABL_ARG(v_)
-#endif
-#ifdef SLS_BWD_WAVES      // (experiment builds: a register cap for that many waves per SIMD; HISTORY #75)
-#define SLS_BWD_OCC __attribute__((amdgpu_waves_per_eu(SLS_BWD_WAVES, SLS_BWD_WAVES)))
-#else
-#define SLS_BWD_OCC
-#endif
 template <int BW, int BH, bool LEAN, int FUSED, int DET, bool DENSE>
-__global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
+__global__ __launch_bounds__(64) void render_bwd_block_kernel(
     DevCam cam, const uint2 *__restrict__ ranges, const uint32_t *__restrict__ vals,
     const float4 *__restrict__ rec, const float2 *__restrict__ col_cs, const float2 *__restrict__ row_cs,
     const float4 *__restrict__ pix_state, const uint2 *__restrict__ pix_contrib,
@@ -802,11 +710,10 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
     uint8_t *__restrict__ touched, uint32_t *__restrict__ dbg_cycles, ConsumerArgs ca, int consumer_blocks,
     uint32_t *__restrict__ det_max, unsigned long long *__restrict__ det_acc, const uint32_t *__restrict__ block_order,
     int vstride, const uint8_t *__restrict__ det_prev, const uint32_t *__restrict__ det_gex, uint32_t *__restrict__ det_flag,
-    uint32_t order_tag SLS_ABL_PARAM)
+    uint32_t order_tag)
 {
     static_assert(DET != 3 || DENSE, "the one-pass deterministic accumulation walks the forward's compact lists");
     static_assert(!FUSED || LEAN, "the fused consumer gradient has no median / distortion channel");
-    SLS_TRACE_BEGIN();
     if (FUSED == 1 && blockIdx.x == 0) consumer_reduce_partials_wave(ca, consumer_blocks, (int)threadIdx.x);
     static_assert(BW * BH == 16 && kTileW % BW == 0 && kTileH % BH == 0, "16-pixel blocks tiling a tile");
     constexpr int kPerTile = kTilePix / 16, kBX = kTileW / BW;
@@ -815,8 +722,8 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
     __shared__ uint32_t s_list[64 + 4];          // culling path: the round's survivors; DENSE: its entries' list positions
     __shared__ uint32_t s_gidx[65];
     __shared__ uint4 s_ex[DET == 3 ? 65 : 1];    // DET = 3: the predicted-scale bytes (16 fields) of the round's entries
-    // DENSE: blk_mask is the compact-list hand-over of a forward with the same block shape (the launcher checks what
-    // it can, the tag settles it: another producer's buffer is not walked)
+    // DENSE: blk_mask is the compact-list hand-over of this iteration's forward (the launcher checks what it can, the
+    // tag settles it: another producer's buffer is not walked)
     const int T = cam.GX * cam.GY;
     // The three words that decide where this block works — the hand-over's tag, the launch order's tag (order_tag: the
     // order is the keyframe's own buffer, walked only once an iteration has filled it; it has its full size either
@@ -831,9 +738,9 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
     const uint32_t oidx = ob[block_order ? (order_tag ? 1 : 0) + oxcd * (T * kPerTile / 8) + (int)blockIdx.x / 8 : 0];
     const uint32_t otag = (block_order && order_tag) ? otag_w : order_tag;
     if (DENSE && tagw != block_mask_tag(BW)) {
-        // the hand-over was written by a forward of another block shape (debug variants switched between the two
-        // launches): nothing here can be trusted — say so (bit 4 of the iteration's void word: the engine raises) instead
-        // of dropping the block's gradients and loss terms silently
+        // the hand-over buffer is not this forward's (its tag does not name the 8x2 blocks' compact lists): nothing here
+        // can be trusted — say so (bit 4 of the iteration's void word: the engine raises) instead of dropping the block's
+        // gradients and loss terms silently
         if (det_flag && threadIdx.x == 0) atomicOr(det_flag, 16u);
         return;
     }
@@ -851,7 +758,6 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
         tile_of_block<kPerTile>(blockIdx.x, T, tile, sub);
     }
     const int ty = tile / cam.GX, tx = tile - ty * cam.GX;
-    SLS_MARK(1, 0, tile);
     const uint2 range = ranges[tile];
     const int x0 = tx * kTileW + (sub % kBX) * BW, y0 = ty * kTileH + (sub / kBX) * BH;
     const int px = x0 + (p % BW), py = y0 + (p / BW);
@@ -982,8 +888,6 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor(wmax, off, 64));
     const int tmax = (int)wmax;
-    SLS_MARK(1, 1, tmax);
-    SLS_MARK(1, 2, dD + dA + dN2);
     float Tr = Tf, S = 0.0f;   // replicated over the quad
     // One step: the list entries in slots j (LDS record slot of my quad lane; 64 = the empty padding record) with
     // contributor numbers `contributor`, back to front: slot 0 of a quad holds the LAST entry of the four.
@@ -999,7 +903,6 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
         //  entries that reached a pixel of this block, and on the culling path a step whose 64 pairs are all inactive
         //  is rare — no dead-step test: its ballot costs more than it saves, as in the forward)
         const bool act = inside & (contributor <= last) & !e.skip;
-        SLS_TRACE_STEP();
         const float a = act ? e.alpha : 0.0f;          // 0: the entry passes through (1 - a = 1, w = 0)
         const float om = 1.0f - a;
         const float rom = __builtin_amdgcn_rcpf(om);
@@ -1059,10 +962,6 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
         const uint32_t gidx = s_gidx[j];
         // (the padding entry is never active: its sums are exact zeros)
         if (DET == 0) {
-#ifdef SLS_ABL_EXTRA
-            if (abl == 1) asm volatile("" :: "v"(tot), "v"(gidx));
-            else
-#endif
             if (tot != 0.0f) atomicAdd(&grec[(size_t)gidx * kGrec + field], tot);
         } else if (DET == 1) {
             if (tot != 0.0f) atomicMax(&det_max[(size_t)gidx * kGrec + field], __float_as_uint(fabsf(tot)));
@@ -1111,12 +1010,8 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
                 if (nr > 1) mine_next2 = clist[SLS_CENTRY(nr - 2, lane)];
                 if (lane == 0) s_ex[64] = make_uint4(0u, 0u, 0u, 0u);
             }
-            SLS_PHASE_DECL();
             for (int r = nr - 1; r >= 0; --r) {
-                SLS_PHASE_RESET();
                 SLS_WSTAGE_STORE()
-                if (r == nr - 1) SLS_MARK(1, 3, sp4.x);
-                SLS_TRACE_ROUND();
                 const uint2 mine = mine_next;
                 s_gidx[lane] = mine.y;
                 s_list[lane] = mine.x + 1u;              // (the contributor numbers of the round's entries)
@@ -1138,18 +1033,14 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
                 // the records of the others not at all.  One byte store per entry; same value from every block.
                 if (touched && lane < cnt) touched[mine.y] = 1;
                 __builtin_amdgcn_wave_barrier();
-                SLS_PHASE(0);
-                SLS_PHASE(1);
                 for (int k = 0; k < cnt; k += 4) blend_step(k + slot, s_list[k + slot]);
-                SLS_PHASE(2);
             }
 #undef SLS_CENTRY
 #undef SLS_CIDX1
 #undef SLS_CSTAGE_LOAD_IDX
-            SLS_PHASE_END_B();
         }
     } else if (tmax > 0) {
-        // ---- no list from a forward of this block shape: rounds of 64 consecutive list entries, culled here
+        // ---- no compact list from the forward: rounds of 64 consecutive list entries, culled here
         // (the list: surfel indices `vstride` words apart — 2 where the tile sort delivered (surfel, block mask) pairs)
         const int nr = (tmax + 63) / 64;
         if (lane < kRec4) s_rec[64 * kRec4 + lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1163,7 +1054,6 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
         if (nr > 1) { SLS_SSTAGE_LOAD_IDX(nr - 2) }
         for (int r = nr - 1; r >= 0; --r) {
             SLS_WSTAGE_STORE()
-            SLS_TRACE_ROUND();
             const uint32_t my_idx = next_idx;
             s_gidx[lane] = my_idx;
             if (r > 0) {
@@ -1196,63 +1086,41 @@ __global__ __launch_bounds__(64) SLS_BWD_OCC void render_bwd_block_kernel(
     }
 
     if (dbg_cycles && lane == 0) dbg_cycles[tile * kPerTile + sub] = (uint32_t)(clock64() - t_start);
-    SLS_TRACE_END(1);
 }
 
 // ---------------------------------------------------------------------------
 // the hand-over buffer carries a launch order for the backward (8x2 blocks, XCD-interleaved tile mapping)
-bool handover_has_order(int T) { return T % 32 == 0 && kTileW == 16 && kTileH == 16; }
-const uint32_t *handover_block_order(const uint64_t *block_masks, int T)
-{
-    return reinterpret_cast<const uint32_t *>(block_masks + block_list_order_word(T, kTilePix / 16));
-}
+static bool handover_has_order(int T) { return T % 32 == 0 && kTileW == 16 && kTileH == 16; }
 
-#ifdef SLS_TRACE
-extern "C" int sls_debug_read_trace(uint32_t *host)
-{
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace), sizeof(g_trace));
-}
-extern "C" int sls_debug_read_trace_phases(uint32_t *host)
-{
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace_phase), sizeof(g_trace_phase));
-}
-extern "C" int sls_debug_read_trace_phases_b(uint32_t *host)
-{
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace_phase_b), sizeof(g_trace_phase_b));
-}
-extern "C" int sls_debug_read_trace_marks(uint32_t *host)
-{
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace_mark), sizeof(g_trace_mark));
-}
-#endif
-
-int launch_render_fwd_block(const DevCam &cam, const uint32_t *ranges, const uint32_t *vals, const float *rec,
-                            const float *col_cs, const float *row_cs, float *allmap, float *pix_state,
-                            uint32_t *pix_contrib, uint32_t *tile_consumed, uint64_t *block_masks, int shape,
-                            hipStream_t st, bool lean, uint32_t *block_cost, const uint2 *bmask, bool order_in_handover)
+int launch_render_fwd(const DevCam &cam, const uint32_t *ranges, const uint32_t *vals, const float *rec,
+                      const float *col_cs, const float *row_cs, float *allmap, float *pix_state,
+                      uint32_t *pix_contrib, uint32_t *tile_consumed, hipStream_t st, bool consumed_zeroed,
+                      uint64_t *block_masks, bool lean, uint32_t *block_cost, const uint2 *bmask,
+                      bool order_in_handover)
 {
     const int T = cam.GX * cam.GY;
+    // the block kernels combine their blocks' counters with atomicMax: start from zero
+    if (tile_consumed && !consumed_zeroed)
+        SLS_HIP_CHECK(hipMemsetAsync(tile_consumed, 0, sizeof(uint32_t) * (size_t)T, st));
     ScopedTimer tm(T_RENDER_FWD, st);
     const dim3 grid(T * (kTilePix / 16)), block(64);
     uint32_t *const g_dbg_fwd_cycles = debug_state().dbg_fwd_cycles;
-    SLS_REQUIRE(shape == 0 || shape == 1, "tile-kernel variant must be 2 (4x4 blocks) or 3 (8x2 blocks)");
 #define SLS_FWD_ARGS grid, block, 0, st, block_masks, cam, (const uint2 *)ranges, vals, (const float4 *)rec,     \
                      (const float2 *)col_cs, (const float2 *)row_cs, allmap, (float4 *)pix_state,                \
                      (uint2 *)pix_contrib, tile_consumed, g_dbg_fwd_cycles, block_cost
-#define SLS_FWD_BLOCK(BW_, BH_, DBG_, LEAN_) hipLaunchKernelGGL((render_fwd_block_kernel<BW_, BH_, DBG_, LEAN_>), SLS_FWD_ARGS)
+#define SLS_FWD_BLOCK(DBG_, LEAN_) hipLaunchKernelGGL((render_fwd_block_kernel<8, 2, DBG_, LEAN_>), SLS_FWD_ARGS)
 #define SLS_FWD_DENSE(DBG_, LEAN_) hipLaunchKernelGGL((render_fwd_dense_kernel<8, 2, DBG_, LEAN_>), SLS_FWD_ARGS, bmask)
-    // the instances' block masks in list order (a passenger of the tile sort): dense rounds, 8x2 blocks only
-    if (bmask && shape == 1) {
+    // the instances' block masks in list order (a passenger of the tile sort): dense rounds
+    if (bmask) {
         if (g_dbg_fwd_cycles) SLS_FWD_DENSE(true, false); else if (lean) SLS_FWD_DENSE(false, true); else SLS_FWD_DENSE(false, false);
-    } else
-    if (g_dbg_fwd_cycles) { if (shape == 1) SLS_FWD_BLOCK(8, 2, true, false); else SLS_FWD_BLOCK(4, 4, true, false); }
-    else if (lean) { if (shape == 1) SLS_FWD_BLOCK(8, 2, false, true); else SLS_FWD_BLOCK(4, 4, false, true); }
-    else { if (shape == 1) SLS_FWD_BLOCK(8, 2, false, false); else SLS_FWD_BLOCK(4, 4, false, false); }
+    } else {
+        if (g_dbg_fwd_cycles) SLS_FWD_BLOCK(true, false); else if (lean) SLS_FWD_BLOCK(false, true); else SLS_FWD_BLOCK(false, false);
+    }
 #undef SLS_FWD_BLOCK
 #undef SLS_FWD_DENSE
 #undef SLS_FWD_ARGS
     SLS_LAUNCH_CHECK("render_fwd_block_kernel");
-    if (order_in_handover && block_masks && shape == 1 && handover_has_order(T)) {
+    if (order_in_handover && block_masks && handover_has_order(T)) {
         // the staged API: the order the backward launches its blocks in, from the counts the forward just wrote
         hipLaunchKernelGGL(block_order_kernel, dim3(8), dim3(256), 0, st, block_masks, T);
         SLS_LAUNCH_CHECK("block_order_kernel");
@@ -1260,71 +1128,61 @@ int launch_render_fwd_block(const DevCam &cam, const uint32_t *ranges, const uin
     return SLS_OK;
 }
 
-int launch_render_bwd_block(const DevCam &cam, const uint32_t *ranges, const uint32_t *vals, const float *rec,
-                            const float *col_cs, const float *row_cs, const float *pix_state,
-                            const uint32_t *pix_contrib, const float *dL_dallmap, float *grec,
-                            const uint64_t *block_masks, int shape, hipStream_t st, bool lean, uint8_t *touched,
-                            const ConsumerArgs *fused_consumer, uint32_t *det_max, unsigned long long *det_acc,
-                            const uint32_t *block_order, int vals_stride, bool dense, const uint8_t *det_prev,
-                            const uint32_t *det_gex, uint32_t *det_flag, bool consumer_b_inline, uint32_t order_tag)
+int launch_render_bwd(const DevCam &cam, const uint32_t *ranges, const uint32_t *vals, const float *rec,
+                      const float *col_cs, const float *row_cs, const float *pix_state,
+                      const uint32_t *pix_contrib, const float *dL_dallmap, float *grec, hipStream_t st,
+                      const uint64_t *block_masks, bool lean, uint8_t *touched,
+                      const ConsumerArgs *fused_consumer, uint32_t *det_max, unsigned long long *det_acc,
+                      const uint32_t *block_order, int vals_stride, int block_masks_shape, bool order_in_handover,
+                      const uint8_t *det_prev, const uint32_t *det_gex, uint32_t *det_flag, bool consumer_b_inline,
+                      uint32_t order_tag)
 {
     const int T = cam.GX * cam.GY;
+    // vals_stride: 1 = plain list of surfel indices, 2 = the tile sort's (surfel, block mask) pairs.
+    // block_masks_shape: the producer's tag of the compact lists in `block_masks` (0 = no hand-over, 3 = the 8x2
+    // forward's): they are walked only for 3 — any other value culls the tile's list itself (the buffer's tag word is
+    // the kernel's last guard).
+    const bool dense = block_masks != nullptr && block_masks_shape == 3;
+    // no order from the caller: the staged forward left one in the hand-over buffer (block_order_kernel)
+    if (!block_order && order_in_handover && dense && handover_has_order(T))
+        block_order = reinterpret_cast<const uint32_t *>(block_masks + block_list_order_word(T, kTilePix / 16));
     ScopedTimer tm(T_RENDER_BWD, st);
     const dim3 grid(T * (kTilePix / 16)), block(64);
     uint32_t *const g_dbg_bwd_cycles = debug_state().dbg_bwd_cycles;
-    SLS_REQUIRE(shape == 0 || shape == 1, "tile-kernel variant must be 2 (4x4 blocks) or 3 (8x2 blocks)");
     ConsumerArgs ca;
     memset(&ca, 0, sizeof(ca));
     int cblocks = 0;
-#ifdef SLS_ABL_EXTRA
-    int abl_mode = 0;
-#endif
     if (fused_consumer) {
         ca = *fused_consumer;
         cblocks = ((ca.W + 63) / 64) * ((ca.H + 3) / 4);
     }
-    // `dense`: the forward's compact lists come from a forward of THIS block shape (the caller carries the producer's
-    // shape next to the buffer; the kernel checks the buffer's tag as a last guard); otherwise the backward culls.
-#define SLS_BWD_LAUNCH(BW_, BH_, LEAN_, FUSED_, DET_, DENSE_)                                                        \
-    hipLaunchKernelGGL((render_bwd_block_kernel<BW_, BH_, LEAN_, FUSED_, DET_, DENSE_>), grid, block, 0, st, cam, (const uint2 *)ranges, \
+#define SLS_BWD_LAUNCH(LEAN_, FUSED_, DET_, DENSE_)                                                                  \
+    hipLaunchKernelGGL((render_bwd_block_kernel<8, 2, LEAN_, FUSED_, DET_, DENSE_>), grid, block, 0, st, cam, (const uint2 *)ranges, \
                        vals, (const float4 *)rec, (const float2 *)col_cs, (const float2 *)row_cs,                    \
                        (const float4 *)pix_state, (const uint2 *)pix_contrib, dL_dallmap, grec, block_masks,         \
-                       touched, g_dbg_bwd_cycles, ca, cblocks, det_max, det_acc, block_order, vals_stride, det_prev, det_gex, det_flag, order_tag SLS_ABL_ARG(abl_mode))
-#define SLS_BWD_BLOCK(BW_, BH_, LEAN_, FUSED_, DET_)                                                                 \
-    do { if (dense) SLS_BWD_LAUNCH(BW_, BH_, LEAN_, FUSED_, DET_, true); else SLS_BWD_LAUNCH(BW_, BH_, LEAN_, FUSED_, DET_, false); } while (0)
+                       touched, g_dbg_bwd_cycles, ca, cblocks, det_max, det_acc, block_order, vals_stride, det_prev, det_gex, det_flag, order_tag)
+#define SLS_BWD_BLOCK(LEAN_, FUSED_, DET_)                                                                           \
+    do { if (dense) SLS_BWD_LAUNCH(LEAN_, FUSED_, DET_, true); else SLS_BWD_LAUNCH(LEAN_, FUSED_, DET_, false); } while (0)
     if (det_prev) {
-        // deterministic accumulation in ONE launch: predicted scales (8x2 kernel on the forward's compact lists only)
-        SLS_REQUIRE(det_acc && det_gex && det_flag && shape == 1 && dense, "the one-pass deterministic accumulation needs the 8x2 kernel on the forward's compact lists");
+        // deterministic accumulation in ONE launch: predicted scales (on the forward's compact lists only)
+        SLS_REQUIRE(det_acc && det_gex && det_flag && dense, "the one-pass deterministic accumulation needs the forward's compact lists");
         if (fused_consumer) { SLS_REQUIRE(lean, "the fused consumer gradient exists for the lean kernel only");
-                              if (consumer_b_inline) SLS_BWD_LAUNCH(8, 2, true, 2, 3, true); else SLS_BWD_LAUNCH(8, 2, true, 1, 3, true); }
-        else if (lean) SLS_BWD_LAUNCH(8, 2, true, 0, 3, true);
-        else SLS_BWD_LAUNCH(8, 2, false, 0, 3, true);
+                              if (consumer_b_inline) SLS_BWD_LAUNCH(true, 2, 3, true); else SLS_BWD_LAUNCH(true, 1, 3, true); }
+        else if (lean) SLS_BWD_LAUNCH(true, 0, 3, true);
+        else SLS_BWD_LAUNCH(false, 0, 3, true);
     } else if (det_max) {
-        // deterministic accumulation: two launches of the 8x2 kernel (maximum, then fixed-point sum)
-        SLS_REQUIRE(det_acc && shape == 1, "deterministic accumulation exists for the 8x2 kernel");
+        // deterministic accumulation: two launches (maximum, then fixed-point sum)
+        SLS_REQUIRE(det_acc, "deterministic accumulation needs both accumulators");
         if (fused_consumer) { SLS_REQUIRE(lean, "the fused consumer gradient exists for the lean kernel only");
-                              if (consumer_b_inline) { SLS_BWD_BLOCK(8, 2, true, 2, 1); SLS_BWD_BLOCK(8, 2, true, 2, 2); }
-                              else { SLS_BWD_BLOCK(8, 2, true, 1, 1); SLS_BWD_BLOCK(8, 2, true, 1, 2); } }
-        else if (lean) { SLS_BWD_BLOCK(8, 2, true, 0, 1); SLS_BWD_BLOCK(8, 2, true, 0, 2); }
-        else { SLS_BWD_BLOCK(8, 2, false, 0, 1); SLS_BWD_BLOCK(8, 2, false, 0, 2); }
+                              if (consumer_b_inline) { SLS_BWD_BLOCK(true, 2, 1); SLS_BWD_BLOCK(true, 2, 2); }
+                              else { SLS_BWD_BLOCK(true, 1, 1); SLS_BWD_BLOCK(true, 1, 2); } }
+        else if (lean) { SLS_BWD_BLOCK(true, 0, 1); SLS_BWD_BLOCK(true, 0, 2); }
+        else { SLS_BWD_BLOCK(false, 0, 1); SLS_BWD_BLOCK(false, 0, 2); }
     } else if (fused_consumer) {
-        SLS_REQUIRE(lean && shape == 1, "the fused consumer gradient exists for the lean 8x2 kernel only");
-        if (consumer_b_inline) SLS_BWD_BLOCK(8, 2, true, 2, 0); else SLS_BWD_BLOCK(8, 2, true, 1, 0);
-#ifdef SLS_ABL_EXTRA
-        if (consumer_b_inline && dense) {
-            tm.end_now();
-            ScopedTimer tm2(T_KNN, st);
-            abl_mode = SLS_ABL_EXTRA;
-            static float *abl_grec = nullptr;
-            if (abl_mode == 2) {
-                if (!abl_grec) { if (hipMalloc(&abl_grec, (size_t)1 << 28) != hipSuccess) return SLS_E_HIP; (void)hipMemsetAsync(abl_grec, 0, (size_t)1 << 28, st); }
-                grec = abl_grec;
-            }
-            SLS_BWD_LAUNCH(8, 2, true, 2, 0, true);
-        }
-#endif
-    } else if (lean) { if (shape == 1) SLS_BWD_BLOCK(8, 2, true, 0, 0); else SLS_BWD_BLOCK(4, 4, true, 0, 0); }
-    else { if (shape == 1) SLS_BWD_BLOCK(8, 2, false, 0, 0); else SLS_BWD_BLOCK(4, 4, false, 0, 0); }
+        SLS_REQUIRE(lean, "the fused consumer gradient exists for the lean kernel only");
+        if (consumer_b_inline) SLS_BWD_BLOCK(true, 2, 0); else SLS_BWD_BLOCK(true, 1, 0);
+    } else if (lean) SLS_BWD_BLOCK(true, 0, 0);
+    else SLS_BWD_BLOCK(false, 0, 0);
 #undef SLS_BWD_LAUNCH
 #undef SLS_BWD_BLOCK
     SLS_LAUNCH_CHECK("render_bwd_block_kernel");

@@ -105,25 +105,6 @@ __device__ __forceinline__ uint32_t block_mask_of(const BlockMaskArgs &a, uint32
 // gather per position anyway.  Tiles <= 512 (every size the reference's mapper meets and BASELINE config 3), D10 off;
 // anything else takes the emission + radix pass below.
 // ---------------------------------------------------------------------------
-#ifdef SLS_TRACE
-// Experiment build only (tools/build_variant.sh trace ... -DSLS_TRACE; read back with sls_debug_read_bin_trace, profiles/r04f_bin_trace.txt): every wave of bin_direct_kernel
-// and every workgroup of the counting merge records the 100 MHz wall clock at its phases.
-__device__ uint32_t g_bin_trace[32768 * 8];      // per wave: start, loads done, counted, cursors ready, end, rounds, S, (pad)
-__device__ uint32_t g_merge_trace[1024 * 4];     // per workgroup: start, network done, counted + stored, end
-extern "C" int sls_debug_read_bin_trace(uint32_t *host_bin, uint32_t *host_merge)
-{
-    int rc = (int)hipMemcpyFromSymbol(host_bin, HIP_SYMBOL(g_bin_trace), sizeof(g_bin_trace));
-    if (rc == 0) rc = (int)hipMemcpyFromSymbol(host_merge, HIP_SYMBOL(g_merge_trace), sizeof(g_merge_trace));
-    return rc;
-}
-#define SLS_BT(k_) do { if (lane == 0) { const int wi_ = (int)blockIdx.x * WAVES + w; if (wi_ < 32768) g_bin_trace[8 * wi_ + (k_)] = (uint32_t)wall_clock64(); } } while (0)
-#define SLS_BTV(k_, v_) do { if (lane == 0) { const int wi_ = (int)blockIdx.x * WAVES + w; if (wi_ < 32768) g_bin_trace[8 * wi_ + (k_)] = (uint32_t)(v_); } } while (0)
-#define SLS_MT(k_) do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_merge_trace[4 * blockIdx.x + (k_)] = (uint32_t)wall_clock64(); } while (0)
-#else
-#define SLS_BT(k_)
-#define SLS_BTV(k_, v_)
-#define SLS_MT(k_)
-#endif
 
 // The emission record of a surfel, 8 bytes: x = its tile rectangle in ONE word — txlo (9 bits) | ncols (10) | tylo (6) |
 // nrows (7), zero: nothing emitted; grids up to 512 x 64 tiles (bin_direct_possible) — y = its block box.
@@ -750,7 +731,6 @@ __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, con
         if (threadIdx.x == 0) s_wide = 0;
     }
     const int base = blockIdx.x * kResortWindow - kResortWindow / 2, o0 = 2 * (int)threadIdx.x;
-    SLS_MT(0);
     uint64_t e[2];
     if (PRE) {
         uint64_t f[2][2];
@@ -785,7 +765,6 @@ __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, con
         }
     }
     bitonic_pairs<kResortWindow>(e[0], e[1], s_pairs);
-    SLS_MT(1);
     if (comp_out) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -834,7 +813,6 @@ __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, con
         if (o0 + q == hi) edges[2 * blockIdx.x + 1] = e[q];
     }
     __syncthreads();
-    SLS_MT(2);
     if (DIRECT && use_diff && s_wide) {          // (workgroup-uniform: read behind the barrier)
         diff_finish(GX, db.bins, s_hist, s_diff, (int)threadIdx.x, kResortThreads);
         __syncthreads();
@@ -845,7 +823,6 @@ __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, con
             db.cnt[(size_t)d * db.stride + blockIdx.x] = c;
             if (db.coarse && c) atomicAdd(&db.coarse[(size_t)(blockIdx.x / kDirectGroup) * db.bins + d], c);
         }
-        SLS_MT(3);
     } else if (threadIdx.x < 4) {
         const int blk = (base + (int)threadIdx.x * 256) / 256;      // aligned 256-block of positions
         if (base + (int)threadIdx.x * 256 >= 0 && blk * 256 < N)
@@ -953,7 +930,6 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
     const int sub = helper ? 0 : ((int)blockIdx.x - nhelp) % SPLIT;
     const int part = helper ? 1 + (int)blockIdx.x % (kHeavyParts - 1) : 0;
     const bool lead = !helper && chunk == 0 && sub == 0;      // the launch's first chunk: ranges, R, the void bits, the status mirror
-    SLS_BT(0);
     if (resort_windows > 0 && lead) {
         for (int b = tid; b + 1 < resort_windows; b += TPB)
             if (resort_edges[2 * b + 1] >= resort_edges[2 * (b + 1)]) atomicOr(fail_flag, kResortFailed);
@@ -1034,7 +1010,6 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
     s_lane[w][lane] = make_uint4(er.x, er.y, g, first);
     if (lane == 63) s_ws[w] = S;
     __syncthreads();
-    SLS_BT(1);
     bool heavy = false;                          // (workgroup-uniform)
     if (SPLIT == 1) {
 #pragma unroll
@@ -1045,7 +1020,6 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
     if (!heavy) count_rect_tiles_wave(er.x, GX, s_cur + w * BINS);
 #pragma unroll
     for (int m = 0; m < SPLIT - 1; ++m) count_rect_tiles_wave(front[m], GX, s_pre);
-    SLS_BT(2);
     // digit bases: exclusive scan of the tile totals (PER consecutive ones per thread)
     uint32_t loc[PER], dsum = 0;
 #pragma unroll
@@ -1106,9 +1080,6 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
         __threadfence_system();
         __builtin_nontemporal_store(0u, status_mirror + 7);      // (the host polls words 0 and 7: sls_common.hpp, mirror_status_block)
     }
-    SLS_BT(3);
-    SLS_BTV(5, (S + 63u) / 64u);
-    SLS_BTV(6, S);
     // The wave's S instances, 64 at a time in emission order (lane-major, then the rectangle row-major).  Owner of slot q:
     // the last lane whose first instance is <= q — every lane marks the slot its instances start at, a max-scan over the
     // round's 64 slots (carried on from the previous round) names the owner: one LDS round trip and six DPP steps.
@@ -1207,7 +1178,6 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
             });
             __syncthreads();
         }
-        SLS_BT(4);
         return;
     }
     uint32_t *const cur = s_cur + w * BINS;
@@ -1295,7 +1265,6 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
         }
         __builtin_amdgcn_wave_barrier();
     }
-    SLS_BT(4);
 }
 
 // A2 on the depth-ordered surfels, level 1: per-block sums of tiles[order[i]]
@@ -1686,7 +1655,6 @@ int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_
     // The emission's workgroups as the chunks of the (single) sort pass: they count their instances' tiles themselves,
     // the pass is row scan + scatter — one dependent launch less.
     // Needs the count table (tiles x workgroups) and the chunk starts to fit the sort's scratch.
-    constexpr bool no_emit_hist = false;
     // Only while the count table (tiles x chunks words, written, scanned and read back as scattered words) stays small:
     // at 500 k surfels / 64 x 2048 its 512 x 1954 words cost 14 us more than the launch saves, and chunks of 512
     // positions (half the table) make the scatter's waves too few and too long (+16 us); measured gains: -3.3 us per
@@ -1695,7 +1663,7 @@ int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_
     constexpr int eb = 256;
     const int nemit = (N + eb - 1) / eb;
     uint32_t *cnt = (uint32_t *)scratch, *totals = cnt + (size_t)bins * nemit, *chunk_start = totals + bins;
-    const bool emit_hist = fused_ranges && !no_emit_hist && (size_t)bins * nemit <= (size_t)400000 &&
+    const bool emit_hist = fused_ranges && (size_t)bins * nemit <= (size_t)400000 &&
                            ((size_t)bins * nemit + bins + nemit + 1) * sizeof(uint32_t) <= sort_core_bytes(cap);
     // Block masks (the forward's dense rounds) only where the tiles' lists are long enough for the forward to gain more than the binning pays:
     // capacity per tile as the host-side proxy (bmask_mode = SlsMappingConfig.block_masks: 0 auto, 1 always, 2 never)

@@ -1,6 +1,6 @@
-// sls_tile.hpp — device helpers shared by the tile kernels (sls_render.hip,
-// sls_render_block.hip): the (pixel, surfel) evaluation, the support-box cull
-// and the wave-private LDS staging of a tile's list.  Maths in DESIGN.md §2.
+// sls_tile.hpp — device helpers of the tile kernels (sls_render_block.hip):
+// the (pixel, surfel) evaluation, the support-box cull and the wave-private
+// LDS staging of a tile's list.  Maths in DESIGN.md §2.
 #pragma once
 #include "sls_common.hpp"
 

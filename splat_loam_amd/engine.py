@@ -356,8 +356,8 @@ class MappingEngine:
             raise RuntimeError("a surfel outside the agreed union of the touched sets had a non-zero gradient: the early "
                                "gradient bitmap was no superset (sparse exchange) — the iteration's update is void")
         if st.get("handover_mismatch"):
-            raise RuntimeError("the tile backward found a forward -> backward hand-over written by another tile-kernel variant "
-                               "(sls_debug_variant switched between the two launches): the iteration's gradients are void")
+            raise RuntimeError("the tile backward found a forward -> backward hand-over buffer that is not this forward's "
+                               "(its tag word does not match): the iteration's gradients are void")
         if self._sx is not None and (not st["overflow"] or st["exchange_too_small"]):
             want = int(st["exchange_count"] * 1.5) + 4096
             self._sx["send"] = int(min(self.N, max(want, int(self._sx["send"] * 0.97))))

@@ -1091,45 +1091,27 @@ def test_depth_order_repair_at_awkward_sizes(device):
     assert mod.run(dev=str(device), verbose=False) == 0
 
 
-@pytest.mark.parametrize("fwd_variant,bwd_variant", [(2, 2), (2, 3), (3, 2), (3, 3)],
-                         ids=["block4x4", "block4x4-fwd", "block4x4-bwd", "block8x2"])
-def test_tile_kernel_variants_agree_with_checker(device, oracle32, fwd_variant, bwd_variant):
-    """Both pixel-block shapes of the tile kernels (4x4 and 8x2, also mixed: the backward of one reading the
-    forward of the other, whose contribution masks it then cannot use) pass the same parity bar."""
+@pytest.mark.parametrize("walk", [True, False], ids=["walk", "cull"])
+@pytest.mark.parametrize("list_pairs", [1, 2], ids=["pairs", "plain"])
+def test_tile_kernel_paths_agree_with_checker(device, oracle32, list_pairs, walk):
+    """The tile backward's paths pass the same parity bar: the dense rounds on the forward's compact lists (walk) and
+    the culling rounds over the tile's list (cull: the state names no hand-over), each on the tile sort's (surfel,
+    block mask) pairs (vals_stride 2) and on plain lists (vals_stride 1)."""
     from splat_loam_amd import _abi
     lib = _abi.lib()
-    lib.sls_debug_variant(fwd_variant, bwd_variant)
-    try:
-        N, H, W = 20000, 64, 512
-        sc, view, proj = scene_and_camera(N, H, W, seed=21, range_lo=2.0, range_hi=30.0)
-        # (pairs wherever the forward can use them: the 8x2 forward then hands the 4x4 backward a list two words apart)
-        st, t = hip_forward(device, sc, view, proj, H, W, list_pairs=1)
-        assert st.vals_stride == (2 if fwd_variant == 3 else 1) and st.block_masks_shape == fwd_variant
-        cam = oracle32.camera(H, W, view, proj, tile=_abi.tile_size())
-        ost = oracle32.forward(cam, sc["means"], sc["scales"], sc["rots"], sc["opac"])
-        _compare_forward(oracle32, st, ost, cam, f"variant{fwd_variant}")
-        _compare_backward(oracle32, st, t, ost, sc, f"variant{bwd_variant}")
-    finally:
-        lib.sls_debug_variant(3, 3)
-
-
-def test_backward_after_the_variants_changed(device, oracle32):
-    """a forward at 4x4 pixel blocks, then BOTH variants switched to 8x2 before the backward.  The
-    hand-over buffer was written by another block shape: the backward must cull for itself (the state carries the
-    producer's shape), not walk — or silently skip — a list that is not its own."""
-    from splat_loam_amd import _abi
-    lib = _abi.lib()
-    N, H, W = 8000, 32, 512
-    sc, view, proj = scene_and_camera(N, H, W, seed=22, range_lo=2.0, range_hi=20.0)
+    # the 8x2 pixel blocks are the only tile kernels: sls_debug_variant keeps its ABI slot and accepts nothing else
+    assert lib.sls_debug_variant(2, 2) != 0
+    assert lib.sls_debug_variant(3, 3) == 0 and lib.sls_debug_variant(-1, -1) == 0
+    N, H, W = 20000, 64, 512
+    sc, view, proj = scene_and_camera(N, H, W, seed=21, range_lo=2.0, range_hi=30.0)
+    st, t = hip_forward(device, sc, view, proj, H, W, list_pairs=list_pairs)
+    assert st.vals_stride == (2 if list_pairs == 1 else 1) and st.block_masks_shape == 3
     cam = oracle32.camera(H, W, view, proj, tile=_abi.tile_size())
     ost = oracle32.forward(cam, sc["means"], sc["scales"], sc["rots"], sc["opac"])
-    lib.sls_debug_variant(2, 2)
-    try:
-        st, t = hip_forward(device, sc, view, proj, H, W)
-        assert st.block_masks_shape == 2
-    finally:
-        lib.sls_debug_variant(3, 3)
-    _compare_backward(oracle32, st, t, ost, sc, "fwd4x4-then-8x2")
+    _compare_forward(oracle32, st, ost, cam, f"list_pairs{list_pairs}")
+    if not walk:
+        st.block_masks_shape = 0
+    _compare_backward(oracle32, st, t, ost, sc, f"list_pairs{list_pairs}-{'walk' if walk else 'cull'}")
 
 
 def _engine_rank(rank, world, port, out_dir, mode="sync", dp_mode="rs_ag"):

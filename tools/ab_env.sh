@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of environment switches inside ONE gpurun call, at three sizes:   VARIANTS="_ SLS_NO_DIRECT_BIN=1" bash tools/ab_env.sh
+# A/B of environment switches inside ONE GPU session, at three sizes:   VARIANTS="_ SLS_BLOCK_MASKS=2" bash tools/ab_env.sh
 # ("_" = no switch).  Each command under its own timeout; REPS interleaved repetitions (default 2); prints Msplats/s,
 # ms per step and the kernels whose name contains $KERNELS (default: all).
 export TMPDIR=/tmp

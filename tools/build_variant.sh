@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of libsls_hip.so WITHOUT touching the tree's objects: tools/build_variant.sh <name> [make variables...]
-#   tools/build_variant.sh trace "FAST=--offload-arch=gfx950 -O3 -std=c++17 -fPIC -DSLS_TILE_W=16 -DSLS_TILE_H=16 -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -munsafe-fp-atomics -fno-slp-vectorize -DSLS_TRACE"
+#   tools/build_variant.sh fwd3 "FAST=--offload-arch=gfx950 -O3 -std=c++17 -fPIC -DSLS_TILE_W=16 -DSLS_TILE_H=16 -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -munsafe-fp-atomics -fno-slp-vectorize -DSLS_FWD_WAVES=3"
 # -> ./gpurun_tmp_<name>.so (travels to the GPU box with the snapshot; git ignores it).  EXTRA="-DFOO" is appended to
 # both flag sets through the COMMON variable when given as EXTRA=...
 set -e
