@@ -415,6 +415,48 @@ int sls_mapping_step(const SlsCamera *cam, int N,
                      void *workspace, size_t workspace_bytes,
                      SlsMappingStatus *status_dev, float **allmap_out, void *stream);
 
+/* ---- keyframe-batched mapping step: G keyframes, gradients summed, ONE Adam update ------------------------------
+ * sls_mapping_step_batch computes sum_g dL_g/dtheta over G distinct keyframes of the same H x W (each keyframe's pixel
+ * loss exactly as sls_mapping_step computes it) plus the scale regulariser ONCE, and applies one Adam update (adam_step:
+ * the batch's step number).  The keyframes' fronts (forward, loss, tile backward: the kernels of sls_mapping_step, G
+ * launches each) run one after another and share the workspace's scratch; each keeps only what the last launch reads
+ * (radii, gradient records, loss terms, block costs) in a part of its own.  ONE launch then reads the parameters once, chains every
+ * keyframe's gradient record through its camera, sums them in the order 0..G-1, adds the regulariser and applies Adam.
+ * If any keyframe's iteration is void (instance overflow, failed depth-order repair) the whole batch is void: no
+ * parameter and no moment changes.
+ *   cfg: shared by the keyframes; cfg->depth_order / block_order / det_prev / reuse_depth_order are not read (they are
+ *        per keyframe, below).  phase must be 0; grad_chunk, grad_bitmap and union_bitmap are not served.
+ *        apply_adam = 0 writes the summed gradient to the flat bucket `grads` and the batch's void flags to
+ *        cfg->void_flags_out (the keyframe-parallel all-reduce consumes both).  deterministic = 2 runs as 1 (two
+ *        launches per keyframe); det_prev, where given, is still rewritten (the fields' defaults that a one-launch
+ *        sls_mapping_step keeps in ITS workspace are not: a keyframe without history there predicts from them).
+ *        status_mirror receives status_dev[0].
+ *   status_dev: G + 1 blocks in DEVICE memory.  [0] the batch: OR of the keyframes' overflow bits, the largest R, the
+ *        loss sums added over the keyframes, the regulariser; [1 + g] keyframe g (its R, bits, loss sums; no regulariser).
+ *   SLS_E_ARG (sls_last_error says why), before anything is enqueued: G outside [1, SLS_MAX_BATCH], keyframes of
+ *        different H x W, a null per-keyframe pointer (block_order and det_prev are optional, block_order on all
+ *        keyframes or none), the same depth_order / block_order / det_prev buffer on two keyframes. */
+#define SLS_MAX_BATCH 8
+typedef struct SlsKeyframeInputs {
+    SlsCamera cam;
+    const float *gt_depth;        /* H x W */
+    const uint8_t *valid;         /* H x W */
+    int32_t n_valid;
+    int32_t reuse_depth_order;    /* as SlsMappingConfig.reuse_depth_order, for this keyframe's depth_order */
+    const float *col_cs, *row_cs;           /* sls_ray_tables */
+    const float *col_cs_half, *row_cs_half; /* the same at pixel offset 0.5 */
+    uint32_t *depth_order;        /* N uint32: the keyframe's depth order (as SlsMappingConfig.depth_order; required) */
+    uint32_t *block_order;        /* optional: sls_block_order_bytes(H, W) (as SlsMappingConfig.block_order) */
+    uint8_t *det_prev;            /* optional: 16 N bytes (as SlsMappingConfig.det_prev) */
+} SlsKeyframeInputs;
+/* One sls_mapping_workspace_bytes_cfg workspace + G - 1 per-keyframe parts (0 for G outside [1, SLS_MAX_BATCH]) */
+size_t sls_mapping_workspace_bytes_batch(int G, int N, int H, int W, uint64_t R_capacity, const SlsMappingConfig *cfg);
+int sls_mapping_step_batch(int G, const SlsKeyframeInputs *keyframes, int N,
+                           float *xyz, float *scaling_raw, float *rotation_raw, float *opacity_raw,
+                           float *grads, float *exp_avg, float *exp_avg_sq, int64_t adam_step,
+                           const SlsMappingConfig *cfg, uint64_t R_capacity, void *workspace, size_t workspace_bytes,
+                           SlsMappingStatus *status_dev, void *stream);
+
 /* ---- frame-to-keyframe registration on spherical range images -------
  * The job of the reference's `gsaligner` extension (slam/tracker.py:141-197: set_query /
  * set_reference / align(iguess) -> (T, fitness, _)).  That submodule is not vendored, so the

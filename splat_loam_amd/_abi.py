@@ -63,6 +63,17 @@ class SlsMappingStatus(C.Structure):
                 ("loss_reg", C.c_float), ("exchange_count", C.c_uint32)]
 
 
+class SlsKeyframeInputs(C.Structure):
+    _fields_ = [
+        ("cam", SlsCamera), ("gt_depth", C.c_void_p), ("valid", C.c_void_p), ("n_valid", C.c_int32),
+        ("reuse_depth_order", C.c_int32), ("col_cs", C.c_void_p), ("row_cs", C.c_void_p), ("col_cs_half", C.c_void_p),
+        ("row_cs_half", C.c_void_p), ("depth_order", C.c_void_p), ("block_order", C.c_void_p), ("det_prev", C.c_void_p),
+    ]
+
+
+SLS_MAX_BATCH = 8
+
+
 class SlsAdamGroup(C.Structure):
     _fields_ = [
         ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
@@ -101,6 +112,10 @@ _PROTOS = {
     "sls_mapping_step": (C.c_int, [C.POINTER(SlsCamera), C.c_int] + [_VP] * 7 + [C.c_int64, _VP, _VP, C.c_int] +
                          [_VP] * 4 + [C.POINTER(SlsMappingConfig), C.c_uint64, _VP, C.c_size_t, _VP,
                                       C.POINTER(C.c_void_p), _VP]),
+    "sls_mapping_workspace_bytes_batch": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                                       C.POINTER(SlsMappingConfig)]),
+    "sls_mapping_step_batch": (C.c_int, [C.c_int, C.POINTER(SlsKeyframeInputs), C.c_int] + [_VP] * 7 +
+                               [C.c_int64, C.POINTER(SlsMappingConfig), C.c_uint64, _VP, C.c_size_t, _VP, _VP]),
     "sls_backward": (C.c_int, [C.POINTER(SlsCamera), C.c_int, C.c_uint64] + [_VP] * 7 + [C.c_int] + [_VP] * 11 +
                      [C.c_int, _VP]),
     "sls_forward_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_uint64]),

@@ -391,6 +391,34 @@ struct AdamFuse {
     uint32_t compact_cap;
 };
 
+// One keyframe of a batched step (sls_mapping_step_batch): what the batched projection backward reads of it.
+struct BatchKeyframe {
+    DevCam cam;
+    const int32_t *radii;
+    float4 *grec;
+    uint8_t *touched;
+    uint32_t *status;                     // the keyframe's own status block (complete before the launch)
+    // deterministic accumulation, two-pass scheme only (det_prev optional: the predictions for the keyframe's later
+    // one-launch iterations; det_gex optional: the fields' defaults, raised where given)
+    const uint32_t *det_max;
+    long long *det_acc;
+    uint8_t *det_prev;
+    uint32_t *det_gex;
+    const float *loss_partials;           // the loss stage folded into the tile backward: as AdamFuse.loss_partials
+    float loss_w[3];
+    const uint32_t *order_cost;           // + the keyframe's next launch order (AdamFuse.order_*)
+    uint32_t *order_out;
+};
+
+// The batched projection backward's arguments: the keyframes, and the fields of AdamFuse it shares (Adam, the flat
+// bucket + void flags, the batch's status block = af.status_src, its mirror, the regulariser's accumulator)
+struct BatchFuse {
+    int G;
+    int n_loss_partials, order_T;
+    BatchKeyframe kf[SLS_MAX_BATCH];
+    AdamFuse af;
+};
+
 // Copy of an iteration's finished status block (8 words) into its pinned host mirror, by ONE lane.  The host polls
 // words 0 and 7 (engine.py: it arms them with a value the device never writes): words 0..6 are made visible at
 // system scope BEFORE word 7 is stored, so a host that sees word 7 sees the whole row.

@@ -27,6 +27,9 @@ int launch_preprocess_bwd(const DevCam &cam, int raw, float smax, float pen, int
                           const float *scales, const float *rots, const float *opac, const int32_t *radii,
                           const float *grec, float *dmeans, float *dscales, float *drots, float *dopac,
                           hipStream_t st, const AdamFuse *fuse = nullptr);
+int launch_preprocess_bwd_batch(float smax, float pen, int N, float *means, float *scales, float *rots, float *opac,
+                                float *dmeans, float *dscales, float *drots, float *dopac, const BatchFuse &bf,
+                                hipStream_t st);
 size_t sort_scratch_bytes(uint64_t cap);
 size_t order_scratch_bytes(int N);
 int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_t cap, const uint32_t *order,
@@ -133,6 +136,46 @@ static MapWs carve(int N, int H, int W, uint64_t cap, void *base, bool determini
     }
     w.total = off;
     return w;
+}
+
+// Workspace of sls_mapping_step_batch.  The keyframes' fronts run one after another on the stream, so everything a
+// front uses and leaves behind for nobody (instances, lists, sort scratch, pixel state, maps, dL/dallmap, block masks)
+// is SHARED: keyframe 0's slice is a whole workspace.  Each further keyframe gets only what the batched projection
+// backward reads after all fronts: radii, the loss stage's scratch (its per-block loss terms), the forward's block
+// costs, the zeroed group [reg_accum | det_gex | tile_consumed | touched | grec] and the fixed-point accumulators.
+// w[g] is keyframe g's view; the return value is the total size.
+static size_t carve_batch(int G, int N, int H, int W, uint64_t cap, void *base, bool deterministic, MapWs *w)
+{
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const MapWs w0 = carve(N, H, W, cap, base, deterministic);
+    const size_t n = (size_t)(N > 0 ? N : 1);
+    const int GX = (W + kTileW - 1) / kTileW, GY = (H + kTileH - 1) / kTileH;
+    const size_t T = (size_t)GX * GY;
+    size_t off = w0.total;
+    for (int g = 0; g < G; ++g) {
+        MapWs k = w0;
+        if (g > 0) {
+            char *p = (char *)base;
+            auto take = [&](size_t bytes) { void *r = (void *)(p + off); off += al(bytes); return r; };
+            k.radii = (int32_t *)take(n * 4);
+            k.consumer_scratch = take(k.consumer_scratch_bytes);
+            k.block_cost = (uint32_t *)take(T * (kTilePix / 16) * 4);
+            k.reg_accum = (float *)take(4);
+            k.det_gex = (uint32_t *)take(16 * 4);
+            k.tile_consumed = (uint32_t *)take(T * 4);
+            k.touched = (uint8_t *)take(n);
+            k.grec = (float *)take(n * SLS_GREC_STRIDE * 4);
+            k.zero_bytes = (size_t)((char *)k.grec - (char *)k.reg_accum) + n * SLS_GREC_STRIDE * 4;
+            if (deterministic) {
+                k.det_max = (uint32_t *)take(n * SLS_GREC_STRIDE * 4);
+                k.det_acc = (unsigned long long *)take(n * SLS_GREC_STRIDE * 8);
+                k.det_bytes = (size_t)((char *)k.det_acc - (char *)k.det_max) + n * SLS_GREC_STRIDE * 8;
+            }
+        }
+        k.total = 0;
+        if (w) w[g] = k;
+    }
+    return off;
 }
 
 }  // namespace sls
@@ -428,6 +471,115 @@ int sls_backward_ws(const SlsCamera *cam, int N, const float *means3D, const flo
                                  dL_dscales, dL_drotations, dL_dopacities, st, &fuse);
 }
 
+// The front of an iteration (forward, loss, tile backward) on ONE keyframe, into ONE workspace slice: sls_mapping_step
+// and, per keyframe, sls_mapping_step_batch
+static int mapping_front(const SlsCamera *cam, int N, const float *xyz, const float *scaling_raw, const float *rotation_raw,
+                         const float *opacity_raw, const float *gt_depth, const uint8_t *valid, int n_valid,
+                         const float *col_cs, const float *row_cs, const float *col_cs_half, const float *row_cs_half,
+                         const SlsMappingConfig *cfg, uint32_t cap, const MapWs &w, SlsMappingStatus *status_dev,
+                         hipStream_t st)
+{
+    const int H = cam->H, W = cam->W;
+    const DevCam dc = make_devcam(*cam);
+    uint8_t *touched = w.touched;
+    const bool det = cfg->deterministic != 0;
+    const bool det_one = cfg->deterministic == 2 && cfg->det_prev != nullptr;
+    const bool fuse_c = cfg->depth_ratio == 0.0f;
+    const bool fuse_b = fuse_c && cfg->block_order != nullptr;
+    const bool order_bwd = (dc.GX * dc.GY) % 32 == 0 && kTileW == 16 && kTileH == 16;
+    // (the status block is zeroed by thread 0 of preprocess_fwd, the iteration's first kernel)
+    if (!cfg->workspace_ready) {
+        // first use of this workspace: the gradient records must start from zero; afterwards the backward
+        // of the projection leaves them zeroed behind itself (no 64*N-byte memset per iteration)
+        ScopedTimer tm(T_GREC_MEMSET, st);
+        SLS_HIP_CHECK(hipMemsetAsync(w.reg_accum, 0, w.zero_bytes, st));
+    }
+
+    // ---- forward ---------------------------------------------------------------
+    uint32_t *okeys, *ovals, *n_dev;
+    // the depth order lives in the workspace, or in a caller-owned buffer (one per keyframe, so that every
+    // keyframe of a window can repair ITS order when the mapper samples keyframes at random)
+    uint32_t *order = cfg->depth_order ? cfg->depth_order : w.order;
+    depth_order_key_buffers(N, w.order_scratch, order, &okeys, &ovals, &n_dev);
+    // Repairing the previous order: its first step (sorting windows of the old order by the new keys) rides in the
+    // preprocess launch — it needs nothing the preprocess produces
+    const bool merged_sort = cfg->reuse_depth_order >= 1;
+    // Direct binning (sls_sort.hip) where it applies: no unsorted instance array, no scan of tiles_touched; the preprocess
+    // then leaves the emission records in the form its first kernel gathers (rectangle + block box)
+    const bool direct = bin_direct_possible(dc, N, cap);
+    // (the staged API scans the count table's rows with a launch of its own instead)
+    DirectBin db;
+    if (direct) db = make_direct_bin(dc, N, w.sort_scratch, (uint2 *)w.serec, cfg->reuse_depth_order >= 1, true);
+    // (the direct binning reads the emission records only — not the rectangles, the tile counts, the depths or the
+    //  block boxes as arrays of their own; a repair whose window sort rides in the preprocess launch computes its
+    //  keys itself: 32 bytes per surfel that are not written)
+    const bool trim = direct;
+    int rc = launch_preprocess_fwd(dc, 1, cfg->scaling_max, cfg->scaling_max_penalty, w.reg_accum, N, xyz,
+                                   scaling_raw, rotation_raw, opacity_raw, w.rec, w.radii, trim ? nullptr : w.rect,
+                                   trim ? nullptr : w.tiles, trim ? nullptr : w.depth,
+                                   (trim && merged_sort) ? nullptr : okeys, ovals, n_dev, st,
+                                   (uint32_t *)status_dev, col_cs, row_cs, w.tmask, w.erec,
+                                   merged_sort ? order : nullptr,
+                                   merged_sort ? resort_comp_buffer(N, w.order_scratch) : nullptr, trim ? nullptr : w.sbox, direct ? 1 : 0,
+                                   (direct && db.coarse) ? db.coarse : nullptr,
+                                   (direct && db.coarse) ? (int)direct_coarse_words(dc, N) : 0);
+    if (rc) return rc;
+    ScanHandoff handoff = { nullptr, 0, nullptr, 0 };   // the binning finishes (or does not need) the scan of tiles_touched
+    rc = launch_depth_order_scan(N, w.depth, w.tiles, order, w.offsets, &status_dev->R, w.order_scratch,
+                                 w.order_scratch_bytes, 1, st, cfg->reuse_depth_order, &status_dev->overflow, &handoff,
+                                 merged_sort, direct ? &db : nullptr, (const int4 *)w.erec, dc.GX);
+    if (rc) return rc;
+    int in_tmp = 0;
+    const uint2 *bmask = nullptr;
+    if (direct) {
+        rc = launch_bin_direct(dc, N, cap, db, handoff.counted != 0, order, w.erec, nullptr, nullptr, w.sort_scratch, w.vals,
+                               w.ranges, &status_dev->R, &status_dev->overflow, handoff.resort_windows,
+                               handoff.resort_edges, &bmask, cfg->block_masks, st);
+    } else {
+        rc = launch_bin_sort(dc, N, &status_dev->R, cap, order, w.rect, w.tiles, dc.tile_cull ? w.tmask : nullptr,
+                             (dc.GX < 65536 && dc.GY < 65536) ? w.erec : nullptr, w.depth,
+                             w.offsets, w.tkeys, w.vals,
+                             w.tkeys_tmp, w.vals_tmp, w.sort_scratch, w.sort_scratch_bytes, &in_tmp, w.ranges, nullptr,
+                             &status_dev->overflow, st, &handoff, &status_dev->R,
+                             w.sbox, &bmask, cfg->block_masks);
+    }
+    if (rc) return rc;
+    // (with the pairs the plain value arrays are not written: the list IS the pairs, two words apart)
+    const uint32_t *sorted_vals = bmask ? (const uint32_t *)bmask : (in_tmp ? w.vals_tmp : w.vals);
+    const int vals_stride = bmask ? 2 : 1;
+    rc = launch_render_fwd(dc, w.ranges, sorted_vals, w.rec, col_cs, row_cs, w.allmap, w.pix_state, w.pix_contrib,
+                           nullptr, st, true, w.block_masks,    // (nobody reads the consumed counters here)
+                           cfg->depth_ratio == 0.0f,            // (nor, then, the median / distortion planes: not tracked)
+                           w.block_cost, bmask);
+    if (rc) return rc;
+    // ---- loss + dL/dallmap --------------------------------------------------------
+    // With the keyframe's own launch-order buffer kernel B is folded in as well (fuse_b, above): the loss stage has no
+    // launch; the order the backward walks is the one the keyframe's previous iteration left.
+    ConsumerArgs cargs;
+    rc = launch_consumer(H, W, w.allmap, gt_depth, valid, col_cs_half, row_cs_half, cfg->depth_ratio,
+                         cfg->lambda_normal, cfg->lambda_alpha, n_valid, status_dev->loss_sums, w.dL_dallmap,
+                         w.consumer_scratch, w.consumer_scratch_bytes, st, true, fuse_c ? &cargs : nullptr,
+                         order_bwd ? dc.GX * dc.GY : 0, w.block_cost, w.block_order, fuse_b);
+    if (rc) return rc;
+    // ---- backward -----------------------------------------------------------------
+    // (two launches: both accumulators start from zero; one launch: det_acc is left zeroed by every deterministic
+    //  iteration's preprocess_bwd where it was written — and the first deterministic iteration on a workspace is a
+    //  two-launch one, which also sets the fields' default scales)
+    if (det && !det_one) SLS_HIP_CHECK(hipMemsetAsync(w.det_max, 0, w.det_bytes, st));
+    const uint32_t *block_order = order_bwd ? (fuse_b ? cfg->block_order : w.block_order) : nullptr;
+    rc = launch_render_bwd(dc, w.ranges, sorted_vals, w.rec, col_cs, row_cs, w.pix_state, w.pix_contrib, w.dL_dallmap,
+                           w.grec, st, w.block_masks, cfg->depth_ratio == 0.0f, touched,    // the consumer's dL/d(median, distortion) are 0 then
+                           fuse_c ? &cargs : nullptr, (det && !det_one) ? w.det_max : nullptr, det ? w.det_acc : nullptr, block_order,
+                           vals_stride, 3, false,
+                           det_one ? cfg->det_prev : nullptr, w.det_gex, &status_dev->overflow, fuse_b,
+                           (fuse_b && order_bwd) ? block_order_tag(dc.GX * dc.GY) : 0u);
+    if (rc) return rc;
+    if (cfg->phase == 1 && cfg->grad_bitmap)      // the bitmap EARLY: an all-gather of it can overlap phase 2
+        return launch_touched_bitmap(N, touched, scaling_raw, cfg->scaling_max, cfg->scaling_max_penalty,
+                                     (const uint32_t *)status_dev, cfg->grad_bitmap, st);
+    return SLS_OK;
+}
+
 size_t sls_mapping_workspace_bytes(int N, int H, int W, uint64_t R_capacity)
 {
     if (N < 0 || H <= 0 || W <= 0) return 0;
@@ -500,102 +652,10 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
     // passenger workgroups — of the consumer's launch, or with fuse_b of the previous iteration's last launch): 8x2
     // kernels, XCD-interleaved tile mapping (T % 32 == 0)
     const bool order_bwd = (dc.GX * dc.GY) % 32 == 0 && kTileW == 16 && kTileH == 16;
-    // cfg->phase: 0 = the whole iteration; 1 = up to the tile backward (+ the early gradient bitmap); 2 = the rest
-    auto front = [&]() -> int {
-        // (the status block is zeroed by thread 0 of preprocess_fwd, the iteration's first kernel)
-        if (!cfg->workspace_ready) {
-            // first use of this workspace: the gradient records must start from zero; afterwards the backward
-            // of the projection leaves them zeroed behind itself (no 64*N-byte memset per iteration)
-            ScopedTimer tm(T_GREC_MEMSET, st);
-            SLS_HIP_CHECK(hipMemsetAsync(w.reg_accum, 0, w.zero_bytes, st));
-        }
-
-        // ---- forward ---------------------------------------------------------------
-        uint32_t *okeys, *ovals, *n_dev;
-        // the depth order lives in the workspace, or in a caller-owned buffer (one per keyframe, so that every
-        // keyframe of a window can repair ITS order when the mapper samples keyframes at random)
-        uint32_t *order = cfg->depth_order ? cfg->depth_order : w.order;
-        depth_order_key_buffers(N, w.order_scratch, order, &okeys, &ovals, &n_dev);
-        // Repairing the previous order: its first step (sorting windows of the old order by the new keys) rides in the
-        // preprocess launch — it needs nothing the preprocess produces
-        const bool merged_sort = cfg->reuse_depth_order >= 1;
-        // Direct binning (sls_sort.hip) where it applies: no unsorted instance array, no scan of tiles_touched; the preprocess
-        // then leaves the emission records in the form its first kernel gathers (rectangle + block box)
-        const bool direct = bin_direct_possible(dc, N, cap);
-        // (the staged API scans the count table's rows with a launch of its own instead)
-        DirectBin db;
-        if (direct) db = make_direct_bin(dc, N, w.sort_scratch, (uint2 *)w.serec, cfg->reuse_depth_order >= 1, true);
-        // (the direct binning reads the emission records only — not the rectangles, the tile counts, the depths or the
-        //  block boxes as arrays of their own; a repair whose window sort rides in the preprocess launch computes its
-        //  keys itself: 32 bytes per surfel that are not written)
-        const bool trim = direct;
-        int rc = launch_preprocess_fwd(dc, 1, cfg->scaling_max, cfg->scaling_max_penalty, w.reg_accum, N, xyz,
-                                       scaling_raw, rotation_raw, opacity_raw, w.rec, w.radii, trim ? nullptr : w.rect,
-                                       trim ? nullptr : w.tiles, trim ? nullptr : w.depth,
-                                       (trim && merged_sort) ? nullptr : okeys, ovals, n_dev, st,
-                                       (uint32_t *)status_dev, col_cs, row_cs, w.tmask, w.erec,
-                                       merged_sort ? order : nullptr,
-                                       merged_sort ? resort_comp_buffer(N, w.order_scratch) : nullptr, trim ? nullptr : w.sbox, direct ? 1 : 0,
-                                       (direct && db.coarse) ? db.coarse : nullptr,
-                                       (direct && db.coarse) ? (int)direct_coarse_words(dc, N) : 0);
-        if (rc) return rc;
-        ScanHandoff handoff = { nullptr, 0, nullptr, 0 };   // the binning finishes (or does not need) the scan of tiles_touched
-        rc = launch_depth_order_scan(N, w.depth, w.tiles, order, w.offsets, &status_dev->R, w.order_scratch,
-                                     w.order_scratch_bytes, 1, st, cfg->reuse_depth_order, &status_dev->overflow, &handoff,
-                                     merged_sort, direct ? &db : nullptr, (const int4 *)w.erec, dc.GX);
-        if (rc) return rc;
-        int in_tmp = 0;
-        const uint2 *bmask = nullptr;
-        if (direct) {
-            rc = launch_bin_direct(dc, N, cap, db, handoff.counted != 0, order, w.erec, nullptr, nullptr, w.sort_scratch, w.vals,
-                                   w.ranges, &status_dev->R, &status_dev->overflow, handoff.resort_windows,
-                                   handoff.resort_edges, &bmask, cfg->block_masks, st);
-        } else {
-            rc = launch_bin_sort(dc, N, &status_dev->R, cap, order, w.rect, w.tiles, dc.tile_cull ? w.tmask : nullptr,
-                                 (dc.GX < 65536 && dc.GY < 65536) ? w.erec : nullptr, w.depth,
-                                 w.offsets, w.tkeys, w.vals,
-                                 w.tkeys_tmp, w.vals_tmp, w.sort_scratch, w.sort_scratch_bytes, &in_tmp, w.ranges, nullptr,
-                                 &status_dev->overflow, st, &handoff, &status_dev->R,
-                                 w.sbox, &bmask, cfg->block_masks);
-        }
-        if (rc) return rc;
-        // (with the pairs the plain value arrays are not written: the list IS the pairs, two words apart)
-        const uint32_t *sorted_vals = bmask ? (const uint32_t *)bmask : (in_tmp ? w.vals_tmp : w.vals);
-        const int vals_stride = bmask ? 2 : 1;
-        rc = launch_render_fwd(dc, w.ranges, sorted_vals, w.rec, col_cs, row_cs, w.allmap, w.pix_state, w.pix_contrib,
-                               nullptr, st, true, w.block_masks,    // (nobody reads the consumed counters here)
-                               cfg->depth_ratio == 0.0f,            // (nor, then, the median / distortion planes: not tracked)
-                               w.block_cost, bmask);
-        if (rc) return rc;
-        // ---- loss + dL/dallmap --------------------------------------------------------
-        // With the keyframe's own launch-order buffer kernel B is folded in as well (fuse_b, above): the loss stage has no
-        // launch; the order the backward walks is the one the keyframe's previous iteration left.
-        ConsumerArgs cargs;
-        rc = launch_consumer(H, W, w.allmap, gt_depth, valid, col_cs_half, row_cs_half, cfg->depth_ratio,
-                             cfg->lambda_normal, cfg->lambda_alpha, n_valid, status_dev->loss_sums, w.dL_dallmap,
-                             w.consumer_scratch, w.consumer_scratch_bytes, st, true, fuse_c ? &cargs : nullptr,
-                             order_bwd ? dc.GX * dc.GY : 0, w.block_cost, w.block_order, fuse_b);
-        if (rc) return rc;
-        // ---- backward -----------------------------------------------------------------
-        // (two launches: both accumulators start from zero; one launch: det_acc is left zeroed by every deterministic
-        //  iteration's preprocess_bwd where it was written — and the first deterministic iteration on a workspace is a
-        //  two-launch one, which also sets the fields' default scales)
-        if (det && !det_one) SLS_HIP_CHECK(hipMemsetAsync(w.det_max, 0, w.det_bytes, st));
-        const uint32_t *block_order = order_bwd ? (fuse_b ? cfg->block_order : w.block_order) : nullptr;
-        rc = launch_render_bwd(dc, w.ranges, sorted_vals, w.rec, col_cs, row_cs, w.pix_state, w.pix_contrib, w.dL_dallmap,
-                               w.grec, st, w.block_masks, cfg->depth_ratio == 0.0f, touched,    // the consumer's dL/d(median, distortion) are 0 then
-                               fuse_c ? &cargs : nullptr, (det && !det_one) ? w.det_max : nullptr, det ? w.det_acc : nullptr, block_order,
-                               vals_stride, 3, false,
-                               det_one ? cfg->det_prev : nullptr, w.det_gex, &status_dev->overflow, fuse_b,
-                               (fuse_b && order_bwd) ? block_order_tag(dc.GX * dc.GY) : 0u);
-        if (rc) return rc;
-        if (cfg->phase == 1 && cfg->grad_bitmap)      // the bitmap EARLY: an all-gather of it can overlap phase 2
-            return launch_touched_bitmap(N, touched, scaling_raw, cfg->scaling_max, cfg->scaling_max_penalty,
-                                         (const uint32_t *)status_dev, cfg->grad_bitmap, st);
-        return SLS_OK;
-    };
     int rc = SLS_OK;
-    if (cfg->phase != 2) rc = front();
+    if (cfg->phase != 2)
+        rc = mapping_front(cam, N, xyz, scaling_raw, rotation_raw, opacity_raw, gt_depth, valid, n_valid, col_cs, row_cs,
+                           col_cs_half, row_cs_half, cfg, cap, w, status_dev, st);
     if (rc || cfg->phase == 1) return rc;
     // flat gradient bucket: [xyz 3N | opacity N | scaling 2N | rotation 4N] (optimizer group order)
     float *g_xyz = grads, *g_op = grads + (size_t)3 * N, *g_sc = grads + (size_t)4 * N, *g_rot = grads + (size_t)6 * N;
@@ -655,6 +715,138 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
                                opacity_raw, w.radii, w.grec, g_xyz, g_sc, g_rot, g_op, st, &fuse);
     if (rc) return rc;
     if (cfg->apply_adam && !fuse.enabled) {
+        SlsAdamGroup grp[4];
+        memset(grp, 0, sizeof(grp));
+        float *params[4] = { xyz, opacity_raw, scaling_raw, rotation_raw };
+        const size_t offs[4] = { 0, (size_t)3 * N, (size_t)4 * N, (size_t)6 * N };
+        const int64_t numel[4] = { (int64_t)3 * N, (int64_t)N, (int64_t)2 * N, (int64_t)4 * N };
+        const float lrs[4] = { cfg->lr_xyz, cfg->lr_opacity, cfg->lr_scaling, cfg->lr_rotation };
+        for (int k = 0; k < 4; ++k) {
+            grp[k].param = params[k];
+            grp[k].grad = grads + offs[k];
+            grp[k].exp_avg = exp_avg + offs[k];
+            grp[k].exp_avg_sq = exp_avg_sq + offs[k];
+            grp[k].numel = numel[k];
+            grp[k].lr = lrs[k];
+        }
+        rc = launch_adam(grp, 4, cfg->beta1, cfg->beta2, cfg->eps, adam_step, &status_dev->overflow, st);
+        if (rc) return rc;
+    }
+    return SLS_OK;
+}
+
+
+// ---- keyframe-batched step -----------------------------------------------------------------------------------------
+size_t sls_mapping_workspace_bytes_batch(int G, int N, int H, int W, uint64_t R_capacity, const SlsMappingConfig *cfg)
+{
+    if (G < 1 || G > SLS_MAX_BATCH || N < 0 || H <= 0 || W <= 0) return 0;
+    return carve_batch(G, N, H, W, R_capacity, nullptr, !cfg || cfg->deterministic != 0, nullptr);
+}
+
+int sls_mapping_step_batch(int G, const SlsKeyframeInputs *kfs, int N, float *xyz, float *scaling_raw, float *rotation_raw,
+                           float *opacity_raw, float *grads, float *exp_avg, float *exp_avg_sq, int64_t adam_step,
+                           const SlsMappingConfig *cfg, uint64_t R_capacity, void *workspace, size_t workspace_bytes,
+                           SlsMappingStatus *status_dev, void *stream)
+{
+    // (every argument check before the first launch, as in sls_mapping_step)
+    SLS_REQUIRE(G >= 1 && G <= SLS_MAX_BATCH, "G: 1 to SLS_MAX_BATCH keyframes");
+    SLS_REQUIRE(kfs && cfg && status_dev && workspace, "null pointer");
+    SLS_REQUIRE(N > 0, "N must be positive");
+    SLS_REQUIRE(xyz && scaling_raw && rotation_raw && opacity_raw && grads, "null pointer");
+    SLS_REQUIRE(!cfg->apply_adam || (exp_avg && exp_avg_sq && adam_step >= 1), "Adam state missing");
+    SLS_REQUIRE(R_capacity > 0 && R_capacity < (1ull << 32), "bad instance capacity");
+    SLS_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    SLS_REQUIRE(cfg->phase == 0 && !cfg->grad_chunk && !cfg->grad_bitmap && !cfg->union_bitmap,
+                "a batch is one whole step on the flat bucket: phase 0, no grad_chunk, grad_bitmap or union_bitmap");
+    SLS_REQUIRE(cfg->deterministic >= 0 && cfg->deterministic <= 2, "deterministic: 0 off, 1 two launches, 2 one launch with predicted scales");
+    const int H = kfs[0].cam.H, W = kfs[0].cam.W;
+    SLS_REQUIRE(H > 0 && W > 0, "bad image size");
+    for (int g = 0; g < G; ++g) {
+        const SlsKeyframeInputs &k = kfs[g];
+        SLS_REQUIRE(k.cam.H == H && k.cam.W == W, "the keyframes of a batch share one image size");
+        SLS_REQUIRE(k.gt_depth && k.valid && k.col_cs && k.row_cs && k.col_cs_half && k.row_cs_half && k.depth_order,
+                    "null per-keyframe pointer");
+        SLS_REQUIRE((k.block_order != nullptr) == (kfs[0].block_order != nullptr), "block_order on every keyframe or on none");
+        SLS_REQUIRE(k.reuse_depth_order >= 0 && k.reuse_depth_order <= 4, "reuse_depth_order: 0 from scratch, 1..4 repair rounds");
+        for (int h = 0; h < g; ++h) {
+            SLS_REQUIRE(kfs[h].depth_order != k.depth_order, "two keyframes share one depth_order buffer");
+            SLS_REQUIRE(!k.block_order || kfs[h].block_order != k.block_order, "two keyframes share one block_order buffer");
+            SLS_REQUIRE(!k.det_prev || kfs[h].det_prev != k.det_prev, "two keyframes share one det_prev buffer");
+        }
+    }
+    const bool det = cfg->deterministic != 0;
+    MapWs ws[SLS_MAX_BATCH];
+    const size_t need = carve_batch(G, N, H, W, R_capacity, workspace, det, ws);
+    const MapWs &w0 = ws[0];
+    if (workspace_bytes < need) {
+        set_error("batch workspace too small: %zu < %zu", workspace_bytes, need);
+        return SLS_E_SCRATCH;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t cap = (uint32_t)R_capacity;
+    const DevCam dc0 = make_devcam(kfs[0].cam);
+    const int T = dc0.GX * dc0.GY;
+    const bool fuse_b = cfg->depth_ratio == 0.0f && kfs[0].block_order != nullptr;
+    const bool order_bwd = T % 32 == 0 && kTileW == 16 && kTileH == 16;
+    BatchFuse bf;
+    memset(&bf, 0, sizeof(bf));
+    bf.G = G;
+    // ---- every keyframe's front (forward, loss, tile backward) into its own workspace slice ----------------------------
+    for (int g = 0; g < G; ++g) {
+        const SlsKeyframeInputs &k = kfs[g];
+        const MapWs &w = ws[g];
+        SlsMappingConfig kc = *cfg;
+        kc.reuse_depth_order = k.reuse_depth_order;
+        kc.depth_order = k.depth_order;
+        kc.block_order = k.block_order;
+        kc.det_prev = k.det_prev;
+        kc.deterministic = det ? 1 : 0;          // (the one-launch scheme runs as the two-launch one in a batch)
+        if (g > 0) kc.scaling_max_penalty = 0.0f;  // the regulariser once: summed by keyframe 0's preprocess
+        int rc = mapping_front(&k.cam, N, xyz, scaling_raw, rotation_raw, opacity_raw, k.gt_depth, k.valid, k.n_valid,
+                               k.col_cs, k.row_cs, k.col_cs_half, k.row_cs_half, &kc, cap, w, status_dev + 1 + g, st);
+        if (rc) return rc;
+        BatchKeyframe &b = bf.kf[g];
+        b.cam = make_devcam(k.cam);
+        b.radii = w.radii;
+        b.grec = (float4 *)w.grec;
+        b.touched = w.touched;
+        b.status = (uint32_t *)(status_dev + 1 + g);
+        if (det) {
+            b.det_max = w.det_max; b.det_acc = (long long *)w.det_acc;
+            b.det_prev = k.det_prev;     // (det_gex stays null: no launch reads a batch slice's defaults)
+        }
+        if (fuse_b) {
+            b.loss_partials = (const float *)w.consumer_scratch;
+            b.loss_w[0] = 1.0f / ((float)H * (float)W);
+            b.loss_w[1] = k.n_valid > 0 ? cfg->lambda_normal * (1.0f / (float)k.n_valid) : 0.0f;
+            b.loss_w[2] = k.n_valid > 0 ? cfg->lambda_alpha * (1.0f / (float)k.n_valid) : 0.0f;
+            if (order_bwd) { b.order_cost = w.block_cost; b.order_out = k.block_order; }
+        }
+    }
+    if (fuse_b) {
+        bf.n_loss_partials = T * (kTilePix / 16);
+        if (order_bwd) bf.order_T = T;
+    }
+    // ---- ONE backward of the projection over the batch + Adam -----------------------------------------------------------
+    AdamFuse &af = bf.af;
+    af.status_src = (uint32_t *)status_dev;
+    af.reg_accum = w0.reg_accum;
+    af.status_mirror = (uint32_t *)cfg->status_mirror;
+    af.void_flags = cfg->void_flags_out;
+    const bool aligned = (N % 2 == 0) && ((((uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0);
+    if (cfg->apply_adam && aligned) {
+        af.enabled = 1;
+        af.write_grads = cfg->keep_grads;
+        af.c = make_adam_coef(cfg->beta1, cfg->beta2, cfg->eps, adam_step);
+        af.lr_xyz = cfg->lr_xyz; af.lr_opacity = cfg->lr_opacity;
+        af.lr_scaling = cfg->lr_scaling; af.lr_rotation = cfg->lr_rotation;
+        af.exp_avg = exp_avg; af.exp_avg_sq = exp_avg_sq;
+    }
+    float *g_xyz = grads, *g_op = grads + (size_t)3 * N, *g_sc = grads + (size_t)4 * N, *g_rot = grads + (size_t)6 * N;
+    int rc = launch_preprocess_bwd_batch(cfg->scaling_max, cfg->scaling_max_penalty, N, xyz, scaling_raw, rotation_raw,
+                                         opacity_raw, g_xyz, g_sc, g_rot, g_op, bf, st);
+    if (rc) return rc;
+    if (cfg->apply_adam && !af.enabled) {      // (odd N or unaligned moments: the separate optimiser kernel, as sls_mapping_step)
         SlsAdamGroup grp[4];
         memset(grp, 0, sizeof(grp));
         float *params[4] = { xyz, opacity_raw, scaling_raw, rotation_raw };

@@ -476,6 +476,63 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // ---------------------------------------------------------------------------
 // A8 preprocess backward: gradient record (sls_spec.h) -> input gradients.
 // ---------------------------------------------------------------------------
+// The chain of one gradient record (g0..g3) through one camera: dL/d(mean, activated scale before the modifier's
+// product, opacity, normalised rotation), for the batched kernel below: the arithmetic of preprocess_bwd_kernel,
+// which keeps its own copy inline (as a shared function the compiler allocates that kernel's registers
+// differently, and its code is to stay as it is)
+__device__ __forceinline__ void chain_grad_record(const DevCam &cam, const SurfelGeom &g, const float4 q, const float4 g0,
+                                                  const float4 g1, const float4 g2, const float4 g3, float *dm, float2 &ds,
+                                                  float &dop, float4 &dq)
+{
+    const float gHu[3] = { g0.x, g0.y, g0.z }, gHv[3] = { g1.x, g1.y, g1.z }, gn[3] = { g2.x, g2.y, g2.z };
+    const float gnpv = g0.w, grhoc = g1.w, go = g2.w, Su = g3.x, Sv = g3.y, gcpx = g3.z, gcpy = g3.w;
+    float dc[3];
+    const float irho = frcp(g.rho), isu = frcp(g.su), isv = frcp(g.sv);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dc[k] = g.p[k] * irho;
+    float dp[3], dA[3], dB[3], t1[3], t2[3];
+    cross3(g.p, gHu, dA); cross3(gHu, g.A, t1);
+    cross3(g.p, gHv, dB); cross3(gHv, g.B, t2);
+    float dTu[3], dTv[3], dTn[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        dp[k] = t1[k] + t2[k];
+        dTv[k] = g.sig * dA[k] * isu;
+        dTu[k] = -g.sig * dB[k] * isv;
+    }
+    const float dsu = -dot3(dA, g.A) * isu, dsv = -dot3(dB, g.B) * isv;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        dTn[k] = g.sig * (gn[k] + gnpv * g.p[k]);
+        dp[k] += gnpv * g.n[k];
+        dp[k] += grhoc * dc[k];
+    }
+    float gdc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gdc[k] = -(Su * g.Hu[k] + Sv * g.Hv[k]);
+    const float gd = dot3(gdc, dc);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dp[k] += (gdc[k] - gd * dc[k]) * irho;
+    if (g.rxy2 > 1e-30f) {
+        const float gaz = gcpx * cam.fx, gel = gcpy * cam.fy;
+        const float irxy2 = frcp(g.rxy2), irr = frcp(g.rxy * g.rho2), irho2 = irho * irho;
+        dp[0] += gaz * (-g.p[1] * irxy2) + gel * (-g.p[2] * g.p[0] * irr);
+        dp[1] += gaz * (g.p[0] * irxy2) + gel * (-g.p[2] * g.p[1] * irr);
+        dp[2] += gel * (g.rxy * irho2);
+    }
+    matTvec(cam.R, dp, dm);
+    ds = make_float2(cam.mod * dsu, cam.mod * dsv);
+    dop = go;
+    float G0[3], G1[3], G2[3];
+    matTvec(cam.R, dTu, G0); matTvec(cam.R, dTv, G1); matTvec(cam.R, dTn, G2);
+    const float r = q.x, x = q.y, y = q.z, z = q.w;
+    // G[i][j] = dL/dR_ij, column j in {tu, tv, tn}: Gj[i]
+    dq.x = 2.0f * (-z * G1[0] + y * G2[0] + z * G0[1] - x * G2[1] - y * G0[2] + x * G1[2]);
+    dq.y = 2.0f * (y * G1[0] + z * G2[0] + y * G0[1] - 2.0f * x * G1[1] - r * G2[1] + z * G0[2] + r * G1[2] - 2.0f * x * G2[2]);
+    dq.z = 2.0f * (-2.0f * y * G0[0] + x * G1[0] + r * G2[0] + x * G0[1] + z * G2[1] - r * G0[2] + z * G1[2] - 2.0f * y * G2[2]);
+    dq.w = 2.0f * (-2.0f * z * G0[0] - r * G1[0] + x * G2[0] + r * G0[1] - 2.0f * z * G1[1] + y * G2[1] + x * G0[2] + y * G1[2]);
+}
+
 // With ra.raw the inputs are raw parameters, the activations are re-applied here
 // and the outputs are gradients w.r.t. the RAW parameters (exp / sigmoid /
 // normalize backward + the scale regulariser's gradient), opacity needed too.
@@ -763,6 +820,212 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
     }
 }
 
+// The same for a BATCH of keyframes (sls_mapping_step_batch): one thread per surfel reads its parameters once, chains
+// the gradient record of every keyframe that reached it through THAT keyframe's camera, sums the results in the order
+// 0..G-1, then adds the regulariser and applies the activations' backward and Adam once.  The batch is void if any
+// keyframe's iteration is (every keyframe's status block is complete before this launch: each thread ORs them itself).
+// Deterministic accumulation: the two-pass scheme only (the one-launch scheme runs as it in a batch).
+// Passenger workgroups first, as above: the publisher (per-keyframe loss sums, the batch's status block, its mirror,
+// the void flags), then 8 per keyframe for each keyframe's next tile-backward launch order.
+__global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, BatchFuse bf, int N, float *means, float2 *scales,
+                                                                   float4 *rots, float *opac, float *__restrict__ dmeans,
+                                                                   float2 *__restrict__ dscales, float4 *__restrict__ drots,
+                                                                   float *__restrict__ dopac)
+{
+    const AdamFuse &af = bf.af;
+    const int n_ord = bf.order_T > 0 ? 8 * bf.G : 0;
+    if (blockIdx.x == 0) {
+        __shared__ float s_loss[SLS_MAX_BATCH][3][4];
+        if (bf.n_loss_partials > 0) {
+            const int n4 = bf.n_loss_partials / 4;
+#pragma unroll
+            for (int g = 0; g < SLS_MAX_BATCH; ++g) {
+                if (g >= bf.G) break;
+                float t[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float4 *src = reinterpret_cast<const float4 *>(bf.kf[g].loss_partials + (size_t)k * bf.n_loss_partials);
+#pragma unroll 8
+                    for (int b = threadIdx.x; b < n4; b += 256) {
+                        const float4 v = src[b];
+                        t[k] += (v.x + v.y) + (v.z + v.w);
+                    }
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                    t[0] += __shfl_down(t[0], off, 64); t[1] += __shfl_down(t[1], off, 64); t[2] += __shfl_down(t[2], off, 64);
+                }
+                if ((threadIdx.x & 63) == 0) {
+                    s_loss[g][0][threadIdx.x >> 6] = t[0]; s_loss[g][1][threadIdx.x >> 6] = t[1]; s_loss[g][2][threadIdx.x >> 6] = t[2];
+                }
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            uint32_t R = 0u, bits = 0u;
+            float sums[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+#pragma unroll
+            for (int g = 0; g < SLS_MAX_BATCH; ++g) {
+                if (g >= bf.G) break;
+                uint32_t *st = bf.kf[g].status;
+                if (bf.n_loss_partials > 0) {      // (as the one-keyframe publisher: the same sums in the same order)
+                    float r[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) r[k] = (s_loss[g][k][0] + s_loss[g][k][1]) + (s_loss[g][k][2] + s_loss[g][k][3]);
+                    const float* w = bf.kf[g].loss_w;
+                    st[2] = __float_as_uint(r[0]); st[3] = __float_as_uint(r[1]); st[4] = __float_as_uint(r[2]);
+                    st[5] = __float_as_uint(r[0] * w[0] + w[1] * r[1] + w[2] * r[2]);
+                }
+                R = max(R, st[0]);
+                bits |= st[1];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sums[k] = g == 0 ? __uint_as_float(st[2 + k]) : sums[k] + __uint_as_float(st[2 + k]);
+            }
+            uint32_t *out = af.status_src;
+            out[0] = R; out[1] = bits;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) out[2 + k] = __float_as_uint(sums[k]);
+            out[6] = 0u;
+            if (af.reg_accum) {
+                out[6] = __float_as_uint(*af.reg_accum);
+                *af.reg_accum = 0.0f;
+            }
+            out[7] = 0u;
+            if (af.void_flags) {
+                af.void_flags[0] = (bits & 1u) ? 1.0f : 0.0f;
+                af.void_flags[1] = (bits & ~1u) ? 1.0f : 0.0f;
+            }
+            if (af.status_mirror) mirror_status_block(out, af.status_mirror);
+        }
+        return;
+    }
+    if ((int)blockIdx.x < 1 + n_ord) {
+        const int b = (int)blockIdx.x - 1, g = b >> 3, xcd = b & 7;
+        const BatchKeyframe *kf = bf.kf;
+        order_blocks_by_cost(bf.order_T, kf[g].order_cost, kf[g].order_out + 1, xcd);
+        if (xcd == 0 && threadIdx.x == 0) kf[g].order_out[0] = block_order_tag(bf.order_T);
+        return;
+    }
+    const int i = ((int)blockIdx.x - 1 - n_ord) * 256 + threadIdx.x;
+    if (i >= N) return;
+    uint32_t skip = 0u;
+#pragma unroll
+    for (int g = 0; g < SLS_MAX_BATCH; ++g) {
+        if (g >= bf.G) break;
+        skip |= bf.kf[g].status[1];
+    }
+    float dm[3] = { 0, 0, 0 };
+    float2 ds = make_float2(0, 0);
+    float4 dq = make_float4(0, 0, 0, 0);
+    float dop = 0.0f;
+    const float2 s_in = scales[i];
+    float2 s = s_in;
+    const float4 q_in = rots[i];
+    float4 q = q_in;
+    const float o_in = opac[i];
+    float o = o_in;
+    activate<false>(ra, s, q, o);
+    const float m[3] = { means[3 * i], means[3 * i + 1], means[3 * i + 2] };
+#pragma unroll
+    for (int kg = 0; kg < SLS_MAX_BATCH; ++kg) {
+        if (kg >= bf.G) break;
+        const BatchKeyframe &kf = bf.kf[kg];
+        if (kf.touched[i] == 0) continue;          // (an unmarked surfel's record is all zeros: nothing to read or clear)
+        kf.touched[i] = 0;
+        if (kf.radii[i] <= 0) continue;
+        SurfelGeom g;
+        surfel_geom<false>(kf.cam, m, s, q, g);
+        float4 g0, g1, g2, g3;
+        if (kf.det_acc) {
+            float gv[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int ex = (int)((kf.det_max[(size_t)i * 16 + k] >> 23) & 0xFFu);
+                gv[k] = (float)ldexp((double)kf.det_acc[(size_t)i * 16 + k], ex - 166);
+                kf.det_acc[(size_t)i * 16 + k] = 0;
+            }
+            if (kf.det_prev && skip == 0u) {
+                uint32_t pw[4];
+#pragma unroll
+                for (int w4 = 0; w4 < 4; ++w4) {
+                    pw[w4] = 0u;
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) pw[w4] |= det_predict(gv[4 * w4 + b]) << (8 * b);
+                }
+                reinterpret_cast<uint4 *>(kf.det_prev)[i] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
+                if (kf.det_gex) {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const uint32_t pe = (pw[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+                        if (pe > kf.det_gex[k]) atomicMax(&kf.det_gex[k], pe);
+                    }
+                }
+            }
+            g0 = make_float4(gv[0], gv[1], gv[2], gv[3]); g1 = make_float4(gv[4], gv[5], gv[6], gv[7]);
+            g2 = make_float4(gv[8], gv[9], gv[10], gv[11]); g3 = make_float4(gv[12], gv[13], gv[14], gv[15]);
+        } else {
+            float4 *rec = kf.grec + (size_t)i * 4;
+            g0 = rec[0]; g1 = rec[1]; g2 = rec[2]; g3 = rec[3];
+            const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            rec[0] = z; rec[1] = z; rec[2] = z; rec[3] = z;
+        }
+        float dmk[3], dopk;
+        float2 dsk;
+        float4 dqk;
+        chain_grad_record(kf.cam, g, q, g0, g1, g2, g3, dmk, dsk, dopk, dqk);
+        dm[0] += dmk[0]; dm[1] += dmk[1]; dm[2] += dmk[2];
+        ds.x += dsk.x; ds.y += dsk.y;
+        dop += dopk;
+        dq.x += dqk.x; dq.y += dqk.y; dq.z += dqk.z; dq.w += dqk.w;
+    }
+    if (ra.pen != 0.0f) {   // the regulariser once, as preprocess_bwd_kernel
+        const bool first = s.x >= s.y;
+        if ((first ? s.x : s.y) >= ra.smax) { if (first) ds.x += ra.pen; else ds.y += ra.pen; }
+    }
+    ds.x *= s.x; ds.y *= s.y;
+    dop *= o * (1.0f - o);
+    {
+        const float nrm = fsqrt(q_in.x * q_in.x + q_in.y * q_in.y + q_in.z * q_in.z + q_in.w * q_in.w);
+        const float inv = frcp(fmaxf(nrm, 1e-12f));
+        const float dd = dq.x * q.x + dq.y * q.y + dq.z * q.z + dq.w * q.w;
+        dq.x = (dq.x - dd * q.x) * inv; dq.y = (dq.y - dd * q.y) * inv;
+        dq.z = (dq.z - dd * q.z) * inv; dq.w = (dq.w - dd * q.w) * inv;
+    }
+    if (!af.enabled || af.write_grads) {
+        dmeans[3 * i] = dm[0]; dmeans[3 * i + 1] = dm[1]; dmeans[3 * i + 2] = dm[2];
+        dscales[i] = ds;
+        drots[i] = dq;
+        dopac[i] = dop;
+    }
+    if (af.enabled && skip == 0u) {
+        const size_t n = (size_t)N, ix = 3 * (size_t)i, io = 3 * n + i, is = 4 * n + 2 * (size_t)i, ir = 6 * n + 4 * (size_t)i;
+        float *M = af.exp_avg, *V = af.exp_avg_sq;
+        float p, mm, vv;
+        const float ibc1 = frcp(af.c.bc1);
+        const float st_x = af.lr_xyz * ibc1, st_o = af.lr_opacity * ibc1;
+        const float st_s = af.lr_scaling * ibc1, st_r = af.lr_rotation * ibc1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p = m[k]; mm = M[ix + k]; vv = V[ix + k];
+            adam_one(p, dm[k], mm, vv, st_x, af.c);
+            means[3 * i + k] = p; M[ix + k] = mm; V[ix + k] = vv;
+        }
+        p = o_in; mm = M[io]; vv = V[io];
+        adam_one(p, dop, mm, vv, st_o, af.c);
+        opac[i] = p; M[io] = mm; V[io] = vv;
+        float2 ps = s_in, ms = *reinterpret_cast<float2 *>(M + is), vs = *reinterpret_cast<float2 *>(V + is);
+        adam_one(ps.x, ds.x, ms.x, vs.x, st_s, af.c);
+        adam_one(ps.y, ds.y, ms.y, vs.y, st_s, af.c);
+        scales[i] = ps; *reinterpret_cast<float2 *>(M + is) = ms; *reinterpret_cast<float2 *>(V + is) = vs;
+        float4 pq = q_in, mq = *reinterpret_cast<float4 *>(M + ir), vq = *reinterpret_cast<float4 *>(V + ir);
+        adam_one(pq.x, dq.x, mq.x, vq.x, st_r, af.c);
+        adam_one(pq.y, dq.y, mq.y, vq.y, st_r, af.c);
+        adam_one(pq.z, dq.z, mq.z, vq.z, st_r, af.c);
+        adam_one(pq.w, dq.w, mq.w, vq.w, st_r, af.c);
+        rots[i] = pq; *reinterpret_cast<float4 *>(M + ir) = mq; *reinterpret_cast<float4 *>(V + ir) = vq;
+    }
+}
+
 __global__ __launch_bounds__(256) void mark_visible_kernel(DevCam cam, int N, const float *__restrict__ means,
                                                            uint8_t *__restrict__ visible)
 {
@@ -835,6 +1098,21 @@ int launch_preprocess_bwd(const DevCam &cam, int raw, float smax, float pen, int
                        const_cast<float *>(opac), radii, (float4 *)const_cast<float *>(grec), dmeans, (float2 *)dscales,
                        (float4 *)drots, dopac);
     SLS_LAUNCH_CHECK("preprocess_bwd_kernel");
+    return SLS_OK;
+}
+
+int launch_preprocess_bwd_batch(float smax, float pen, int N, float *means, float *scales, float *rots, float *opac,
+                                float *dmeans, float *dscales, float *drots, float *dopac, const BatchFuse &bf,
+                                hipStream_t st)
+{
+    const int nb = (N + 255) / 256;
+    RegArgs ra;
+    ra.raw = 1; ra.smax = smax; ra.pen = pen; ra.reg_out = nullptr; ra.status_clear = nullptr;
+    ra.zero_words = nullptr; ra.n_zero_words = 0;
+    ScopedTimer tm(T_PREPROCESS_BWD, st);
+    hipLaunchKernelGGL(preprocess_bwd_batch_kernel, dim3(nb + 1 + (bf.order_T > 0 ? 8 * bf.G : 0)), dim3(256), 0, st, ra, bf, N,
+                       means, (float2 *)scales, (float4 *)rots, opac, dmeans, (float2 *)dscales, (float4 *)drots, dopac);
+    SLS_LAUNCH_CHECK("preprocess_bwd_batch_kernel");
     return SLS_OK;
 }
 

@@ -247,24 +247,11 @@ class MappingEngine:
         self.max_order_age_extra = int(48 * scale)
         self.order_age_round4 = 1000000
 
-    def _params(self):
-        m = self.model
-        ps = (m._xyz, m._scaling, m._rotation, m._opacity)
-        for p in ps:
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.shape[0] != self.N:
-                raise RuntimeError("model parameters must stay contiguous float32 of the engine's size")
-        return ps
-
-    def _enqueue(self, camera, apply_adam, with_regulariser, status=None, mirror=None, allow_reuse=True, phase=0):
+    def _order_for(self, camera, allow_reuse, H, W, advance=True):
+        """The keyframe's cached depth order and tile-backward launch order (created on its first visit), and how the
+        iteration enqueued next brings the depth order up to date: 0 = from scratch, 1..4 = repair rounds.
+        advance=False: the caller counts the iteration and stamps the entry itself (a batch is ONE update)."""
         lib = _abi.lib()
-        H, W = int(camera.image_height), int(camera.image_width)
-        settings = GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix)
-        ce = get_camera(settings, self.dev)
-        aux = camera_aux(camera)
-        if self.capacity == 0:
-            self.capacity = max(4 * self.N, 1 << 16)
-        ws_ptr, ws_bytes = self._ensure_workspace(H, W, self.capacity)
-        xyz, scaling, rotation, opacity = self._params()
         ent = self._order_entry(camera)
         if ent is None:
             stale = [k for k, e in self._orders.items() if e[2]() is None]
@@ -287,21 +274,48 @@ class MappingEngine:
         reuse = min(self._repair_rounds + (1 if age is not None and age > self.max_order_age else 0)
                     + (1 if age is not None and age > self.order_age_round3 else 0)
                     + (1 if age is not None and age > self.order_age_round4 else 0), 4) if reuse else 0
-        self._enq += 1
-        ent[1] = self._enq
+        if advance:
+            self._enq += 1
+            ent[1] = self._enq
+        return ent, reuse
+
+    def _det_prev_for(self, camera):
+        """The keyframe's predicted scales (deterministic = 2) and whether this is its first visit."""
+        dent = self._det_prev.get(id(camera))
+        first_visit = dent is None or dent[1]() is not camera
+        if first_visit:
+            for k in [k for k, e in self._det_prev.items() if e[1]() is None]:
+                del self._det_prev[k]
+            # (bounded like the depth orders: 16 N bytes per keyframe; an evicted keyframe's next visit is a
+            #  two-launch iteration, as a first visit is)
+            while len(self._det_prev) >= self.max_cached_orders:
+                self._det_prev.pop(next(iter(self._det_prev)))
+            dent = [torch.zeros((self.N, 16), dtype=torch.uint8, device=self.dev), weakref.ref(camera)]
+            self._det_prev[id(camera)] = dent
+        return dent, first_visit
+
+    def _params(self):
+        m = self.model
+        ps = (m._xyz, m._scaling, m._rotation, m._opacity)
+        for p in ps:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.shape[0] != self.N:
+                raise RuntimeError("model parameters must stay contiguous float32 of the engine's size")
+        return ps
+
+    def _enqueue(self, camera, apply_adam, with_regulariser, status=None, mirror=None, allow_reuse=True, phase=0):
+        lib = _abi.lib()
+        H, W = int(camera.image_height), int(camera.image_width)
+        settings = GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix)
+        ce = get_camera(settings, self.dev)
+        aux = camera_aux(camera)
+        if self.capacity == 0:
+            self.capacity = max(4 * self.N, 1 << 16)
+        ws_ptr, ws_bytes = self._ensure_workspace(H, W, self.capacity)
+        xyz, scaling, rotation, opacity = self._params()
+        ent, reuse = self._order_for(camera, allow_reuse, H, W)
         cfg = self._config(apply_adam, with_regulariser, reuse)
         if self.deterministic == 2:
-            dent = self._det_prev.get(id(camera))
-            first_visit = dent is None or dent[1]() is not camera
-            if first_visit:
-                for k in [k for k, e in self._det_prev.items() if e[1]() is None]:
-                    del self._det_prev[k]
-                # (bounded like the depth orders: 16 N bytes per keyframe; an evicted keyframe's next visit is a
-                #  two-launch iteration, as a first visit is)
-                while len(self._det_prev) >= self.max_cached_orders:
-                    self._det_prev.pop(next(iter(self._det_prev)))
-                dent = [torch.zeros((self.N, 16), dtype=torch.uint8, device=self.dev), weakref.ref(camera)]
-                self._det_prev[id(camera)] = dent
+            dent, first_visit = self._det_prev_for(camera)
             cfg.det_prev = dent[0].data_ptr()
             # two launches where there is nothing to predict from: a workspace's first deterministic iteration (it sets
             # the fields' default scales) and a keyframe's first visit (measured: predicting a new view from the
@@ -446,6 +460,134 @@ class MappingEngine:
                     need = int(t.item())
                 self.capacity = int(max(need, self.capacity) * self.capacity_factor) + 1024
                 self.workspace = None
+
+    def _ensure_batch_workspace(self, G, H, W, capacity):
+        """The batch's workspace: one slice per keyframe, kept apart from step()'s (re-carved for more keyframes, another
+        size, more room or another accumulation mode)."""
+        lib = _abi.lib()
+        b = getattr(self, "_bws", None)
+        det = bool(self.deterministic)
+        # (capacity: the slices are laid out by it, so ANY change re-carves — a smaller one would move the zeroed records)
+        if b is None or G > b["G"] or capacity != b["cap"] or (H, W) != b["hw"] or det != b["det"] or self.N != b["n"]:
+            wcfg = _abi.SlsMappingConfig()
+            wcfg.deterministic = 1 if det else 0
+            Gw = max(G, b["G"] if b is not None and (H, W) == b["hw"] else 1)
+            nbytes = int(lib.sls_mapping_workspace_bytes_batch(Gw, self.N, H, W, capacity, C.byref(wcfg)))
+            self._bws = None
+            b = self._bws = {"G": Gw, "cap": int(capacity), "hw": (H, W), "det": det, "n": self.N, "ready": 0,
+                             "buf": torch.empty((nbytes + 256,), dtype=torch.uint8, device=self.dev),
+                             "status": torch.zeros((_abi.SLS_MAX_BATCH + 1, 8), dtype=torch.int32, device=self.dev)}
+        base = b["buf"].data_ptr()
+        return b, (base + 255) & ~255, b["buf"].numel() - 256
+
+    def _enqueue_batch(self, cameras, apply_adam, with_regulariser, allow_reuse=True):
+        """sls_mapping_step_batch on `cameras` with the keyframes' own cached orders (as _enqueue)."""
+        lib = _abi.lib()
+        G = len(cameras)
+        H, W = int(cameras[0].image_height), int(cameras[0].image_width)
+        if self.capacity == 0:
+            self.capacity = max(4 * self.N, 1 << 16)
+        b, ws_ptr, ws_bytes = self._ensure_batch_workspace(G, H, W, self.capacity)
+        xyz, scaling, rotation, opacity = self._params()
+        kfs = (_abi.SlsKeyframeInputs * G)()
+        keep = []                       # (the camera tables must outlive the call)
+        reuse_used, ents = [], []
+        for g, camera in enumerate(cameras):
+            settings = GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix)
+            ce = get_camera(settings, self.dev)
+            aux = camera_aux(camera)
+            # (an order's age counts parameter updates: the whole batch is one, so a keyframe batched at every step stays
+            #  one update old)
+            ent, reuse = self._order_for(camera, allow_reuse, H, W, advance=False)
+            ents.append(ent)
+            k = kfs[g]
+            k.cam = ce.cam
+            k.gt_depth, k.valid, k.n_valid = aux.gt.data_ptr(), aux.valid.data_ptr(), aux.n_valid
+            k.reuse_depth_order = int(reuse)
+            k.col_cs, k.row_cs = ce.col_cs.data_ptr(), ce.row_cs.data_ptr()
+            k.col_cs_half, k.row_cs_half = aux.col_h.data_ptr(), aux.row_h.data_ptr()
+            k.depth_order = ent[0].data_ptr()
+            k.block_order = ent[3].data_ptr() if self.inline_loss_stage else None
+            # (deterministic = 2 runs as 1 in a batch; the keyframe's predictions are still rewritten for its step())
+            k.det_prev = self._det_prev_for(camera)[0][0].data_ptr() if self.deterministic == 2 else None
+            keep.append((ce, aux))
+            reuse_used.append(int(reuse))
+        self._enq += 1
+        for ent in ents:
+            ent[1] = self._enq
+        ready = self._ws_ready
+        cfg = self._config(apply_adam, with_regulariser)
+        self._ws_ready = ready          # (that flag is step()'s workspace's)
+        # the slices whose accumulation buffers are known to be zero (a first use zeroes the batch's G slices)
+        cfg.workspace_ready = 1 if G <= b["ready"] else 0
+        b["ready"] = max(b["ready"], G)
+        cfg.void_flags_out = None if apply_adam else self.grads.data_ptr() + 4 * 10 * self.N
+        self.last_batch_reuse = reuse_used
+        _abi.check(lib.sls_mapping_step_batch(G, kfs, self.N, xyz.data_ptr(), scaling.data_ptr(), rotation.data_ptr(),
+                                              opacity.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
+                                              self.exp_avg_sq.data_ptr(), self.t + 1, C.byref(cfg), b["cap"],
+                                              ws_ptr, ws_bytes, b["status"].data_ptr(),
+                                              torch.cuda.current_stream(self.dev).cuda_stream),
+                   "sls_mapping_step_batch")
+        return b["status"]
+
+    @torch.no_grad()
+    def step_batch(self, cameras, group=None, sync: bool = True):
+        """ONE mapping iteration over up to eight distinct keyframes of the same size: the keyframes' pixel-loss gradients
+        summed, the scale regulariser once, one Adam update (`self.t` + 1).  Returns the batch's status dict, with the
+        keyframes' own statuses (R, bits, loss sums) under "keyframes" (sync=True), or None (sync=False, as step()).
+        A void keyframe voids the batch; it is repeated as step() repeats an iteration.
+        With `group` (dp_mode "allreduce"), every rank batches ITS keyframes and the summed gradient is all-reduced over
+        the ranks before the guarded Adam: 8 keyframes on 2 or 4 GPUs; the regulariser counts on rank 0 only."""
+        cams = list(cameras)
+        if sync == "lagged":
+            raise ValueError("step_batch has no lagged mode")
+        if not 1 <= len(cams) <= _abi.SLS_MAX_BATCH:
+            raise ValueError(f"a batch holds 1 to {_abi.SLS_MAX_BATCH} keyframes, not {len(cams)}")
+        if len({id(c) for c in cams}) != len(cams):
+            raise ValueError("a keyframe appears twice in the batch")
+        if len({(int(c.image_height), int(c.image_width)) for c in cams}) != 1:
+            raise ValueError("the keyframes of a batch must share one image size")
+        sharded = self._sharded(group)
+        if sharded and self.dp_mode != "allreduce":
+            raise NotImplementedError(f"step_batch over a process group needs dp_mode 'allreduce', not {self.dp_mode!r}")
+        if self._dp is not None or self._sx is not None:
+            raise RuntimeError("this engine's optimiser state is laid out for another exchange: step_batch cannot use it")
+        self._group = group
+        if self._lag_pending is not None:
+            self.flush()
+        reuse_ok = sync is not False
+        while True:
+            if not sharded:
+                status = self._enqueue_batch(cams, apply_adam=True, with_regulariser=True, allow_reuse=reuse_ok)
+            else:
+                self._ensure_dp(group)
+                status = self._enqueue_batch(cams, apply_adam=False, with_regulariser=(dist.get_rank(group) == 0),
+                                             allow_reuse=reuse_ok)
+                self._exchange_and_adam(group, status[0], None)
+            if not sync:
+                self.t += 1
+                return None
+            h = status[:len(cams) + 1].cpu()
+            st = self._note(self._parse_status(h[0]))
+            st["keyframes"] = [self._parse_status(h[1 + g]) for g in range(len(cams))]
+            if not st["overflow"]:
+                self.t += 1
+                self.last = st
+                return st
+            for cam, kst in zip(cams, st["keyframes"]):
+                if kst["too_small"] or kst["resort_failed"]:
+                    self._forget_order(cam, failed_repair=kst["resort_failed"])
+            self.stats[self._void_reason(st)] += 1
+            if st["too_small"]:
+                need = st["R"]
+                if sharded:
+                    t = torch.tensor([need], dtype=torch.int64, device=self.dev)
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+                    need = int(t.item())
+                self.capacity = int(max(need, self.capacity) * self.capacity_factor) + 1024
+                self.workspace = None
+                self._bws = None
 
     def _step_lagged(self, camera):
         slot = 0 if self._lag_pending is None else self._lag_pending[0] ^ 1
