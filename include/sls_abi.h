@@ -193,6 +193,26 @@ int sls_backward(const SlsCamera *cam, int N, uint64_t R,
                  float *dL_dmeans3D, float *dL_dscales, float *dL_drotations,
                  float *dL_dopacities, const uint64_t *block_masks, int block_masks_shape, void *stream);
 
+/* ---- pose gradient -------------------------------------------------------------
+ * Every backward below has a `_pose` form that also returns g = dL/dxi at xi = 0 for the LEFT perturbation of the view
+ * transform, T_vw(xi) = Exp(xi) T_vw with xi = (v, w): to first order p_view -> p_view + w x p_view + v.  pose_grad: 6
+ * floats [v | w] in DEVICE memory, written by the backward of the projection itself (a reduction over its surfels: one
+ * row per workgroup, added in a fixed order — the same bits from run to run wherever the gradient records are).
+ * pose_scratch: sls_pose_grad_scratch_bytes(N) bytes of DEVICE memory, 8-byte aligned, caller-kept, zero-initialised ONCE
+ * by the caller; every call leaves it ready for the next (one call at a time per buffer).  A null pose_grad is the
+ * call without the suffix, bit for bit.  The discrete choices of the forward are frozen as for the surfels' gradients. */
+size_t sls_pose_grad_scratch_bytes(int N);
+int sls_backward_pose(const SlsCamera *cam, int N, uint64_t R,
+                      const float *means3D, const float *scales, const float *rotations,
+                      const int32_t *radii, const float *rec,
+                      const uint32_t *ranges, const uint32_t *vals_sorted, int vals_stride,
+                      const float *col_cs, const float *row_cs,
+                      const float *pix_state, const uint32_t *pix_contrib,
+                      const float *dL_dallmap, float *grec,
+                      float *dL_dmeans3D, float *dL_dscales, float *dL_drotations,
+                      float *dL_dopacities, const uint64_t *block_masks, int block_masks_shape,
+                      float *pose_grad, void *pose_scratch, size_t pose_scratch_bytes, void *stream);
+
 /* The same backward with DETERMINISTIC accumulation of the per-surfel gradient records: integer atomics
  * instead of float atomics (first launch: the largest |contribution| per surfel and field; second launch:
  * every contribution scaled by 2^(39 - unbiased exponent of that maximum), rounded, added as a 64-bit integer:
@@ -208,6 +228,14 @@ int sls_backward_det(const SlsCamera *cam, int N, uint64_t R,
                      float *dL_dmeans3D, float *dL_dscales, float *dL_drotations, float *dL_dopacities,
                      const uint64_t *block_masks, int block_masks_shape, void *det_scratch, size_t det_scratch_bytes,
                      void *stream);
+int sls_backward_det_pose(const SlsCamera *cam, int N, uint64_t R,
+                          const float *means3D, const float *scales, const float *rotations, const int32_t *radii,
+                          const float *rec, const uint32_t *ranges, const uint32_t *vals_sorted, int vals_stride,
+                          const float *col_cs, const float *row_cs, const float *pix_state, const uint32_t *pix_contrib,
+                          const float *dL_dallmap,
+                          float *dL_dmeans3D, float *dL_dscales, float *dL_drotations, float *dL_dopacities,
+                          const uint64_t *block_masks, int block_masks_shape, void *det_scratch, size_t det_scratch_bytes,
+                          float *pose_grad, void *pose_scratch, size_t pose_scratch_bytes, void *stream);
 
 /* ---- forward / backward in ONE call each, against a capacity (no host read of R) ---------------------------
  * What `GaussianRasterizer` runs by default (gaussian_renderer/__init__.py:26,40-47; slam/mapper.py:201): the kernels
@@ -249,6 +277,12 @@ int sls_backward_ws(const SlsCamera *cam, int N, const float *means3D, const flo
                     uint64_t R_capacity, void *workspace, size_t workspace_bytes, const uint32_t *sorted_list,
                     int sorted_stride, int block_masks_shape, uint32_t *block_order, float *dL_dmeans3D,
                     float *dL_dscales, float *dL_drotations, float *dL_dopacities, void *stream);
+int sls_backward_ws_pose(const SlsCamera *cam, int N, const float *means3D, const float *scales, const float *rotations,
+                         const int32_t *radii, const float *col_cs, const float *row_cs, const float *dL_dallmap,
+                         uint64_t R_capacity, void *workspace, size_t workspace_bytes, const uint32_t *sorted_list,
+                         int sorted_stride, int block_masks_shape, uint32_t *block_order, float *dL_dmeans3D,
+                         float *dL_dscales, float *dL_drotations, float *dL_dopacities, float *pose_grad,
+                         void *pose_scratch, size_t pose_scratch_bytes, void *stream);
 
 /* ---- fused consumer of allmap: render() post-processing + mapper loss ------
  * Computes, from allmap (7*H*W, NOT modified), the three per-pixel loss terms of
@@ -388,6 +422,18 @@ typedef struct SlsMappingConfig {
     uint32_t *grad_compact_index;  /* capacity uint32: the surfel of every slot (for sls_adam_step_union) */
     uint32_t grad_compact_capacity;
     uint32_t reserved2;
+    float *pose_grad;        /* optional DEVICE pointer to 6 floats [v | w]: the keyframe's pose gradient (D11, see
+                              * sls_backward_pose) of the pixel loss, written by the iteration's last launch — served with
+                              * apply_adam 0 and 1, deterministic 0 / 1 / 2 (1 and 2: the same bits from run to run), phase 0
+                              * and 2 (phase 1 ends before that launch and does not touch it).  With the touched-set
+                              * exchange (union_bitmap) the kernel takes the same reduction, but no test runs that
+                              * combination: treat it as unexercised.  The scale regulariser does not depend on the
+                              * pose.  Void iteration: void gradient.
+                              * Null: the iteration as it was, bit for bit.  sls_mapping_step_batch: must be null here (one
+                              * pointer per SlsKeyframeInputs instead) */
+    void *pose_scratch;      /* with pose_grad: sls_pose_grad_scratch_bytes(N) bytes (x G for a batch), 8-byte aligned,
+                              * zero-initialised once by the caller; NOT part of the workspace, whose sizes are unchanged */
+    size_t pose_scratch_bytes;
 } SlsMappingConfig;
 typedef struct SlsMappingStatus {
     uint32_t R;           /* tile instances of this iteration */
@@ -435,7 +481,8 @@ int sls_mapping_step(const SlsCamera *cam, int N,
  *        loss sums added over the keyframes, the regulariser; [1 + g] keyframe g (its R, bits, loss sums; no regulariser).
  *   SLS_E_ARG (sls_last_error says why), before anything is enqueued: G outside [1, SLS_MAX_BATCH], keyframes of
  *        different H x W, a null per-keyframe pointer (block_order and det_prev are optional, block_order on all
- *        keyframes or none), the same depth_order / block_order / det_prev buffer on two keyframes. */
+ *        keyframes or none; pose_grad likewise), the same depth_order / block_order / det_prev / pose_grad buffer on
+ *        two keyframes, a non-null cfg->pose_grad. */
 #define SLS_MAX_BATCH 8
 typedef struct SlsKeyframeInputs {
     SlsCamera cam;
@@ -448,6 +495,8 @@ typedef struct SlsKeyframeInputs {
     uint32_t *depth_order;        /* N uint32: the keyframe's depth order (as SlsMappingConfig.depth_order; required) */
     uint32_t *block_order;        /* optional: sls_block_order_bytes(H, W) (as SlsMappingConfig.block_order) */
     uint8_t *det_prev;            /* optional: 16 N bytes (as SlsMappingConfig.det_prev) */
+    float *pose_grad;             /* optional, on every keyframe or on none: 6 DEVICE floats, this keyframe's pose gradient
+                                   * through its own camera (scratch: cfg->pose_scratch, G x sls_pose_grad_scratch_bytes(N)) */
 } SlsKeyframeInputs;
 /* One sls_mapping_workspace_bytes_cfg workspace + G - 1 per-keyframe parts (0 for G outside [1, SLS_MAX_BATCH]) */
 size_t sls_mapping_workspace_bytes_batch(int G, int N, int H, int W, uint64_t R_capacity, const SlsMappingConfig *cfg);

@@ -44,6 +44,7 @@ class SlsMappingConfig(C.Structure):
         ("block_order", C.c_void_p),
         ("union_bitmap", C.c_void_p), ("union_prefix", C.c_void_p), ("grad_compact", C.c_void_p),
         ("grad_compact_index", C.c_void_p), ("grad_compact_capacity", C.c_uint32), ("reserved2", C.c_uint32),
+        ("pose_grad", C.c_void_p), ("pose_scratch", C.c_void_p), ("pose_scratch_bytes", C.c_size_t),
     ]
 
 
@@ -68,6 +69,7 @@ class SlsKeyframeInputs(C.Structure):
         ("cam", SlsCamera), ("gt_depth", C.c_void_p), ("valid", C.c_void_p), ("n_valid", C.c_int32),
         ("reuse_depth_order", C.c_int32), ("col_cs", C.c_void_p), ("row_cs", C.c_void_p), ("col_cs_half", C.c_void_p),
         ("row_cs_half", C.c_void_p), ("depth_order", C.c_void_p), ("block_order", C.c_void_p), ("det_prev", C.c_void_p),
+        ("pose_grad", C.c_void_p),
     ]
 
 
@@ -126,6 +128,13 @@ _PROTOS = {
     "sls_backward_det_scratch_bytes": (C.c_size_t, [C.c_int]),
     "sls_backward_det": (C.c_int, [C.POINTER(SlsCamera), C.c_int, C.c_uint64] + [_VP] * 7 + [C.c_int] + [_VP] * 10 +
                          [C.c_int, _VP, C.c_size_t, _VP]),
+    "sls_pose_grad_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_backward_pose": (C.c_int, [C.POINTER(SlsCamera), C.c_int, C.c_uint64] + [_VP] * 7 + [C.c_int] + [_VP] * 11 +
+                          [C.c_int, _VP, _VP, C.c_size_t, _VP]),
+    "sls_backward_ws_pose": (C.c_int, [C.POINTER(SlsCamera), C.c_int] + [_VP] * 7 + [C.c_uint64, _VP, C.c_size_t, _VP, C.c_int, C.c_int] +
+                             [_VP] * 5 + [_VP, _VP, C.c_size_t, _VP]),
+    "sls_backward_det_pose": (C.c_int, [C.POINTER(SlsCamera), C.c_int, C.c_uint64] + [_VP] * 7 + [C.c_int] + [_VP] * 10 +
+                              [C.c_int, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP]),
     "sls_adam_step": (C.c_int, [C.POINTER(SlsAdamGroup), C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _VP]),
     "sls_adam_step_guarded": (C.c_int, [C.POINTER(SlsAdamGroup), C.c_int, C.c_double, C.c_double, C.c_double,
                                         C.c_int64, _VP, _VP]),

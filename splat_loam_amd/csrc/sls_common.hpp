@@ -419,6 +419,17 @@ struct BatchFuse {
     AdamFuse af;
 };
 
+// Pose gradient out of the projection's backward: every workgroup of surfels leaves one row of
+// kPoseRow floats [g_v 3 | g_w 3 | 0 0] per keyframe in `rows` (keyframe g's rows start at g * n_blocks * kPoseRow), the
+// last workgroup to arrive at `counter` adds the rows in a fixed order, in double, writes out[g][0..5] and re-zeroes the
+// counter.  Without a pose gradient the kernels are the instantiations without any of this, and take no such argument.
+constexpr int kPoseRow = 8;
+struct PoseOut {
+    float *rows;
+    uint32_t *counter;
+    float *out[SLS_MAX_BATCH];
+};
+
 // Copy of an iteration's finished status block (8 words) into its pinned host mirror, by ONE lane.  The host polls
 // words 0 and 7 (engine.py: it arms them with a value the device never writes): words 0..6 are made visible at
 // system scope BEFORE word 7 is stored, so a host that sees word 7 sees the whole row.

@@ -26,10 +26,10 @@ void depth_order_key_buffers(int N, void *scratch, uint32_t *order, uint32_t **k
 int launch_preprocess_bwd(const DevCam &cam, int raw, float smax, float pen, int N, const float *means,
                           const float *scales, const float *rots, const float *opac, const int32_t *radii,
                           const float *grec, float *dmeans, float *dscales, float *drots, float *dopac,
-                          hipStream_t st, const AdamFuse *fuse = nullptr);
+                          hipStream_t st, const AdamFuse *fuse = nullptr, const PoseOut *pose = nullptr);
 int launch_preprocess_bwd_batch(float smax, float pen, int N, float *means, float *scales, float *rots, float *opac,
                                 float *dmeans, float *dscales, float *drots, float *dopac, const BatchFuse &bf,
-                                hipStream_t st);
+                                hipStream_t st, const PoseOut *pose = nullptr);
 size_t sort_scratch_bytes(uint64_t cap);
 size_t order_scratch_bytes(int N);
 int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_t cap, const uint32_t *order,
@@ -278,6 +278,39 @@ int sls_forward_stage2(const SlsCamera *cam, int N, uint64_t R, const float *rec
                              true);       // (+ the backward's launch order into the hand-over buffer)
 }
 
+// ---- pose gradient (D11): the caller's scratch = one arrival counter (a 256-byte slot) + one row per workgroup of the
+// projection's backward and keyframe
+static size_t pose_scratch_bytes(int G, int N)
+{
+    // (G times the single keyframe's: one counter is used, the documented size is the simple one)
+    return (size_t)G * (256 + (size_t)((N + 255) / 256) * kPoseRow * sizeof(float));
+}
+size_t sls_pose_grad_scratch_bytes(int N) { return N > 0 ? pose_scratch_bytes(1, N) : 0; }
+
+// Checks a call's pose arguments (before anything is enqueued) and fills the launcher's view of them; *use = false
+// where no pose gradient is asked for (pose_grad[g] all null).
+static int make_pose_out(int G, int N, float *const *pose_grad, void *scratch, size_t scratch_bytes, PoseOut *po, bool *use)
+{
+    memset(po, 0, sizeof(*po));
+    int n = 0;
+    for (int g = 0; g < G; ++g) n += pose_grad[g] ? 1 : 0;
+    *use = n > 0;
+    if (n == 0) return SLS_OK;
+    SLS_REQUIRE(n == G, "pose_grad on every keyframe of the batch or on none");
+    SLS_REQUIRE(scratch && ((uintptr_t)scratch & 7) == 0, "pose_grad needs pose_scratch (8-byte aligned, sls_pose_grad_scratch_bytes)");
+    if (scratch_bytes < pose_scratch_bytes(G, N)) {
+        set_error("pose-gradient scratch too small: %zu < %zu", scratch_bytes, pose_scratch_bytes(G, N));
+        return SLS_E_SCRATCH;
+    }
+    po->counter = (uint32_t *)scratch;
+    po->rows = (float *)((char *)scratch + 256);
+    for (int g = 0; g < G; ++g) {
+        for (int h = 0; h < g; ++h) SLS_REQUIRE(pose_grad[h] != pose_grad[g], "two keyframes share one pose_grad buffer");
+        po->out[g] = pose_grad[g];
+    }
+    return SLS_OK;
+}
+
 int sls_backward(const SlsCamera *cam, int N, uint64_t R, const float *means3D, const float *scales,
                  const float *rotations, const int32_t *radii, const float *rec, const uint32_t *ranges,
                  const uint32_t *vals_sorted, int vals_stride, const float *col_cs, const float *row_cs,
@@ -286,9 +319,28 @@ int sls_backward(const SlsCamera *cam, int N, uint64_t R, const float *means3D, 
                  float *dL_dscales, float *dL_drotations, float *dL_dopacities, const uint64_t *block_masks,
                  int block_masks_shape, void *stream)
 {
+    return sls_backward_pose(cam, N, R, means3D, scales, rotations, radii, rec, ranges, vals_sorted, vals_stride, col_cs,
+                             row_cs, pix_state, pix_contrib, dL_dallmap, grec, dL_dmeans3D, dL_dscales, dL_drotations,
+                             dL_dopacities, block_masks, block_masks_shape, nullptr, nullptr, 0, stream);
+}
+
+int sls_backward_pose(const SlsCamera *cam, int N, uint64_t R, const float *means3D, const float *scales,
+                      const float *rotations, const int32_t *radii, const float *rec, const uint32_t *ranges,
+                      const uint32_t *vals_sorted, int vals_stride, const float *col_cs, const float *row_cs,
+                      const float *pix_state,
+                      const uint32_t *pix_contrib, const float *dL_dallmap, float *grec, float *dL_dmeans3D,
+                      float *dL_dscales, float *dL_drotations, float *dL_dopacities, const uint64_t *block_masks,
+                      int block_masks_shape, float *pose_grad, void *pose_scratch, size_t pose_scratch_bytes_, void *stream)
+{
     SLS_REQUIRE(cam, "null pointer");
     SLS_REQUIRE(N >= 0, "negative N");
-    if (N == 0) return SLS_OK;
+    if (N == 0) {
+        if (pose_grad) SLS_HIP_CHECK(hipMemsetAsync(pose_grad, 0, 6 * sizeof(float), (hipStream_t)stream));
+        return SLS_OK;
+    }
+    PoseOut po;
+    bool use_pose;
+    if (int prc = make_pose_out(1, N, &pose_grad, pose_scratch, pose_scratch_bytes_, &po, &use_pose)) return prc;
     SLS_REQUIRE(means3D && scales && rotations && radii && grec && dL_dmeans3D && dL_dscales && dL_drotations &&
                     dL_dopacities,
                 "null pointer");
@@ -308,7 +360,7 @@ int sls_backward(const SlsCamera *cam, int N, uint64_t R, const float *means3D, 
         if (rc) return rc;
     }
     return launch_preprocess_bwd(dc, 0, 0.0f, 0.0f, N, means3D, scales, rotations, nullptr, radii, grec, dL_dmeans3D,
-                                 dL_dscales, dL_drotations, dL_dopacities, st);
+                                 dL_dscales, dL_drotations, dL_dopacities, st, nullptr, use_pose ? &po : nullptr);
 }
 
 size_t sls_backward_det_scratch_bytes(int N) { return N > 0 ? (size_t)N * SLS_GREC_STRIDE * 12 + 256 : 256; }
@@ -321,9 +373,30 @@ int sls_backward_det(const SlsCamera *cam, int N, uint64_t R, const float *means
                      float *dL_drotations, float *dL_dopacities, const uint64_t *block_masks, int block_masks_shape,
                      void *det_scratch, size_t det_scratch_bytes, void *stream)
 {
+    return sls_backward_det_pose(cam, N, R, means3D, scales, rotations, radii, rec, ranges, vals_sorted, vals_stride,
+                                 col_cs, row_cs, pix_state, pix_contrib, dL_dallmap, dL_dmeans3D, dL_dscales,
+                                 dL_drotations, dL_dopacities, block_masks, block_masks_shape, det_scratch,
+                                 det_scratch_bytes, nullptr, nullptr, 0, stream);
+}
+
+int sls_backward_det_pose(const SlsCamera *cam, int N, uint64_t R, const float *means3D, const float *scales,
+                          const float *rotations, const int32_t *radii, const float *rec, const uint32_t *ranges,
+                          const uint32_t *vals_sorted, int vals_stride, const float *col_cs, const float *row_cs,
+                          const float *pix_state,
+                          const uint32_t *pix_contrib, const float *dL_dallmap, float *dL_dmeans3D, float *dL_dscales,
+                          float *dL_drotations, float *dL_dopacities, const uint64_t *block_masks, int block_masks_shape,
+                          void *det_scratch, size_t det_scratch_bytes, float *pose_grad, void *pose_scratch,
+                          size_t pose_scratch_bytes_, void *stream)
+{
     SLS_REQUIRE(cam, "null pointer");
     SLS_REQUIRE(N >= 0, "negative N");
-    if (N == 0) return SLS_OK;
+    if (N == 0) {
+        if (pose_grad) SLS_HIP_CHECK(hipMemsetAsync(pose_grad, 0, 6 * sizeof(float), (hipStream_t)stream));
+        return SLS_OK;
+    }
+    PoseOut po;
+    bool use_pose;
+    if (int prc = make_pose_out(1, N, &pose_grad, pose_scratch, pose_scratch_bytes_, &po, &use_pose)) return prc;
     SLS_REQUIRE(means3D && scales && rotations && radii && det_scratch && dL_dmeans3D && dL_dscales && dL_drotations &&
                     dL_dopacities,
                 "null pointer");
@@ -351,7 +424,7 @@ int sls_backward_det(const SlsCamera *cam, int N, uint64_t R, const float *means
     fuse.det_max = mx;
     fuse.det_acc = (const long long *)acc;
     return launch_preprocess_bwd(dc, 0, 0.0f, 0.0f, N, means3D, scales, rotations, nullptr, radii, nullptr, dL_dmeans3D,
-                                 dL_dscales, dL_drotations, dL_dopacities, st, &fuse);
+                                 dL_dscales, dL_drotations, dL_dopacities, st, &fuse, use_pose ? &po : nullptr);
 }
 
 // ---- the drop-in forward without the host read of R --------------------------------------------------------------
@@ -434,8 +507,23 @@ int sls_backward_ws(const SlsCamera *cam, int N, const float *means3D, const flo
                     int sorted_stride, int block_masks_shape, uint32_t *block_order, float *dL_dmeans3D,
                     float *dL_dscales, float *dL_drotations, float *dL_dopacities, void *stream)
 {
+    return sls_backward_ws_pose(cam, N, means3D, scales, rotations, radii, col_cs, row_cs, dL_dallmap, R_capacity, workspace,
+                                workspace_bytes, sorted_list, sorted_stride, block_masks_shape, block_order, dL_dmeans3D,
+                                dL_dscales, dL_drotations, dL_dopacities, nullptr, nullptr, 0, stream);
+}
+
+int sls_backward_ws_pose(const SlsCamera *cam, int N, const float *means3D, const float *scales, const float *rotations,
+                         const int32_t *radii, const float *col_cs, const float *row_cs, const float *dL_dallmap,
+                         uint64_t R_capacity, void *workspace, size_t workspace_bytes, const uint32_t *sorted_list,
+                         int sorted_stride, int block_masks_shape, uint32_t *block_order, float *dL_dmeans3D,
+                         float *dL_dscales, float *dL_drotations, float *dL_dopacities, float *pose_grad,
+                         void *pose_scratch, size_t pose_scratch_bytes_, void *stream)
+{
     SLS_REQUIRE(cam && workspace && sorted_list, "null pointer");
     SLS_REQUIRE(N > 0, "N must be positive");
+    PoseOut po;
+    bool use_pose;
+    if (int prc = make_pose_out(1, N, &pose_grad, pose_scratch, pose_scratch_bytes_, &po, &use_pose)) return prc;
     SLS_REQUIRE(means3D && scales && rotations && radii && col_cs && row_cs && dL_dallmap && dL_dmeans3D && dL_dscales &&
                     dL_drotations && dL_dopacities,
                 "null pointer");
@@ -468,7 +556,7 @@ int sls_backward_ws(const SlsCamera *cam, int N, const float *means3D, const flo
     fuse.touched = w.touched;
     if (order_bwd) { fuse.order_T = T; fuse.order_cost = w.block_cost; fuse.order_out = block_order; }
     return launch_preprocess_bwd(dc, 0, 0.0f, 0.0f, N, means3D, scales, rotations, nullptr, radii, w.grec, dL_dmeans3D,
-                                 dL_dscales, dL_drotations, dL_dopacities, st, &fuse);
+                                 dL_dscales, dL_drotations, dL_dopacities, st, &fuse, use_pose ? &po : nullptr);
 }
 
 // The front of an iteration (forward, loss, tile backward) on ONE keyframe, into ONE workspace slice: sls_mapping_step
@@ -616,6 +704,12 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
     SLS_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     // (every argument check before the first launch: an argument error must not leave half an iteration on the stream)
     SLS_REQUIRE(cfg->phase >= 0 && cfg->phase <= 2, "phase: 0 whole iteration, 1 up to the tile backward, 2 the rest");
+    PoseOut po;
+    bool use_pose;
+    {
+        float *pg = cfg->pose_grad;
+        if (int prc = make_pose_out(1, N, &pg, cfg->pose_scratch, cfg->pose_scratch_bytes, &po, &use_pose)) return prc;
+    }
     SLS_REQUIRE(!cfg->grad_bitmap || ((!cfg->apply_adam || cfg->union_bitmap) && !cfg->grad_chunk),
                 "the gradient bitmap belongs to apply_adam = 0 with the flat bucket");
     SLS_REQUIRE(!cfg->union_bitmap || (cfg->phase == 2 && cfg->apply_adam && cfg->union_prefix && cfg->grad_compact && cfg->grad_compact_index &&
@@ -712,7 +806,7 @@ int sls_mapping_step(const SlsCamera *cam, int N, float *xyz, float *scaling_raw
         fuse.compact = cfg->grad_compact; fuse.compact_idx = cfg->grad_compact_index; fuse.compact_cap = cfg->grad_compact_capacity;
     }
     rc = launch_preprocess_bwd(dc, 1, cfg->scaling_max, cfg->scaling_max_penalty, N, xyz, scaling_raw, rotation_raw,
-                               opacity_raw, w.radii, w.grec, g_xyz, g_sc, g_rot, g_op, st, &fuse);
+                               opacity_raw, w.radii, w.grec, g_xyz, g_sc, g_rot, g_op, st, &fuse, use_pose ? &po : nullptr);
     if (rc) return rc;
     if (cfg->apply_adam && !fuse.enabled) {
         SlsAdamGroup grp[4];
@@ -773,6 +867,14 @@ int sls_mapping_step_batch(int G, const SlsKeyframeInputs *kfs, int N, float *xy
             SLS_REQUIRE(!k.block_order || kfs[h].block_order != k.block_order, "two keyframes share one block_order buffer");
             SLS_REQUIRE(!k.det_prev || kfs[h].det_prev != k.det_prev, "two keyframes share one det_prev buffer");
         }
+    }
+    SLS_REQUIRE(!cfg->pose_grad, "a batch takes its pose gradients per keyframe: SlsKeyframeInputs.pose_grad");
+    PoseOut po;
+    bool use_pose;
+    {
+        float *pg[SLS_MAX_BATCH];
+        for (int g = 0; g < G; ++g) pg[g] = kfs[g].pose_grad;
+        if (int prc = make_pose_out(G, N, pg, cfg->pose_scratch, cfg->pose_scratch_bytes, &po, &use_pose)) return prc;
     }
     const bool det = cfg->deterministic != 0;
     MapWs ws[SLS_MAX_BATCH];
@@ -844,7 +946,7 @@ int sls_mapping_step_batch(int G, const SlsKeyframeInputs *kfs, int N, float *xy
     }
     float *g_xyz = grads, *g_op = grads + (size_t)3 * N, *g_sc = grads + (size_t)4 * N, *g_rot = grads + (size_t)6 * N;
     int rc = launch_preprocess_bwd_batch(cfg->scaling_max, cfg->scaling_max_penalty, N, xyz, scaling_raw, rotation_raw,
-                                         opacity_raw, g_xyz, g_sc, g_rot, g_op, bf, st);
+                                         opacity_raw, g_xyz, g_sc, g_rot, g_op, bf, st, use_pose ? &po : nullptr);
     if (rc) return rc;
     if (cfg->apply_adam && !af.enabled) {      // (odd N or unaligned moments: the separate optimiser kernel, as sls_mapping_step)
         SlsAdamGroup grp[4];

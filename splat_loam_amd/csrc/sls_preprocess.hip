@@ -476,13 +476,104 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // ---------------------------------------------------------------------------
 // A8 preprocess backward: gradient record (sls_spec.h) -> input gradients.
 // ---------------------------------------------------------------------------
+// ---- pose gradient ------------------------------------------------------------------------
+// One surfel's six terms of dL/dxi for the left perturbation T_vw -> Exp(xi) T_vw, from the four VIEW-frame vectors the
+// chain holds before it rotates them to the world: g_v += dL/dp, g_w += p x dL/dp + Tu x dL/dTu + Tv x dL/dTv + Tn x dL/dTn.
+__device__ __forceinline__ void pose_terms(const SurfelGeom &g, const float *dp, const float *dTu, const float *dTv,
+                                           const float *dTn, float *pg)
+{
+    float c0[3], c1[3], c2[3], c3[3];
+    cross3(g.p, dp, c0); cross3(g.Tu, dTu, c1); cross3(g.Tv, dTv, c2); cross3(g.Tn, dTn, c3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        pg[k] = dp[k];
+        pg[3 + k] = (c0[k] + c1[k]) + (c2[k] + c3[k]);
+    }
+}
+// The workgroup's row: every thread brings six terms (zeros where it has no surfel) — the wave adds them, the four waves
+// meet in LDS, threads 0..5 store the row WRITE-THROUGH (device-scope stores: they need no release fence behind them — a
+// fence would write back everything the fused Adam has left dirty in the XCD's L2, once per workgroup: measured, +70 us
+// at 500 k surfels).  Reached by ALL 256 threads.
+__device__ __forceinline__ void pose_block_row(const float *pg, float *row)
+{
+    __shared__ float s_w[4][6];
+    float v[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = pg[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v[k] += __shfl_down(v[k], off, 64);
+    }
+    __syncthreads();     // (a previous keyframe's row has been read)
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_w[threadIdx.x >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 6)
+        __hip_atomic_store(row + threadIdx.x, (s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + (s_w[2][threadIdx.x] + s_w[3][threadIdx.x]),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// After the rows: the last workgroup to arrive adds them — component c by 32 threads, thread j the rows j, j + 32, ...
+// ascending, then the 32 partial sums ascending, all in double: a fixed order whatever the schedule, so two runs on the
+// same records return the same bits.  Nobody waits for anybody; the counter is left at zero for the next launch.
+// Reached by ALL 256 threads of every surfel workgroup.
+__device__ __forceinline__ void pose_finish(const PoseOut &po, int G, int nb)
+{
+    __shared__ double s_fin[32][kPoseRow];
+    __shared__ uint32_t s_last;
+    if (threadIdx.x < 64) {
+        // the wave that stored the row (write-through, past the XCD's L2, which is not coherent with the others'): its
+        // stores complete, and only then the arrival
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (threadIdx.x == 0)
+            s_last = (__hip_atomic_fetch_add(po.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)(nb - 1)) ? 1u : 0u;
+    }
+    __syncthreads();
+    if (s_last == 0u) return;
+    // (the rows are read with device-scope loads below; the acquire on top of them costs ONE workgroup a microsecond)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int c = threadIdx.x & (kPoseRow - 1), j = threadIdx.x >> 3;
+    for (int g = 0; g < G; ++g) {
+        const float *rows = po.rows + (size_t)g * nb * kPoseRow;
+        double a = 0.0;
+        if (c < 6) {
+            // (sixteen loads in flight per thread, then added in the rows' order: this workgroup runs alone behind all the
+            //  others, so every memory round trip it waits for is on the kernel's critical path)
+            for (int b0 = j; b0 < nb; b0 += 32 * 16) {
+                float v[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const int b = b0 + 32 * u;
+                    v[u] = b < nb ? __hip_atomic_load(rows + (size_t)b * kPoseRow + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < 16; ++u) a += (double)v[u];
+            }
+        }
+        s_fin[j][c] = a;
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            double t = 0.0;
+            for (int k = 0; k < 32; ++k) t += s_fin[k][threadIdx.x];
+            po.out[g][threadIdx.x] = (float)t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(po.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The chain of one gradient record (g0..g3) through one camera: dL/d(mean, activated scale before the modifier's
 // product, opacity, normalised rotation), for the batched kernel below: the arithmetic of preprocess_bwd_kernel,
 // which keeps its own copy inline (as a shared function the compiler allocates that kernel's registers
 // differently, and its code is to stay as it is)
+template <bool POSE>
 __device__ __forceinline__ void chain_grad_record(const DevCam &cam, const SurfelGeom &g, const float4 q, const float4 g0,
                                                   const float4 g1, const float4 g2, const float4 g3, float *dm, float2 &ds,
-                                                  float &dop, float4 &dq)
+                                                  float &dop, float4 &dq, float *pg)
 {
     const float gHu[3] = { g0.x, g0.y, g0.z }, gHv[3] = { g1.x, g1.y, g1.z }, gn[3] = { g2.x, g2.y, g2.z };
     const float gnpv = g0.w, grhoc = g1.w, go = g2.w, Su = g3.x, Sv = g3.y, gcpx = g3.z, gcpy = g3.w;
@@ -520,6 +611,7 @@ __device__ __forceinline__ void chain_grad_record(const DevCam &cam, const Surfe
         dp[1] += gaz * (g.p[0] * irxy2) + gel * (-g.p[2] * g.p[1] * irr);
         dp[2] += gel * (g.rxy * irho2);
     }
+    if constexpr (POSE) pose_terms(g, dp, dTu, dTv, dTn, pg);
     matTvec(cam.R, dp, dm);
     ds = make_float2(cam.mod * dsu, cam.mod * dsv);
     dop = go;
@@ -539,10 +631,16 @@ __device__ __forceinline__ void chain_grad_record(const DevCam &cam, const Surfe
 // With af.enabled (raw mode only) the Adam update of the surfel's ten parameters follows at once:
 // the gradients never travel through HBM (af.write_grads = 0) and no separate optimiser launch
 // reads the parameters again.  The parameter pointers are therefore NOT restrict-qualified.
+// POSE: the surfels' workgroups also reduce the pose gradient (D11, above).  A thread then never leaves before the
+// workgroup's reduction (`goto pose_reduce` where the kernel returns otherwise): the body is a scope of its own for that.
+// Without POSE the kernel is what it was, instruction for instruction, and so is its argument list: the pose arguments
+// are a parameter pack that is empty then (P = PoseOut with POSE).
+__device__ __forceinline__ const PoseOut &pose_arg(const PoseOut &po) { return po; }
+template <bool POSE, typename... P>
 __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
     DevCam cam, RegArgs ra, AdamFuse af, int N, float *means, float2 *scales, float4 *rots, float *opac,
     const int *__restrict__ radii, float4 *grec, float *__restrict__ dmeans,
-    float2 *__restrict__ dscales, float4 *__restrict__ drots, float *__restrict__ dopac)
+    float2 *__restrict__ dscales, float4 *__restrict__ drots, float *__restrict__ dopac, P... pose_args)
 {
     // Passenger workgroups come FIRST in the grid: they start with the launch and run beside the surfels' blocks.  Each
     // is a chain of latencies (cold loads, barriers, a system-scope fence) with little work: at the end of the grid — or
@@ -609,7 +707,9 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
         return;
     }
     const int i = ((int)blockIdx.x - n_pub - n_ord) * 256 + threadIdx.x;
-    if (i >= N) return;
+    [[maybe_unused]] float pg[6] = { 0, 0, 0, 0, 0, 0 };
+    if (i >= N) { if constexpr (POSE) goto pose_reduce; else return; }
+    {
     float dm[3] = { 0, 0, 0 };
     float2 ds = make_float2(0, 0);
     float4 dq = make_float4(0, 0, 0, 0);
@@ -717,6 +817,7 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
             dp[1] += gaz * (g.p[0] * irxy2) + gel * (-g.p[2] * g.p[1] * irr);
             dp[2] += gel * (g.rxy * irho2);
         }
+        if constexpr (POSE) pose_terms(g, dp, dTu, dTv, dTn, pg);
         matTvec(cam.R, dp, dm);
         ds = make_float2(cam.mod * dsu, cam.mod * dsv);
         dop = go;
@@ -781,7 +882,7 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
                 o[6] = dq.x; o[7] = dq.y; o[8] = dq.z; o[9] = dq.w;
                 af.compact_idx[slot] = (uint32_t)i;
             }
-            return;
+            if constexpr (POSE) goto pose_reduce; else return;
         }
         // (the early bitmap is a superset of the non-zero gradients by construction: say so if it ever is not)
         if (dm[0] != 0.0f || dm[1] != 0.0f || dm[2] != 0.0f || dop != 0.0f || ds.x != 0.0f || ds.y != 0.0f ||
@@ -818,6 +919,14 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
         adam_one(pq.w, dq.w, mq.w, vq.w, st_r, af.c);
         rots[i] = pq; *reinterpret_cast<float4 *>(M + ir) = mq; *reinterpret_cast<float4 *>(V + ir) = vq;
     }
+    }
+pose_reduce:
+    if constexpr (POSE) {
+        const PoseOut &po = pose_arg(pose_args...);
+        const int row = (int)blockIdx.x - n_pub - n_ord;
+        pose_block_row(pg, po.rows + (size_t)row * kPoseRow);
+        pose_finish(po, 1, (int)gridDim.x - n_pub - n_ord);
+    }
 }
 
 // The same for a BATCH of keyframes (sls_mapping_step_batch): one thread per surfel reads its parameters once, chains
@@ -827,10 +936,12 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
 // Deterministic accumulation: the two-pass scheme only (the one-launch scheme runs as it in a batch).
 // Passenger workgroups first, as above: the publisher (per-keyframe loss sums, the batch's status block, its mirror,
 // the void flags), then 8 per keyframe for each keyframe's next tile-backward launch order.
+// POSE: one pose gradient per keyframe, each through that keyframe's camera (as preprocess_bwd_kernel<true>).
+template <bool POSE, typename... P>
 __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, BatchFuse bf, int N, float *means, float2 *scales,
                                                                    float4 *rots, float *opac, float *__restrict__ dmeans,
                                                                    float2 *__restrict__ dscales, float4 *__restrict__ drots,
-                                                                   float *__restrict__ dopac)
+                                                                   float *__restrict__ dopac, P... pose_args)
 {
     const AdamFuse &af = bf.af;
     const int n_ord = bf.order_T > 0 ? 8 * bf.G : 0;
@@ -907,7 +1018,16 @@ __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, B
         return;
     }
     const int i = ((int)blockIdx.x - 1 - n_ord) * 256 + threadIdx.x;
-    if (i >= N) return;
+    [[maybe_unused]] float pg[POSE ? SLS_MAX_BATCH : 1][6];
+    if constexpr (POSE) {
+#pragma unroll
+        for (int g = 0; g < SLS_MAX_BATCH; ++g) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) pg[g][k] = 0.0f;
+        }
+    }
+    if (i >= N) { if constexpr (POSE) goto pose_reduce; else return; }
+    {
     uint32_t skip = 0u;
 #pragma unroll
     for (int g = 0; g < SLS_MAX_BATCH; ++g) {
@@ -972,7 +1092,7 @@ __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, B
         float dmk[3], dopk;
         float2 dsk;
         float4 dqk;
-        chain_grad_record(kf.cam, g, q, g0, g1, g2, g3, dmk, dsk, dopk, dqk);
+        chain_grad_record<POSE>(kf.cam, g, q, g0, g1, g2, g3, dmk, dsk, dopk, dqk, pg[POSE ? kg : 0]);
         dm[0] += dmk[0]; dm[1] += dmk[1]; dm[2] += dmk[2];
         ds.x += dsk.x; ds.y += dsk.y;
         dop += dopk;
@@ -1023,6 +1143,18 @@ __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, B
         adam_one(pq.z, dq.z, mq.z, vq.z, st_r, af.c);
         adam_one(pq.w, dq.w, mq.w, vq.w, st_r, af.c);
         rots[i] = pq; *reinterpret_cast<float4 *>(M + ir) = mq; *reinterpret_cast<float4 *>(V + ir) = vq;
+    }
+    }
+pose_reduce:
+    if constexpr (POSE) {
+        const PoseOut &po = pose_arg(pose_args...);
+        const int row = (int)blockIdx.x - 1 - n_ord, nb = (int)gridDim.x - 1 - n_ord;
+#pragma unroll
+        for (int g = 0; g < SLS_MAX_BATCH; ++g) {
+            if (g >= bf.G) break;
+            pose_block_row(pg[g], po.rows + ((size_t)g * nb + row) * kPoseRow);
+        }
+        pose_finish(po, bf.G, nb);
     }
 }
 
@@ -1080,7 +1212,7 @@ int launch_preprocess_fwd(const DevCam &cam, int raw, float smax, float pen, flo
 int launch_preprocess_bwd(const DevCam &cam, int raw, float smax, float pen, int N, const float *means,
                           const float *scales, const float *rots, const float *opac, const int32_t *radii,
                           const float *grec, float *dmeans, float *dscales, float *drots, float *dopac,
-                          hipStream_t st, const AdamFuse *fuse)
+                          hipStream_t st, const AdamFuse *fuse, const PoseOut *pose)
 {
     const int nb = (N + 255) / 256;
     RegArgs ra;
@@ -1093,25 +1225,35 @@ int launch_preprocess_bwd(const DevCam &cam, int raw, float smax, float pen, int
     af.publisher = (af.loss_partials || af.reg_accum || af.void_flags || af.status_mirror || af.grad_bitmap) ? 1 : 0;
     ScopedTimer tm(T_PREPROCESS_BWD, st);
     // (parameters are only written when af.enabled, which the caller sets for its own mutable tensors)
-    hipLaunchKernelGGL(preprocess_bwd_kernel, dim3(nb + af.publisher + (af.order_out ? 8 : 0)), dim3(256), 0, st, cam, ra, af, N, const_cast<float *>(means),
-                       (float2 *)const_cast<float *>(scales), (float4 *)const_cast<float *>(rots),
-                       const_cast<float *>(opac), radii, (float4 *)const_cast<float *>(grec), dmeans, (float2 *)dscales,
-                       (float4 *)drots, dopac);
+    if (pose)
+        hipLaunchKernelGGL((preprocess_bwd_kernel<true, PoseOut>), dim3(nb + af.publisher + (af.order_out ? 8 : 0)), dim3(256), 0, st, cam, ra, af, N,
+                           const_cast<float *>(means), (float2 *)const_cast<float *>(scales), (float4 *)const_cast<float *>(rots),
+                           const_cast<float *>(opac), radii, (float4 *)const_cast<float *>(grec), dmeans, (float2 *)dscales,
+                           (float4 *)drots, dopac, *pose);
+    else
+        hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3(nb + af.publisher + (af.order_out ? 8 : 0)), dim3(256), 0, st, cam, ra, af, N,
+                           const_cast<float *>(means), (float2 *)const_cast<float *>(scales), (float4 *)const_cast<float *>(rots),
+                           const_cast<float *>(opac), radii, (float4 *)const_cast<float *>(grec), dmeans, (float2 *)dscales,
+                           (float4 *)drots, dopac);
     SLS_LAUNCH_CHECK("preprocess_bwd_kernel");
     return SLS_OK;
 }
 
 int launch_preprocess_bwd_batch(float smax, float pen, int N, float *means, float *scales, float *rots, float *opac,
                                 float *dmeans, float *dscales, float *drots, float *dopac, const BatchFuse &bf,
-                                hipStream_t st)
+                                hipStream_t st, const PoseOut *pose)
 {
     const int nb = (N + 255) / 256;
     RegArgs ra;
     ra.raw = 1; ra.smax = smax; ra.pen = pen; ra.reg_out = nullptr; ra.status_clear = nullptr;
     ra.zero_words = nullptr; ra.n_zero_words = 0;
     ScopedTimer tm(T_PREPROCESS_BWD, st);
-    hipLaunchKernelGGL(preprocess_bwd_batch_kernel, dim3(nb + 1 + (bf.order_T > 0 ? 8 * bf.G : 0)), dim3(256), 0, st, ra, bf, N,
-                       means, (float2 *)scales, (float4 *)rots, opac, dmeans, (float2 *)dscales, (float4 *)drots, dopac);
+    if (pose)
+        hipLaunchKernelGGL((preprocess_bwd_batch_kernel<true, PoseOut>), dim3(nb + 1 + (bf.order_T > 0 ? 8 * bf.G : 0)), dim3(256), 0, st, ra, bf, N,
+                           means, (float2 *)scales, (float4 *)rots, opac, dmeans, (float2 *)dscales, (float4 *)drots, dopac, *pose);
+    else
+        hipLaunchKernelGGL(preprocess_bwd_batch_kernel<false>, dim3(nb + 1 + (bf.order_T > 0 ? 8 * bf.G : 0)), dim3(256), 0, st, ra, bf, N,
+                           means, (float2 *)scales, (float4 *)rots, opac, dmeans, (float2 *)dscales, (float4 *)drots, dopac);
     SLS_LAUNCH_CHECK("preprocess_bwd_batch_kernel");
     return SLS_OK;
 }

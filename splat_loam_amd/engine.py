@@ -170,6 +170,12 @@ class MappingEngine:
         self.exchange_at_world_1 = False  # take the keyframe-parallel path (collectives + separate Adam) in a 1-rank group too
         self.comm_events = None           # list -> (start, after exchange, after Adam[, after all-gather]) events per step
         self._last_call = None            # (arguments, config) of the last sls_mapping_step: phase 2 repeats them
+        # pose gradient: dL/dxi of the pixel loss for the left perturbation of the keyframe's
+        # view transform — (6,) [v | w] after step(..., pose_grad=True) / pose_step(), (G, 6) after step_batch(...,
+        # pose_grad=True); views of one device buffer, valid until the next such call
+        self.pose_grad = None
+        self._pose_buf = torch.zeros((_abi.SLS_MAX_BATCH, 6), dtype=torch.float32, device=self.dev)
+        self._pose_scratch = None
 
     # views of the flat gradient bucket in the optimiser's group order (single GPU: only filled
     # when keep_grads is set; keyframe-parallel mode always fills and all-reduces it)
@@ -294,6 +300,13 @@ class MappingEngine:
             self._det_prev[id(camera)] = dent
         return dent, first_visit
 
+    def _pose_args(self, cfg, slots):
+        """The pose gradient's scratch (zeroed once; every call leaves it ready) into `cfg`."""
+        need = int(_abi.lib().sls_pose_grad_scratch_bytes(self.N)) * int(slots)
+        if self._pose_scratch is None or self._pose_scratch.numel() < need:
+            self._pose_scratch = torch.zeros((need,), dtype=torch.uint8, device=self.dev)
+        cfg.pose_scratch, cfg.pose_scratch_bytes = self._pose_scratch.data_ptr(), int(self._pose_scratch.numel())
+
     def _params(self):
         m = self.model
         ps = (m._xyz, m._scaling, m._rotation, m._opacity)
@@ -302,7 +315,8 @@ class MappingEngine:
                 raise RuntimeError("model parameters must stay contiguous float32 of the engine's size")
         return ps
 
-    def _enqueue(self, camera, apply_adam, with_regulariser, status=None, mirror=None, allow_reuse=True, phase=0):
+    def _enqueue(self, camera, apply_adam, with_regulariser, status=None, mirror=None, allow_reuse=True, phase=0,
+                 pose_grad=False):
         lib = _abi.lib()
         H, W = int(camera.image_height), int(camera.image_width)
         settings = GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix)
@@ -328,6 +342,9 @@ class MappingEngine:
         # keyframe-parallel mode: the void bits leave the step as two floats behind the gradient bucket
         cfg.void_flags_out = None if (apply_adam or self._dp is not None) else self.grads.data_ptr() + 4 * 10 * self.N
         cfg.phase = int(phase)
+        if pose_grad:
+            cfg.pose_grad = self._pose_buf.data_ptr()
+            self._pose_args(cfg, 1)
         args = (C.byref(ce.cam), self.N, xyz.data_ptr(), scaling.data_ptr(), rotation.data_ptr(), opacity.data_ptr(),
                 self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.t + 1,
                 aux.gt.data_ptr(), aux.valid.data_ptr(), aux.n_valid, ce.col_cs.data_ptr(), ce.row_cs.data_ptr(),
@@ -404,7 +421,7 @@ class MappingEngine:
                 "loss": float(f[5]) + float(f[6]), "sums": [float(f[2]), float(f[3]), float(f[4])]}
 
     @torch.no_grad()
-    def step(self, camera, group=None, sync: bool = True):
+    def step(self, camera, group=None, sync: bool = True, pose_grad: bool = False):
         """One mapping iteration on `camera`.  Returns the status dict (sync=True)
         or None (sync=False: fire-and-forget — nobody reads the status, so an iteration
         that overflowed its instance buffers is DROPPED, not repeated (its Adam update
@@ -414,8 +431,17 @@ class MappingEngine:
         sync="lagged": the iteration is enqueued BEFORE the status of
         the previous one is read, so the GPU queue never runs dry while the host
         waits for a loss value; returns the PREVIOUS iteration's status (None on
-        the first call) — finish with flush()."""
+        the first call) — finish with flush().
+        pose_grad=True (sync=True, one process): the iteration also leaves dL/dxi of the keyframe's pixel loss in
+        `self.pose_grad` ((6,) device tensor, [v | w]) — the gradient at the parameters the
+        iteration STARTED from; valid when the returned status is not void (a void iteration is repeated, as ever).
+        Over a process group it raises: nothing about the pose is exchanged between ranks, and that path is not covered."""
         sharded = self._sharded(group)
+        if pose_grad:
+            if sync is not True:
+                raise ValueError("pose_grad needs sync=True: the gradient belongs to the iteration whose status is returned")
+            if sharded:
+                raise NotImplementedError("pose_grad is served on the single-process path only")
         if self._dp is not None and not sharded:
             raise RuntimeError("this engine's optimiser state is sharded over a process group (dp_mode rs_ag): "
                                "it cannot take a single-process step")
@@ -429,7 +455,7 @@ class MappingEngine:
         reuse_ok = sync is not False
         while True:
             if not sharded:
-                self._enqueue(camera, apply_adam=True, with_regulariser=True, allow_reuse=reuse_ok)
+                self._enqueue(camera, apply_adam=True, with_regulariser=True, allow_reuse=reuse_ok, pose_grad=pose_grad)
             else:
                 rank = dist.get_rank(group)
                 self._ensure_dp(group)
@@ -446,6 +472,7 @@ class MappingEngine:
             if not st["overflow"]:
                 self.t += 1
                 self.last = st
+                self.pose_grad = self._pose_buf[0] if pose_grad else None
                 return st
             # repeat the iteration (parameters were not touched): with the full sort, and with more
             # room if the instance buffers were too small
@@ -459,6 +486,30 @@ class MappingEngine:
                     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
                     need = int(t.item())
                 self.capacity = int(max(need, self.capacity) * self.capacity_factor) + 1024
+                self.workspace = None
+
+    @torch.no_grad()
+    def pose_step(self, camera):
+        """One iteration on `camera` with the MODEL FROZEN: forward, pixel loss, backward — no Adam, no scale regulariser;
+        parameters, moments and the step count stay as they are.  Leaves dL/dxi in `self.pose_grad` ((6,), [v | w]) and
+        returns the status dict (its "loss" is the pixel loss).  What a model-frozen pose refinement iterates
+        (pose.refine_pose); a void iteration is repeated as step() repeats one."""
+        if self._dp is not None or self._sx is not None:
+            raise RuntimeError("this engine's gradient bucket is laid out for a keyframe-parallel exchange: pose_step "
+                               "needs the single-process engine")
+        if self._lag_pending is not None:
+            self.flush()
+        while True:
+            self._enqueue(camera, apply_adam=False, with_regulariser=False, pose_grad=True)
+            st = self._read_status()
+            if not st["overflow"]:
+                self.pose_grad = self._pose_buf[0]
+                return st
+            if st["too_small"] or st["resort_failed"]:
+                self._forget_order(camera, failed_repair=st["resort_failed"])
+            self.stats[self._void_reason(st)] += 1
+            if st["too_small"]:
+                self.capacity = int(max(st["R"], self.capacity) * self.capacity_factor) + 1024
                 self.workspace = None
 
     def _ensure_batch_workspace(self, G, H, W, capacity):
@@ -480,7 +531,7 @@ class MappingEngine:
         base = b["buf"].data_ptr()
         return b, (base + 255) & ~255, b["buf"].numel() - 256
 
-    def _enqueue_batch(self, cameras, apply_adam, with_regulariser, allow_reuse=True):
+    def _enqueue_batch(self, cameras, apply_adam, with_regulariser, allow_reuse=True, pose_grad=False):
         """sls_mapping_step_batch on `cameras` with the keyframes' own cached orders (as _enqueue)."""
         lib = _abi.lib()
         G = len(cameras)
@@ -510,6 +561,7 @@ class MappingEngine:
             k.block_order = ent[3].data_ptr() if self.inline_loss_stage else None
             # (deterministic = 2 runs as 1 in a batch; the keyframe's predictions are still rewritten for its step())
             k.det_prev = self._det_prev_for(camera)[0][0].data_ptr() if self.deterministic == 2 else None
+            k.pose_grad = self._pose_buf[g].data_ptr() if pose_grad else None
             keep.append((ce, aux))
             reuse_used.append(int(reuse))
         self._enq += 1
@@ -522,6 +574,8 @@ class MappingEngine:
         cfg.workspace_ready = 1 if G <= b["ready"] else 0
         b["ready"] = max(b["ready"], G)
         cfg.void_flags_out = None if apply_adam else self.grads.data_ptr() + 4 * 10 * self.N
+        if pose_grad:
+            self._pose_args(cfg, G)
         self.last_batch_reuse = reuse_used
         _abi.check(lib.sls_mapping_step_batch(G, kfs, self.N, xyz.data_ptr(), scaling.data_ptr(), rotation.data_ptr(),
                                               opacity.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
@@ -532,14 +586,20 @@ class MappingEngine:
         return b["status"]
 
     @torch.no_grad()
-    def step_batch(self, cameras, group=None, sync: bool = True):
+    def step_batch(self, cameras, group=None, sync: bool = True, pose_grad: bool = False):
         """ONE mapping iteration over up to eight distinct keyframes of the same size: the keyframes' pixel-loss gradients
         summed, the scale regulariser once, one Adam update (`self.t` + 1).  Returns the batch's status dict, with the
         keyframes' own statuses (R, bits, loss sums) under "keyframes" (sync=True), or None (sync=False, as step()).
         A void keyframe voids the batch; it is repeated as step() repeats an iteration.
         With `group` (dp_mode "allreduce"), every rank batches ITS keyframes and the summed gradient is all-reduced over
-        the ranks before the guarded Adam: 8 keyframes on 2 or 4 GPUs; the regulariser counts on rank 0 only."""
+        the ranks before the guarded Adam: 8 keyframes on 2 or 4 GPUs; the regulariser counts on rank 0 only.
+        pose_grad=True (sync=True, one process): `self.pose_grad` is (G, 6) afterwards, row g = dL_g/dxi of keyframe g's
+        pixel loss through its own camera (as step()); what to do with the G gradients is the caller's."""
         cams = list(cameras)
+        if pose_grad and sync is not True:
+            raise ValueError("pose_grad needs sync=True: the gradients belong to the iteration whose status is returned")
+        if pose_grad and self._sharded(group):
+            raise NotImplementedError("pose_grad is served on the single-process path only")
         if sync == "lagged":
             raise ValueError("step_batch has no lagged mode")
         if not 1 <= len(cams) <= _abi.SLS_MAX_BATCH:
@@ -559,7 +619,8 @@ class MappingEngine:
         reuse_ok = sync is not False
         while True:
             if not sharded:
-                status = self._enqueue_batch(cams, apply_adam=True, with_regulariser=True, allow_reuse=reuse_ok)
+                status = self._enqueue_batch(cams, apply_adam=True, with_regulariser=True, allow_reuse=reuse_ok,
+                                             pose_grad=pose_grad)
             else:
                 self._ensure_dp(group)
                 status = self._enqueue_batch(cams, apply_adam=False, with_regulariser=(dist.get_rank(group) == 0),
@@ -574,6 +635,7 @@ class MappingEngine:
             if not st["overflow"]:
                 self.t += 1
                 self.last = st
+                self.pose_grad = self._pose_buf[:len(cams)] if pose_grad else None
                 return st
             for cam, kst in zip(cams, st["keyframes"]):
                 if kst["too_small"] or kst["resort_failed"]:
@@ -913,6 +975,7 @@ class MappingEngine:
         self._orders.clear()                         # surfel indices changed: every kept depth order is void
         self._det_prev.clear()                       # ... and so is every predicted scale
         self._det_two_pass_next = True
+        self._pose_scratch = None                    # (sized by N)
         self._params()
 
     @torch.no_grad()

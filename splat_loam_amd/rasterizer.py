@@ -330,11 +330,45 @@ def deterministic_mode() -> bool:
     return os.environ.get("SLS_DETERMINISTIC", "0") in ("1", "2")
 
 
-def rasterize_backward(state: ForwardState, means3D, scales, rotations, dL_dallmap, deterministic=None):
+_POSE_SCRATCH: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
+
+
+def pose_scratch(dev, N: int, slots: int = 1) -> torch.Tensor:
+    """The pose gradient's scratch (sls_pose_grad_scratch_bytes x slots): zeroed once, left ready by every call — one
+    buffer per (device, stream, size), since calls on one stream follow one another."""
+    key = (str(dev), _stream(dev), int(N), int(slots))
+    buf = _POSE_SCRATCH.get(key)
+    if buf is None:
+        nbytes = int(_abi.lib().sls_pose_grad_scratch_bytes(int(N))) * int(slots)
+        buf = _POSE_SCRATCH[key] = torch.zeros((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        while len(_POSE_SCRATCH) > 8:
+            _POSE_SCRATCH.popitem(last=False)
+    else:
+        _POSE_SCRATCH.move_to_end(key)
+    return buf
+
+
+def check_pose_delta(pose_delta, dev) -> None:
+    """`pose_delta`: a (6,) float32 tensor on the render's device.  Its values are not read (the render is AT
+    `viewmatrix`; no host sync to look at them): it is the leaf whose .grad receives dL/dxi."""
+    if not isinstance(pose_delta, torch.Tensor):
+        raise TypeError("pose_delta must be a torch.Tensor")
+    if tuple(pose_delta.shape) != (6,):
+        raise ValueError(f"pose_delta must have shape (6,) [v | w], got {tuple(pose_delta.shape)}")
+    if pose_delta.dtype != torch.float32:
+        raise ValueError(f"pose_delta must be float32, got {pose_delta.dtype}")
+    if pose_delta.device != dev:
+        raise ValueError(f"pose_delta is on {pose_delta.device}, the surfels on {dev}")
+
+
+def rasterize_backward(state: ForwardState, means3D, scales, rotations, dL_dallmap, deterministic=None, pose_grad=None):
+    """`pose_grad` (optional, (6,) float32 device tensor): receives dL/dxi (sls_backward_pose / sls_backward_det_pose)."""
     lib = _abi.lib()
     dev = means3D.device
     N = state.N
     dL = _f32c(dL_dallmap)
+    ps = pose_scratch(dev, N) if pose_grad is not None else None
+    pose_args = (pose_grad.data_ptr(), ps.data_ptr(), ps.numel()) if pose_grad is not None else (None, None, 0)
     det = deterministic_mode() if deterministic is None else deterministic
     nbytes = int(lib.sls_backward_det_scratch_bytes(N)) if det else 0
     out = _Arena(dev, (("dmeans", "f32", (N, 3)), ("dscales", "f32", (N, 2)), ("drots", "f32", (N, 4)), ("dopac", "f32", (N, 1)))
@@ -342,21 +376,21 @@ def rasterize_backward(state: ForwardState, means3D, scales, rotations, dL_dallm
     ce, a1, a2 = state.cam, state.a1, state.a2
     bm = a2.ptr("block_masks") if "block_masks" in a2.spec else None
     if det:
-        _abi.check(lib.sls_backward_det(C.byref(ce.cam), N, state.R, means3D.data_ptr(), scales.data_ptr(),
-                                        rotations.data_ptr(), state.radii.data_ptr(), a1.ptr("rec"),
-                                        a2.ptr("ranges"), state.vals_ptr, state.vals_stride, ce.col_cs.data_ptr(),
-                                        ce.row_cs.data_ptr(), a2.ptr("pix_state"), a2.ptr("pix_contrib"),
-                                        dL.data_ptr(), out.ptr("dmeans"), out.ptr("dscales"), out.ptr("drots"),
-                                        out.ptr("dopac"), bm, state.block_masks_shape,
-                                        out.ptr("scratch"), nbytes, _stream(dev)), "sls_backward_det")
+        _abi.check(lib.sls_backward_det_pose(C.byref(ce.cam), N, state.R, means3D.data_ptr(), scales.data_ptr(),
+                                             rotations.data_ptr(), state.radii.data_ptr(), a1.ptr("rec"),
+                                             a2.ptr("ranges"), state.vals_ptr, state.vals_stride, ce.col_cs.data_ptr(),
+                                             ce.row_cs.data_ptr(), a2.ptr("pix_state"), a2.ptr("pix_contrib"),
+                                             dL.data_ptr(), out.ptr("dmeans"), out.ptr("dscales"), out.ptr("drots"),
+                                             out.ptr("dopac"), bm, state.block_masks_shape,
+                                             out.ptr("scratch"), nbytes, *pose_args, _stream(dev)), "sls_backward_det")
         return out.view("dmeans"), out.view("dscales"), out.view("drots"), out.view("dopac"), None
-    _abi.check(lib.sls_backward(C.byref(ce.cam), N, state.R, means3D.data_ptr(), scales.data_ptr(),
-                                rotations.data_ptr(), state.radii.data_ptr(), a1.ptr("rec"),
-                                a2.ptr("ranges"), state.vals_ptr, state.vals_stride, ce.col_cs.data_ptr(),
-                                ce.row_cs.data_ptr(), a2.ptr("pix_state"), a2.ptr("pix_contrib"),
-                                dL.data_ptr(), out.ptr("grec"), out.ptr("dmeans"), out.ptr("dscales"),
-                                out.ptr("drots"), out.ptr("dopac"), bm,
-                                state.block_masks_shape, _stream(dev)),
+    _abi.check(lib.sls_backward_pose(C.byref(ce.cam), N, state.R, means3D.data_ptr(), scales.data_ptr(),
+                                     rotations.data_ptr(), state.radii.data_ptr(), a1.ptr("rec"),
+                                     a2.ptr("ranges"), state.vals_ptr, state.vals_stride, ce.col_cs.data_ptr(),
+                                     ce.row_cs.data_ptr(), a2.ptr("pix_state"), a2.ptr("pix_contrib"),
+                                     dL.data_ptr(), out.ptr("grec"), out.ptr("dmeans"), out.ptr("dscales"),
+                                     out.ptr("drots"), out.ptr("dopac"), bm,
+                                     state.block_masks_shape, *pose_args, _stream(dev)),
                "sls_backward")
     return out.view("dmeans"), out.view("dscales"), out.view("drots"), out.view("dopac"), out.view("grec")
 
@@ -544,18 +578,20 @@ def rasterize_forward_ws(settings: GaussianRasterizationSettings, means3D, opaci
     return s
 
 
-def rasterize_backward_ws(state: WsState, means3D, scales, rotations, dL_dallmap):
+def rasterize_backward_ws(state: WsState, means3D, scales, rotations, dL_dallmap, pose_grad=None):
     lib = _abi.lib()
     dev = means3D.device
     N, ce = state.N, state.cam
     dL = _f32c(dL_dallmap)
+    ps = pose_scratch(dev, N) if pose_grad is not None else None
+    pose_args = (pose_grad.data_ptr(), ps.data_ptr(), ps.numel()) if pose_grad is not None else (None, None, 0)
     out = _Arena(dev, (("dmeans", "f32", (N, 3)), ("dscales", "f32", (N, 2)), ("drots", "f32", (N, 4)), ("dopac", "f32", (N, 1))))
     try:
-        _abi.check(lib.sls_backward_ws(C.byref(ce.cam), N, means3D.data_ptr(), scales.data_ptr(), rotations.data_ptr(),
-                                       state.radii.data_ptr(), ce.col_cs.data_ptr(), ce.row_cs.data_ptr(), dL.data_ptr(),
-                                       state.cap, state.ws_ptr, state.ws_bytes, state.list_ptr, state.stride, state.shape,
-                                       state.block_order.data_ptr(), out.ptr("dmeans"), out.ptr("dscales"), out.ptr("drots"), out.ptr("dopac"),
-                                       _stream(dev)), "sls_backward_ws")
+        _abi.check(lib.sls_backward_ws_pose(C.byref(ce.cam), N, means3D.data_ptr(), scales.data_ptr(), rotations.data_ptr(),
+                                            state.radii.data_ptr(), ce.col_cs.data_ptr(), ce.row_cs.data_ptr(), dL.data_ptr(),
+                                            state.cap, state.ws_ptr, state.ws_bytes, state.list_ptr, state.stride, state.shape,
+                                            state.block_order.data_ptr(), out.ptr("dmeans"), out.ptr("dscales"), out.ptr("drots"), out.ptr("dopac"),
+                                            *pose_args, _stream(dev)), "sls_backward_ws")
     except Exception:
         state.entry.ready = False         # (whatever state the records are in: the next forward clears them)
         raise
@@ -633,15 +669,18 @@ def _autograd_policy() -> None:
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, raster_settings):
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3D_precomp, raster_settings, pose_delta=None):
         if scales is None or rotations is None:
             raise ValueError("scales and rotations are required")
+        if pose_delta is not None:          # (every argument error before the first launch)
+            check_pose_delta(pose_delta, means3D.device)
         m, o, s_, r = map(_f32c, (means3D.detach(), opacities.detach(), scales.detach(), rotations.detach()))
         for name, t in (("means3D", m), ("opacities", o), ("scales", s_), ("rotations", r)):
             _need_cuda(t, name)
         if m.shape != (m.shape[0], 3) or s_.shape != (m.shape[0], 2) or r.shape != (m.shape[0], 4) or o.numel() != m.shape[0]:
             raise ValueError("expected means3D (N,3), scales (N,2), rotations (N,4), opacities (N,1)")
-        needs_grad = any(ctx.needs_input_grad[:5])
+        ctx.want_pose = pose_delta is not None and ctx.needs_input_grad[7]
+        needs_grad = any(ctx.needs_input_grad[:5]) or ctx.want_pose
         if needs_grad:
             _autograd_policy()
         ctx.debug = bool(raster_settings.debug)
@@ -673,16 +712,18 @@ class _RasterizeGaussians(torch.autograd.Function):
             # a second walk of the graph (retain_graph=True): the workspace went back with the first one.  The forward is
             # repeated through the staged calls, whose buffers this node then owns — later walks reuse them
             st = ctx.state = rasterize_forward(ctx.settings, m, o, s_, r)
+        # (the pose gradient leaves the projection's backward itself: six floats)
+        pose = torch.empty((6,), dtype=torch.float32, device=m.device) if ctx.want_pose else None
         if isinstance(st, WsState):
             try:
-                dmeans, dscales, drots, dopac = rasterize_backward_ws(st, m, s_, r, grad_allmap)
+                dmeans, dscales, drots, dopac = rasterize_backward_ws(st, m, s_, r, grad_allmap, pose_grad=pose)
             finally:
                 ctx.lease.release()
         else:
-            dmeans, dscales, drots, dopac, _ = rasterize_backward(st, m, s_, r, grad_allmap)
+            dmeans, dscales, drots, dopac, _ = rasterize_backward(st, m, s_, r, grad_allmap, pose_grad=pose)
         if ctx.debug:
             torch.cuda.synchronize(m.device)
-        return dmeans, None, dopac, dscales, drots, None, None
+        return dmeans, None, dopac, dscales, drots, None, None, pose
 
 
 # run-time bindings that wait for their target to exist: fused_mapper (SLS_FUSED_MAPPER=1: slam/mapper.py imports this
@@ -708,11 +749,15 @@ class GaussianRasterizer(nn.Module):
         return vis.bool()
 
     def forward(self, means3D, means2D, opacities, scales: Optional[torch.Tensor] = None,
-                rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None):
+                rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None,
+                pose_delta: Optional[torch.Tensor] = None):
+        """`pose_delta` (extension, optional): a (6,) float32 device tensor that requires grad — the twist xi = (v, w) of
+        the LEFT perturbation T_vw(xi) = Exp(xi) T_vw of the view transform.  The render is at `viewmatrix` (the values
+        of pose_delta are not read); pose_delta.grad receives dL/dxi at xi = 0."""
         if (scales is None or rotations is None) == (cov3D_precomp is None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         if cov3D_precomp is not None:
             # the precomputed frame carries no gradient (autograd returns None for it, as for means2D)
             scales, rotations = frame_from_precomp(cov3D_precomp.detach())
         return _RasterizeGaussians.apply(means3D, means2D, opacities, scales, rotations, None,
-                                         self.raster_settings)
+                                         self.raster_settings, pose_delta)

@@ -60,11 +60,14 @@ def depth_to_normal(camera, depth: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def render(camera, model, depth_ratio: float = 0.0, rasterizer_cls=GaussianRasterizer) -> dict:
+def render(camera, model, depth_ratio: float = 0.0, rasterizer_cls=GaussianRasterizer, pose_delta=None) -> dict:
     """Same contract as gaussian_renderer.render (gaussian_renderer/__init__.py:11-93).
     `rasterizer_cls` exists so the CPU tests can drive this function with the
     checker's rasterizer; the default (and only product path) is the HIP one, which
-    refuses CPU tensors."""
+    refuses CPU tensors.
+    `pose_delta` (extension): see GaussianRasterizer.forward — its .grad receives dL/dxi for the left perturbation of
+    camera.world_view_transform, chained through allmap (what the mapper's and the tracker's losses depend on; the
+    rotation that takes rend_normal and surf_normal to the world frame together is a constant of this call)."""
     settings = GaussianRasterizationSettings(
         image_height=int(camera.image_height), image_width=int(camera.image_width), scale_modifier=1.0,
         viewmatrix=camera.world_view_transform, projmatrix=camera.projection_matrix,
@@ -72,8 +75,9 @@ def render(camera, model, depth_ratio: float = 0.0, rasterizer_cls=GaussianRaste
     rasterizer = rasterizer_cls(raster_settings=settings)
     means3D = model.get_xyz
     means2D = torch.zeros_like(means3D, dtype=torch.float32)
+    extra = {} if pose_delta is None else {"pose_delta": pose_delta}
     radii, allmap = rasterizer(means3D=means3D, means2D=means2D, opacities=model.get_opacity,
-                               scales=model.get_scaling, rotations=model.get_rotation, cov3D_precomp=None)
+                               scales=model.get_scaling, rotations=model.get_rotation, cov3D_precomp=None, **extra)
     if allmap.is_cuda and not allmap.requires_grad and rasterizer_cls is GaussianRasterizer:
         # nobody differentiates this call (Mapper.densify, the tracker's target, the logger, meshing): the maps in ONE launch
         return render_maps(camera, settings, allmap, depth_ratio, radii=radii, means2D=means2D)

@@ -12,7 +12,8 @@ for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_V
            "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC SQ_LDS_BANK_CONFLICT SQ_LDS_ACTIVE"; do
   g=$((g+1))
   rm -rf /tmp/pmcsq_$g
-  timeout 120 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pmcsq_$g -o p -- python tools/one_iter.py 4 > /tmp/pmcsq_$g.log 2>&1
+  # (a pass that fails ends the script: nothing more is started on the GPU behind it)
+  timeout -k 10 120 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pmcsq_$g -o p -- python tools/one_iter.py 4 > /tmp/pmcsq_$g.log 2>&1 || { echo "counter pass $g failed"; tail -n 20 /tmp/pmcsq_$g.log; exit 1; }
   python - "$g" <<'PY' >> gpurun_out/pmc_sq.txt
 import csv, collections, sys, glob
 g = sys.argv[1]
