@@ -317,6 +317,31 @@ int sls_render_maps(int H, int W, const float *allmap, const float *view_rot9, c
 int sls_densify_weights(int H, int W, const float *image_depth, const uint8_t *valid, const float *rend_alpha,
                         float threshold_opacity, float *weights_out, uint32_t *stats_out, void *stream);
 
+/* Mapper.densify's draw on the device: sls_densify_weights, then WHICH candidates become surfels — weighted sampling
+ * without replacement, proportional to the weights (the distribution of torch.multinomial(replacement=False)), as an
+ * exponential race whose every random word is a pure function of (pixel, seed, draw_index): include/sls_draw_math.h
+ * states the arithmetic, DESIGN.md section 2 the selection (the k = (uint32)(percentage * #candidates) smallest of
+ * (key bits, pixel); nothing where k < 2, the gradient's maximum is not > 0 or sum / maximum <= 1e-5).  The same
+ * (weights, seed, draw_index) give the same pixels on every run and device.
+ *   weights_out (H*W floats), stats_out[0..2]: as sls_densify_weights leaves them.
+ *   pixels_out (capacity H*W int64): the n_drawn drawn pixels, row-major indices in ascending order (what torch's
+ *       nonzero() of the drawn mask holds: sls_densify_rows takes them as they are); the rest is not written.
+ *   stats_out (8 words, device): [#candidates, gradient maximum bits, weight sum bits, n_drawn, k, bits of the k-th
+ *       key, how many pixels of exactly that key are drawn, 1].
+ *   stats_mirror (optional, PINNED HOST, 8 words): the same block written by the device as soon as n_drawn is known
+ *       (words 5 and 6 still 0); arm words 0 and 7 with a value the device never writes (0xFFFFFFFF) and wait with
+ *       sls_wait_status_mirror — the one host read of the draw.
+ *   scratch: sls_densify_draw_scratch_bytes(H, W) bytes, 16-byte aligned.
+ * Serves H*W <= SLS_DENSIFY_DRAW_MAX_PIXELS (the selection is one workgroup over keys resident in L2); SLS_E_UNSUPPORTED
+ * beyond.  SLS_E_ARG before anything is enqueued: a null pointer (rend_alpha and stats_mirror may be null), a
+ * non-positive size, percentage outside [0, 1] or NaN, too little scratch. */
+#define SLS_DENSIFY_DRAW_MAX_PIXELS 262144
+size_t sls_densify_draw_scratch_bytes(int H, int W);
+int sls_densify_draw(int H, int W, const float *image_depth, const uint8_t *valid, const float *rend_alpha,
+                     float threshold_opacity, double percentage, uint64_t seed, uint32_t draw_index, float *weights_out,
+                     int64_t *pixels_out, uint32_t *stats_out, uint32_t *stats_mirror, void *scratch, size_t scratch_bytes,
+                     void *stream);
+
 /* Mapper.densify's new rows (slam/mapper.py:104-137) for n drawn pixels (row-major indices, int64 as torch's nonzero
  * leaves them): centres = the measured points in the model frame, rotations = unit quaternions (w,x,y,z; w >= 0) whose
  * third axis is the measured normal (utils/general_utils.py:85-187).  All pointers DEVICE; cam_to_model16 =

@@ -101,6 +101,10 @@ int launch_densify_weights(int H, int W, const float *depth, const uint8_t *vali
                            uint32_t *stats, hipStream_t st);
 int launch_densify_rows(int n, int H, int W, const int64_t *pix, const float *depth, const float *normal, const float *col_h,
                         const float *row_h, const float *c2w, const float *mTf, float *xyz, float *quat, hipStream_t st);
+size_t densify_draw_scratch_bytes(int H, int W);
+int launch_densify_draw(int H, int W, const float *depth, const uint8_t *valid, const float *alpha, float thr, double percentage,
+                        uint64_t seed, uint32_t draw_index, float *w_out, int64_t *pixels_out, uint32_t *stats,
+                        uint32_t *stats_mirror, void *scratch, hipStream_t st);
 size_t knn_scratch_bytes(int M);
 int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratch_bytes, hipStream_t st, int Mq = -1);
 
@@ -376,6 +380,27 @@ int sls_densify_rows(int n, int H, int W, const int64_t *pixels, const float *im
                     xyz_out && quat_out, "null pointer");
     return launch_densify_rows(n, H, W, pixels, image_depth, image_normal, col_cs_half, row_cs_half, cam_to_model16,
                                model_T_frame16, xyz_out, quat_out, (hipStream_t)stream);
+}
+
+size_t sls_densify_draw_scratch_bytes(int H, int W) { return (H > 0 && W > 0) ? densify_draw_scratch_bytes(H, W) : 0; }
+
+int sls_densify_draw(int H, int W, const float *image_depth, const uint8_t *valid, const float *rend_alpha,
+                     float threshold_opacity, double percentage, uint64_t seed, uint32_t draw_index, float *weights_out,
+                     int64_t *pixels_out, uint32_t *stats_out, uint32_t *stats_mirror, void *scratch, size_t scratch_bytes,
+                     void *stream)
+{
+    SLS_REQUIRE(H > 0 && W > 0, "bad size");
+    SLS_REQUIRE(image_depth && valid && weights_out && pixels_out && stats_out && scratch, "null pointer");
+    SLS_REQUIRE(percentage >= 0.0 && percentage <= 1.0, "percentage outside [0, 1]");      // (false for a NaN too)
+    if ((uint64_t)H * (uint64_t)W > SLS_DENSIFY_DRAW_MAX_PIXELS) {
+        set_error("sls_densify_draw: %d x %d pixels, the selection serves at most %d (one workgroup, keys resident in L2); "
+                  "draw with torch.multinomial over sls_densify_weights", H, W, SLS_DENSIFY_DRAW_MAX_PIXELS);
+        return SLS_E_UNSUPPORTED;
+    }
+    SLS_REQUIRE(scratch_bytes >= densify_draw_scratch_bytes(H, W), "scratch smaller than sls_densify_draw_scratch_bytes(H, W)");
+    SLS_REQUIRE(((uintptr_t)scratch & 15u) == 0, "scratch not 16-byte aligned");
+    return launch_densify_draw(H, W, image_depth, valid, rend_alpha, threshold_opacity, percentage, seed, draw_index,
+                               weights_out, pixels_out, stats_out, stats_mirror, scratch, (hipStream_t)stream);
 }
 
 size_t sls_knn_scratch_bytes(int M) { return knn_scratch_bytes(M); }

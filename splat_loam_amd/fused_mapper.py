@@ -100,6 +100,59 @@ def _densify_draw_hip(cam, rend_alpha, threshold_opacity: float, percentage: flo
     return drawn.view(H, W), n_cand
 
 
+_DRAW_INDEX_ATTR = "_sls_draw_index"    # the next draw's index, kept ON the model next to its engine
+_DRAW_BUFFERS = {}                      # (device, H, W) -> (status words, their pinned mirror, scratch)
+_DRAW_SENTINEL = -1                     # 0xFFFFFFFF as int32: the device never writes it into words 0 and 7
+
+
+def _densify_draw_device(cam, rend_alpha, threshold_opacity: float, percentage: float, seed: int, draw_index: int,
+                         details: bool = False):
+    """The same candidates, weights and rules as `_densify_draw_hip`, the DRAW included, through sls_densify_draw: an
+    exponential race whose keys are a pure function of (weights, seed, draw_index) (include/sls_draw_math.h; DESIGN.md
+    section 2), the k-th key selected and the pixels compacted on the device, ONE host read (the status words, through
+    a pinned mirror the device writes as soon as the count is known).  Returns (pixels, number of candidates): the drawn
+    pixels' row-major indices, ascending, int64 (n,) on the device — what `nonzero()` of the drawn mask holds — or None
+    where nothing is drawn.  `details=True` adds dict(weights, stats (the eight device words), k).  There is no
+    fall-back: an image the call does not serve (more than 2^18 pixels) raises."""
+    from . import _abi
+    from .fused import camera_aux
+    from .rasterizer import _stream
+    dev = cam.image_depth.device
+    if not cam.image_depth.is_cuda:
+        raise RuntimeError("the device draw needs the keyframe on a ROCm device; there is no CPU fallback")
+    H, W = int(cam.image_height), int(cam.image_width)
+    lib = _abi.lib()
+    aux = camera_aux(cam)
+    key = (str(dev), H, W)
+    bufs = _DRAW_BUFFERS.get(key)
+    if bufs is None:
+        mirror = torch.zeros((8,), dtype=torch.int32).pin_memory()
+        scratch = torch.empty((max(int(lib.sls_densify_draw_scratch_bytes(H, W)), 16),), dtype=torch.uint8, device=dev)
+        bufs = _DRAW_BUFFERS[key] = (torch.zeros((8,), dtype=torch.int32, device=dev), mirror, mirror.numpy(), scratch)
+    stats, mirror, row, scratch = bufs
+    w = torch.empty((H * W,), dtype=torch.float32, device=dev)
+    pix = torch.empty((H * W,), dtype=torch.int64, device=dev)
+    alpha = None if rend_alpha is None else rend_alpha.reshape(-1).float().contiguous()
+    st = _stream(dev)
+    row[0] = _DRAW_SENTINEL
+    row[7] = _DRAW_SENTINEL
+    _abi.check(lib.sls_densify_draw(H, W, aux.gt.data_ptr(), aux.valid.data_ptr(), None if alpha is None else alpha.data_ptr(),
+                                    float(threshold_opacity), float(percentage), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    int(draw_index) & 0xFFFFFFFF, w.data_ptr(), pix.data_ptr(), stats.data_ptr(),
+                                    mirror.data_ptr(), scratch.data_ptr(), int(scratch.numel()), st), "sls_densify_draw")
+    _abi.check(lib.sls_wait_status_mirror(mirror.data_ptr(), 0xFFFFFFFF, st), "sls_wait_status_mirror")
+    n_cand, n_drawn, k = (int(row[i]) & 0xFFFFFFFF for i in (0, 3, 4))
+    pixels = pix[:n_drawn] if n_drawn > 0 else None
+    if details:
+        return pixels, n_cand, {"weights": w, "stats": stats.cpu().numpy().view(np.uint32).copy(), "k": k}
+    return pixels, n_cand
+
+
+def _is_pixel_list(drawn: torch.Tensor) -> bool:
+    """A drawn set comes as an (H,W) bool mask or as the int64 (n,) list of its row-major pixel indices, ascending."""
+    return drawn.dtype == torch.int64 and drawn.dim() == 1
+
+
 def _densify_rows_hip(frame, drawn: torch.Tensor):
     """(centres (n,3), quaternions (n,4)) of the drawn pixels through sls_densify_rows: what depth_to_points + the normals'
     rotation + normal_aligned_quaternions compute with ~65 torch kernels (the torch form stays the CPU path and the
@@ -110,7 +163,10 @@ def _densify_rows_hip(frame, drawn: torch.Tensor):
     cam = frame.camera
     dev = cam.image_depth.device
     H, W = int(cam.image_height), int(cam.image_width)
-    pix = drawn.reshape(-1).nonzero().reshape(-1)                # row-major, the order `[..., drawn]` gathers in
+    if _is_pixel_list(drawn):
+        pix = drawn.contiguous()                                 # (the device draw's list: already in that order)
+    else:
+        pix = drawn.reshape(-1).nonzero().reshape(-1)            # row-major, the order `[..., drawn]` gathers in
     n = int(pix.numel())
     xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
     quat = torch.empty((n, 4), dtype=torch.float32, device=dev)
@@ -135,13 +191,18 @@ def densify_model(gmodel, frame, drawn: torch.Tensor, opt_scaling_max: float, kn
     """slam/mapper.py:104-137: one surfel per drawn pixel of the keyframe — centre = the pixel's measured point in the
     model frame, both scales = sqrt(mean squared distance to the 3 nearest of (new + existing) centres) clamped to
     [sqrt(1e-7), opt_scaling_max], third axis = the measured normal rotated into the model frame, opacity 0.9 —
-    appended with `gmodel.densification_postfix`.  `drawn`: (H,W) bool.  Returns the number added."""
+    appended with `gmodel.densification_postfix`.  `drawn`: (H,W) bool, or the int64 (n,) list of the drawn pixels'
+    row-major indices in ascending order (`_densify_draw_device`).  Returns the number added."""
     from .renderer import depth_to_points
     own_knn = knn is None
     if own_knn:
         from .knn import distCUDA2 as knn
     cam = frame.camera
     quats = None
+    if _is_pixel_list(drawn) and not cam.image_depth.is_cuda:   # (the torch form gathers with a mask)
+        mask = torch.zeros((int(cam.image_height) * int(cam.image_width),), dtype=torch.bool, device=drawn.device)
+        mask[drawn] = True
+        drawn = mask.view(int(cam.image_height), int(cam.image_width))
     if cam.image_depth.is_cuda:
         points, quats = _densify_rows_hip(frame, drawn)          # centres + rotations in one launch
     else:
@@ -322,11 +383,17 @@ def fused_optimize(gmodel, keyframes, cfg, logger=None, rng=None, marks=None):
 
 @torch.no_grad()
 def update_model(gmodel, keyframes, frame, cfg, initialize_model: bool = False, drawn=None, generator=None,
-                 logger=None, rng=None, timings: bool = False):
+                 logger=None, rng=None, timings: bool = False, draw=None, seed=None, draw_index=None):
     """`Mapper.update_model` (slam/mapper.py:33-47) for callers without a Splat-LOAM checkout: densify `frame`
     (already in `keyframes`), optimise over `keyframes`, prune.  `drawn`: the (H,W) mask of densified pixels, instead
     of drawing it (`slam_rules.densify_sample`, torch.multinomial with `generator`) from the candidates.
-    Returns dict(added, removed (mask), loss_ema, candidates (None where the draw ran in one launch)); `timings=True` (bench_extras.update_model) synchronises
+    `draw`: "torch" (the default: torch.multinomial on the device's random stream) or "device" (the seeded draw of
+    sls_densify_draw: the drawn pixels are a pure function of the weights, `seed` — None: torch.initial_seed() — and
+    `draw_index` — None: a counter kept on the model, one step per device draw — with one host read; it needs device
+    tensors and densify_threshold_egeom <= 0 and raises otherwise).  SLS_DEVICE_DRAW=1 makes "device" the default for
+    device tensors where the caller passed neither `drawn` nor `generator`.
+    Returns dict(added, removed (mask), loss_ema, candidates (None where the draw ran in one launch), draw, seed,
+    draw_index (None on the torch path)); `timings=True` (bench_extras.update_model) synchronises
     the device between the stages and adds `timings_ms`."""
     import time
     from .renderer import render
@@ -339,8 +406,31 @@ def update_model(gmodel, keyframes, frame, cfg, initialize_model: bool = False, 
             torch.cuda.synchronize(gmodel._xyz.device)
             marks.append((name, time.perf_counter()))
     mark("start")
+    egeom = bool(m.densify_threshold_egeom and m.densify_threshold_egeom > 0.0)
+    if draw is None:
+        by_env = (os.environ.get("SLS_DEVICE_DRAW", "0") == "1" and drawn is None and generator is None
+                  and cam.image_depth.is_cuda)
+        draw = "device" if by_env else "torch"
+    if draw not in ("torch", "device"):
+        raise ValueError(f"update_model: draw must be 'torch' or 'device', not {draw!r}")
+    used_seed = used_index = None
+    if draw == "device":
+        if drawn is not None or generator is not None:
+            raise ValueError("update_model: draw='device' draws the pixels itself from (seed, draw_index): pass neither "
+                             "`drawn` nor `generator`")
+        if not cam.image_depth.is_cuda or egeom:
+            raise RuntimeError("update_model: draw='device' needs the keyframe on a ROCm device and densify_threshold_egeom "
+                               "<= 0 (the quantile of the egeom branch stays on the torch path); there is no fall-back")
+        used_seed = (torch.initial_seed() if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        used_index = int(getattr(gmodel, _DRAW_INDEX_ATTR, 0) if draw_index is None else draw_index) & 0xFFFFFFFF
     pkg = None if initialize_model else render(cam, gmodel, cfg.opt.depth_ratio)
-    if drawn is None and cam.image_depth.is_cuda and not (m.densify_threshold_egeom and m.densify_threshold_egeom > 0.0):
+    if draw == "device":
+        candidates = None
+        drawn, _ = _densify_draw_device(cam, None if pkg is None else pkg["rend_alpha"], m.densify_threshold_opacity,
+                                        m.densify_percentage, used_seed, used_index)
+        if draw_index is None:
+            setattr(gmodel, _DRAW_INDEX_ATTR, (used_index + 1) & 0xFFFFFFFF)
+    elif drawn is None and cam.image_depth.is_cuda and not (m.densify_threshold_egeom and m.densify_threshold_egeom > 0.0):
         # (the usual configuration — configs/*: densify_threshold_egeom = -1: candidates, weights and their sums in one launch)
         candidates = None
         drawn, _ = _densify_draw_hip(cam, None if pkg is None else pkg["rend_alpha"], m.densify_threshold_opacity,
@@ -358,7 +448,8 @@ def update_model(gmodel, keyframes, frame, cfg, initialize_model: bool = False, 
     mark("adam_state_out")
     removed = prune_model(gmodel, m.pruning_min_opacity, m.pruning_min_size or 0.0)
     mark("prune")
-    out = {"added": added, "removed": removed, "loss_ema": ema, "candidates": candidates}
+    out = {"added": added, "removed": removed, "loss_ema": ema, "candidates": candidates, "draw": draw, "seed": used_seed,
+           "draw_index": used_index}
     if timings:
         out["timings_ms"] = {b[0]: (b[1] - a[1]) * 1e3 for a, b in zip(marks[:-1], marks[1:])}
     return out

@@ -8,6 +8,9 @@ render the keyframe from the model (render()), register the scan against it
 (GSAligner, as slam/tracker.py:141-197 does) and compare with the ground-truth motion.
 
     python tools/slam_demo.py [H W n_frames n_iterations]
+    python tools/slam_demo.py sequence [H W n_frames] [--device-draw [--draw-seed S]]
+        (--device-draw: the keyframes' densify pixels from the seeded device draw, sls_densify_draw — a rerun with the
+         same seed densifies the same pixels; without it torch.multinomial on a generator seeded per keyframe)
 """
 import math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -125,7 +128,7 @@ def run_sequence(H=64, W=1024, n_frames=13, kf_every=None, n_iter=60, verbose=Tr
                  first_stride=None, el_deg=None, densify_percentage=0.15, densify_threshold_opacity=0.5,
                  densify_threshold_egeom=-1.0, prob_view_last_keyframe=0.4, keyframe_threshold_distance=0.9,
                  keyframe_threshold_fitness=0.30, keyframe_threshold_nframes=-1, pruning_min_opacity=0.1,
-                 step=(0.25, 0.04, 1.2)):
+                 step=(0.25, 0.04, 1.2), device_draw=False, draw_seed=0):
     """Odometry + mapping over a sequence, the reference's per-frame loop with this repository's
     components: every scan is registered against the latest keyframe as the MODEL renders it (tracker); a frame
     becomes a keyframe — at its ESTIMATED pose — when Tracker.require_new_keyframe says so (slam/tracker.py:61-84:
@@ -137,7 +140,8 @@ def run_sequence(H=64, W=1024, n_frames=13, kf_every=None, n_iter=60, verbose=Tr
     reference's rule builds, kept as a stress option), then engine.remap, `n_iter` iterations over keyframes
     sampled as Mapper.optimize does (sample_geometric over the keyframe list), pruning (Mapper.prune) — all three through
     fused_mapper.update_model, the code behind the SLS_FUSED_MAPPER=1 binding.
-    step: (dx, dy, yaw_deg) of the generating trajectory per frame."""
+    step: (dx, dy, yaw_deg) of the generating trajectory per frame.  device_draw: the densify pixels from the seeded
+    device draw (update_model(draw="device", seed=draw_seed), the draw index counted on the model)."""
     dev = torch.device(dev)
     rng = np.random.default_rng(0)
     K = (synth.spherical_K(H, W) if el_deg is None else synth.spherical_K(H, W, el_deg[0], el_deg[1])).astype(np.float64)
@@ -175,8 +179,11 @@ def run_sequence(H=64, W=1024, n_frames=13, kf_every=None, n_iter=60, verbose=Tr
             if first_stride > 1:
                 keep_cols = torch.zeros(drawn.shape[1], dtype=torch.bool, device=dev); keep_cols[::first_stride] = True
                 drawn &= keep_cols[None, :]
-        res = fused_mapper.update_model(model, kfs, frm, mcfg, initialize_model=first, drawn=drawn, rng=rng,
-                                        generator=torch.Generator(device=dev).manual_seed(len(kfs) - 1))
+        if device_draw and drawn is None:
+            res = fused_mapper.update_model(model, kfs, frm, mcfg, initialize_model=first, rng=rng, draw="device", seed=draw_seed)
+        else:
+            res = fused_mapper.update_model(model, kfs, frm, mcfg, initialize_model=first, drawn=drawn, rng=rng,
+                                            generator=torch.Generator(device=dev).manual_seed(len(kfs) - 1))
         eng = fused_mapper.engine_of(model)
         for k_, v_ in (eng.stats.items() if eng else ()):
             totals[k_] = totals.get(k_, 0) + v_
@@ -245,7 +252,13 @@ if __name__ == "__main__":
     off = None
     if "--half-pixel" in sys.argv:
         sys.argv.remove("--half-pixel"); off = (-0.5, -0.5)
+    extra = {}
+    if "--device-draw" in sys.argv:
+        sys.argv.remove("--device-draw"); extra["device_draw"] = True
+    if "--draw-seed" in sys.argv:
+        at = sys.argv.index("--draw-seed")
+        extra["draw_seed"] = int(sys.argv[at + 1]); del sys.argv[at:at + 2]
     if len(sys.argv) > 1 and sys.argv[1] == "sequence":
-        run_sequence(*[int(x) for x in sys.argv[2:]], pix_offset=off)
+        run_sequence(*[int(x) for x in sys.argv[2:]], pix_offset=off, **extra)
     else:
         run(*[int(x) for x in sys.argv[1:]], pix_offset=off)
