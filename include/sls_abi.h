@@ -351,6 +351,31 @@ int sls_densify_rows(int n, int H, int W, const int64_t *pixels, const float *im
                      const float *col_cs_half, const float *row_cs_half, const float *cam_to_model16,
                      const float *model_T_frame16, float *xyz_out, float *quat_out, void *stream);
 
+/* Oriented surface points of a rendered keyframe — steps 3-4 of the reference's mesh_poisson
+ * (scene/postprocessing.py:164-188): filter by rend_alpha / rend_dist, back-project, sample kf_samples pixels, move to
+ * the world frame — without its boolean gather, its host copies and its unseeded np.random.choice.  DESIGN.md section 2,
+ * "Surface samples", states every step; include/sls_draw_math.h the random word and the rank (sls_sample_word,
+ * sls_sample_index).
+ *   allmap: the rasterizer forward's 7*H*W floats, FULL (plane 6, rend_dist, is read: not a lean_allmap render).
+ *   valid pixel: !(alpha < min_opacity) && !(dist > max_depth_dist); sample j takes the valid pixel of row-major rank
+ *       sls_sample_index(sls_sample_word(j, seed, frame_id), n_valid): uniform, with replacement, row j of the output.
+ *   points_out / normals_out (n_samples*3 each): M (depth ray) and R(M) (N / alpha); depth = (1 - depth_ratio) D / alpha +
+ *       depth_ratio median (the divisions where alpha > 0), ray from the half-pixel tables (sls_ray_tables_at(-.5, -.5)).
+ *   cam_to_world12: DEVICE, 3x4 row-major, M = world_T_model inv(world_view_transform^T).
+ *   pixels_out (optional, n_samples int32): the selected row-major pixel of each row.
+ *   status_out (DEVICE, 4 words): [n_valid, rows written (n_samples, or 0 where n_valid == 0: nothing else is written
+ *       then), 0, 1].  Nothing is read back: a run keeps its keyframes' words in one array and reads it once.
+ *   scratch: sls_surface_scratch_bytes(H, W) bytes, 8-byte aligned (one validity bit per pixel).
+ * Two launches, ordered by the stream alone.  Serves H*W <= SLS_SURFACE_MAX_PIXELS (the prefix of the validity words'
+ * popcounts lives in LDS); SLS_E_UNSUPPORTED beyond.  SLS_E_ARG before anything is enqueued: a null pointer (pixels_out
+ * may be null), a non-positive size, n_samples < 1, a NaN threshold or depth_ratio, too little scratch. */
+#define SLS_SURFACE_MAX_PIXELS 262144
+size_t sls_surface_scratch_bytes(int H, int W);
+int sls_surface_samples(int H, int W, const float *allmap, const float *col_cs_half, const float *row_cs_half,
+                        const float *cam_to_world12, float min_opacity, float max_depth_dist, float depth_ratio,
+                        int n_samples, uint64_t seed, uint32_t frame_id, float *points_out, float *normals_out,
+                        int32_t *pixels_out, uint32_t *status_out, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- one whole mapping iteration, enqueued without any host sync -----------
  * slam/mapper.py:150-204 for one keyframe: activations (scene/gaussian_model.py:
  * 39-44) -> rasterizer forward -> sls_consumer_fwd_bwd -> rasterizer backward ->

@@ -69,6 +69,25 @@ SLS_HD uint32_t sls_draw_word(uint32_t pixel, uint64_t seed, uint32_t draw_index
     return c[0];
 }
 
+/* The surface sampler's random word of sample j of keyframe frame_id (sls_surface_samples; DESIGN.md section 2,
+ * "Surface samples"): counter (j, 1, frame_id, 0) — the 1 keeps the stream disjoint from the densify draw's
+ * (pixel, 0, draw_index, 0) under the same seed. */
+SLS_HD uint32_t sls_sample_word(uint32_t sample, uint64_t seed, uint32_t frame_id)
+{
+    uint32_t c[4];
+    c[0] = sample; c[1] = 1u; c[2] = frame_id; c[3] = 0u;
+    sls_philox4x32_10(c, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32));
+    return c[0];
+}
+
+/* A rank in [0, n) from a random word by multiply-shift: floor(r n / 2^32).  Uniform with replacement, as
+ * np.random.choice(n, k) is, up to the multiply-shift bias: a rank is hit by floor(2^32 / n) or that + 1 words, so the
+ * probabilities differ from 1 / n by at most n / 2^32 relative (<= 6.2e-5 at n = 2^18, the largest image served). */
+SLS_HD uint32_t sls_sample_index(uint32_t r, uint32_t n)
+{
+    return (uint32_t)(((uint64_t)r * (uint64_t)n) >> 32);
+}
+
 SLS_HD float sls_draw_bits_float(uint32_t bits)
 {
     float f;

@@ -101,6 +101,9 @@ _PROTOS = {
     "sls_densify_draw_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_densify_draw": (C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, C.c_float, C.c_double, C.c_uint64, C.c_uint32] +
                          [_VP] * 5 + [C.c_size_t, _VP]),
+    "sls_surface_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_surface_samples": (C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_int, C.c_uint64,
+                                      C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_consumer_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_consumer_fwd_bwd": (C.c_int, [C.c_int, C.c_int] + [_VP] * 5 + [C.c_float] * 3 + [C.c_int, _VP, _VP, _VP,
                                                                                          C.c_size_t, _VP]),

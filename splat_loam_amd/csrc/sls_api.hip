@@ -105,6 +105,11 @@ size_t densify_draw_scratch_bytes(int H, int W);
 int launch_densify_draw(int H, int W, const float *depth, const uint8_t *valid, const float *alpha, float thr, double percentage,
                         uint64_t seed, uint32_t draw_index, float *w_out, int64_t *pixels_out, uint32_t *stats,
                         uint32_t *stats_mirror, void *scratch, hipStream_t st);
+size_t surface_scratch_bytes(int H, int W);
+int launch_surface_samples(int H, int W, const float *allmap, const float *col_h, const float *row_h, const float *M,
+                           float min_opacity, float max_depth_dist, float depth_ratio, int n_samples, uint64_t seed,
+                           uint32_t frame_id, float *points, float *normals, int32_t *pixels, uint32_t *status, void *scratch,
+                           hipStream_t st);
 size_t knn_scratch_bytes(int M);
 int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratch_bytes, hipStream_t st, int Mq = -1);
 
@@ -401,6 +406,30 @@ int sls_densify_draw(int H, int W, const float *image_depth, const uint8_t *vali
     SLS_REQUIRE(((uintptr_t)scratch & 15u) == 0, "scratch not 16-byte aligned");
     return launch_densify_draw(H, W, image_depth, valid, rend_alpha, threshold_opacity, percentage, seed, draw_index,
                                weights_out, pixels_out, stats_out, stats_mirror, scratch, (hipStream_t)stream);
+}
+
+size_t sls_surface_scratch_bytes(int H, int W) { return (H > 0 && W > 0) ? surface_scratch_bytes(H, W) : 0; }
+
+int sls_surface_samples(int H, int W, const float *allmap, const float *col_cs_half, const float *row_cs_half,
+                        const float *cam_to_world12, float min_opacity, float max_depth_dist, float depth_ratio,
+                        int n_samples, uint64_t seed, uint32_t frame_id, float *points_out, float *normals_out,
+                        int32_t *pixels_out, uint32_t *status_out, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(H > 0 && W > 0, "bad size");
+    SLS_REQUIRE(n_samples >= 1, "n_samples < 1");
+    SLS_REQUIRE(allmap && col_cs_half && row_cs_half && cam_to_world12 && points_out && normals_out && status_out && scratch,
+                "null pointer");
+    SLS_REQUIRE(min_opacity == min_opacity && max_depth_dist == max_depth_dist && depth_ratio == depth_ratio, "NaN threshold");
+    if ((uint64_t)H * (uint64_t)W > SLS_SURFACE_MAX_PIXELS) {
+        set_error("sls_surface_samples: %d x %d pixels, the sampler serves at most %d (the validity prefix lives in LDS)", H, W,
+                  SLS_SURFACE_MAX_PIXELS);
+        return SLS_E_UNSUPPORTED;
+    }
+    SLS_REQUIRE(scratch_bytes >= surface_scratch_bytes(H, W), "scratch smaller than sls_surface_scratch_bytes(H, W)");
+    SLS_REQUIRE(((uintptr_t)scratch & 7u) == 0, "scratch not 8-byte aligned");
+    return launch_surface_samples(H, W, allmap, col_cs_half, row_cs_half, cam_to_world12, min_opacity, max_depth_dist, depth_ratio,
+                                  n_samples, seed, frame_id, points_out, normals_out, pixels_out, status_out, scratch,
+                                  (hipStream_t)stream);
 }
 
 size_t sls_knn_scratch_bytes(int M) { return knn_scratch_bytes(M); }

@@ -1,0 +1,222 @@
+"""From a saved map to the oriented point cloud Poisson reconstruction eats: steps 1-4 of the reference's
+`mesh_poisson` (scene/postprocessing.py:93-190) — for every keyframe of the results graph render the model it belongs
+to, filter by `rend_alpha` / `rend_dist`, back-project, sample `kf_samples` pixels, move them to the world frame and
+merge.  The Poisson solve itself (Open3D, on the CPU) is not part of this tree: `ply_io.save_point_cloud` writes the
+cloud in the form Open3D's `read_point_cloud` loads.
+
+Per keyframe, after the rasterizer forward, everything is ONE native call of two launches (sls_surface_samples,
+csrc/sls_surface.hip): no boolean gather, no copy to the host, no host read — the keyframes' status words live in one
+device array that is read once at the end.  The reference draws with an unseeded `np.random.choice`; here the sample is
+a pure function of (allmap, thresholds, seed, frame id, kf_samples): DESIGN.md section 2, "Surface samples".
+
+`mesh_poisson` itself could not be run where this was written (Open3D is not installed there), so the sampling
+semantics are restated from reading postprocessing.py:161-188, not pinned by a reference-generated fixture; what it
+shares with `render()` (the maps, the back-projection) is pinned by goldens G1 / G2.
+"""
+from __future__ import annotations
+
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import _abi
+
+_SURFACE_BUFFERS = {}                   # (device, H, W) -> scratch (the validity words)
+
+
+def frames_to_sample(graph: dict, kf_interval: int = -1) -> list:
+    """[(index of the model in graph["models"], frame id)] of the keyframes `mesh_poisson` processes
+    (postprocessing.py:126-140): one counter of processed frames runs across all models, starts at 1 with the first
+    frame, and a frame is skipped when `kf_interval > 0 and counter % kf_interval != 0`."""
+    used, processed = [], 0
+    for mi, rmodel in enumerate(graph["models"]):
+        for fid in rmodel["frame_ids"]:
+            processed += 1
+            if kf_interval is not None and kf_interval > 0 and processed % kf_interval:
+                continue
+            used.append((mi, int(fid)))
+    return used
+
+
+def _pose44(v) -> np.ndarray:
+    a = np.asarray(v, dtype=np.float64)
+    if a.size == 16:
+        return a.reshape(4, 4).copy()
+    return np.vstack([a.reshape(3, 4), [0.0, 0.0, 0.0, 1.0]])
+
+
+def compose_cam_to_world(world_T_model, view32) -> np.ndarray:
+    """M = world_T_model inv(world_view_transform^T) as 12 float32 (3x4 row-major): composed in float64 from the float32
+    view matrix the rasterizer renders with (`view32` = world_view_transform^T, i.e. inv(model_T_frame) rounded), rounded
+    once."""
+    c2w = np.linalg.inv(np.asarray(view32, dtype=np.float32).astype(np.float64).reshape(4, 4))
+    return np.ascontiguousarray((_pose44(world_T_model) @ c2w)[:3].reshape(12), dtype=np.float32)
+
+
+def _host(world_T_model):
+    return world_T_model.detach().cpu().numpy() if isinstance(world_T_model, torch.Tensor) else world_T_model
+
+
+@torch.no_grad()
+def sample_keyframe(allmap: torch.Tensor, camera, world_T_model, *, kf_samples: int = 5000, min_opacity: float = 0.5,
+                    max_depth_dist: float = 0.1, use_median_depth: bool = False, seed: int = 0, frame_id: int = 0, out=None,
+                    details: bool = False, cam_to_world: torch.Tensor = None):
+    """`kf_samples` oriented world-frame points of one rendered keyframe through sls_surface_samples.
+
+    allmap: the rasterizer forward's raw (7,H,W) device tensor, the FULL one (`lean_allmap=False`: plane 6 is read);
+    camera: the `scene.Camera` it was rendered with; world_T_model: 4x4 (or 3x4 / 12 floats) on the host.
+    out: None, or (points (k,3) f32, normals (k,3) f32, pixels (k,) i32 or None, status (4,) i32) — contiguous device
+        tensors, e.g. slices of a run's slabs, that the call fills.  With `out` NOTHING is read back: the tuple is
+        returned as it is and the caller reads status = [n_valid, rows written (k, or 0 for a keyframe without a valid
+        pixel, whose rows stay untouched), 0, 1] when it wants to.
+        Without `out` the status is read once: returns (points, normals), empty (0,3) where no pixel is valid;
+        `details=True` adds dict(n_valid, pixels (the selected row-major pixels, int32), status).
+    cam_to_world (extension): the composed M = world_T_model inv(world_view_transform^T) as a (12,) float32 device tensor
+        when the caller holds it already (`sample_surface` uploads every keyframe's in one copy); world_T_model is not
+        read then.
+    Device tensors only; there is no CPU fall-back."""
+    from .rasterizer import GaussianRasterizationSettings, _stream, get_camera, half_pixel_tables
+    if not isinstance(allmap, torch.Tensor) or not allmap.is_cuda:
+        raise RuntimeError("sample_keyframe needs the allmap on a ROCm device; there is no CPU fallback")
+    if allmap.dim() != 3 or allmap.shape[0] != 7:
+        raise ValueError("allmap must be (7, H, W)")
+    if int(kf_samples) < 1:
+        raise ValueError("kf_samples must be at least 1")
+    dev = allmap.device
+    am = allmap.detach()
+    if am.dtype != torch.float32 or not am.is_contiguous():
+        am = am.float().contiguous()
+    _, H, W = am.shape
+    k = int(kf_samples)
+    lib = _abi.lib()
+    ce = get_camera(GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix), dev)
+    col_h, row_h = half_pixel_tables(ce, dev)
+    if cam_to_world is None:
+        view = np.eye(4, dtype=np.float32)            # world_view_transform^T from the camera entry's host copy: no device read
+        view[:3, :3] = np.asarray(ce.cam.Rvw, dtype=np.float32).reshape(3, 3)
+        view[:3, 3] = np.asarray(ce.cam.tvw, dtype=np.float32)
+        cam_to_world = torch.from_numpy(compose_cam_to_world(_host(world_T_model), view)).to(dev)
+    elif (not cam_to_world.is_cuda or cam_to_world.dtype != torch.float32 or cam_to_world.numel() != 12
+          or not cam_to_world.is_contiguous()):
+        raise ValueError("cam_to_world must be a contiguous (12,) float32 device tensor")
+    key = (str(dev), H, W)
+    scratch = _SURFACE_BUFFERS.get(key)
+    if scratch is None:
+        need = int(lib.sls_surface_scratch_bytes(H, W))
+        scratch = _SURFACE_BUFFERS[key] = torch.empty((max(need, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    own = out is None
+    if own:
+        points = torch.empty((k, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((k, 3), dtype=torch.float32, device=dev)
+        pixels = torch.empty((k,), dtype=torch.int32, device=dev) if details else None
+        status = torch.empty((4,), dtype=torch.int32, device=dev)
+    else:
+        points, normals, pixels, status = out
+        for name, t, shape, dt in (("points", points, (k, 3), torch.float32), ("normals", normals, (k, 3), torch.float32),
+                                   ("pixels", pixels, (k,), torch.int32), ("status", status, (4,), torch.int32)):
+            if t is None and name == "pixels":
+                continue
+            if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and tuple(t.shape) == shape
+                    and t.is_contiguous()):
+                raise ValueError(f"out: {name} must be a contiguous {shape} {dt} tensor on {dev}")
+    _abi.check(lib.sls_surface_samples(H, W, am.data_ptr(), col_h.data_ptr(), row_h.data_ptr(), cam_to_world.data_ptr(),
+                                       float(min_opacity), float(max_depth_dist), 1.0 if use_median_depth else 0.0, k,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(frame_id) & 0xFFFFFFFF, points.data_ptr(),
+                                       normals.data_ptr(), None if pixels is None else pixels.data_ptr(), status.data_ptr(),
+                                       scratch.data_ptr(), int(scratch.numel()) * 8, _stream(dev)), "sls_surface_samples")
+    if not own:
+        return out
+    words = status.cpu().numpy().view(np.uint32).copy()         # the one host read of a stand-alone call
+    rows = int(words[1])
+    if details:
+        return points[:rows], normals[:rows], {"n_valid": int(words[0]), "pixels": pixels[:rows], "status": words}
+    return points[:rows], normals[:rows]
+
+
+def _image_size(graph_dir: Path, image_height, image_width):
+    cfg_file = graph_dir / "cfg.yaml"
+    if cfg_file.exists():
+        import yaml
+        pre = (yaml.safe_load(open(cfg_file)) or {}).get("preprocessing") or {}
+        if "image_height" in pre and "image_width" in pre:
+            return int(pre["image_height"]), int(pre["image_width"])
+    if image_height is None or image_width is None:
+        raise ValueError(f"the image size is neither in {cfg_file} (preprocessing.image_height / image_width) nor given "
+                         "as image_height= / image_width=")
+    return int(image_height), int(image_width)
+
+
+@torch.no_grad()
+def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int = 5000, min_opacity: float = 0.5,
+                   max_depth_dist: float = 0.1, use_median_depth: bool = False, seed=None, device="cuda",
+                   details: bool = False, image_height=None, image_width=None):
+    """`mesh_poisson`'s steps 1-4 (postprocessing.py:122-190) over a results directory (`graph.yaml`, `models/*.ply`,
+    optionally `cfg.yaml` for the image size): returns (points (M,3), normals (M,3)), float32 device tensors in keyframe
+    order, `kf_samples` rows per keyframe that has a valid pixel (the reference raises on one that has none; here it
+    contributes no rows).  `details=True` adds dict(frame_ids: the frames used, n_valid: their counts of valid pixels,
+    pixels: (frames used, kf_samples) int32, the selected row-major pixels, -1 in the rows of an empty keyframe, kept:
+    which of the frames used contributed rows).  seed=None: torch.initial_seed().  Sample j of frame f depends on
+    (seed, f, j) and the render alone — not on kf_interval or the order of processing."""
+    from . import ply_io, traj_io
+    from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+    from .scene import Camera, SurfelModel
+    path = Path(graph_dir_or_yaml)
+    graph_file = path / "graph.yaml" if path.is_dir() else path
+    graph_dir = graph_file.parent
+    graph = traj_io.read_graph(graph_file)
+    H, W = _image_size(graph_dir, image_height, image_width)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("sample_surface runs on a ROCm device; there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    used_seed = int(torch.initial_seed() if seed is None else seed)
+    k = int(kf_samples)
+    if k < 1:
+        raise ValueError("kf_samples must be at least 1")
+    used = frames_to_sample(graph, kf_interval)
+    frames = {int(fr["id"]): fr for fr in graph["frames"]}
+    F = len(used)
+    points = torch.empty((F * k, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((F * k, 3), dtype=torch.float32, device=dev)
+    pixels = torch.full((F, k), -1, dtype=torch.int32, device=dev) if details else None
+    status = torch.zeros((max(F, 1), 4), dtype=torch.int32, device=dev)
+    # every keyframe's view matrix (as scene.Camera rounds it) and composed M on the host, one upload of the latter
+    poses = [_pose44(frames[fid]["model_T_frame"]) for _, fid in used]
+    views = [np.linalg.inv(p).astype(np.float32) for p in poses]
+    Ms = np.stack([compose_cam_to_world(graph["models"][mi]["world_T_model"], v) for (mi, _), v in zip(used, views)]) \
+        if F else np.zeros((0, 12), np.float32)
+    Ms_dev = torch.from_numpy(np.ascontiguousarray(Ms)).to(dev)
+    zeros = {"d": torch.zeros((1, H, W), dtype=torch.float32, device=dev), "n": torch.zeros((3, H, W), dtype=torch.float32, device=dev),
+             "v": torch.zeros((1, H, W), dtype=torch.uint8, device=dev)}
+    loaded = (None, None)
+    for i, (mi, fid) in enumerate(used):
+        if loaded[0] != mi:                             # the frames of a model are consecutive: one load per model
+            raw = ply_io.load_ply(graph_dir / graph["models"][mi]["filename"])
+            gm = SurfelModel(*(np.array(raw[n]) for n in ("xyz", "scaling", "rotation", "opacity")), device=dev)   # (writable copies)
+            loaded = (mi, (gm.get_xyz.detach(), gm.get_opacity.detach(), gm.get_scaling.detach(), gm.get_rotation.detach()))
+        xyz, opac, scal, rot = loaded[1]
+        fr = frames[fid]
+        if int(fr["model_id"]) != int(graph["models"][mi]["id"]):
+            raise ValueError(f"frame {fid} is listed by model {graph['models'][mi]['id']} but belongs to model {fr['model_id']}")
+        fx, fy, cx, cy = (float(v) for v in fr["projmatrix"])
+        cam = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32), zeros["d"], zeros["n"], zeros["v"],
+                     world_T_lidar=poses[i], data_device=dev)
+        settings = GaussianRasterizationSettings(H, W, 1.0, cam.world_view_transform, cam.projection_matrix, lean_allmap=False)
+        _, allmap = GaussianRasterizer(raster_settings=settings)(means3D=xyz, means2D=xyz, opacities=opac, scales=scal,
+                                                                 rotations=rot)
+        sample_keyframe(allmap, cam, None, kf_samples=k, min_opacity=min_opacity, max_depth_dist=max_depth_dist,
+                        use_median_depth=use_median_depth, seed=used_seed, frame_id=fid, cam_to_world=Ms_dev[i],
+                        out=(points[i * k:(i + 1) * k], normals[i * k:(i + 1) * k], None if pixels is None else pixels[i],
+                             status[i]))
+    words = status.cpu().numpy().view(np.uint32)[:F]            # the run's one host read
+    kept = words[:, 1] > 0
+    if not kept.all():                                          # empty keyframes leave: one gather over whole blocks
+        idx = torch.from_numpy(np.flatnonzero(kept)).to(dev)
+        points = points.view(F, k, 3).index_select(0, idx).reshape(-1, 3)
+        normals = normals.view(F, k, 3).index_select(0, idx).reshape(-1, 3)
+    if details:
+        return points, normals, {"frame_ids": [fid for _, fid in used], "n_valid": words[:, 0].astype(np.int64), "pixels": pixels,
+                                 "kept": kept.copy(), "seed": used_seed}
+    return points, normals

@@ -15,6 +15,7 @@ import numpy as np
 
 PROPS = ["x", "y", "z", "opacity", "scale_0", "scale_1", "rot_0", "rot_1", "rot_2", "rot_3",
          "f_dc_0", "f_dc_1", "f_dc_2"]
+CLOUD_PROPS = ["x", "y", "z", "nx", "ny", "nz"]
 
 
 def save_ply(path, xyz, opacity_raw, scaling_raw, rotation_raw) -> None:
@@ -26,6 +27,24 @@ def save_ply(path, xyz, opacity_raw, scaling_raw, rotation_raw) -> None:
                            rotation_raw.reshape(n, 4), np.zeros((n, 3), np.float32)], axis=1).astype("<f4")
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % n
     header += "".join(f"property float {p}\n" for p in PROPS) + "end_header\n"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(data.tobytes())
+
+
+def save_point_cloud(path, points, normals) -> None:
+    """An oriented point cloud (`meshing.sample_surface`) as binary little-endian PLY: one `vertex` element with float32
+    `x y z nx ny nz`, the property names Open3D's `read_point_cloud` looks up — the input of Poisson reconstruction."""
+    def host(a):
+        return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
+    points, normals = host(points).reshape(-1, 3), host(normals).reshape(-1, 3)
+    if points.shape != normals.shape:
+        raise ValueError("points and normals must have the same number of rows")
+    n = points.shape[0]
+    data = np.concatenate([points, normals], axis=1).astype("<f4")
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % n
+    header += "".join(f"property float {p}\n" for p in CLOUD_PROPS) + "end_header\n"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
