@@ -6,7 +6,8 @@
 
 #include <mutex>
 
-#include "sls_common.hpp"
+#include "sls_consumer_dev.hpp"
+#include "sls_launch.hpp"
 
 namespace sls {
 
@@ -85,33 +86,6 @@ void timer_end(int slot, hipStream_t st)
     g_timer.open = -1;
     ++g_timer.used;
 }
-
-// launchers implemented in the other translation units
-int launch_mark_visible(const DevCam &, int, const float *, uint8_t *, hipStream_t);
-size_t consumer_scratch_bytes(int H, int W);
-int launch_consumer(int H, int W, const float *allmap, const float *gt_depth, const uint8_t *valid,
-                    const float *col_h, const float *row_h, float depth_ratio, float lambda_n, float lambda_a,
-                    int n_valid, float *sums, float *dL_dallmap, void *scratch, size_t scratch_bytes,
-                    hipStream_t st, bool sums_zeroed = false, struct ConsumerArgs *args_out_skip_c = nullptr,
-                    int order_tiles = 0, const uint32_t *block_cost = nullptr, uint32_t *block_order = nullptr,
-                    bool no_launch = false);
-int launch_render_maps(int H, int W, const float *allmap, const float *rot9, const float *col_h, const float *row_h,
-                       float depth_ratio, float *rend_normal, float *surf_depth, float *surf_normal, hipStream_t st);
-int launch_densify_weights(int H, int W, const float *depth, const uint8_t *valid, const float *alpha, float thr, float *w_out,
-                           uint32_t *stats, hipStream_t st);
-int launch_densify_rows(int n, int H, int W, const int64_t *pix, const float *depth, const float *normal, const float *col_h,
-                        const float *row_h, const float *c2w, const float *mTf, float *xyz, float *quat, hipStream_t st);
-size_t densify_draw_scratch_bytes(int H, int W);
-int launch_densify_draw(int H, int W, const float *depth, const uint8_t *valid, const float *alpha, float thr, double percentage,
-                        uint64_t seed, uint32_t draw_index, float *w_out, int64_t *pixels_out, uint32_t *stats,
-                        uint32_t *stats_mirror, void *scratch, hipStream_t st);
-size_t surface_scratch_bytes(int H, int W);
-int launch_surface_samples(int H, int W, const float *allmap, const float *col_h, const float *row_h, const float *M,
-                           float min_opacity, float max_depth_dist, float depth_ratio, int n_samples, uint64_t seed,
-                           uint32_t frame_id, float *points, float *normals, int32_t *pixels, uint32_t *status, void *scratch,
-                           hipStream_t st);
-size_t knn_scratch_bytes(int M);
-int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratch_bytes, hipStream_t st, int Mq = -1);
 
 // ---------------------------------------------------------------------------
 // P6 fused Adam: every parameter tensor of the model in ONE launch.
@@ -351,9 +325,11 @@ int sls_consumer_fwd_bwd(int H, int W, const float *allmap, const float *gt_dept
     SLS_REQUIRE(H > 0 && W > 0 && n_valid >= 0, "bad size");
     SLS_REQUIRE(allmap && gt_depth && valid && col_cs_half && row_cs_half && loss_sums && dL_dallmap && scratch,
                 "null pointer");
-    return launch_consumer(H, W, allmap, gt_depth, valid, col_cs_half, row_cs_half, depth_ratio, lambda_normal,
-                           lambda_alpha, n_valid, loss_sums, dL_dallmap, scratch, scratch_bytes,
-                           (hipStream_t)stream);
+    ConsumerArgs c{};
+    c.H = H; c.W = W; c.allmap = allmap; c.gt_depth = gt_depth; c.valid = valid; c.sums = loss_sums; c.dL_dallmap = dL_dallmap;
+    c.col_h = (const float2 *)col_cs_half; c.row_h = (const float2 *)row_cs_half;
+    c.depth_ratio = depth_ratio; c.lambda_n = lambda_normal; c.lambda_a = lambda_alpha;
+    return launch_consumer(c, n_valid, scratch, scratch_bytes, false, (hipStream_t)stream, nullptr);
 }
 
 int sls_render_maps(int H, int W, const float *allmap, const float *view_rot9, const float *col_cs_half,
@@ -439,7 +415,7 @@ int sls_knn_dist2(int M, const float *xyz, float *out, void *scratch, size_t scr
     SLS_REQUIRE(M >= 0, "negative M");
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(xyz && out && scratch, "null pointer");
-    return launch_knn(M, xyz, out, scratch, scratch_bytes, (hipStream_t)stream);
+    return launch_knn(M, xyz, out, scratch, scratch_bytes, (hipStream_t)stream, -1);
 }
 
 int sls_wait_status_mirror(const void *mirror_host, uint32_t sentinel, void *stream)

@@ -19,6 +19,7 @@
 // gathers the four neighbours' pieces and writes dL/dallmap.  HBM-bound,
 // ~100 B/pixel.
 #include "sls_consumer_dev.hpp"
+#include "sls_launch.hpp"
 
 namespace sls {
 
@@ -97,32 +98,22 @@ size_t consumer_scratch_bytes(int H, int W)
     return sizeof(float4) * 3 * (size_t)H * (size_t)W + sizeof(float) * 3 * nblocks;
 }
 
-int launch_consumer(int H, int W, const float *allmap, const float *gt_depth, const uint8_t *valid,
-                    const float *col_h, const float *row_h, float depth_ratio, float lambda_n, float lambda_a,
-                    int n_valid, float *sums, float *dL_dallmap, void *scratch, size_t scratch_bytes,
-                    hipStream_t st, bool sums_zeroed, ConsumerArgs *args_out_skip_c, int order_tiles,
-                    const uint32_t *block_cost, uint32_t *block_order, bool no_launch)
+int launch_consumer(const ConsumerArgs &in, int n_valid, void *scratch, size_t scratch_bytes, bool no_launch, hipStream_t st,
+                    ConsumerArgs *args_out_skip_c)
 {
+    const int H = in.H, W = in.W;
     if (scratch_bytes < consumer_scratch_bytes(H, W)) {
         set_error("consumer scratch too small");
         return SLS_E_SCRATCH;
     }
-    ConsumerArgs a;
-    a.H = H; a.W = W;
-    a.depth_ratio = depth_ratio; a.lambda_n = lambda_n; a.lambda_a = lambda_a;
+    ConsumerArgs a = in;
     a.inv_P = 1.0f / ((float)H * (float)W);
     a.inv_nv = n_valid > 0 ? 1.0f / (float)n_valid : 0.0f;
-    a.allmap = allmap; a.gt_depth = gt_depth; a.valid = valid;
-    a.col_h = (const float2 *)col_h; a.row_h = (const float2 *)row_h;
     a.du = (float4 *)scratch;
     a.dv = a.du + (size_t)H * W;
     a.ns = a.dv + (size_t)H * W;
     a.partials = (float *)(a.ns + (size_t)H * W);
-    a.sums = sums;
-    a.dL_dallmap = dL_dallmap;
-    a.order_tiles = (order_tiles > 0 && order_tiles % 32 == 0 && block_cost && block_order && kTilePix / 16 == 16) ? order_tiles : 0;
-    a.block_cost = block_cost;
-    a.block_order = block_order;
+    a.order_tiles = (in.order_tiles > 0 && in.order_tiles % 32 == 0 && in.block_cost && in.block_order && kTilePix / 16 == 16) ? in.order_tiles : 0;
     if (no_launch) {
         // kernel B runs inside the backward tile kernel (FUSED = 2 there): no plane is written, the blocks' loss terms —
         // three floats per 16-pixel block — take the planes' place at the head of the scratch
@@ -133,7 +124,6 @@ int launch_consumer(int H, int W, const float *allmap, const float *gt_depth, co
         return SLS_OK;
     }
     ScopedTimer tm(T_CONSUMER, st);
-    (void)sums_zeroed;   // (the sums are written, not accumulated)
     const dim3 grid((W + 63) / 64, (H + 3) / 4);
     const int cb = (int)(grid.x * grid.y);
     hipLaunchKernelGGL(consumer_b_kernel, dim3(cb + (a.order_tiles ? 8 : 0)), dim3(256), 0, st, a, (int)grid.x, cb);

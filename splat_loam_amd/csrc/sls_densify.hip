@@ -11,13 +11,10 @@
 //   densify_select_kernel, ONE workgroup of 1024           k and the no-draw verdict -> status (+ pinned mirror, at
 //       once: the host reads n_drawn while the selection runs), a 12 + 10 + 10 bit radix select of the k-th key
 //       (LDS histograms, the keys stay in L2: <= 1 MB), the tie on the pixel index, an ordered compaction.
-#include "sls_common.hpp"
+#include "sls_launch.hpp"
 #include "../../include/sls_draw_math.h"
 
 namespace sls {
-
-int launch_densify_weights(int H, int W, const float *depth, const uint8_t *valid, const float *alpha, float thr, float *w_out,
-                           uint32_t *stats, hipStream_t st);
 
 constexpr int kSelThreads = 1024;
 constexpr int kSelTile = 4 * kSelThreads;        // keys per compaction tile: one uint4 per thread

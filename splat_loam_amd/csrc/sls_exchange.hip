@@ -22,7 +22,7 @@
 // is a pure function of it.  Results equal the dense all-reduce path's to the bit (same operands per element).
 #include <string.h>
 
-#include "sls_common.hpp"
+#include "sls_launch.hpp"
 
 namespace sls {
 

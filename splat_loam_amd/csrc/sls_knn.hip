@@ -15,14 +15,9 @@
 // the result is reproducible bit for bit by a CPU brute force.
 #include <float.h>
 
-#include "sls_common.hpp"
+#include "sls_launch.hpp"
 
 namespace sls {
-
-size_t sort_scratch_bytes(uint64_t R);
-int radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uint32_t *vals_tmp,
-                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
-                         int *result_in_tmp, hipStream_t st);
 
 constexpr int kKnnBox = 256;
 constexpr int kKnnSub = 32;    // points per sub-box (8 per box)

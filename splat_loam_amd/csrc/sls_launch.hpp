@@ -1,0 +1,182 @@
+// sls_launch.hpp — the internal prototypes: every function one translation unit of libsls_hip.so defines and another
+// calls is declared HERE and nowhere else; the defining file and every caller include this header.  No default
+// arguments.  The wide launchers take one plain struct each: value-initialise it at the call site (`XLaunch a{};`) and
+// fill it by field name — a zero / null field means "option off".  What a caller reads back stays a parameter.
+#pragma once
+#include "sls_common.hpp"
+
+namespace sls {
+
+struct ConsumerArgs;    // sls_consumer_dev.hpp
+
+// The tile backward can walk its blocks most expensive first (8x2 blocks, XCD-interleaved tile mapping) — the one rule
+// for "this image has a launch order", for the hand-over buffer and for the callers' block_order buffers alike
+inline bool launch_order_possible(int T) { return T % 32 == 0 && kTileW == 16 && kTileH == 16; }
+
+// ---- sls_sort.hip: depth order, binning ----------------------------------------------------------------------------
+// What the depth-order stage hands to the binning that follows it
+struct ScanHandoff {
+    const uint32_t *block_sums;     // sums of tiles_touched over 256-blocks of depth-order positions (the emission
+                                    // finishes the scan itself; null: it reads precomputed offsets)
+    int resort_windows;             // > 0: the order was repaired, check these window edges (resort_verify)
+    const uint64_t *resort_edges;
+    int counted;                    // direct binning: the repair's merge already filled the count table
+};
+
+constexpr int kDirectChunk = 1024;     // depth positions per chunk of the direct binning (= the repair's window)
+constexpr int kDirectMaxBins = 512;    // tiles it serves
+
+// Direct binning (sls_sort.hip): the count table over chunks of 1024 depth positions and the per-position records
+struct DirectBin {
+    uint32_t *cnt;          // count table cnt[tile][chunk]: bins x nchunks words
+    uint32_t *totals;       // bins words
+    uint2 *serec;           // optional: per depth position the surfel's emission record {rectangle in one word, block box}
+    int bins, nchunks, pos0;    // pos0: first depth position of chunk 0 (0, or -512: the repair's shifted windows)
+    int stride;             // words per row of cnt (>= nchunks; a multiple of kDirectGroup with the coarse table: a group's
+                            // counts of one tile are then one aligned 64-byte line)
+    // optional (sls_mapping_step): coarse[group][tile] = the tile's instances in the chunks of group g (kDirectGroup
+    // chunks each), summed with atomics by the counting kernels and ZEROED by the iteration's first kernel.  With it
+    // bin_direct sums what lies in front of its chunk itself — the groups in front + the chunks of its own group — and
+    // the row-scan launch disappears (one dependent launch less); cnt then keeps the RAW counts.
+    uint32_t *coarse;
+};
+constexpr int kDirectGroup = 16;
+
+size_t sort_scratch_bytes(uint64_t cap);
+size_t order_scratch_bytes(int N);
+int radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uint32_t *vals_tmp,
+                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
+                         int *result_in_tmp, hipStream_t st);
+// where preprocess writes the depth sort's input (keys, identity permutation, N on the device) and the repair its pairs
+void depth_order_key_buffers(int N, void *scratch, uint32_t *order, uint32_t **keys, uint32_t **vals0, uint32_t **n_dev);
+uint64_t *resort_comp_buffer(int N, void *scratch);
+bool bin_direct_possible(const DevCam &cam, int N, uint32_t cap);
+DirectBin make_direct_bin(const DevCam &cam, int N, void *sort_scratch, uint2 *serec, bool repaired, bool coarse);
+size_t direct_coarse_words(const DevCam &cam, int N);
+
+// Depth order of the surfels (keys written by preprocess) + scan of tiles_touched in that order
+struct DepthOrderScan {
+    int N; const uint32_t *tiles; uint32_t *order, *offsets, *total_out;
+    void *scratch; size_t scratch_bytes;
+    int reuse_order;            // > 0: `order` holds the camera's previous permutation, repaired in so many rounds ...
+    uint32_t *fail_flag;        // ... with failure reported here (null: sorted from scratch)
+    bool window_sort_done;      // step A of the repair already ran, merged into the preprocess launch
+    const DirectBin *direct;    // the direct binning follows (with handoff: the repair's last merge fills its count table)
+    const int4 *erec_box; int GX;
+};
+// handoff (optional, out): the binning finishes — or does not need — the scan of tiles_touched
+int launch_depth_order_scan(const DepthOrderScan &a, hipStream_t st, ScanHandoff *handoff);
+
+// Emission in depth order + stable sort by tile + ranges
+struct BinSortLaunch {
+    int N;
+    const uint32_t *count_ptr; uint32_t cap;    // device R; host-side capacity of the buffers
+    const uint32_t *order; const int32_t *rect; const uint32_t *tiles; const uint64_t *tile_mask; const int32_t *erec;
+    const float *depth; const uint32_t *offsets;
+    uint32_t *tkeys, *vals, *tkeys_tmp, *vals_tmp;      // cap u32 each (ping-pong)
+    void *scratch; size_t scratch_bytes;
+    uint32_t *ranges; uint64_t *keys64_out; uint32_t *overflow;
+    const ScanHandoff *handoff; uint32_t *total_out;
+    const uint32_t *sbox; int bmask_mode;       // block boxes + SlsMappingConfig.block_masks (0 auto, 1 always, 2 never)
+};
+// out: *sorted_in_tmp (which value array holds the list), *bmask_out (optional; the list as (surfel, block mask) pairs,
+// null where that is not possible)
+int launch_bin_sort(const DevCam &cam, const BinSortLaunch &a, hipStream_t st, int *sorted_in_tmp, const uint2 **bmask_out);
+
+// order (+ erec_box, or rect + sbox) -> sorted list, ranges, R
+struct BinDirectLaunch {
+    int N; uint32_t cap;
+    DirectBin db; bool counted;     // counted: the count table was filled by the repair's merge
+    const uint32_t *order; const int32_t *erec_box; const int32_t *rect; const uint32_t *sbox;
+    void *scratch; uint32_t *vals_out, *ranges, *total_out, *overflow;
+    int resort_windows; const uint64_t *resort_edges; int bmask_mode;
+    uint32_t *status_mirror;        // pinned host memory: the status block, early (sls_forward_ws)
+};
+int launch_bin_direct(const DevCam &cam, const BinDirectLaunch &a, hipStream_t st, const uint2 **bmask_out);
+
+// ---- sls_preprocess.hip --------------------------------------------------------------------------------------------
+struct PreFwdLaunch {
+    int N;
+    int raw; float smax, pen; float *reg_out;   // raw parameters + the scale regulariser (RegArgs)
+    const float *means, *scales, *rots, *opac;
+    float *rec; int32_t *radii, *rect; uint32_t *tiles; float *depth;
+    uint32_t *order_keys, *order_vals, *n_dev;  // depth_order_key_buffers
+    uint32_t *status_clear;                     // the iteration's status block, zeroed by this first kernel
+    const float *col_cs, *row_cs; uint64_t *tile_mask;
+    int32_t *erec; int erec_box;                // emission records; 1: in the form the direct binning gathers
+    const uint32_t *resort_prev_order; uint64_t *resort_comp;   // both: the repair's window sort rides in this launch
+    uint32_t *sbox;
+    uint32_t *zero_words; int n_zero_words;     // the direct binning's coarse table, zeroed here
+};
+int launch_preprocess_fwd(const DevCam &cam, const PreFwdLaunch &a, hipStream_t st);
+
+// One struct for the single-keyframe and the batched backward of the projection
+struct PreBwdLaunch {
+    int N;
+    int raw; float smax, pen;                   // (a batch always runs on raw parameters)
+    const float *means, *scales, *rots, *opac;  // written only by the fused Adam update of the caller's own tensors
+    float *dmeans, *dscales, *drots, *dopac; const PoseOut *pose;
+    const int32_t *radii; const float *grec; const AdamFuse *fuse;      // one keyframe; a batch has them in its BatchFuse
+};
+int launch_preprocess_bwd(const DevCam &cam, const PreBwdLaunch &a, hipStream_t st);
+int launch_preprocess_bwd_batch(const PreBwdLaunch &a, const BatchFuse &bf, hipStream_t st);
+int launch_mark_visible(const DevCam &cam, int N, const float *means, uint8_t *visible, hipStream_t st);
+
+// ---- sls_render_block.hip ------------------------------------------------------------------------------------------
+size_t block_mask_bytes(uint64_t cap, int T);
+struct RenderFwdLaunch {
+    const uint32_t *ranges, *vals; const float *rec, *col_cs, *row_cs;
+    float *allmap, *pix_state; uint32_t *pix_contrib, *tile_consumed; bool consumed_zeroed;
+    uint64_t *block_masks;          // the hand-over buffer: the blocks' compact lists for the backward
+    bool lean; uint32_t *block_cost;    // lean: no median / distortion planes
+    const uint2 *bmask;             // the list as (surfel, block mask) pairs: dense rounds
+    bool order_in_handover;         // + the backward's launch order into the hand-over buffer (the staged API)
+};
+int launch_render_fwd(const DevCam &cam, const RenderFwdLaunch &a, hipStream_t st);
+
+struct RenderBwdLaunch {
+    const uint32_t *ranges, *vals; int vals_stride;     // vals_stride (required): 1 plain list, 2 (surfel, block mask) pairs
+    const float *rec, *col_cs, *row_cs, *pix_state; const uint32_t *pix_contrib; const float *dL_dallmap;
+    float *grec; uint8_t *touched; bool lean;
+    const uint64_t *block_masks; int block_masks_shape; // the producer's tag of the compact lists: walked only for 3
+    const ConsumerArgs *fused_consumer; bool consumer_b_inline;     // the loss stage's kernel C (and B) inside this one
+    uint32_t *det_max; unsigned long long *det_acc;                 // deterministic accumulation, two launches ...
+    const uint8_t *det_prev; const uint32_t *det_gex; uint32_t *det_flag;   // ... or one, with predicted scales
+    const uint32_t *block_order; uint32_t order_tag;    // the caller's launch order, or ...
+    bool order_in_handover;                             // ... the one the staged forward left in the hand-over buffer
+};
+int launch_render_bwd(const DevCam &cam, const RenderBwdLaunch &a, hipStream_t st);
+
+// ---- sls_consumer.hip ----------------------------------------------------------------------------------------------
+size_t consumer_scratch_bytes(int H, int W);
+// in: the kernels' own argument struct, the caller's fields filled by name (sizes, weights, inputs, sums, dL_dallmap, the
+// launch-order passenger); the launcher adds the derived ones.  no_launch: kernel B too runs inside the tile backward.
+// args_out_skip_c (optional, out): the complete arguments for the tile backward, which then does kernel C's work
+int launch_consumer(const ConsumerArgs &in, int n_valid, void *scratch, size_t scratch_bytes, bool no_launch, hipStream_t st,
+                    ConsumerArgs *args_out_skip_c);
+int launch_render_maps(int H, int W, const float *allmap, const float *rot9, const float *col_h, const float *row_h,
+                       float depth_ratio, float *rend_normal, float *surf_depth, float *surf_normal, hipStream_t st);
+int launch_densify_weights(int H, int W, const float *depth, const uint8_t *valid, const float *alpha, float thr, float *w_out,
+                           uint32_t *stats, hipStream_t st);
+int launch_densify_rows(int n, int H, int W, const int64_t *pix, const float *depth, const float *normal, const float *col_h,
+                        const float *row_h, const float *c2w, const float *mTf, float *xyz, float *quat, hipStream_t st);
+
+// ---- sls_densify.hip, sls_surface.hip, sls_knn.hip, sls_exchange.hip, sls_api.hip ----------------------------------
+size_t densify_draw_scratch_bytes(int H, int W);
+int launch_densify_draw(int H, int W, const float *depth, const uint8_t *valid, const float *alpha, float thr, double percentage,
+                        uint64_t seed, uint32_t draw_index, float *w_out, int64_t *pixels_out, uint32_t *stats,
+                        uint32_t *stats_mirror, void *scratch, hipStream_t st);
+size_t surface_scratch_bytes(int H, int W);
+int launch_surface_samples(int H, int W, const float *allmap, const float *col_h, const float *row_h, const float *M,
+                           float min_opacity, float max_depth_dist, float depth_ratio, int n_samples, uint64_t seed,
+                           uint32_t frame_id, float *points, float *normals, int32_t *pixels, uint32_t *status, void *scratch,
+                           hipStream_t st);
+size_t knn_scratch_bytes(int M);
+int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratch_bytes, hipStream_t st, int Mq);   // Mq < 0: all
+int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_raw, float smax, float pen,
+                          const uint32_t *status_block, uint64_t *bitmap, hipStream_t st);
+int launch_adam(const SlsAdamGroup *groups, int ngroups, double beta1, double beta2, double eps, int64_t step,
+                const uint32_t *skip_flag, hipStream_t stream, const float *void_flags, uint32_t *status_block,
+                uint32_t *status_mirror);
+
+}  // namespace sls

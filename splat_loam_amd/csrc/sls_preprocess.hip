@@ -11,6 +11,7 @@
 #include "sls_common.hpp"
 #include "sls_consumer_dev.hpp"
 #include "sls_resort.hpp"
+#include "sls_launch.hpp"
 
 namespace sls {
 
@@ -1172,35 +1173,30 @@ __global__ __launch_bounds__(256) void mark_visible_kernel(DevCam cam, int N, co
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers used by sls_api.hip
+// host-side launchers (sls_launch.hpp), used by sls_pipeline.hip and sls_api.hip
 // ---------------------------------------------------------------------------
-int launch_preprocess_fwd(const DevCam &cam, int raw, float smax, float pen, float *reg_out, int N,
-                          const float *means, const float *scales, const float *rots, const float *opac, float *rec,
-                          int32_t *radii, int32_t *rect, uint32_t *tiles, float *depth, uint32_t *order_keys,
-                          uint32_t *order_vals, uint32_t *n_dev, hipStream_t st, uint32_t *status_clear,
-                          const float *col_cs, const float *row_cs, uint64_t *tile_mask, int32_t *erec,
-                          const uint32_t *resort_prev_order, uint64_t *resort_comp, uint32_t *sbox, int erec_box,
-                          uint32_t *zero_words, int n_zero_words)
+int launch_preprocess_fwd(const DevCam &cam, const PreFwdLaunch &a, hipStream_t st)
 {
+    const int N = a.N;
     RegArgs ra;
-    ra.raw = raw; ra.smax = smax; ra.pen = pen; ra.reg_out = reg_out; ra.status_clear = status_clear;
-    ra.zero_words = zero_words; ra.n_zero_words = n_zero_words;
+    ra.raw = a.raw; ra.smax = a.smax; ra.pen = a.pen; ra.reg_out = a.reg_out; ra.status_clear = a.status_clear;
+    ra.zero_words = a.zero_words; ra.n_zero_words = a.n_zero_words;
     PreFwdArgs pa;
-    pa.means = means; pa.scales = (const float2 *)scales; pa.rots = (const float4 *)rots; pa.opac = opac;
-    pa.rec = (float4 *)rec; pa.radii = radii; pa.rect = (int4 *)rect; pa.tiles = tiles; pa.depth = depth;
-    pa.order_keys = order_keys; pa.order_vals = order_vals; pa.n_dev = n_dev;
-    pa.col_cs = (const float2 *)col_cs; pa.row_cs = (const float2 *)row_cs;
-    pa.tile_mask = (col_cs && row_cs) ? tile_mask : nullptr;
-    pa.erec = (cam.GX < 65536 && cam.GY < 65536) ? (int4 *)erec : nullptr;
-    pa.sbox = block_box_fits(cam.GX * kTileW, cam.H) ? sbox : nullptr;
-    pa.erec_box = (erec_box && pa.erec && block_box_fits(cam.GX * kTileW, cam.H)) ? 1 : 0;
+    pa.means = a.means; pa.scales = (const float2 *)a.scales; pa.rots = (const float4 *)a.rots; pa.opac = a.opac;
+    pa.rec = (float4 *)a.rec; pa.radii = a.radii; pa.rect = (int4 *)a.rect; pa.tiles = a.tiles; pa.depth = a.depth;
+    pa.order_keys = a.order_keys; pa.order_vals = a.order_vals; pa.n_dev = a.n_dev;
+    pa.col_cs = (const float2 *)a.col_cs; pa.row_cs = (const float2 *)a.row_cs;
+    pa.tile_mask = (a.col_cs && a.row_cs) ? a.tile_mask : nullptr;
+    pa.erec = (cam.GX < 65536 && cam.GY < 65536) ? (int4 *)a.erec : nullptr;
+    pa.sbox = block_box_fits(cam.GX * kTileW, cam.H) ? a.sbox : nullptr;
+    pa.erec_box = (a.erec_box && pa.erec && block_box_fits(cam.GX * kTileW, cam.H)) ? 1 : 0;
     ScopedTimer tm(T_PREPROCESS_FWD, st);
-    if (resort_prev_order && resort_comp) {
+    if (a.resort_prev_order && a.resort_comp) {
         // merged with the repair's window sort (which overwrites the sort's identity permutation: not written here)
         pa.order_vals = nullptr;
         const int nw = (N + kResortWindow - 1) / kResortWindow, nb = (N + 511) / 512;
-        hipLaunchKernelGGL(preprocess_fwd_resort_kernel, dim3(nw + nb), dim3(512), 0, st, cam, ra, N, pa, nw, resort_prev_order,
-                           resort_comp);
+        hipLaunchKernelGGL(preprocess_fwd_resort_kernel, dim3(nw + nb), dim3(512), 0, st, cam, ra, N, pa, nw, a.resort_prev_order,
+                           a.resort_comp);
         SLS_LAUNCH_CHECK("preprocess_fwd_resort_kernel");
         return SLS_OK;
     }
@@ -1209,51 +1205,46 @@ int launch_preprocess_fwd(const DevCam &cam, int raw, float smax, float pen, flo
     return SLS_OK;
 }
 
-int launch_preprocess_bwd(const DevCam &cam, int raw, float smax, float pen, int N, const float *means,
-                          const float *scales, const float *rots, const float *opac, const int32_t *radii,
-                          const float *grec, float *dmeans, float *dscales, float *drots, float *dopac,
-                          hipStream_t st, const AdamFuse *fuse, const PoseOut *pose)
+int launch_preprocess_bwd(const DevCam &cam, const PreBwdLaunch &a, hipStream_t st)
 {
-    const int nb = (N + 255) / 256;
-    RegArgs ra;
-    ra.raw = raw; ra.smax = smax; ra.pen = pen; ra.reg_out = nullptr; ra.status_clear = nullptr;
-    ra.zero_words = nullptr; ra.n_zero_words = 0;
+    const int N = a.N, nb = (N + 255) / 256;
+    RegArgs ra{};
+    ra.raw = a.raw; ra.smax = a.smax; ra.pen = a.pen;
     AdamFuse af;
     memset(&af, 0, sizeof(af));
-    if (fuse) af = *fuse;
+    if (a.fuse) af = *a.fuse;
     // (a block of its own for the status duties, if there are any: see the kernel)
     af.publisher = (af.loss_partials || af.reg_accum || af.void_flags || af.status_mirror || af.grad_bitmap) ? 1 : 0;
     ScopedTimer tm(T_PREPROCESS_BWD, st);
     // (parameters are only written when af.enabled, which the caller sets for its own mutable tensors)
-    if (pose)
+    if (a.pose)
         hipLaunchKernelGGL((preprocess_bwd_kernel<true, PoseOut>), dim3(nb + af.publisher + (af.order_out ? 8 : 0)), dim3(256), 0, st, cam, ra, af, N,
-                           const_cast<float *>(means), (float2 *)const_cast<float *>(scales), (float4 *)const_cast<float *>(rots),
-                           const_cast<float *>(opac), radii, (float4 *)const_cast<float *>(grec), dmeans, (float2 *)dscales,
-                           (float4 *)drots, dopac, *pose);
+                           const_cast<float *>(a.means), (float2 *)const_cast<float *>(a.scales), (float4 *)const_cast<float *>(a.rots),
+                           const_cast<float *>(a.opac), a.radii, (float4 *)const_cast<float *>(a.grec), a.dmeans, (float2 *)a.dscales,
+                           (float4 *)a.drots, a.dopac, *a.pose);
     else
         hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3(nb + af.publisher + (af.order_out ? 8 : 0)), dim3(256), 0, st, cam, ra, af, N,
-                           const_cast<float *>(means), (float2 *)const_cast<float *>(scales), (float4 *)const_cast<float *>(rots),
-                           const_cast<float *>(opac), radii, (float4 *)const_cast<float *>(grec), dmeans, (float2 *)dscales,
-                           (float4 *)drots, dopac);
+                           const_cast<float *>(a.means), (float2 *)const_cast<float *>(a.scales), (float4 *)const_cast<float *>(a.rots),
+                           const_cast<float *>(a.opac), a.radii, (float4 *)const_cast<float *>(a.grec), a.dmeans, (float2 *)a.dscales,
+                           (float4 *)a.drots, a.dopac);
     SLS_LAUNCH_CHECK("preprocess_bwd_kernel");
     return SLS_OK;
 }
 
-int launch_preprocess_bwd_batch(float smax, float pen, int N, float *means, float *scales, float *rots, float *opac,
-                                float *dmeans, float *dscales, float *drots, float *dopac, const BatchFuse &bf,
-                                hipStream_t st, const PoseOut *pose)
+int launch_preprocess_bwd_batch(const PreBwdLaunch &a, const BatchFuse &bf, hipStream_t st)
 {
-    const int nb = (N + 255) / 256;
-    RegArgs ra;
-    ra.raw = 1; ra.smax = smax; ra.pen = pen; ra.reg_out = nullptr; ra.status_clear = nullptr;
-    ra.zero_words = nullptr; ra.n_zero_words = 0;
+    const int N = a.N, nb = (N + 255) / 256;
+    float *means = const_cast<float *>(a.means), *scales = const_cast<float *>(a.scales), *rots = const_cast<float *>(a.rots),
+          *opac = const_cast<float *>(a.opac);
+    RegArgs ra{};
+    ra.raw = 1; ra.smax = a.smax; ra.pen = a.pen;
     ScopedTimer tm(T_PREPROCESS_BWD, st);
-    if (pose)
+    if (a.pose)
         hipLaunchKernelGGL((preprocess_bwd_batch_kernel<true, PoseOut>), dim3(nb + 1 + (bf.order_T > 0 ? 8 * bf.G : 0)), dim3(256), 0, st, ra, bf, N,
-                           means, (float2 *)scales, (float4 *)rots, opac, dmeans, (float2 *)dscales, (float4 *)drots, dopac, *pose);
+                           means, (float2 *)scales, (float4 *)rots, opac, a.dmeans, (float2 *)a.dscales, (float4 *)a.drots, a.dopac, *a.pose);
     else
         hipLaunchKernelGGL(preprocess_bwd_batch_kernel<false>, dim3(nb + 1 + (bf.order_T > 0 ? 8 * bf.G : 0)), dim3(256), 0, st, ra, bf, N,
-                           means, (float2 *)scales, (float4 *)rots, opac, dmeans, (float2 *)dscales, (float4 *)drots, dopac);
+                           means, (float2 *)scales, (float4 *)rots, opac, a.dmeans, (float2 *)a.dscales, (float4 *)a.drots, a.dopac);
     SLS_LAUNCH_CHECK("preprocess_bwd_batch_kernel");
     return SLS_OK;
 }

@@ -23,6 +23,7 @@
 #include <cstring>
 #include "sls_tile.hpp"
 #include "sls_consumer_dev.hpp"
+#include "sls_launch.hpp"
 
 namespace sls {
 
@@ -1089,62 +1090,50 @@ __global__ __launch_bounds__(64) void render_bwd_block_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// the hand-over buffer carries a launch order for the backward (8x2 blocks, XCD-interleaved tile mapping)
-static bool handover_has_order(int T) { return T % 32 == 0 && kTileW == 16 && kTileH == 16; }
-
-int launch_render_fwd(const DevCam &cam, const uint32_t *ranges, const uint32_t *vals, const float *rec,
-                      const float *col_cs, const float *row_cs, float *allmap, float *pix_state,
-                      uint32_t *pix_contrib, uint32_t *tile_consumed, hipStream_t st, bool consumed_zeroed,
-                      uint64_t *block_masks, bool lean, uint32_t *block_cost, const uint2 *bmask,
-                      bool order_in_handover)
+int launch_render_fwd(const DevCam &cam, const RenderFwdLaunch &a, hipStream_t st)
 {
     const int T = cam.GX * cam.GY;
     // the block kernels combine their blocks' counters with atomicMax: start from zero
-    if (tile_consumed && !consumed_zeroed)
-        SLS_HIP_CHECK(hipMemsetAsync(tile_consumed, 0, sizeof(uint32_t) * (size_t)T, st));
+    if (a.tile_consumed && !a.consumed_zeroed)
+        SLS_HIP_CHECK(hipMemsetAsync(a.tile_consumed, 0, sizeof(uint32_t) * (size_t)T, st));
     ScopedTimer tm(T_RENDER_FWD, st);
     const dim3 grid(T * (kTilePix / 16)), block(64);
     uint32_t *const g_dbg_fwd_cycles = debug_state().dbg_fwd_cycles;
-#define SLS_FWD_ARGS grid, block, 0, st, block_masks, cam, (const uint2 *)ranges, vals, (const float4 *)rec,     \
-                     (const float2 *)col_cs, (const float2 *)row_cs, allmap, (float4 *)pix_state,                \
-                     (uint2 *)pix_contrib, tile_consumed, g_dbg_fwd_cycles, block_cost
+#define SLS_FWD_ARGS grid, block, 0, st, a.block_masks, cam, (const uint2 *)a.ranges, a.vals, (const float4 *)a.rec, \
+                     (const float2 *)a.col_cs, (const float2 *)a.row_cs, a.allmap, (float4 *)a.pix_state,          \
+                     (uint2 *)a.pix_contrib, a.tile_consumed, g_dbg_fwd_cycles, a.block_cost
 #define SLS_FWD_BLOCK(DBG_, LEAN_) hipLaunchKernelGGL((render_fwd_block_kernel<8, 2, DBG_, LEAN_>), SLS_FWD_ARGS)
-#define SLS_FWD_DENSE(DBG_, LEAN_) hipLaunchKernelGGL((render_fwd_dense_kernel<8, 2, DBG_, LEAN_>), SLS_FWD_ARGS, bmask)
+#define SLS_FWD_DENSE(DBG_, LEAN_) hipLaunchKernelGGL((render_fwd_dense_kernel<8, 2, DBG_, LEAN_>), SLS_FWD_ARGS, a.bmask)
     // the instances' block masks in list order (a passenger of the tile sort): dense rounds
-    if (bmask) {
-        if (g_dbg_fwd_cycles) SLS_FWD_DENSE(true, false); else if (lean) SLS_FWD_DENSE(false, true); else SLS_FWD_DENSE(false, false);
+    if (a.bmask) {
+        if (g_dbg_fwd_cycles) SLS_FWD_DENSE(true, false); else if (a.lean) SLS_FWD_DENSE(false, true); else SLS_FWD_DENSE(false, false);
     } else {
-        if (g_dbg_fwd_cycles) SLS_FWD_BLOCK(true, false); else if (lean) SLS_FWD_BLOCK(false, true); else SLS_FWD_BLOCK(false, false);
+        if (g_dbg_fwd_cycles) SLS_FWD_BLOCK(true, false); else if (a.lean) SLS_FWD_BLOCK(false, true); else SLS_FWD_BLOCK(false, false);
     }
 #undef SLS_FWD_BLOCK
 #undef SLS_FWD_DENSE
 #undef SLS_FWD_ARGS
     SLS_LAUNCH_CHECK("render_fwd_block_kernel");
-    if (order_in_handover && block_masks && handover_has_order(T)) {
+    if (a.order_in_handover && a.block_masks && launch_order_possible(T)) {
         // the staged API: the order the backward launches its blocks in, from the counts the forward just wrote
-        hipLaunchKernelGGL(block_order_kernel, dim3(8), dim3(256), 0, st, block_masks, T);
+        hipLaunchKernelGGL(block_order_kernel, dim3(8), dim3(256), 0, st, a.block_masks, T);
         SLS_LAUNCH_CHECK("block_order_kernel");
     }
     return SLS_OK;
 }
 
-int launch_render_bwd(const DevCam &cam, const uint32_t *ranges, const uint32_t *vals, const float *rec,
-                      const float *col_cs, const float *row_cs, const float *pix_state,
-                      const uint32_t *pix_contrib, const float *dL_dallmap, float *grec, hipStream_t st,
-                      const uint64_t *block_masks, bool lean, uint8_t *touched,
-                      const ConsumerArgs *fused_consumer, uint32_t *det_max, unsigned long long *det_acc,
-                      const uint32_t *block_order, int vals_stride, int block_masks_shape, bool order_in_handover,
-                      const uint8_t *det_prev, const uint32_t *det_gex, uint32_t *det_flag, bool consumer_b_inline,
-                      uint32_t order_tag)
+int launch_render_bwd(const DevCam &cam, const RenderBwdLaunch &a, hipStream_t st)
 {
     const int T = cam.GX * cam.GY;
-    // vals_stride: 1 = plain list of surfel indices, 2 = the tile sort's (surfel, block mask) pairs.
-    // block_masks_shape: the producer's tag of the compact lists in `block_masks` (0 = no hand-over, 3 = the 8x2
-    // forward's): they are walked only for 3 — any other value culls the tile's list itself (the buffer's tag word is
-    // the kernel's last guard).
-    const bool dense = block_masks != nullptr && block_masks_shape == 3;
+    const uint32_t *block_order = a.block_order;
+    const uint64_t *block_masks = a.block_masks;
+    const ConsumerArgs *fused_consumer = a.fused_consumer;
+    const bool lean = a.lean, consumer_b_inline = a.consumer_b_inline;
+    // the compact lists are walked only for the 8x2 forward's tag — any other value culls the tile's list itself (the
+    // buffer's tag word is the kernel's last guard)
+    const bool dense = block_masks != nullptr && a.block_masks_shape == 3;
     // no order from the caller: the staged forward left one in the hand-over buffer (block_order_kernel)
-    if (!block_order && order_in_handover && dense && handover_has_order(T))
+    if (!block_order && a.order_in_handover && dense && launch_order_possible(T))
         block_order = reinterpret_cast<const uint32_t *>(block_masks + block_list_order_word(T, kTilePix / 16));
     ScopedTimer tm(T_RENDER_BWD, st);
     const dim3 grid(T * (kTilePix / 16)), block(64);
@@ -1157,22 +1146,22 @@ int launch_render_bwd(const DevCam &cam, const uint32_t *ranges, const uint32_t 
         cblocks = ((ca.W + 63) / 64) * ((ca.H + 3) / 4);
     }
 #define SLS_BWD_LAUNCH(LEAN_, FUSED_, DET_, DENSE_)                                                                  \
-    hipLaunchKernelGGL((render_bwd_block_kernel<8, 2, LEAN_, FUSED_, DET_, DENSE_>), grid, block, 0, st, cam, (const uint2 *)ranges, \
-                       vals, (const float4 *)rec, (const float2 *)col_cs, (const float2 *)row_cs,                    \
-                       (const float4 *)pix_state, (const uint2 *)pix_contrib, dL_dallmap, grec, block_masks,         \
-                       touched, g_dbg_bwd_cycles, ca, cblocks, det_max, det_acc, block_order, vals_stride, det_prev, det_gex, det_flag, order_tag)
+    hipLaunchKernelGGL((render_bwd_block_kernel<8, 2, LEAN_, FUSED_, DET_, DENSE_>), grid, block, 0, st, cam, (const uint2 *)a.ranges, \
+                       a.vals, (const float4 *)a.rec, (const float2 *)a.col_cs, (const float2 *)a.row_cs,            \
+                       (const float4 *)a.pix_state, (const uint2 *)a.pix_contrib, a.dL_dallmap, a.grec, block_masks, \
+                       a.touched, g_dbg_bwd_cycles, ca, cblocks, a.det_max, a.det_acc, block_order, a.vals_stride, a.det_prev, a.det_gex, a.det_flag, a.order_tag)
 #define SLS_BWD_BLOCK(LEAN_, FUSED_, DET_)                                                                           \
     do { if (dense) SLS_BWD_LAUNCH(LEAN_, FUSED_, DET_, true); else SLS_BWD_LAUNCH(LEAN_, FUSED_, DET_, false); } while (0)
-    if (det_prev) {
+    if (a.det_prev) {
         // deterministic accumulation in ONE launch: predicted scales (on the forward's compact lists only)
-        SLS_REQUIRE(det_acc && det_gex && det_flag && dense, "the one-pass deterministic accumulation needs the forward's compact lists");
+        SLS_REQUIRE(a.det_acc && a.det_gex && a.det_flag && dense, "the one-pass deterministic accumulation needs the forward's compact lists");
         if (fused_consumer) { SLS_REQUIRE(lean, "the fused consumer gradient exists for the lean kernel only");
                               if (consumer_b_inline) SLS_BWD_LAUNCH(true, 2, 3, true); else SLS_BWD_LAUNCH(true, 1, 3, true); }
         else if (lean) SLS_BWD_LAUNCH(true, 0, 3, true);
         else SLS_BWD_LAUNCH(false, 0, 3, true);
-    } else if (det_max) {
+    } else if (a.det_max) {
         // deterministic accumulation: two launches (maximum, then fixed-point sum)
-        SLS_REQUIRE(det_acc, "deterministic accumulation needs both accumulators");
+        SLS_REQUIRE(a.det_acc, "deterministic accumulation needs both accumulators");
         if (fused_consumer) { SLS_REQUIRE(lean, "the fused consumer gradient exists for the lean kernel only");
                               if (consumer_b_inline) { SLS_BWD_BLOCK(true, 2, 1); SLS_BWD_BLOCK(true, 2, 2); }
                               else { SLS_BWD_BLOCK(true, 1, 1); SLS_BWD_BLOCK(true, 1, 2); } }

@@ -31,7 +31,7 @@
 #include <cstdlib>
 #include "sls_common.hpp"
 #include "sls_resort.hpp"
-#include "sls_bin.hpp"
+#include "sls_launch.hpp"
 
 namespace sls {
 
@@ -1472,7 +1472,6 @@ static int bits_for(uint32_t max_value)
 //   order   : N u32, surfel index at each depth-order position
 //   offsets : N u32, inclusive scan of tiles_touched[order[.]]
 //   total   : device u32 = R
-// scratch: order keys (N) | tmp keys (N) | tmp vals (N) | 2 pad | block sums | N on device | sort scratch
 size_t order_scratch_bytes(int N)
 {
     const size_t n = (size_t)(N > 0 ? N : 1);
@@ -1480,64 +1479,59 @@ size_t order_scratch_bytes(int N)
     return sizeof(uint32_t) * (3 * n + (n + 255) / 256 + 64) + sort_scratch_bytes(n) + 16 + n / 32 + 128;
 }
 
+// The scratch of the depth-order stage, carved:
+//   order keys (N) | tmp keys (N) | tmp vals (N) | 2 pad | block sums | N on device | sort scratch
+struct OrderScratch {
+    uint32_t *keys, *keys_tmp, *vals_tmp, *block_sums, *n_dev;
+    void *sort_scratch;
+    uint64_t *comp;     // where the repair keeps its (key, surfel) pairs: N u64 over the sort's two temporary arrays
+    bool odd;           // an odd number of passes: the sorted values land in the "other" buffer, so the identity
+                        // permutation starts in vals_tmp and the result ends in `order`
+    OrderScratch(int N, void *scratch)
+    {
+        keys = (uint32_t *)scratch; keys_tmp = keys + N; vals_tmp = keys_tmp + N;
+        block_sums = vals_tmp + N + 2;      // padding: the 8-byte aligned u64 view of the temporaries may end one word late
+        n_dev = block_sums + (N + 255) / 256;   // device copy of N for the count_ptr protocol
+        sort_scratch = (void *)(n_dev + 32);
+        comp = (uint64_t *)(((uintptr_t)keys_tmp + 7) & ~(uintptr_t)7);
+        odd = (sort_passes(kDepthKeyBits) & 1) != 0;
+    }
+};
+
 // where preprocess may write the sort input directly (saves the depth_keys launch)
-void depth_order_key_buffers(int N, void *scratch, uint32_t *order, uint32_t **keys, uint32_t **vals0,
-                             uint32_t **n_dev)
+void depth_order_key_buffers(int N, void *scratch, uint32_t *order, uint32_t **keys, uint32_t **vals0, uint32_t **n_dev)
 {
-    const int nb = (N + 255) / 256;
-    *keys = (uint32_t *)scratch;
-    // with an odd number of passes the sorted values land in the "other" buffer, so the
-    // identity permutation starts in the scratch buffer and the result ends in `order`
-    *vals0 = (sort_passes(kDepthKeyBits) & 1) ? *keys + 2 * (size_t)N : order;
-    *n_dev = *keys + 3 * (size_t)N + 2 + nb;   // (2 words of padding: see launch_depth_order_scan)
+    const OrderScratch s(N, scratch);
+    *keys = s.keys;
+    *vals0 = s.odd ? s.vals_tmp : order;
+    *n_dev = s.n_dev;
 }
 
-// reuse_order != 0: `order` holds the permutation of the previous iteration (same surfels, same
-// keyframe) and the keys were written by preprocess (keys_prefilled): temporal re-sort, failure is
-// reported in *fail_flag (see above).
-// where the repair keeps its (key, surfel) pairs: N u64 over the sort's two temporary arrays
-uint64_t *resort_comp_buffer(int N, void *scratch)
-{
-    uint32_t *keys_tmp = (uint32_t *)scratch + N;
-    return (uint64_t *)(((uintptr_t)keys_tmp + 7) & ~(uintptr_t)7);
-}
+uint64_t *resort_comp_buffer(int N, void *scratch) { return OrderScratch(N, scratch).comp; }
 
-// window_sort_done: step A of the repair (resort_sort) already ran — merged into the preprocess launch
-int launch_depth_order_scan(int N, const float *depth, const uint32_t *tiles, uint32_t *order, uint32_t *offsets,
-                            uint32_t *total_out, void *scratch, size_t scratch_bytes, int keys_prefilled,
-                            hipStream_t st, int reuse_order, uint32_t *fail_flag, ScanHandoff *handoff,
-                            bool window_sort_done, const DirectBin *direct, const int4 *erec_box, int GX)
+int launch_depth_order_scan(const DepthOrderScan &a, hipStream_t st, ScanHandoff *handoff)
 {
-    // direct (+ handoff): the direct binning follows — the repair's last merge fills the count table (handoff->counted),
-    // no scan of tiles_touched is needed at all
-    if (scratch_bytes < order_scratch_bytes(N)) {
-        set_error("depth-order scratch too small: %zu < %zu", scratch_bytes, order_scratch_bytes(N));
+    const int N = a.N, reuse_order = a.reuse_order;
+    uint32_t *order = a.order;
+    const DirectBin *direct = a.direct;
+    if (a.scratch_bytes < order_scratch_bytes(N)) {
+        set_error("depth-order scratch too small: %zu < %zu", a.scratch_bytes, order_scratch_bytes(N));
         return SLS_E_SCRATCH;
     }
     const int nb = (N + 255) / 256;
-    uint32_t *keys = (uint32_t *)scratch;
-    uint32_t *keys_tmp = keys + N;
-    uint32_t *vals_tmp = keys_tmp + N;
-    uint32_t *block_sums = vals_tmp + N + 2;    // padding: the 8-byte aligned u64 view of the temporaries may end one word late
-    uint32_t *n_dev = block_sums + nb;          // device copy of N for the count_ptr protocol
-    void *sort_scratch = (void *)(n_dev + 32);
-    const size_t sort_bytes = sort_scratch_bytes((uint64_t)N);
-    const bool odd = (sort_passes(kDepthKeyBits) & 1) != 0;
-    uint32_t *v0 = odd ? vals_tmp : order, *v1 = odd ? order : vals_tmp;
-    if (!keys_prefilled) {
-        set_error("internal: the depth keys are written by preprocess");
-        return SLS_E_ARG;
-    }
+    const OrderScratch s(N, a.scratch);
+    uint32_t *keys = s.keys, *block_sums = s.block_sums;
+    uint32_t *v0 = s.odd ? s.vals_tmp : order, *v1 = s.odd ? order : s.vals_tmp;
     int resort_windows = 0;
     const uint64_t *resort_edges = nullptr;
-    if (reuse_order && keys_prefilled && fail_flag) {
+    if (reuse_order && a.fail_flag) {
         // comp: N u64 over the two temporary arrays (8-byte aligned), edges in the sort's count table
-        uint64_t *comp = resort_comp_buffer(N, scratch);
-        uint64_t *edges = (uint64_t *)(((uintptr_t)sort_scratch + 7) & ~(uintptr_t)7);
+        uint64_t *comp = s.comp;
+        uint64_t *edges = (uint64_t *)(((uintptr_t)s.sort_scratch + 7) & ~(uintptr_t)7);
         const int nA = (N + kResortWindow - 1) / kResortWindow;
         const int nB = (N + kResortWindow / 2 + kResortWindow - 1) / kResortWindow;   // windows that hold a real element
         ScopedTimer tm(T_RESORT, st);
-        if (!window_sort_done) {
+        if (!a.window_sort_done) {
             hipLaunchKernelGGL(resort_sort_kernel, dim3(nA), dim3(kResortThreads), 0, st, N, (const uint32_t *)order,
                                (const uint32_t *)keys, comp);
             SLS_LAUNCH_CHECK("resort_sort_kernel");
@@ -1551,11 +1545,11 @@ int launch_depth_order_scan(int N, const float *depth, const uint32_t *tiles, ui
         do {                                                                                                                 \
             if (count_here && (last_))                                                                                       \
                 hipLaunchKernelGGL((resort_merge_kernel<true, PRE_>), dim3(nB), dim3(kResortThreads), 0, st, N,               \
-                                   (const uint64_t *)(in_), order, edges, tiles, block_sums, GX, (const uint2 *)erec_box,      \
+                                   (const uint64_t *)(in_), order, edges, a.tiles, block_sums, a.GX, (const uint2 *)a.erec_box,      \
                                    *direct, (uint64_t *)(out_));                                                              \
             else                                                                                                             \
                 hipLaunchKernelGGL((resort_merge_kernel<false, PRE_>), dim3(nB), dim3(kResortThreads), 0, st, N,              \
-                                   (const uint64_t *)(in_), order, edges, tiles, block_sums, GX, (const uint2 *)erec_box,      \
+                                   (const uint64_t *)(in_), order, edges, a.tiles, block_sums, a.GX, (const uint2 *)a.erec_box,      \
                                    no_db, (uint64_t *)(out_));                                                                \
         } while (0)
         SLS_MERGE(false, reuse_order <= 1, comp, reuse_order > 1 ? comp : nullptr);
@@ -1579,74 +1573,61 @@ int launch_depth_order_scan(int N, const float *depth, const uint32_t *tiles, ui
         resort_edges = edges;
     } else {
         int which = 0;
-        int rc = radix_sort_pairs_t<uint32_t>(keys, v0, keys_tmp, v1, n_dev, (uint32_t)N, kDepthKeyBits, sort_scratch,
-                                              sort_bytes, &which, st, nullptr, 0, true);   // only the order is used
+        int rc = radix_sort_pairs_t<uint32_t>(keys, v0, s.keys_tmp, v1, s.n_dev, (uint32_t)N, kDepthKeyBits, s.sort_scratch,
+                                              sort_scratch_bytes((uint64_t)N), &which, st, nullptr, 0, true);   // only the order is used
         if (rc) return rc;
-        if ((which != 0) != odd) {
+        if ((which != 0) != s.odd) {
             set_error("internal: depth order ended in the wrong buffer");
             return SLS_E_ARG;
         }
     }
     if (handoff && direct && resort_windows == 0) {      // from scratch + direct binning: nothing to scan
-        handoff->block_sums = nullptr;
-        handoff->resort_windows = 0;
-        handoff->resort_edges = nullptr;
-        handoff->counted = 0;
+        *handoff = ScanHandoff{ nullptr, 0, nullptr, 0 };
         return SLS_OK;
     }
     if (handoff && resort_windows > 0) {   // the emission finishes the scan and checks the repaired order
-        handoff->block_sums = block_sums;
-        handoff->resort_windows = resort_windows;
-        handoff->resort_edges = resort_edges;
+        *handoff = ScanHandoff{ block_sums, resort_windows, resort_edges, handoff->counted };
         return SLS_OK;
     }
     ScopedTimer tm(T_SCAN, st);
     if (resort_windows == 0) {   // (the merge kernel of the repair already summed the blocks)
-        hipLaunchKernelGGL(gather_block_sums_kernel, dim3(nb), dim3(256), 0, st, N, (const uint32_t *)order, tiles,
+        hipLaunchKernelGGL(gather_block_sums_kernel, dim3(nb), dim3(256), 0, st, N, (const uint32_t *)order, a.tiles,
                            block_sums);
         SLS_LAUNCH_CHECK("gather_block_sums_kernel");
     }
     if (handoff) {
-        handoff->block_sums = block_sums;
-        handoff->resort_windows = 0;
-        handoff->resort_edges = nullptr;
+        *handoff = ScanHandoff{ block_sums, 0, nullptr, handoff->counted };
         return SLS_OK;
     }
-    hipLaunchKernelGGL(gather_scan_final_kernel, dim3(nb), dim3(256), 0, st, N, (const uint32_t *)order, tiles,
-                       (const uint32_t *)block_sums, offsets, total_out, resort_windows, resort_edges, fail_flag);
+    hipLaunchKernelGGL(gather_scan_final_kernel, dim3(nb), dim3(256), 0, st, N, (const uint32_t *)order, a.tiles,
+                       (const uint32_t *)block_sums, a.offsets, a.total_out, resort_windows, resort_edges, a.fail_flag);
     SLS_LAUNCH_CHECK("gather_scan_final_kernel");
     return SLS_OK;
 }
 
-// Emission in depth order + stable sort by tile + ranges.
-//   tkeys/vals, tkeys_tmp/vals_tmp : cap u32 each (ping-pong)
-//   count_ptr: device R; cap: host-side capacity of the buffers (>= R, or the
-//   overflow flag is raised and the excess instances are dropped)
-int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_t cap, const uint32_t *order,
-                    const int32_t *rect, const uint32_t *tiles, const uint64_t *tile_mask, const int32_t *erec,
-                    const float *depth, const uint32_t *offsets,
-                    uint32_t *tkeys, uint32_t *vals, uint32_t *tkeys_tmp, uint32_t *vals_tmp, void *scratch,
-                    size_t scratch_bytes, int *sorted_in_tmp, uint32_t *ranges, uint64_t *keys64_out,
-                    uint32_t *overflow, hipStream_t st, const ScanHandoff *handoff, uint32_t *total_out,
-                    const uint32_t *sbox, const uint2 **bmask_out, int bmask_mode)
+// Emission in depth order + stable sort by tile + ranges (cap >= R, or the overflow flag is raised and the excess
+// instances are dropped)
+int launch_bin_sort(const DevCam &cam, const BinSortLaunch &a, hipStream_t st, int *sorted_in_tmp, const uint2 **bmask_out)
 {
-    // sbox + bmask_out (optional): the sorted list comes out as (surfel, mask of reachable 8x2 pixel blocks) pairs in
-    // *bmask_out (sort_bmask_buffer) and the plain value arrays are NOT written; *bmask_out stays null — and the values
-    // are written as ever — where that is not possible (more than one sort pass, other tile sizes, switched off)
-    const int T = cam.GX * cam.GY;
+    // sbox + bmask_out: the list comes out as (surfel, mask of reachable 8x2 pixel blocks) pairs (sort_bmask_buffer) and the
+    // plain value arrays are NOT written — where possible (one sort pass, 16x16 tiles, not switched off)
+    const int T = cam.GX * cam.GY, N = a.N;
+    const uint32_t cap = a.cap;
+    void *scratch = a.scratch;
+    uint32_t *ranges = a.ranges, *tkeys = a.tkeys, *vals = a.vals, *tkeys_tmp = a.tkeys_tmp, *vals_tmp = a.vals_tmp;
     *sorted_in_tmp = 0;
     if (bmask_out) *bmask_out = nullptr;
     if (cap == 0 || N == 0) {
         SLS_HIP_CHECK(hipMemsetAsync(ranges, 0, sizeof(uint32_t) * 2 * (size_t)T, st));
         return SLS_OK;
     }
-    if (scratch_bytes < sort_scratch_bytes(cap)) {
-        set_error("sort scratch too small: %zu < %zu", scratch_bytes, sort_scratch_bytes(cap));
+    if (a.scratch_bytes < sort_scratch_bytes(cap)) {
+        set_error("sort scratch too small: %zu < %zu", a.scratch_bytes, sort_scratch_bytes(cap));
         return SLS_E_SCRATCH;
     }
     const int tile_bits = bits_for((uint32_t)(T - 1));
     // one pass over the tile ids (T <= 2048): the sort's digit bases are the ranges
-    const bool fused_ranges = sort_passes(tile_bits) == 1 && keys64_out == nullptr;
+    const bool fused_ranges = sort_passes(tile_bits) == 1 && a.keys64_out == nullptr;
     if (!fused_ranges) SLS_HIP_CHECK(hipMemsetAsync(ranges, 0, sizeof(uint32_t) * 2 * (size_t)T, st));
     // ... and if tile id and surfel index fit one word together, an instance IS one word:
     // half the traffic in emit, histogram and scatter
@@ -1667,10 +1648,10 @@ int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_
                            ((size_t)bins * nemit + bins + nemit + 1) * sizeof(uint32_t) <= sort_core_bytes(cap);
     // Block masks (the forward's dense rounds) only where the tiles' lists are long enough for the forward to gain more than the binning pays:
     // capacity per tile as the host-side proxy (bmask_mode = SlsMappingConfig.block_masks: 0 auto, 1 always, 2 never)
-    const bool long_lists = bmask_mode == 1 || (bmask_mode == 0 && (uint64_t)cap >= 1500ull * (uint64_t)T);
+    const bool long_lists = a.bmask_mode == 1 || (a.bmask_mode == 0 && (uint64_t)cap >= 1500ull * (uint64_t)T);
     BlockMaskArgs bm = { nullptr, cam.GX, 1.0f / (float)cam.GX, (cam.GX * kTileW) / 8 };
     uint64_t *wide = nullptr;
-    if (sbox && bmask_out && packed && kTileW == 16 && kTileH == 16 && long_lists &&
+    if (a.sbox && bmask_out && packed && kTileW == 16 && kTileH == 16 && long_lists &&
         block_box_fits(cam.GX * kTileW, cam.H)) {
         bm.out = sort_bmask_buffer(scratch, cap);
         wide = sort_wide_buffer(scratch, cap);
@@ -1678,13 +1659,11 @@ int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_
     }
     {
         ScopedTimer tm(T_EMIT_KEYS, st);
-#define SLS_EMIT(EB_) hipLaunchKernelGGL(emit_tiles_kernel<EB_>, dim3(nemit), dim3(EB_), 0, st, N, cam.GX, order,                 \
-                           (const int4 *)rect, tiles, tile_mask, (const int4 *)erec, offsets, cap, tkeys, packed ? (uint32_t *)nullptr : vals, overflow, \
-                           packed ? idx_bits : 0, handoff ? *handoff : ScanHandoff{ nullptr, 0, nullptr, 0 }, total_out,  \
-                           overflow, emit_hist ? cnt : (uint32_t *)nullptr, bins, emit_hist ? chunk_start : (uint32_t *)nullptr, \
-                           sbox, wide)
-        SLS_EMIT(eb);
-#undef SLS_EMIT
+        hipLaunchKernelGGL(emit_tiles_kernel<eb>, dim3(nemit), dim3(eb), 0, st, N, cam.GX, a.order, (const int4 *)a.rect, a.tiles,
+                           a.tile_mask, (const int4 *)a.erec, a.offsets, cap, tkeys, packed ? (uint32_t *)nullptr : vals, a.overflow,
+                           packed ? idx_bits : 0, a.handoff ? *a.handoff : ScanHandoff{ nullptr, 0, nullptr, 0 }, a.total_out,
+                           a.overflow, emit_hist ? cnt : (uint32_t *)nullptr, bins, emit_hist ? chunk_start : (uint32_t *)nullptr,
+                           a.sbox, wide);
     }
     SLS_LAUNCH_CHECK("emit_tiles_kernel");
     int which = 0;
@@ -1703,14 +1682,14 @@ int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_
 #undef SLS_CASE
         which = 1;
     } else if (wide) {
-        rc = radix_sort_pairs_t<uint64_t>(wide, nullptr, nullptr, vals_tmp, count_ptr, cap, tile_bits, scratch,
-                                          scratch_bytes, &which, st, (uint2 *)ranges, T, true, idx_bits, bm);
+        rc = radix_sort_pairs_t<uint64_t>(wide, nullptr, nullptr, vals_tmp, a.count_ptr, cap, tile_bits, scratch,
+                                          a.scratch_bytes, &which, st, (uint2 *)ranges, T, true, idx_bits, bm);
     } else if (packed) {
-        rc = radix_sort_pairs_t<uint32_t>(tkeys, nullptr, tkeys_tmp, vals_tmp, count_ptr, cap, tile_bits, scratch,
-                                          scratch_bytes, &which, st, (uint2 *)ranges, T, true, idx_bits);
+        rc = radix_sort_pairs_t<uint32_t>(tkeys, nullptr, tkeys_tmp, vals_tmp, a.count_ptr, cap, tile_bits, scratch,
+                                          a.scratch_bytes, &which, st, (uint2 *)ranges, T, true, idx_bits);
     } else {
-        rc = radix_sort_pairs_t<uint32_t>(tkeys, vals, tkeys_tmp, vals_tmp, count_ptr, cap, tile_bits, scratch,
-                                          scratch_bytes, &which, st, fused_ranges ? (uint2 *)ranges : nullptr, T,
+        rc = radix_sort_pairs_t<uint32_t>(tkeys, vals, tkeys_tmp, vals_tmp, a.count_ptr, cap, tile_bits, scratch,
+                                          a.scratch_bytes, &which, st, fused_ranges ? (uint2 *)ranges : nullptr, T,
                                           fused_ranges);   // nobody reads the sorted tile ids then
     }
     if (rc) return rc;
@@ -1719,7 +1698,7 @@ int launch_bin_sort(const DevCam &cam, int N, const uint32_t *count_ptr, uint32_
         ScopedTimer tm(T_TILE_RANGES, st);
         hipLaunchKernelGGL(tile_ranges_kernel, dim3((cap + 255) / 256), dim3(256), 0, st,
                            (const uint32_t *)(which ? tkeys_tmp : tkeys), (const uint32_t *)(which ? vals_tmp : vals),
-                           count_ptr, cap, depth, (uint2 *)ranges, keys64_out);
+                           a.count_ptr, cap, a.depth, (uint2 *)ranges, a.keys64_out);
         SLS_LAUNCH_CHECK("tile_ranges_kernel");
     }
     return SLS_OK;
@@ -1775,19 +1754,16 @@ DirectBin make_direct_bin(const DevCam &cam, int N, void *sort_scratch, uint2 *s
 }
 
 // order (+ erec_box, or rect + sbox) -> sorted list (vals_out, or (surfel, block mask) pairs in *bmask_out), ranges, R.
-// counted: the count table was filled by the repair's merge (launch_depth_order_scan).
-int launch_bin_direct(const DevCam &cam, int N, uint32_t cap, const DirectBin &db, bool counted, const uint32_t *order,
-                      const int32_t *erec_box, const int32_t *rect, const uint32_t *sbox, void *scratch, uint32_t *vals_out,
-                      uint32_t *ranges, uint32_t *total_out, uint32_t *overflow, int resort_windows,
-                      const uint64_t *resort_edges, const uint2 **bmask_out, int bmask_mode, hipStream_t st,
-                      uint32_t *status_mirror)
+int launch_bin_direct(const DevCam &cam, const BinDirectLaunch &a, hipStream_t st, const uint2 **bmask_out)
 {
-    const int T = cam.GX * cam.GY;
+    const int T = cam.GX * cam.GY, N = a.N;
+    const uint32_t cap = a.cap;
+    const DirectBin &db = a.db;
     if (bmask_out) *bmask_out = nullptr;
-    if (!counted) {
+    if (!a.counted) {
         ScopedTimer tm(T_BIN_COUNT, st);
-        hipLaunchKernelGGL(gather_count_kernel, dim3(db.nchunks), dim3(kDirectChunk), 0, st, N, cam.GX, order,
-                           (const uint2 *)erec_box, (const int4 *)rect, sbox, db);
+        hipLaunchKernelGGL(gather_count_kernel, dim3(db.nchunks), dim3(kDirectChunk), 0, st, N, cam.GX, a.order,
+                           (const uint2 *)a.erec_box, (const int4 *)a.rect, a.sbox, db);
         SLS_LAUNCH_CHECK("gather_count_kernel");
     }
     if (!db.coarse) {       // (with the coarse table bin_direct sums what lies in front of a chunk itself)
@@ -1797,11 +1773,11 @@ int launch_bin_direct(const DevCam &cam, int N, uint32_t cap, const DirectBin &d
         SLS_LAUNCH_CHECK("sort_rowscan_kernel");
     }
     // (surfel, block mask) pairs under the rule of launch_bin_sort: long lists (or always / never)
-    const bool long_lists = bmask_mode == 1 || (bmask_mode == 0 && (uint64_t)cap >= 1500ull * (uint64_t)T);
-    const bool have_box = erec_box != nullptr || sbox != nullptr;
+    const bool long_lists = a.bmask_mode == 1 || (a.bmask_mode == 0 && (uint64_t)cap >= 1500ull * (uint64_t)T);
+    const bool have_box = a.erec_box != nullptr || a.sbox != nullptr;
     BlockMaskArgs bm = { nullptr, cam.GX, 1.0f / (float)cam.GX, (cam.GX * kTileW) / 8 };
     if (bmask_out && have_box && long_lists && kTileW == 16 && kTileH == 16 && block_box_fits(cam.GX * kTileW, cam.H)) {
-        bm.out = sort_bmask_buffer(scratch, cap);
+        bm.out = sort_bmask_buffer(a.scratch, cap);
         *bmask_out = bm.out;
     }
     {
@@ -1811,8 +1787,8 @@ int launch_bin_direct(const DevCam &cam, int N, uint32_t cap, const DirectBin &d
         //  what IS split, since round 6, are the heavy chunks at the front of the depth order: the helper workgroups)
         const int nhelp = (db.nchunks < kHeavyChunks ? db.nchunks : kHeavyChunks) * (kHeavyParts - 1);
 #define SLS_DIRECT(B_, P_) hipLaunchKernelGGL((bin_direct_kernel<B_, P_, 1>), dim3(nhelp + db.nchunks), dim3(kDirectChunk), 0, st, N, cam.GX, db, \
-                               order, (const uint2 *)erec_box, (const int4 *)rect, sbox, cap, vals_out, bm, (uint2 *)ranges, T, \
-                               total_out, overflow, resort_windows, resort_edges, overflow, status_mirror)
+                               a.order, (const uint2 *)a.erec_box, (const int4 *)a.rect, a.sbox, cap, a.vals_out, bm, (uint2 *)a.ranges, T, \
+                               a.total_out, a.overflow, a.resort_windows, a.resort_edges, a.overflow, a.status_mirror)
         if (db.bins == 256) { if (bm.out) SLS_DIRECT(8, true); else SLS_DIRECT(8, false); }
         else { if (bm.out) SLS_DIRECT(9, true); else SLS_DIRECT(9, false); }
 #undef SLS_DIRECT

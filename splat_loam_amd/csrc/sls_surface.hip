@@ -16,7 +16,7 @@
 //                           another workgroup's result; workgroup 0 writes the status.  A thread then draws its rank,
 //                           bisects the prefix for the word, picks the rank-th set bit, gathers the seven planes at
 //                           that one pixel (28 B) and writes its two rows (24 B) and its pixel (4 B).
-#include "sls_common.hpp"
+#include "sls_launch.hpp"
 #include "../../include/sls_draw_math.h"
 
 namespace sls {
