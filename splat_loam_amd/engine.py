@@ -39,12 +39,52 @@ import ctypes as C
 import os
 import weakref
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _abi
 from .fused import camera_aux
-from .rasterizer import GaussianRasterizationSettings, get_camera
+from .rasterizer import GaussianRasterizationSettings, deterministic_mode, get_camera
+
+# word 1 of the status block: any bit set = the iteration is void (Adam was skipped) and must be repeated
+TOO_SMALL = 1               # the instance buffers were too small (word 0 = the room asked for)
+RESORT_FAILED = 2           # the repaired depth order was not exact
+EXCHANGE_TOO_SMALL = 4      # sparse exchange: the union of the touched sets outgrew the collective
+DET_MISPREDICTED = 8        # deterministic = 2: a predicted fixed-point scale was too small
+HANDOVER_MISMATCH = 16      # the tile backward met a hand-over buffer of another forward
+OUTSIDE_UNION = 32          # sparse exchange: a gradient outside the agreed union
+
+
+def status_dict(w, f):
+    """The status dict from the block's eight words as Python ints (`w`) and as the floats the same bits spell (`f`)."""
+    flags = w[1]
+    return {"R": w[0] & 0xFFFFFFFF, "overflow": bool(flags), "too_small": bool(flags & TOO_SMALL),
+            "resort_failed": bool(flags & RESORT_FAILED), "exchange_too_small": bool(flags & EXCHANGE_TOO_SMALL),
+            "det_mispredicted": bool(flags & DET_MISPREDICTED), "handover_mismatch": bool(flags & HANDOVER_MISMATCH),
+            "outside_union": bool(flags & OUTSIDE_UNION), "exchange_count": w[7] & 0xFFFFFFFF,
+            "loss_pixel": f[5], "loss_reg": f[6], "loss": f[5] + f[6], "sums": [f[2], f[3], f[4]]}
+
+
+def repair_rounds(age, base_rounds, max_order_age, order_age_round3, max_order_age_extra, order_age_round4, allow):
+    """How a depth order last written `age` iterations ago (None: never) is brought up to date: 0 = from scratch,
+    1..4 = that many repair rounds — `base_rounds`, one more beyond each of `max_order_age`, `order_age_round3` and
+    `order_age_round4` (the surfels have drifted further), four at the most; an order older than
+    `max_order_age_extra` is rebuilt, and so is every order where reuse is not allowed."""
+    if not allow or age is None or age > max_order_age_extra:
+        return 0
+    return min(base_rounds + (age > max_order_age) + (age > order_age_round3) + (age > order_age_round4), 4)
+
+
+class _Keyframe:
+    """What the engine keeps per keyframe: its depth order and the iteration that wrote it (None: void), a weak
+    reference to the camera (an id can be reused by a new object once the old keyframe is gone), the tile backward's
+    launch order (SlsMappingConfig.block_order; zeros: none yet) and, under deterministic = 2 only, the uint8 (N, 16)
+    predicted scales (None: nothing to predict from yet — the visit runs the two-launch scheme)."""
+    __slots__ = ("order", "stamp", "camera", "block_order", "det_prev")
+
+    def __init__(self, order, camera, block_order):
+        self.order, self.stamp, self.camera, self.block_order, self.det_prev = order, None, weakref.ref(camera), block_order, None
 
 
 def carry_bucket(buf: torch.Tensor, keep: torch.Tensor, n_new: int) -> torch.Tensor:
@@ -112,6 +152,10 @@ class MappingEngine:
         self.t = 0
         self.capacity = 0
         self.workspace = None
+        self._ws_n = 0                    # surfels the workspace was sized for
+        self._bucket_store = None         # resize(): the three flat buckets' backing store, with head room
+        self._bws = None                  # step_batch()'s workspace (_ensure_batch_workspace)
+        self.last_batch_reuse = None      # repair rounds of the last batch's keyframes
         self.allmap_ptr = C.c_void_p(0)
         self.last = None
         # lagged status read (sync="lagged"): two status slots on the device, pinned mirrors, events
@@ -144,10 +188,9 @@ class MappingEngine:
         self._ws_hw = None
         self._ws_det = None
         self.status_mirror = True          # (False: the status through a device -> host copy; lagged mode)
-        # one depth-order buffer per keyframe (the mapper samples keyframes at random, slam/mapper.py:152-156):
-        # id(camera) -> [order tensor, iteration it was last written, weak reference to the camera (an id can be
-        # reused by a new object once the old keyframe is gone)]; an order older than max_order_age
-        # iterations gets an extra repair round, one older than max_order_age_extra is rebuilt from scratch
+        # one cache entry per keyframe (the mapper samples keyframes at random, slam/mapper.py:152-156):
+        # id(camera) -> _Keyframe, at most max_cached_orders of them, oldest first out; an order older than
+        # max_order_age iterations gets an extra repair round, one older than max_order_age_extra is rebuilt
         self._orders = {}
         self._set_order_ages()
         self.max_cached_orders = 64
@@ -157,12 +200,10 @@ class MappingEngine:
         self.dp_mode = os.environ.get("SLS_DP_MODE", "rs_ag")
         self._dp = None                   # dict(G, rank, C, flat, gshard) once the reduce-scatter layout is in place
         self._dp_agreed, self._dp_use_rs, self._dp_scheme = None, False, 0    # (G, rank) the scheme was agreed for; the agreed verdict
-        from .rasterizer import deterministic_mode
         # integer-atomic gradient accumulation: False / True (SLS_DETERMINISTIC=1: two tile-backward launches) / 2
         # (SLS_DETERMINISTIC=2: one launch with scales predicted from the keyframe's previous iteration; the first
         # iteration on a workspace, and any iteration after a misprediction, run the two-launch scheme)
         self.deterministic = 2 if os.environ.get("SLS_DETERMINISTIC", "0") == "2" else deterministic_mode()
-        self._det_prev = {}               # id(camera) -> [uint8 (N, 16) predicted scales, weak reference to the camera]
         self._det_two_pass_next = True    # the next deterministic iteration runs the two-launch scheme
         self.block_masks = int(os.environ.get("SLS_BLOCK_MASKS", "0"))   # 0: auto (long lists), 1: always, 2: never (SlsMappingConfig.block_masks)
         self._sx = None                   # sparse exchange: dict(bitmap, prefix, compact, cap, send) once set up
@@ -191,19 +232,28 @@ class MappingEngine:
     def _ensure_workspace(self, H, W, capacity):
         lib = _abi.lib()
         if (self.workspace is None or capacity > self.capacity or (H, W) != self._ws_hw
-                or self._ws_det != bool(self.deterministic) or self.N > getattr(self, "_ws_n", 0)):
+                or self._ws_det != bool(self.deterministic) or self.N > self._ws_n):
             self._ws_det = bool(self.deterministic)
             self.capacity, self._ws_hw = int(max(capacity, self.capacity)), (H, W)   # (keyframes of another size: re-carve)
             wcfg = _abi.SlsMappingConfig()
             wcfg.deterministic = 1 if self.deterministic else 0     # (the fixed-point accumulators only when asked for)
             # (sized for a quarter more surfels than there are: resize() keeps it while the model grows into that room)
-            self._ws_n = self.N + (self.N // 4 if getattr(self, "_bucket_store", None) is not None else 0)
+            self._ws_n = self.N + (self.N // 4 if self._bucket_store is not None else 0)
             nbytes = int(lib.sls_mapping_workspace_bytes_cfg(self._ws_n, H, W, self.capacity, C.byref(wcfg)))
             self.workspace = None     # release before re-allocating
             self.workspace = torch.empty((nbytes + 256,), dtype=torch.uint8, device=self.dev)
             self._ws_ready = False
-        base = self.workspace.data_ptr()
-        return (base + 255) & ~255, self.workspace.numel() - 256
+        return self._aligned(self.workspace)
+
+    @staticmethod
+    def _aligned(buf):
+        """(pointer, bytes) of a workspace buffer allocated with 256 bytes to spare: its first 256-byte boundary on."""
+        return (buf.data_ptr() + 255) & ~255, buf.numel() - 256
+
+    def _first_capacity(self):
+        if self.capacity == 0:
+            self.capacity = max(4 * self.N, 1 << 16)
+        return self.capacity
 
     def _config(self, apply_adam, with_regulariser, reuse_order=False):
         c, cfg = _abi.SlsMappingConfig(), self.cfg
@@ -228,12 +278,12 @@ class MappingEngine:
 
     def _order_entry(self, camera):
         ent = self._orders.get(id(camera))
-        return ent if ent is not None and ent[2]() is camera else None
+        return ent if ent is not None and ent.camera() is camera else None
 
     def _forget_order(self, camera, failed_repair=False):
         ent = self._order_entry(camera)
         if ent is not None:
-            ent[1] = None
+            ent.stamp = None
         if failed_repair:
             self._repair_rounds = min(self._repair_rounds + 1, 3)
             self._repair_until = self._enq + self.repair_span
@@ -253,52 +303,42 @@ class MappingEngine:
         self.max_order_age_extra = int(48 * scale)
         self.order_age_round4 = 1000000
 
-    def _order_for(self, camera, allow_reuse, H, W, advance=True):
-        """The keyframe's cached depth order and tile-backward launch order (created on its first visit), and how the
-        iteration enqueued next brings the depth order up to date: 0 = from scratch, 1..4 = repair rounds.
+    def _keyframe_inputs(self, camera, H, W, allow_reuse, advance=True):
+        """What one keyframe hands to the native step: its camera entry, its aux tables, its cache entry (created on
+        the first visit) and how the iteration enqueued next brings its depth order up to date (repair_rounds).
         advance=False: the caller counts the iteration and stamps the entry itself (a batch is ONE update)."""
-        lib = _abi.lib()
+        ce = get_camera(GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix),
+                        self.dev)
+        aux = camera_aux(camera)
         ent = self._order_entry(camera)
         if ent is None:
-            stale = [k for k, e in self._orders.items() if e[2]() is None]
-            for k in stale:
+            for k in [k for k, e in self._orders.items() if e.camera() is None]:
                 del self._orders[k]
-            if len(self._orders) >= self.max_cached_orders:
+            # (an evicted keyframe's next visit sorts from scratch and, under deterministic = 2, takes two launches,
+            #  as a first visit does; the predicted scales alone are 16 N bytes per keyframe)
+            while len(self._orders) >= self.max_cached_orders:
                 self._orders.pop(next(iter(self._orders)))
-            # + the keyframe's launch order of the tile backward (SlsMappingConfig.block_order; zeros: none yet)
-            ent = [torch.empty((self.N,), dtype=torch.int32, device=self.dev), None, weakref.ref(camera),
-                   torch.zeros((int(lib.sls_block_order_bytes(H, W)) // 4,), dtype=torch.int32, device=self.dev)]
-            self._orders[id(camera)] = ent
-        age = self._enq - ent[1] if ent[1] is not None else None
-        reuse = allow_reuse and self.reuse_depth_order and age is not None and age <= self.max_order_age_extra
+            ent = self._orders[id(camera)] = _Keyframe(
+                torch.empty((self.N,), dtype=torch.int32, device=self.dev), camera,
+                torch.zeros((int(_abi.lib().sls_block_order_bytes(H, W)) // 4,), dtype=torch.int32, device=self.dev))
         # after a failed repair the following iterations repair with one more round (one more window of reach,
         # +16 us); every `repair_span` iterations without a failure the number of rounds steps down again
         if self._repair_rounds > 1 and self._enq >= self._repair_until:
             self._repair_rounds -= 1
             self._repair_until = self._enq + self.repair_span
-        # an order older than max_order_age iterations gets one more round (the surfels have drifted further)
-        reuse = min(self._repair_rounds + (1 if age is not None and age > self.max_order_age else 0)
-                    + (1 if age is not None and age > self.order_age_round3 else 0)
-                    + (1 if age is not None and age > self.order_age_round4 else 0), 4) if reuse else 0
+        reuse = repair_rounds(None if ent.stamp is None else self._enq - ent.stamp, self._repair_rounds,
+                              self.max_order_age, self.order_age_round3, self.max_order_age_extra,
+                              self.order_age_round4, allow_reuse and self.reuse_depth_order)
         if advance:
             self._enq += 1
-            ent[1] = self._enq
-        return ent, reuse
+            ent.stamp = self._enq
+        return ce, aux, ent, reuse
 
-    def _det_prev_for(self, camera):
-        """The keyframe's predicted scales (deterministic = 2) and whether this is its first visit."""
-        dent = self._det_prev.get(id(camera))
-        first_visit = dent is None or dent[1]() is not camera
-        if first_visit:
-            for k in [k for k, e in self._det_prev.items() if e[1]() is None]:
-                del self._det_prev[k]
-            # (bounded like the depth orders: 16 N bytes per keyframe; an evicted keyframe's next visit is a
-            #  two-launch iteration, as a first visit is)
-            while len(self._det_prev) >= self.max_cached_orders:
-                self._det_prev.pop(next(iter(self._det_prev)))
-            dent = [torch.zeros((self.N, 16), dtype=torch.uint8, device=self.dev), weakref.ref(camera)]
-            self._det_prev[id(camera)] = dent
-        return dent, first_visit
+    def _det_prev_ptr(self, ent):
+        """The keyframe's predicted scales (deterministic = 2), allocated where it has none yet."""
+        if ent.det_prev is None:
+            ent.det_prev = torch.zeros((self.N, 16), dtype=torch.uint8, device=self.dev)
+        return ent.det_prev.data_ptr()
 
     def _pose_args(self, cfg, slots):
         """The pose gradient's scratch (zeroed once; every call leaves it ready) into `cfg`."""
@@ -319,25 +359,20 @@ class MappingEngine:
                  pose_grad=False):
         lib = _abi.lib()
         H, W = int(camera.image_height), int(camera.image_width)
-        settings = GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix)
-        ce = get_camera(settings, self.dev)
-        aux = camera_aux(camera)
-        if self.capacity == 0:
-            self.capacity = max(4 * self.N, 1 << 16)
-        ws_ptr, ws_bytes = self._ensure_workspace(H, W, self.capacity)
+        ws_ptr, ws_bytes = self._ensure_workspace(H, W, self._first_capacity())
         xyz, scaling, rotation, opacity = self._params()
-        ent, reuse = self._order_for(camera, allow_reuse, H, W)
+        ce, aux, ent, reuse = self._keyframe_inputs(camera, H, W, allow_reuse)
         cfg = self._config(apply_adam, with_regulariser, reuse)
         if self.deterministic == 2:
-            dent, first_visit = self._det_prev_for(camera)
-            cfg.det_prev = dent[0].data_ptr()
+            first_visit = ent.det_prev is None
+            cfg.det_prev = self._det_prev_ptr(ent)
             # two launches where there is nothing to predict from: a workspace's first deterministic iteration (it sets
             # the fields' default scales) and a keyframe's first visit (measured: predicting a new view from the
             # defaults alone voids the iteration almost every time)
             cfg.deterministic = 1 if (self._det_two_pass_next or first_visit or not cfg.workspace_ready) else 2
             self._det_two_pass_next = False
-        cfg.depth_order = ent[0].data_ptr()
-        cfg.block_order = ent[3].data_ptr() if self.inline_loss_stage else None
+        cfg.depth_order = ent.order.data_ptr()
+        cfg.block_order = ent.block_order.data_ptr() if self.inline_loss_stage else None
         cfg.status_mirror = mirror
         # keyframe-parallel mode: the void bits leave the step as two floats behind the gradient bucket
         cfg.void_flags_out = None if (apply_adam or self._dp is not None) else self.grads.data_ptr() + 4 * 10 * self.N
@@ -361,6 +396,40 @@ class MappingEngine:
         if st["resort_failed"]:
             return "repeated_resort"
         return "repeated_det" if st.get("det_mispredicted") else "repeated_exchange"
+
+    def _grown(self, need):
+        """The instance capacity after an iteration that asked for `need` instances found too little room."""
+        return int(max(need, self.capacity) * self.capacity_factor) + 1024
+
+    def _after_void(self, voided, sharded, verdict=None):
+        """Everything that follows a void status, before the repeat.  `voided`: (camera, status) of every iteration —
+        or keyframe of a batch — the repeat covers; `verdict`: a batch's own status, which then decides in their place.
+        Each void keyframe's depth order is forgotten where it may be broken or was never written (a failed repair
+        raises the repair rounds), stats counts ONE repeat under the reason of the verdict (else of the first status),
+        and if room was what lacked, capacity grows from the largest R and both workspaces are dropped (re-carved at
+        the next enqueue; the batch's would be anyway: any change of capacity re-carves it).
+        What the four callers keep to themselves, on purpose:
+          step()         sharded, the status bits are the group's verdict and R is this rank's: MAX over the ranks;
+          step_batch()   voided = the keyframes with their own statuses (this rank's), verdict = the batch's (R their
+                         maximum, bits their OR; sharded as in step());
+          pose_step()    never sharded; touches neither t nor last;
+          _lag_collect() voided = the one or two in-flight iterations; sharded=False even over a group (no collective
+                         there: a rank grows from the R it saw, the redo goes through step()); its own bookkeeping of t.
+        The MAX all-reduce is issued exactly when `sharded` and the deciding status says too_small: that status is
+        the group's verdict there, identical on every rank, so every rank issues the same collectives."""
+        for camera, st in voided:
+            if st["too_small"] or st["resort_failed"]:
+                self._forget_order(camera, failed_repair=st["resort_failed"])
+        deciding = [st for _, st in voided] if verdict is None else [verdict]
+        self.stats[self._void_reason(deciding[0])] += 1
+        if any(st["too_small"] for st in deciding):
+            need = max(st["R"] for st in deciding)
+            if sharded:
+                t = torch.tensor([need], dtype=torch.int64, device=self.dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self._group)
+                need = int(t.item())
+            self.capacity = self._grown(need)
+            self.workspace = self._bws = None
 
     def _sharded(self, group):
         """Keyframe-parallel path?  World size > 1 — or 1 with `exchange_at_world_1` (the collectives then move
@@ -396,29 +465,12 @@ class MappingEngine:
 
     @staticmethod
     def _parse_status(h):
-        R, flags = int(h[0].item()) & 0xFFFFFFFF, int(h[1].item())
-        f = h.view(torch.float32)
-        # "overflow": the iteration is void (Adam was skipped) and must be repeated; bit 0 = the
-        # instance buffers were too small, bit 1 = the repaired depth order was not exact
-        return {"R": R, "overflow": bool(flags), "too_small": bool(flags & 1), "resort_failed": bool(flags & 2),
-                "exchange_too_small": bool(flags & 4), "det_mispredicted": bool(flags & 8),
-                "handover_mismatch": bool(flags & 16), "outside_union": bool(flags & 32),
-                "exchange_count": int(h[7].item()) & 0xFFFFFFFF,
-                "loss_pixel": float(f[5]), "loss_reg": float(f[6]),
-                "loss": float(f[5]) + float(f[6]), "sums": [float(f[2]), float(f[3]), float(f[4])]}
+        return status_dict(h.tolist(), h.view(torch.float32).tolist())
 
     @staticmethod
     def _parse_status_np(h):
         """_parse_status on a NumPy row (int32 x 8) of the pinned mirror: no tensor ops on the host's critical path"""
-        import numpy as np
-        f = h.view(np.float32)
-        R, flags = int(h[0]) & 0xFFFFFFFF, int(h[1])
-        return {"R": R, "overflow": bool(flags), "too_small": bool(flags & 1), "resort_failed": bool(flags & 2),
-                "exchange_too_small": bool(flags & 4), "det_mispredicted": bool(flags & 8),
-                "handover_mismatch": bool(flags & 16), "outside_union": bool(flags & 32),
-                "exchange_count": int(h[7]) & 0xFFFFFFFF,
-                "loss_pixel": float(f[5]), "loss_reg": float(f[6]),
-                "loss": float(f[5]) + float(f[6]), "sums": [float(f[2]), float(f[3]), float(f[4])]}
+        return status_dict(h.tolist(), h.view(np.float32).tolist())
 
     @torch.no_grad()
     def step(self, camera, group=None, sync: bool = True, pose_grad: bool = False):
@@ -476,17 +528,7 @@ class MappingEngine:
                 return st
             # repeat the iteration (parameters were not touched): with the full sort, and with more
             # room if the instance buffers were too small
-            if st["too_small"] or st["resort_failed"]:
-                self._forget_order(camera, failed_repair=st["resort_failed"])
-            self.stats[self._void_reason(st)] += 1
-            if st["too_small"]:
-                need = st["R"]
-                if sharded:
-                    t = torch.tensor([need], dtype=torch.int64, device=self.dev)
-                    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-                    need = int(t.item())
-                self.capacity = int(max(need, self.capacity) * self.capacity_factor) + 1024
-                self.workspace = None
+            self._after_void([(camera, st)], sharded)
 
     @torch.no_grad()
     def pose_step(self, camera):
@@ -505,18 +547,13 @@ class MappingEngine:
             if not st["overflow"]:
                 self.pose_grad = self._pose_buf[0]
                 return st
-            if st["too_small"] or st["resort_failed"]:
-                self._forget_order(camera, failed_repair=st["resort_failed"])
-            self.stats[self._void_reason(st)] += 1
-            if st["too_small"]:
-                self.capacity = int(max(st["R"], self.capacity) * self.capacity_factor) + 1024
-                self.workspace = None
+            self._after_void([(camera, st)], sharded=False)
 
     def _ensure_batch_workspace(self, G, H, W, capacity):
         """The batch's workspace: one slice per keyframe, kept apart from step()'s (re-carved for more keyframes, another
         size, more room or another accumulation mode)."""
         lib = _abi.lib()
-        b = getattr(self, "_bws", None)
+        b = self._bws
         det = bool(self.deterministic)
         # (capacity: the slices are laid out by it, so ANY change re-carves — a smaller one would move the zeroed records)
         if b is None or G > b["G"] or capacity != b["cap"] or (H, W) != b["hw"] or det != b["det"] or self.N != b["n"]:
@@ -528,45 +565,34 @@ class MappingEngine:
             b = self._bws = {"G": Gw, "cap": int(capacity), "hw": (H, W), "det": det, "n": self.N, "ready": 0,
                              "buf": torch.empty((nbytes + 256,), dtype=torch.uint8, device=self.dev),
                              "status": torch.zeros((_abi.SLS_MAX_BATCH + 1, 8), dtype=torch.int32, device=self.dev)}
-        base = b["buf"].data_ptr()
-        return b, (base + 255) & ~255, b["buf"].numel() - 256
+        return (b,) + self._aligned(b["buf"])
 
     def _enqueue_batch(self, cameras, apply_adam, with_regulariser, allow_reuse=True, pose_grad=False):
         """sls_mapping_step_batch on `cameras` with the keyframes' own cached orders (as _enqueue)."""
         lib = _abi.lib()
         G = len(cameras)
         H, W = int(cameras[0].image_height), int(cameras[0].image_width)
-        if self.capacity == 0:
-            self.capacity = max(4 * self.N, 1 << 16)
-        b, ws_ptr, ws_bytes = self._ensure_batch_workspace(G, H, W, self.capacity)
+        b, ws_ptr, ws_bytes = self._ensure_batch_workspace(G, H, W, self._first_capacity())
         xyz, scaling, rotation, opacity = self._params()
         kfs = (_abi.SlsKeyframeInputs * G)()
-        keep = []                       # (the camera tables must outlive the call)
-        reuse_used, ents = [], []
-        for g, camera in enumerate(cameras):
-            settings = GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix)
-            ce = get_camera(settings, self.dev)
-            aux = camera_aux(camera)
-            # (an order's age counts parameter updates: the whole batch is one, so a keyframe batched at every step stays
-            #  one update old)
-            ent, reuse = self._order_for(camera, allow_reuse, H, W, advance=False)
-            ents.append(ent)
+        # (an order's age counts parameter updates: the whole batch is one, so a keyframe batched at every step stays
+        #  one update old; the camera tables in this list must outlive the call)
+        inputs = [self._keyframe_inputs(camera, H, W, allow_reuse, advance=False) for camera in cameras]
+        for g, (ce, aux, ent, reuse) in enumerate(inputs):
             k = kfs[g]
             k.cam = ce.cam
             k.gt_depth, k.valid, k.n_valid = aux.gt.data_ptr(), aux.valid.data_ptr(), aux.n_valid
-            k.reuse_depth_order = int(reuse)
+            k.reuse_depth_order = reuse
             k.col_cs, k.row_cs = ce.col_cs.data_ptr(), ce.row_cs.data_ptr()
             k.col_cs_half, k.row_cs_half = aux.col_h.data_ptr(), aux.row_h.data_ptr()
-            k.depth_order = ent[0].data_ptr()
-            k.block_order = ent[3].data_ptr() if self.inline_loss_stage else None
+            k.depth_order = ent.order.data_ptr()
+            k.block_order = ent.block_order.data_ptr() if self.inline_loss_stage else None
             # (deterministic = 2 runs as 1 in a batch; the keyframe's predictions are still rewritten for its step())
-            k.det_prev = self._det_prev_for(camera)[0][0].data_ptr() if self.deterministic == 2 else None
+            k.det_prev = self._det_prev_ptr(ent) if self.deterministic == 2 else None
             k.pose_grad = self._pose_buf[g].data_ptr() if pose_grad else None
-            keep.append((ce, aux))
-            reuse_used.append(int(reuse))
         self._enq += 1
-        for ent in ents:
-            ent[1] = self._enq
+        for _, _, ent, _ in inputs:
+            ent.stamp = self._enq
         ready = self._ws_ready
         cfg = self._config(apply_adam, with_regulariser)
         self._ws_ready = ready          # (that flag is step()'s workspace's)
@@ -576,7 +602,7 @@ class MappingEngine:
         cfg.void_flags_out = None if apply_adam else self.grads.data_ptr() + 4 * 10 * self.N
         if pose_grad:
             self._pose_args(cfg, G)
-        self.last_batch_reuse = reuse_used
+        self.last_batch_reuse = [reuse for _, _, _, reuse in inputs]
         _abi.check(lib.sls_mapping_step_batch(G, kfs, self.N, xyz.data_ptr(), scaling.data_ptr(), rotation.data_ptr(),
                                               opacity.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
                                               self.exp_avg_sq.data_ptr(), self.t + 1, C.byref(cfg), b["cap"],
@@ -637,19 +663,7 @@ class MappingEngine:
                 self.last = st
                 self.pose_grad = self._pose_buf[:len(cams)] if pose_grad else None
                 return st
-            for cam, kst in zip(cams, st["keyframes"]):
-                if kst["too_small"] or kst["resort_failed"]:
-                    self._forget_order(cam, failed_repair=kst["resort_failed"])
-            self.stats[self._void_reason(st)] += 1
-            if st["too_small"]:
-                need = st["R"]
-                if sharded:
-                    t = torch.tensor([need], dtype=torch.int64, device=self.dev)
-                    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-                    need = int(t.item())
-                self.capacity = int(max(need, self.capacity) * self.capacity_factor) + 1024
-                self.workspace = None
-                self._bws = None
+            self._after_void(list(zip(cams, st["keyframes"])), sharded, verdict=st)
 
     def _step_lagged(self, camera):
         slot = 0 if self._lag_pending is None else self._lag_pending[0] ^ 1
@@ -714,15 +728,7 @@ class MappingEngine:
         # both in-flight iterations are taken off the step count; the one that did run is put back after the
         # redo below, so that the repeated iteration uses the Adam step number it was meant to have
         self.t -= 2 if cur is not None else 1
-        if st["too_small"] or st["resort_failed"]:
-            self._forget_order(pcam, failed_repair=st["resort_failed"])     # repeat with the full sort
-        if cur_void and (cur_st["too_small"] or cur_st["resort_failed"]):
-            self._forget_order(cur[1], failed_repair=cur_st["resort_failed"])
-        self.stats[self._void_reason(st)] += 1
-        if st["too_small"] or (cur_void and cur_st["too_small"]):
-            need = max(st["R"], cur_st["R"] if cur_void else 0, self.capacity)
-            self.capacity = int(need * self.capacity_factor) + 1024
-            self.workspace = None
+        self._after_void([(pcam, st)] + ([(cur[1], cur_st)] if cur_void else []), sharded=False)
         if cur_st is not None and not cur_void:
             self._lag_ready.append(cur_st)   # (another keyframe that fitted: it did run, nothing to repeat)
         st = self.step(pcam, group=self._group, sync=True)
@@ -887,47 +893,39 @@ class MappingEngine:
         if ev:
             self.comm_events.append(ev)
 
+    def _adam_groups(self, pieces, params, grad0, lo, flags, status, mirror):
+        """sls_adam_step_reduced on the dp_pieces `pieces` of the flat range that starts at element `lo`: `params` = each
+        piece's parameter address, `grad0` = the address of element lo's gradient; the moments are this engine's, element
+        lo first; `flags` = the address of the two reduced void flags."""
+        arr = (_abi.SlsAdamGroup * 4)()
+        for k, ((a, b, lr), param) in enumerate(zip(pieces, params)):
+            off = 4 * (a - lo)
+            arr[k].param, arr[k].grad = param, grad0 + off
+            arr[k].exp_avg, arr[k].exp_avg_sq = self.exp_avg.data_ptr() + off, self.exp_avg_sq.data_ptr() + off
+            arr[k].numel, arr[k].lr = b - a, lr
+        k = len(pieces)
+        if k == 0:       # (a rank whose chunk lies beyond 10 N: nothing to update, but it publishes the verdict)
+            arr[0].param = arr[0].grad = arr[0].exp_avg = arr[0].exp_avg_sq = grad0
+            arr[0].numel, arr[0].lr, k = 0, 0.0, 1
+        _abi.check(_abi.lib().sls_adam_step_reduced(arr, k, self.betas[0], self.betas[1], self.eps, self.t + 1, flags,
+                                                    status.data_ptr(), mirror,
+                                                    torch.cuda.current_stream(self.dev).cuda_stream),
+                   "sls_adam_step_reduced")
+
     def _adam_shard(self, status, mirror):
         """Adam on the flat elements [lo, hi) this rank owns: up to four pieces, one per parameter group the range
         crosses (each has its own learning rate); gradients = the reduce-scattered chunk, moments = the local shard."""
-        lib, d, N = _abi.lib(), self._dp, self.N
-        lo, hi, C = d["lo"], d["hi"], d["C"]
-        arr = (_abi.SlsAdamGroup * 4)()
-        k = 0
-        for a, b, lr in dp_pieces(N, lo, hi, self.lrs):
-            arr[k].param = d["flat"].data_ptr() + 4 * a
-            arr[k].grad = d["gshard"].data_ptr() + 4 * (a - lo)
-            arr[k].exp_avg = self.exp_avg.data_ptr() + 4 * (a - lo)
-            arr[k].exp_avg_sq = self.exp_avg_sq.data_ptr() + 4 * (a - lo)
-            arr[k].numel = b - a
-            arr[k].lr = lr
-            k += 1
-        if k == 0:       # (a rank whose chunk lies beyond 10 N: nothing to update, but it publishes the verdict)
-            arr[0].param = arr[0].grad = arr[0].exp_avg = arr[0].exp_avg_sq = d["gshard"].data_ptr()
-            arr[0].numel, arr[0].lr, k = 0, 0.0, 1
-        _abi.check(lib.sls_adam_step_reduced(arr, k, self.betas[0], self.betas[1], self.eps, self.t + 1,
-                                             d["gshard"].data_ptr() + 4 * C, status.data_ptr(), mirror,
-                                             torch.cuda.current_stream(self.dev).cuda_stream),
-                   "sls_adam_step_reduced")
+        d = self._dp
+        pieces = dp_pieces(self.N, d["lo"], d["hi"], self.lrs)
+        self._adam_groups(pieces, [d["flat"].data_ptr() + 4 * a for a, _, _ in pieces], d["gshard"].data_ptr(), d["lo"],
+                          d["gshard"].data_ptr() + 4 * d["C"], status, mirror)
 
     def _adam_reduced(self, status, mirror):
-        lib = _abi.lib()
-        N = self.N
+        """Adam on the whole model from the all-reduced flat bucket: the four parameter groups, each in its own tensor."""
         xyz, scaling, rotation, opacity = self._params()
-        arr = (_abi.SlsAdamGroup * 4)()
-        spec = ((xyz, 0, 3 * N, self.lrs[0]), (opacity, 3 * N, N, self.lrs[1]),
-                (scaling, 4 * N, 2 * N, self.lrs[2]), (rotation, 6 * N, 4 * N, self.lrs[3]))
-        for k, (p, off, n, lr) in enumerate(spec):
-            arr[k].param = p.data_ptr()
-            arr[k].grad = self.grads.data_ptr() + 4 * off
-            arr[k].exp_avg = self.exp_avg.data_ptr() + 4 * off
-            arr[k].exp_avg_sq = self.exp_avg_sq.data_ptr() + 4 * off
-            arr[k].numel = n
-            arr[k].lr = lr
-        _abi.check(lib.sls_adam_step_reduced(arr, 4, self.betas[0], self.betas[1], self.eps, self.t + 1,
-                                             self.grads.data_ptr() + 4 * 10 * N, status.data_ptr(), mirror,
-                                             torch.cuda.current_stream(self.dev).cuda_stream),
-                   "sls_adam_step_reduced")
+        self._adam_groups(dp_pieces(self.N, 0, 10 * self.N, self.lrs),
+                          [p.data_ptr() for p in (xyz, opacity, scaling, rotation)], self.grads.data_ptr(), 0,
+                          self.grads.data_ptr() + 4 * 10 * self.N, status, mirror)
 
     @torch.no_grad()
     def remap(self, keep=None, appended: int = 0, reset_state: bool = True):
@@ -972,8 +970,7 @@ class MappingEngine:
         self._set_order_ages()
         self.grads = torch.zeros((10 * n_new + 2,), dtype=torch.float32, device=self.dev)
         self.workspace = None                        # sized by N: rebuilt at the next step
-        self._orders.clear()                         # surfel indices changed: every kept depth order is void
-        self._det_prev.clear()                       # ... and so is every predicted scale
+        self._orders.clear()                         # surfel indices changed: every depth order and predicted scale is void
         self._det_two_pass_next = True
         self._pose_scratch = None                    # (sized by N)
         self._params()
@@ -994,7 +991,7 @@ class MappingEngine:
         if int(self.model._xyz.shape[0]) != n_new:
             raise RuntimeError(f"the model holds {int(self.model._xyz.shape[0])} surfels, not {n_new}")
         n10 = 10 * n_new
-        store = getattr(self, "_bucket_store", None)
+        store = self._bucket_store
         if store is None or store[0].numel() < n10 + 2:
             room = n10 + n10 // 4 + 2
             store = [torch.zeros((room,), dtype=torch.float32, device=self.dev) for _ in range(3)]
@@ -1004,10 +1001,9 @@ class MappingEngine:
         self.N, self.t = n_new, 0
         self._set_order_ages()
         for ent in self._orders.values():
-            ent[1] = None                                   # the order itself: from scratch at the keyframe's next visit
-            if ent[0].numel() < n_new:
-                ent[0] = torch.empty((n_new + n_new // 4,), dtype=torch.int32, device=self.dev)
-        self._det_prev.clear()
+            ent.stamp = ent.det_prev = None                 # the order itself: from scratch at the keyframe's next visit
+            if ent.order.numel() < n_new:
+                ent.order = torch.empty((n_new + n_new // 4,), dtype=torch.int32, device=self.dev)
         self._det_two_pass_next = True
         self._ws_ready = False                              # (the records' region moved with N: zeroed at the next step)
         self._params()

@@ -63,7 +63,7 @@ def _single(eng, cam, with_regulariser):
     eng._enqueue(cam, apply_adam=False, with_regulariser=with_regulariser)
     st = eng._parse_status(eng.status.cpu())
     if st["too_small"]:
-        eng.capacity = int(max(st["R"], eng.capacity) * 1.3) + 1024
+        eng.capacity = eng._grown(st["R"])
         eng.workspace = None
         eng._enqueue(cam, apply_adam=False, with_regulariser=with_regulariser, allow_reuse=False)
         st = eng._parse_status(eng.status.cpu())
@@ -79,7 +79,7 @@ def _batch_grad(eng, cams):
         st = eng._parse_status(h[0])
         if not st["too_small"]:
             break
-        eng.capacity = int(max(st["R"], eng.capacity) * 1.3) + 1024
+        eng.capacity = eng._grown(st["R"])
     assert not st["overflow"], st
     assert eng.grads[-2:].abs().sum().item() == 0.0            # the batch's void flags
     return eng.grads[:-2].cpu().numpy().astype(np.float64), st, [eng._parse_status(h[1 + g]) for g in range(len(cams))]

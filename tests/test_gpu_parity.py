@@ -1073,9 +1073,9 @@ def test_depth_order_repair_rounds(device):
     for ls in losses[1:]:
         for a, b in zip(losses[0], ls):
             assert abs(a - b) <= 1e-5 * abs(a), losses
-    o0 = engines[0][0]._orders[id(cam)][0].cpu().numpy()
+    o0 = engines[0][0]._orders[id(cam)].order.cpu().numpy()
     for e, _ in engines[1:]:          # the exact (key, index) order, bit for bit
-        assert np.array_equal(e._orders[id(cam)][0].cpu().numpy(), o0)
+        assert np.array_equal(e._orders[id(cam)].order.cpu().numpy(), o0)
 
 
 def test_depth_order_repair_at_awkward_sizes(device):
@@ -1327,7 +1327,7 @@ def _det2_misprediction_rank(rank, port, out_dir):
         for _ in range(3):
             eng.step(cam)
         before = sum(eng.stats.values())
-        eng._det_prev[id(cam)][0].fill_(1)       # predictions 2^100 too small: every field of every surfel overflows its scale
+        eng._orders[id(cam)].det_prev.fill_(1)       # predictions 2^100 too small: every field of every surfel overflows its scale
         if sync == "lagged":
             eng.step(cam, sync="lagged"); eng.step(cam, sync="lagged"); eng.flush()
         else:

@@ -199,7 +199,7 @@ def _keyframe_sum(N, H, W, flat, device):
         eng._enqueue(cam, apply_adam=False, with_regulariser=(k == 0))
         flags = int(eng.status[1].item())
         if flags & 1:       # instance buffers too small: the engine's own protocol, with the room it asked for
-            eng.capacity = int(max(int(eng.status[0].item()) & 0xFFFFFFFF, eng.capacity) * 1.3) + 1024
+            eng.capacity = eng._grown(int(eng.status[0].item()) & 0xFFFFFFFF)
             eng.workspace = None
             eng._enqueue(cam, apply_adam=False, with_regulariser=(k == 0), allow_reuse=False)
             flags = int(eng.status[1].item())

@@ -534,7 +534,7 @@ def test_loss_stage_inside_the_tile_backward(device, H, W, hfov):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "identical parameters after six iterations"
     # the order buffers were filled: tag word + a permutation per XCD
     ent = next(iter(e._orders.values()))
-    words = ent[3].cpu().numpy().view(np.uint32)
+    words = ent.block_order.cpu().numpy().view(np.uint32)
     T = ((W + 15) // 16) * ((H + 15) // 16)
     if T % 32 == 0:
         assert words[0] == 0x424F0000 + T

@@ -28,7 +28,7 @@ def run(dev="cuda:0", verbose=True):
                 e.inline_loss_stage = inline
                 e._repair_rounds, e._repair_until = max(rounds, 1), 10 ** 9
                 losses = [e.step(cam)["loss"] for _ in range(4)]
-                order = e._orders[id(cam)][0].cpu().numpy()
+                order = e._orders[id(cam)].order.cpu().numpy()
                 params = [p.detach().cpu().numpy() for p in (m._xyz, m._scaling, m._rotation, m._opacity)]
                 if ref is None:
                     ref = (order, losses, params)
