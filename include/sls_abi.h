@@ -702,6 +702,34 @@ int sls_knn_dist2(int M, const float *xyz, float *out, void *scratch, size_t scr
 int sls_knn_dist2_first(int M, int M_first, const float *xyz, float *out, void *scratch, size_t scratch_bytes,
                         void *stream);
 
+/* ---- nearest neighbour between two clouds, distance statistics -------------
+ * For every query point the nearest TARGET point (the exact search of sls_knn_dist2's spatial index, queried by a second
+ * cloud): with d2(q, t) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), d* = t.* - q.* in float32 (include/sls_nn_math.h),
+ *   out_dist2[q] = min over t of d2(q, t),
+ *   out_index[q] = the LOWEST original target index attaining that minimum, bit for bit (optional: may be null),
+ * in the caller's query order.  All pointers DEVICE; target_xyz (Mt x 3) and query_xyz (Mq x 3) row-major floats.
+ *   scratch: sls_nn_scratch_bytes(Mt, Mq) bytes (0 for Mt < 1 or Mq < 0), 256-byte aligned.
+ * Mq == 0 succeeds and writes nothing.  Before anything is enqueued: SLS_E_ARG for Mt < 1, Mq < 0, a null pointer,
+ * scratch that is not 256-byte aligned; SLS_E_SCRATCH for too little scratch. */
+size_t sls_nn_scratch_bytes(int Mt, int Mq);
+int sls_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
+                 void *scratch, size_t scratch_bytes, void *stream);
+/* Statistics of M squared distances (sls_nn_query's out_dist2).  tau2 = truncation * truncation in float32; entry i is
+ * kept when dist2[i] < tau2 and then contributes d = sqrtf(dist2[i]) (correctly rounded); any other entry contributes
+ * d = truncation when include_truncated != 0 and is dropped otherwise.
+ *   out_stats (DEVICE, 4 words): [n = contributing entries, n_below = those with d < threshold in float32,
+ *       the bits of the double sum of (double)d, M].
+ * The sum is taken in a fixed order (per-block partials of a grid that depends on M alone, then one fixed-order pass,
+ * no atomics): the same input gives the same bits on every run.  M == 0 writes [0, 0, bits(0.0), 0] (dist2 may be
+ * null then).
+ *   scratch: SLS_NN_STATS_SCRATCH_BYTES bytes, 256-byte aligned; sls_nn_scratch_bytes(Mt, Mq) is never smaller, so
+ *       the query's scratch serves.
+ * SLS_E_ARG (M < 0, a null pointer, a NaN truncation or threshold, misaligned scratch) and SLS_E_SCRATCH before
+ * anything is enqueued. */
+#define SLS_NN_STATS_SCRATCH_BYTES 32768
+int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
+                 void *scratch, size_t scratch_bytes, void *stream);
+
 /* visible[i] = 1 if surfel centre i survives the near cut (radii would be >0
  * unless it is off-image). */
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible,

@@ -444,6 +444,37 @@ int sls_knn_dist2_first(int M, int M_first, const float *xyz, float *out, void *
     return launch_knn(M, xyz, out, scratch, scratch_bytes, (hipStream_t)stream, M_first);
 }
 
+size_t sls_nn_scratch_bytes(int Mt, int Mq) { return nn_scratch_bytes(Mt, Mq); }
+
+int sls_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
+                 void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(Mt >= 1, "Mt < 1: the target cloud is empty");
+    SLS_REQUIRE(Mq >= 0, "negative Mq");
+    if (Mq == 0) return SLS_OK;
+    SLS_REQUIRE(target_xyz && query_xyz && out_dist2 && scratch, "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < nn_scratch_bytes(Mt, Mq)) {
+        set_error("sls_nn_query: scratch too small: %zu < %zu", scratch_bytes, nn_scratch_bytes(Mt, Mq));
+        return SLS_E_SCRATCH;
+    }
+    return launch_nn_query(Mt, target_xyz, Mq, query_xyz, out_dist2, out_index, scratch, (hipStream_t)stream);
+}
+
+int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
+                 void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE((dist2 || M == 0) && out_stats && scratch, "null pointer");
+    SLS_REQUIRE(truncation == truncation && threshold == threshold, "NaN truncation or threshold");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < (size_t)SLS_NN_STATS_SCRATCH_BYTES) {
+        set_error("sls_nn_stats: scratch too small: %zu < %d", scratch_bytes, SLS_NN_STATS_SCRATCH_BYTES);
+        return SLS_E_SCRATCH;
+    }
+    return launch_nn_stats(M, dist2, truncation, threshold, include_truncated, out_stats, scratch, (hipStream_t)stream);
+}
+
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible, void *stream)
 {
     SLS_REQUIRE(cam && N >= 0, "bad argument");

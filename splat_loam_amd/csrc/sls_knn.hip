@@ -16,6 +16,7 @@
 #include <float.h>
 
 #include "sls_launch.hpp"
+#include "../../include/sls_nn_math.h"
 
 namespace sls {
 
@@ -33,11 +34,12 @@ __device__ __forceinline__ float ord2f(uint32_t o)
     return __uint_as_float(u);
 }
 
-__global__ void knn_init_bbox_kernel(uint32_t *bbox, uint32_t M)
+__global__ void knn_init_bbox_kernel(uint32_t *bbox, uint32_t M, uint32_t M2)
 {
     if (threadIdx.x < 3) bbox[threadIdx.x] = 0xFFFFFFFFu;       // min (ordered domain)
     else if (threadIdx.x < 6) bbox[threadIdx.x] = 0u;           // max
     else if (threadIdx.x == 6) bbox[6] = M;                     // item count for the sorter
+    else if (threadIdx.x == 7) bbox[7] = M2;                    // ... and of the second cloud's sort (sls_nn_query)
 }
 
 __global__ __launch_bounds__(256) void knn_bbox_kernel(int M, const float *__restrict__ xyz, uint32_t *bbox)
@@ -391,6 +393,30 @@ static KnnScratch knn_layout(int M, void *base)
 
 size_t knn_scratch_bytes(int M) { return M > 0 ? knn_layout(M, nullptr).total : 0; }
 
+// The front half of both searches: bounding cube, Hilbert codes, sort, points in curve order, boxes and sub-boxes.
+// M2: the item count of a second sort that follows (bbox[7]).  *which: where the sorted (code, index) pairs ended up.
+static int knn_build(int M, const float *xyz, const KnnScratch &s, int key_bits, uint32_t M2, hipStream_t st, int *which)
+{
+    const int nb = (M + 255) / 256;
+    hipLaunchKernelGGL(knn_init_bbox_kernel, dim3(1), dim3(64), 0, st, s.bbox, (uint32_t)M, M2);
+    SLS_LAUNCH_CHECK("knn_init_bbox_kernel");
+    hipLaunchKernelGGL(knn_bbox_kernel, dim3(nb < 256 ? nb : 256), dim3(256), 0, st, M, xyz, s.bbox);
+    SLS_LAUNCH_CHECK("knn_bbox_kernel");
+    hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(256), 0, st, M, xyz, s.bbox, s.keys, s.vals, key_bits);
+    SLS_LAUNCH_CHECK("knn_morton_kernel");
+    int rc = radix_sort_pairs_u32(s.keys, s.vals, s.keys_tmp, s.vals_tmp, s.bbox + 6, (uint32_t)M, key_bits, s.sort,
+                                  s.sort_bytes, which, st);
+    if (rc) return rc;
+    const int nboxes = (M + kKnnBox - 1) / kKnnBox;
+    hipLaunchKernelGGL(knn_gather_boxes_kernel, dim3(nboxes), dim3(kKnnBox), 0, st, M, xyz,
+                       *which ? s.vals_tmp : s.vals, s.pts, s.boxes, s.subboxes);
+    SLS_LAUNCH_CHECK("knn_gather_boxes_kernel");
+    return SLS_OK;
+}
+
+// small clouds are sorted on 21 code bits (knn_morton_kernel)
+static int knn_key_bits(int M) { return M <= 200000 ? 21 : 30; }
+
 int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratch_bytes, hipStream_t st, int Mq)
 {
     const KnnScratch s = knn_layout(M, scratch);
@@ -402,27 +428,325 @@ int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratc
         set_error("knn scratch must be 256-byte aligned");
         return SLS_E_ARG;
     }
-    const int nb = (M + 255) / 256;
-    const int key_bits = M <= 200000 ? 21 : 30;
     ScopedTimer tm(T_KNN, st);
-    hipLaunchKernelGGL(knn_init_bbox_kernel, dim3(1), dim3(64), 0, st, s.bbox, (uint32_t)M);
-    SLS_LAUNCH_CHECK("knn_init_bbox_kernel");
-    hipLaunchKernelGGL(knn_bbox_kernel, dim3(nb < 256 ? nb : 256), dim3(256), 0, st, M, xyz, s.bbox);
-    SLS_LAUNCH_CHECK("knn_bbox_kernel");
-    hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(256), 0, st, M, xyz, s.bbox, s.keys, s.vals, key_bits);
-    SLS_LAUNCH_CHECK("knn_morton_kernel");
     int which = 0;
-    int rc = radix_sort_pairs_u32(s.keys, s.vals, s.keys_tmp, s.vals_tmp, s.bbox + 6, (uint32_t)M, key_bits, s.sort,
-                                  s.sort_bytes, &which, st);
+    int rc = knn_build(M, xyz, s, knn_key_bits(M), 0u, st, &which);
     if (rc) return rc;
     const int nboxes = (M + kKnnBox - 1) / kKnnBox;
-    hipLaunchKernelGGL(knn_gather_boxes_kernel, dim3(nboxes), dim3(kKnnBox), 0, st, M, xyz,
-                       which ? s.vals_tmp : s.vals, s.pts, s.boxes, s.subboxes);
-    SLS_LAUNCH_CHECK("knn_gather_boxes_kernel");
     static_assert(kKnnBox == 256 && kKnnSub == 32, "the query kernel's lane mappings are written for 8 runs of 32");
     hipLaunchKernelGGL(knn_query_kernel, dim3((M + 63) / 64), dim3(64), 0, st, M, nboxes, s.pts, s.boxes, s.subboxes, out,
                        (uint32_t)(Mq < 0 || Mq > M ? M : Mq));
     SLS_LAUNCH_CHECK("knn_query_kernel");
+    return SLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sls_nn_query: for every point of a SECOND cloud the nearest point of the indexed one — squared distance and the lowest
+// original index attaining it (include/sls_nn_math.h).  The queries get Hilbert codes in the target's cube (clamped to
+// its border cells outside), go through the same sorter and are searched 64 curve-consecutive ones per wave, exactly
+// as above with three differences: the box to start in comes from a binary search of the wave's first code among the
+// targets' sorted codes; the wave's bounding box is a reduction over its own queries; and the best candidate is ONE
+// packed key (bits(d2) << 32 | index), minimised.  A box whose gap EQUALS the bound is kept by every test (<=, and a
+// gap never exceeds the distance to a point inside the box: float subtraction, fma and max are monotone), so an equally
+// near target of lower index in another box is always met.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void nn_gather_kernel(int Mq, const float *__restrict__ xyz,
+                                                        const uint32_t *__restrict__ sorted_idx, float4 *__restrict__ qpts)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= Mq) return;
+    const uint32_t i = sorted_idx[j];
+    qpts[j] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __uint_as_float(i));
+}
+
+__device__ __forceinline__ void nn_scan32(const float4 *s_run, const float4 me, uint64_t &best)
+{
+#pragma unroll 8
+    for (int k = 0; k < kKnnSub; ++k) {
+        const float4 p = s_run[k];
+        const uint64_t key = sls_nn_key(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), __float_as_uint(p.w));
+        best = key < best ? key : best;
+    }
+}
+
+__global__ __launch_bounds__(64) void nn_query_kernel(int Mt, int nboxes, const float4 *__restrict__ pts,
+                                                      const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                      const uint32_t *__restrict__ tkeys, int Mq,
+                                                      const float4 *__restrict__ qpts, const uint32_t *__restrict__ qkeys,
+                                                      float *__restrict__ out_dist2, int32_t *__restrict__ out_index)
+{
+    constexpr int kSubs = kKnnBox / kKnnSub;
+    __shared__ float4 s_run[kKnnSub];                   // wave-private: the workgroup IS one wave
+    __shared__ uint32_t s_box[64];
+    __shared__ uint32_t s_sub[64 * kSubs];
+    const int lane = threadIdx.x;
+    const int q0 = blockIdx.x * 64, q = q0 + lane;      // (the grid has ceil(Mq / 64) waves: q0 < Mq)
+    const bool live = q < Mq;
+    const float4 me = qpts[live ? q : Mq - 1];
+    const int nsub = (Mt + kKnnSub - 1) / kKnnSub;
+    uint64_t best = SLS_NN_KEY_NONE;
+
+    // the box to start in: the one holding the first target whose code is not below the wave's first code
+    int start_box;
+    {
+        const uint32_t code = qkeys[q0];
+        int lo = 0, hi = Mt;                            // lower bound in tkeys[0, Mt): at most 31 halvings
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (tkeys[mid] < code) lo = mid + 1; else hi = mid;
+        }
+        start_box = __builtin_amdgcn_readfirstlane(min(lo, Mt - 1) / kKnnBox);
+    }
+
+    // a. the runs of the starting box: a tight bound.  (A short last run is padded with copies of its first point,
+    //    which change no minimum.)
+    for (int t = 0; t < kSubs; ++t) {
+        const int sb = start_box * kSubs + t;
+        if (sb >= nsub) break;
+        __builtin_amdgcn_wave_barrier();
+        if (lane < kKnnSub) {
+            const int k = sb * kKnnSub + lane;
+            s_run[lane] = pts[k < Mt ? k : sb * kKnnSub];
+        }
+        __syncthreads();
+        nn_scan32(s_run, me, best);
+    }
+
+    // bounding box of the wave's queries, and of its 8 groups of 8 consecutive ones (dead lanes: empty)
+    auto rl = [](float v, int k) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k)); };
+    float4 gmn = live ? me : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f);
+    float4 gmx = live ? me : make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) {
+        gmn.x = fminf(gmn.x, __shfl_xor(gmn.x, off, 64)); gmn.y = fminf(gmn.y, __shfl_xor(gmn.y, off, 64));
+        gmn.z = fminf(gmn.z, __shfl_xor(gmn.z, off, 64));
+        gmx.x = fmaxf(gmx.x, __shfl_xor(gmx.x, off, 64)); gmx.y = fmaxf(gmx.y, __shfl_xor(gmx.y, off, 64));
+        gmx.z = fmaxf(gmx.z, __shfl_xor(gmx.z, off, 64));
+    }
+    float4 wmn = gmn, wmx = gmx;
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+        wmn.x = fminf(wmn.x, __shfl_xor(wmn.x, off, 64)); wmn.y = fminf(wmn.y, __shfl_xor(wmn.y, off, 64));
+        wmn.z = fminf(wmn.z, __shfl_xor(wmn.z, off, 64));
+        wmx.x = fmaxf(wmx.x, __shfl_xor(wmx.x, off, 64)); wmx.y = fmaxf(wmx.y, __shfl_xor(wmx.y, off, 64));
+        wmx.z = fmaxf(wmx.z, __shfl_xor(wmx.z, off, 64));
+    }
+
+    // b. the outward sweep over chunks of 64 boxes, as in knn_query_kernel (the bound is the lane's best distance)
+    const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;
+    for (int it = 0; it < nchunks; ++it) {
+        int chunk;
+        {
+            const int near = min(c0, nchunks - 1 - c0);
+            if (it <= 2 * near) chunk = c0 + ((it & 1) ? (it + 1) / 2 : -(it / 2));
+            else chunk = (c0 < nchunks - 1 - c0) ? it : nchunks - 1 - it;
+        }
+        float gB = live ? sls_nn_key_dist2(best) : 0.0f;
+        gB = fmaxf(gB, __shfl_xor(gB, 1, 64)); gB = fmaxf(gB, __shfl_xor(gB, 2, 64)); gB = fmaxf(gB, __shfl_xor(gB, 4, 64));
+        const float B2 = wave_max(gB);
+        auto reaches = [&](const float4 bmn, const float4 bmx) -> bool {
+            if (!(box_gap2(wmn, wmx, bmn, bmx) * 0.99999f <= B2)) return false;
+            bool r = false;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const float4 mn = make_float4(rl(gmn.x, 8 * g), rl(gmn.y, 8 * g), rl(gmn.z, 8 * g), 0.0f);
+                const float4 mx = make_float4(rl(gmx.x, 8 * g), rl(gmx.y, 8 * g), rl(gmx.z, 8 * g), 0.0f);
+                r = r || (box_gap2(mn, mx, bmn, bmx) * 0.99999f <= rl(gB, 8 * g));
+            }
+            return r;
+        };
+        const int b = chunk * 64 + lane;
+        bool c = false;
+        if (b < nboxes && b != start_box) c = reaches(boxes[2 * b], boxes[2 * b + 1]);
+        const uint64_t cm = __ballot(c);
+        const int nb = __builtin_popcountll(cm);
+        if (nb == 0) continue;
+        __builtin_amdgcn_wave_barrier();
+        if (c) s_box[__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u))] = (uint32_t)b;
+        __syncthreads();
+        int ns = 0;                                     // <= 8 * nb <= 512 = the size of s_sub
+        for (int g = 0; g < nb; g += 8) {
+            const int slot = g + (lane >> 3);
+            bool cs = false;
+            uint32_t sb = 0;
+            if (slot < nb) {
+                sb = s_box[slot] * kSubs + (uint32_t)(lane & 7);
+                if ((int)sb < nsub) cs = reaches(subboxes[2 * (size_t)sb], subboxes[2 * (size_t)sb + 1]);
+            }
+            const uint64_t sm = __ballot(cs);
+            if (cs) s_sub[ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u))] = sb;
+            ns += __builtin_popcountll(sm);
+        }
+        __syncthreads();
+        // c. the listed runs, 64 at a time: can one still improve (or tie) ANY query?  Then its 32 points go through LDS
+        for (int base = 0; base < ns; base += 64) {
+            const int nk = min(64, ns - base);
+            const uint32_t sbl = s_sub[base + min(lane, nk - 1)];
+            const float4 mnl = subboxes[2 * (size_t)sbl], mxl = subboxes[2 * (size_t)sbl + 1];
+            const float qb2 = live ? sls_nn_key_dist2(best) : -1.0f;
+            bool need = false;
+            for (int qi = 0; qi < 64; ++qi) {
+                const float4 qp = make_float4(rl(me.x, qi), rl(me.y, qi), rl(me.z, qi), 0.0f);
+                need = need || (box_gap2(qp, qp, mnl, mxl) * 0.99999f <= rl(qb2, qi));
+            }
+            uint64_t todo = __ballot(need && lane < nk);
+            auto fetch = [&](int k) -> float4 {         // lanes 0..31: the points of candidate k
+                const int r0 = __builtin_amdgcn_readlane((int)sbl, k) * kKnnSub, i = r0 + (lane & (kKnnSub - 1));
+                return pts[i < Mt ? i : r0];
+            };
+            float4 pre = make_float4(0, 0, 0, 0);
+            if (todo) pre = fetch(__builtin_ctzll(todo));
+            while (todo) {
+                todo &= todo - 1;
+                const float4 cur = pre;
+                if (todo) pre = fetch(__builtin_ctzll(todo));
+                __builtin_amdgcn_wave_barrier();
+                if (lane < kKnnSub) s_run[lane] = cur;
+                __syncthreads();
+                nn_scan32(s_run, me, best);
+            }
+        }
+    }
+    if (live) {
+        const uint32_t i = __float_as_uint(me.w);
+        out_dist2[i] = sls_nn_key_dist2(best);
+        if (out_index) out_index[i] = (int32_t)sls_nn_key_index(best);
+    }
+}
+
+// scratch: the target's index (KnnScratch, its sorter scratch sized for the larger cloud), then the queries' buffers
+struct NnScratch {
+    KnnScratch t;
+    uint32_t *qkeys, *qkeys_tmp, *qvals, *qvals_tmp;
+    float4 *qpts;
+    size_t total;
+};
+
+static NnScratch nn_layout(int Mt, int Mq, void *base)
+{
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    NnScratch s;
+    s.t = knn_layout(Mt, base);
+    const size_t sort_bytes = sort_scratch_bytes((uint64_t)(Mt > Mq ? Mt : Mq));
+    char *p = (char *)base;
+    size_t off = s.t.total - al(s.t.sort_bytes) + al(sort_bytes);
+    s.t.sort_bytes = sort_bytes;
+    s.qkeys = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
+    s.qkeys_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
+    s.qvals = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
+    s.qvals_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
+    s.qpts = (float4 *)(p + off); off += al(sizeof(float4) * (size_t)Mq);
+    s.total = off < (size_t)SLS_NN_STATS_SCRATCH_BYTES ? (size_t)SLS_NN_STATS_SCRATCH_BYTES : off;
+    return s;
+}
+
+size_t nn_scratch_bytes(int Mt, int Mq) { return (Mt > 0 && Mq >= 0) ? nn_layout(Mt, Mq, nullptr).total : 0; }
+
+int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
+                    void *scratch, hipStream_t st)
+{
+    const NnScratch s = nn_layout(Mt, Mq, scratch);
+    const int key_bits = knn_key_bits(Mt);
+    ScopedTimer tm(T_KNN, st);
+    int which = 0, qwhich = 0;
+    int rc = knn_build(Mt, target_xyz, s.t, key_bits, (uint32_t)Mq, st, &which);
+    if (rc) return rc;
+    // the queries' codes in the TARGET's cube (knn_morton_kernel clamps to the border cells), the same sorter
+    hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, s.t.bbox, s.qkeys, s.qvals,
+                       key_bits);
+    SLS_LAUNCH_CHECK("knn_morton_kernel");
+    rc = radix_sort_pairs_u32(s.qkeys, s.qvals, s.qkeys_tmp, s.qvals_tmp, s.t.bbox + 7, (uint32_t)Mq, key_bits, s.t.sort,
+                              s.t.sort_bytes, &qwhich, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(nn_gather_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz,
+                       qwhich ? s.qvals_tmp : s.qvals, s.qpts);
+    SLS_LAUNCH_CHECK("nn_gather_kernel");
+    hipLaunchKernelGGL(nn_query_kernel, dim3((Mq + 63) / 64), dim3(64), 0, st, Mt, (Mt + kKnnBox - 1) / kKnnBox, s.t.pts,
+                       s.t.boxes, s.t.subboxes, which ? s.t.keys_tmp : s.t.keys, Mq, s.qpts,
+                       qwhich ? s.qkeys_tmp : s.qkeys, out_dist2, out_index);
+    SLS_LAUNCH_CHECK("nn_query_kernel");
+    return SLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sls_nn_stats: count, count below the threshold and float64 sum of the distances (sls_nn_stats_term), in a FIXED order:
+// block b of a grid that depends on M alone sums its entries b*256 + t, + grid*256, ... per thread, the 64 lanes by a
+// butterfly, the 4 waves in order; one block then adds the partials the same way.  No atomics: the same bits every run.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kNnStatsMaxBlocks = SLS_NN_STATS_SCRATCH_BYTES / 32;     // 32 bytes per partial: n, n_below, sum, pad
+
+struct NnPartial { unsigned long long n, below; double sum; };
+
+__device__ __forceinline__ NnPartial nn_block_sum(NnPartial v)
+{   // valid in thread 0
+    __shared__ unsigned long long s_n[4], s_b[4];
+    __shared__ double s_s[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        v.n += __shfl_xor(v.n, off, 64);
+        v.below += __shfl_xor(v.below, off, 64);
+        v.sum += __shfl_xor(v.sum, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_n[threadIdx.x >> 6] = v.n; s_b[threadIdx.x >> 6] = v.below; s_s[threadIdx.x >> 6] = v.sum; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w) { v.n += s_n[w]; v.below += s_b[w]; v.sum += s_s[w]; }
+    return v;
+}
+
+__global__ __launch_bounds__(256) void nn_stats_partial_kernel(int M, const float *__restrict__ dist2, float truncation,
+                                                               float threshold, int include_truncated,
+                                                               unsigned long long *__restrict__ partials)
+{
+    NnPartial v = { 0ull, 0ull, 0.0 };
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)M; i += (size_t)gridDim.x * 256) {
+        float d;
+        if (sls_nn_stats_term(dist2[i], truncation, include_truncated, &d)) {
+            v.n += 1ull;
+            v.below += d < threshold ? 1ull : 0ull;
+            v.sum += (double)d;
+        }
+    }
+    v = nn_block_sum(v);
+    if (threadIdx.x == 0) {
+        partials[4 * blockIdx.x] = v.n;
+        partials[4 * blockIdx.x + 1] = v.below;
+        partials[4 * blockIdx.x + 2] = (unsigned long long)__double_as_longlong(v.sum);
+    }
+}
+
+__global__ __launch_bounds__(256) void nn_stats_final_kernel(int M, int nblocks, const unsigned long long *__restrict__ partials,
+                                                             unsigned long long *__restrict__ out)
+{
+    NnPartial v = { 0ull, 0ull, 0.0 };
+    for (int b = threadIdx.x; b < nblocks; b += 256) {
+        v.n += partials[4 * b];
+        v.below += partials[4 * b + 1];
+        v.sum += __longlong_as_double((long long)partials[4 * b + 2]);
+    }
+    v = nn_block_sum(v);
+    if (threadIdx.x == 0) {
+        out[0] = v.n;
+        out[1] = v.below;
+        out[2] = (unsigned long long)__double_as_longlong(v.sum);
+        out[3] = (unsigned long long)M;
+    }
+}
+
+int launch_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
+                    void *scratch, hipStream_t st)
+{
+    int nblocks = (M + 255) / 256;
+    if (nblocks > kNnStatsMaxBlocks) nblocks = kNnStatsMaxBlocks;
+    unsigned long long *partials = (unsigned long long *)scratch;
+    if (nblocks > 0) {
+        hipLaunchKernelGGL(nn_stats_partial_kernel, dim3(nblocks), dim3(256), 0, st, M, dist2, truncation, threshold,
+                           include_truncated, partials);
+        SLS_LAUNCH_CHECK("nn_stats_partial_kernel");
+    }
+    hipLaunchKernelGGL(nn_stats_final_kernel, dim3(1), dim3(256), 0, st, M, nblocks, partials,
+                       (unsigned long long *)out_stats);
+    SLS_LAUNCH_CHECK("nn_stats_final_kernel");
     return SLS_OK;
 }
 

@@ -173,6 +173,12 @@ int launch_surface_samples(int H, int W, const float *allmap, const float *col_h
                            hipStream_t st);
 size_t knn_scratch_bytes(int M);
 int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratch_bytes, hipStream_t st, int Mq);   // Mq < 0: all
+size_t nn_scratch_bytes(int Mt, int Mq);
+// (both: the arguments are checked by the caller, sls_api.hip — sizes, pointers, scratch size and alignment)
+int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
+                    void *scratch, hipStream_t st);
+int launch_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
+                    void *scratch, hipStream_t st);
 int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_raw, float smax, float pen,
                           const uint32_t *status_block, uint64_t *bitmap, hipStream_t st);
 int launch_adam(const SlsAdamGroup *groups, int ngroups, double beta1, double beta2, double eps, int64_t step,

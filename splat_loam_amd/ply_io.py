@@ -51,32 +51,66 @@ def save_point_cloud(path, points, normals) -> None:
         f.write(data.tobytes())
 
 
-def load_ply(path) -> dict:
-    """dict(xyz (N,3), opacity (N,1), scaling (N,S), rotation (N,4)) of raw parameters; properties are
-    looked up by name like the reference does, so extra/reordered float properties are tolerated."""
+_KINDS = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1",
+          "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "short": "<i2", "int16": "<i2", "ushort": "<u2",
+          "uint16": "<u2", "char": "i1", "int8": "i1"}
+
+
+def _read_vertices(path):
+    """The `vertex` element of a binary little-endian PLY as a structured array, and its property names in file order.
+    Elements in front of it must be free of list properties (their size is not known from the header otherwise)."""
     with open(path, "rb") as f:
         blob = f.read()
     end = blob.index(b"end_header\n") + len(b"end_header\n")
     lines = blob[:end].decode("ascii").splitlines()
     if lines[0] != "ply" or "binary_little_endian" not in lines[1]:
         raise ValueError("only binary little-endian PLY is supported")
-    n, names = 0, []
-    kinds = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1",
-             "int": "<i4", "int32": "<i4", "uint": "<u4", "short": "<i2", "ushort": "<u2", "char": "i1"}
-    dtype = []
-    in_vertex = False
+    elements = []                                   # [name, count, [(property, dtype)]] in file order
     for ln in lines:
         tok = ln.split()
         if tok[:1] == ["element"]:
-            in_vertex = tok[1] == "vertex"
-            if in_vertex:
-                n = int(tok[2])
-        elif tok[:1] == ["property"] and in_vertex:
-            dtype.append((tok[2], kinds[tok[1]]))
-            names.append(tok[2])
-    rec = np.frombuffer(blob, dtype=np.dtype(dtype), count=n, offset=end)
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[:1] == ["property"] and elements:
+            if tok[1] == "list":
+                elements[-1][2].append((tok[-1], None))
+            else:
+                elements[-1][2].append((tok[2], _KINDS[tok[1]]))
+    offset = end
+    for name, count, props in elements:
+        if name == "vertex":
+            if any(kind is None for _, kind in props):
+                raise ValueError("list properties on the vertex element are not supported")
+            rec = np.frombuffer(blob, dtype=np.dtype(props), count=count, offset=offset)
+            return rec, [p for p, _ in props]
+        if any(kind is None for _, kind in props):
+            raise ValueError(f"element {name} with list properties comes before the vertices")
+        offset += count * np.dtype(props).itemsize
+    raise ValueError("no vertex element")
+
+
+def load_ply(path) -> dict:
+    """dict(xyz (N,3), opacity (N,1), scaling (N,S), rotation (N,4)) of raw parameters; properties are
+    looked up by name like the reference does, so extra/reordered float properties are tolerated."""
+    rec, names = _read_vertices(path)
     col = lambda name: np.asarray(rec[name], dtype=np.float32)
     scale_names = sorted([p for p in names if p.startswith("scale_")], key=lambda s: int(s.split("_")[-1]))
     rot_names = sorted([p for p in names if p.startswith("rot")], key=lambda s: int(s.split("_")[-1]))
     return dict(xyz=np.stack([col("x"), col("y"), col("z")], 1), opacity=col("opacity")[:, None],
                 scaling=np.stack([col(s) for s in scale_names], 1), rotation=np.stack([col(s) for s in rot_names], 1))
+
+
+def load_point_cloud(path):
+    """`(points (N,3) float32, normals (N,3) float32 | None)` of a binary little-endian PLY point cloud: `x y z` as float
+    or double (scan exports often store doubles; they are rounded to float32 once), `nx ny nz` where the file has all
+    three.  Reads what `save_point_cloud` writes; other vertex properties and the elements behind the vertices (faces)
+    are ignored."""
+    rec, names = _read_vertices(path)
+    for p in ("x", "y", "z"):
+        if p not in names:
+            raise ValueError(f"{path}: the vertex element has no property {p}")
+        if rec.dtype[p].kind != "f":
+            raise ValueError(f"{path}: property {p} is not float or double")
+    col = lambda name: np.asarray(rec[name], dtype=np.float32)
+    points = np.stack([col("x"), col("y"), col("z")], 1)
+    normals = np.stack([col("nx"), col("ny"), col("nz")], 1) if all(p in names for p in ("nx", "ny", "nz")) else None
+    return points, normals
