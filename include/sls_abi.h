@@ -730,6 +730,45 @@ int sls_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz
 int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
                  void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- voxel down-sampling and mesh sampling (what evaluate_recon does before its metric block) -----------------------
+ * Open3D's voxel_down_sample for points only, restated (include/sls_cloud_math.h): every point gets the voxel
+ * (ix, iy, iz), i_a = floor(((double)p_a - o_a) / voxel_size), o_a = (double)min_a - 0.5 * voxel_size, packed into the
+ * key ix | iy << 21 | iz << 42.  Output row v is the voxel with the v-th smallest key (Open3D's hash-map order is
+ * unspecified; this is the order this project defines): out_xyz[v] = (float)(float64 sum of the voxel's points / count),
+ * out_count[v] = the number of its points (optional: may be null).  Both have room for M rows; the rows from n_voxels on
+ * are not written.  The sum of a voxel adds its points in ascending input index — one lane for a voxel of at most 64
+ * points, 64 lanes (lane l the points l, l + 64, ... of that order, then a fixed butterfly) beyond — no floating-point
+ * atomics: the same input gives the same bits on every run.
+ *   out_status (DEVICE, 4 words): [n_voxels, points with a non-finite coordinate, points with an index >= 2^21, 0].
+ *       Where either error count is not 0 the output rows are unspecified (every access stays inside the buffers); the
+ *       call still returns SLS_OK and the caller decides after its read.
+ *   scratch: sls_voxel_scratch_bytes(M) bytes (0 for M < 1), 256-byte aligned; never below sls_sort_scratch_bytes(M).
+ * M == 0 succeeds, writes four zeros to out_status when that is non-null and touches nothing else.  Before anything is
+ * enqueued: SLS_E_ARG for M < 0, a null pointer, a voxel_size that is not finite or not > 0, misaligned scratch;
+ * SLS_E_SCRATCH for too little scratch. */
+size_t sls_voxel_scratch_bytes(int M);
+int sls_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count,
+                         uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+
+/* Area-weighted uniform sampling of a triangle mesh, seeded: Open3D's sample_points_uniformly with a defined random
+ * stream — sample i is a pure function of (mesh, crop box, seed, i), include/sls_cloud_math.h states every step.
+ *   vertices (V x 3 floats), faces (F x 3 int32), crop_box (optional: 6 DEVICE floats, min xyz then max xyz).
+ *   A face has weight 0 when an index is outside [0, V) (counted in out_status[1]), when its float64 area is not
+ *   finite, or when a crop box is given and one of its vertices lies outside the closed box (Open3D's crop keeps a
+ *   triangle when all its vertices are kept).  Otherwise w = floor(area / largest area * 2^32): the prefix sum is an
+ *   integer, exact in any order; faces below 2^-32 of the largest one are never drawn.
+ *   out_xyz (n_samples x 3), out_face (optional, n_samples int32): the points and the face each was drawn from.
+ *   out_status (DEVICE, 4 words): [rows written: n_samples, or 0 when no face has weight (nothing else is written
+ *       then), faces with an index outside [0, V), 1 when no face has weight, 0].
+ *   scratch: sls_mesh_sample_scratch_bytes(V, F, n_samples) bytes (0 for a negative argument), 256-byte aligned.
+ * n_samples == 0 succeeds, writes four zeros to out_status when that is non-null and touches nothing else.  Before
+ * anything is enqueued: SLS_E_ARG for a negative size, a null pointer (crop_box and out_face may be null; vertices
+ * with V == 0 and faces with F == 0 too), misaligned scratch; SLS_E_SCRATCH for too little scratch. */
+size_t sls_mesh_sample_scratch_bytes(int V, int F, int n_samples);
+int sls_mesh_sample(int V, const float *vertices, int F, const int32_t *faces, const float *crop_box, int n_samples,
+                    uint64_t seed, float *out_xyz, int32_t *out_face, uint32_t *out_status, void *scratch,
+                    size_t scratch_bytes, void *stream);
+
 /* visible[i] = 1 if surfel centre i survives the near cut (radii would be >0
  * unless it is off-image). */
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible,

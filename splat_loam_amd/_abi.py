@@ -163,6 +163,10 @@ _PROTOS = {
     "sls_nn_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_nn_query": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_nn_stats": (C.c_int, [C.c_int, _VP, C.c_float, C.c_float, C.c_int, _VP, _VP, C.c_size_t, _VP]),
+    "sls_voxel_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_voxel_downsample": (C.c_int, [C.c_int, _VP, C.c_double, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_mesh_sample_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sls_mesh_sample": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_uint64, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_mark_visible": (C.c_int, [C.POINTER(SlsCamera), C.c_int, _VP, _VP, _VP]),
     "sls_aligner_workspace_bytes": (C.c_size_t, []),
     "sls_aligner_normals": (C.c_int, [C.POINTER(SlsCamera), _VP, _VP, C.c_float, _VP, _VP]),

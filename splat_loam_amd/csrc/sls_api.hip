@@ -1,5 +1,6 @@
 // sls_api.hip — the extern "C" boundary (include/sls_abi.h), host helpers,
 // fused Adam (P6) and the device self-test.
+#include <float.h>
 #include <math.h>
 #include <stdarg.h>
 #include <string.h>
@@ -473,6 +474,48 @@ int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, i
         return SLS_E_SCRATCH;
     }
     return launch_nn_stats(M, dist2, truncation, threshold, include_truncated, out_stats, scratch, (hipStream_t)stream);
+}
+
+size_t sls_voxel_scratch_bytes(int M) { return voxel_scratch_bytes(M); }
+
+int sls_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,
+                         void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE(voxel_size > 0.0 && voxel_size <= DBL_MAX, "voxel_size is not a finite number > 0");
+    if (M == 0) {
+        if (out_status) SLS_HIP_CHECK(hipMemsetAsync(out_status, 0, 4 * sizeof(uint32_t), (hipStream_t)stream));
+        return SLS_OK;
+    }
+    SLS_REQUIRE(xyz && out_xyz && out_status && scratch, "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < voxel_scratch_bytes(M)) {
+        set_error("sls_voxel_downsample: scratch too small: %zu < %zu", scratch_bytes, voxel_scratch_bytes(M));
+        return SLS_E_SCRATCH;
+    }
+    return launch_voxel_downsample(M, xyz, voxel_size, out_xyz, out_count, out_status, scratch, (hipStream_t)stream);
+}
+
+size_t sls_mesh_sample_scratch_bytes(int V, int F, int n_samples) { return mesh_sample_scratch_bytes(V, F, n_samples); }
+
+int sls_mesh_sample(int V, const float *vertices, int F, const int32_t *faces, const float *crop_box, int n_samples,
+                    uint64_t seed, float *out_xyz, int32_t *out_face, uint32_t *out_status, void *scratch,
+                    size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(V >= 0 && F >= 0, "negative V or F");
+    SLS_REQUIRE(n_samples >= 0, "negative n_samples");
+    if (n_samples == 0) {
+        if (out_status) SLS_HIP_CHECK(hipMemsetAsync(out_status, 0, 4 * sizeof(uint32_t), (hipStream_t)stream));
+        return SLS_OK;
+    }
+    SLS_REQUIRE((vertices || V == 0) && (faces || F == 0) && out_xyz && out_status && scratch, "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < mesh_sample_scratch_bytes(V, F, n_samples)) {
+        set_error("sls_mesh_sample: scratch too small: %zu < %zu", scratch_bytes, mesh_sample_scratch_bytes(V, F, n_samples));
+        return SLS_E_SCRATCH;
+    }
+    return launch_mesh_sample(V, vertices, F, faces, crop_box, n_samples, seed, out_xyz, out_face, out_status, scratch,
+                              (hipStream_t)stream);
 }
 
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible, void *stream)

@@ -47,6 +47,10 @@ size_t order_scratch_bytes(int N);
 int radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uint32_t *vals_tmp,
                          const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
                          int *result_in_tmp, hipStream_t st);
+// the same sorter on 64-bit keys (sls_cloud.hip: the 63-bit voxel keys)
+int radix_sort_pairs_u64(uint64_t *keys, uint32_t *vals, uint64_t *keys_tmp, uint32_t *vals_tmp,
+                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
+                         int *result_in_tmp, hipStream_t st);
 // where preprocess writes the depth sort's input (keys, identity permutation, N on the device) and the repair its pairs
 void depth_order_key_buffers(int N, void *scratch, uint32_t *order, uint32_t **keys, uint32_t **vals0, uint32_t **n_dev);
 uint64_t *resort_comp_buffer(int N, void *scratch);
@@ -179,6 +183,13 @@ int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_
                     void *scratch, hipStream_t st);
 int launch_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
                     void *scratch, hipStream_t st);
+// ---- sls_cloud.hip (the arguments are checked by the caller, sls_api.hip) ------------------------------------------
+size_t voxel_scratch_bytes(int M);
+int launch_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,
+                            void *scratch, hipStream_t st);
+size_t mesh_sample_scratch_bytes(int V, int F, int n_samples);
+int launch_mesh_sample(int V, const float *vertices, int F, const int32_t *faces, const float *crop_box, int n_samples,
+                       uint64_t seed, float *out_xyz, int32_t *out_face, uint32_t *out_status, void *scratch, hipStream_t st);
 int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_raw, float smax, float pen,
                           const uint32_t *status_block, uint64_t *bitmap, hipStream_t st);
 int launch_adam(const SlsAdamGroup *groups, int ngroups, double beta1, double beta2, double eps, int64_t step,

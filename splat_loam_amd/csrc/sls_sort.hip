@@ -675,6 +675,14 @@ int radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uin
                                         scratch_bytes, result_in_tmp, st);
 }
 
+int radix_sort_pairs_u64(uint64_t *keys, uint32_t *vals, uint64_t *keys_tmp, uint32_t *vals_tmp,
+                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
+                         int *result_in_tmp, hipStream_t st)
+{
+    return radix_sort_pairs_t<uint64_t>(keys, vals, keys_tmp, vals_tmp, count_ptr, cap, nbits, scratch,
+                                        scratch_bytes, result_in_tmp, st);
+}
+
 // ---------------------------------------------------------------------------
 // Temporal re-sort of the depth order.  Between two mapping iterations on the
 // same keyframe a surfel moves by at most ~100 positions in the depth order

@@ -1,13 +1,20 @@
-"""Reconstruction metrics between two point clouds, on the device.
+"""Reconstruction metrics between a reference cloud and an estimated mesh or cloud, on the device.
 
 The reference answers "how good is the map" in utils/eval_utils.py (`evaluate_recon`, `nn_correspondance`,
-`crop_union`) with an Open3D KD-tree queried one point at a time from Python.  Here the nearest-neighbour search
-is one native call (sls_nn_query: the spatial index of `distCUDA2`, queried by a second cloud) and the metric block
-(eval_utils.py:122-153) two more (sls_nn_stats) plus ONE host read of eight words.  Device tensors only; there is no
-CPU path.
+`crop_union`) with Open3D: it samples the estimated mesh, voxel-down-samples both clouds and queries a KD-tree one
+point at a time from Python.  Here the whole of `evaluate_recon` runs on the device: the mesh is sampled by one native
+call (sls_mesh_sample: area-weighted, seeded), both clouds are down-sampled by one each (sls_voxel_downsample), the
+nearest-neighbour search is one call (sls_nn_query: the spatial index of `distCUDA2`, queried by a second cloud) and
+the metric block (eval_utils.py:122-153) two more (sls_nn_stats).  `evaluate_recon` reads the host twice: the status
+words of the sampling and of both down-samples together, then the eight metric words.  Device tensors only; there is
+no CPU path.
 
-Not done here: reading or sampling triangle meshes, the bounding-box crop of a mesh and the voxel
-down-sampling `evaluate_recon` applies to both clouds first.
+Open3D is not a dependency: voxel_down_sample and sample_points_uniformly are restated from their documented behaviour
+(include/sls_cloud_math.h) with the two things Open3D leaves open — the order of the voxels, the random stream — defined
+here, and pinned against NumPy restatements (tests/cloud_ref.py), not against Open3D itself.
+
+Not done here: reading files (splat_loam_amd/ply_io.py: load_point_cloud, load_mesh; tools/eval_recon.py puts the two
+together) and the reference's error map, which it does not implement either.
 """
 from __future__ import annotations
 
@@ -115,4 +122,181 @@ def cloud_metrics(reference: torch.Tensor, estimate: torch.Tensor, threshold: fl
         "precision": precision, "recall": recall, "fscore": fscore,
         "n_accuracy": int(n_acc), "n_completeness": int(n_com),
         "threshold": float(threshold), "truncation_acc": float(truncation_acc), "truncation_com": float(truncation_com),
+    }
+
+
+def _scratch_bytes(nbytes: int, device) -> tuple[torch.Tensor, int, int]:
+    buf = torch.empty((int(nbytes) + 256,), dtype=torch.uint8, device=device)
+    return buf, (buf.data_ptr() + 255) & ~255, int(nbytes)
+
+
+def _voxel_enqueue(lib, points: torch.Tensor, voxel_size: float, want_counts: bool, st):
+    """sls_voxel_downsample without a host read: (rows (M,3), counts (M,) | None, status (4,) int32)."""
+    M = int(points.shape[0])
+    dev = points.device
+    out = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    counts = torch.empty((M,), dtype=torch.int32, device=dev) if want_counts else None
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    scratch, aligned, nbytes = _scratch_bytes(lib.sls_voxel_scratch_bytes(M), dev)
+    _abi.check(lib.sls_voxel_downsample(M, points.data_ptr() if M else None, float(voxel_size), out.data_ptr() if M else None,
+                                        counts.data_ptr() if (want_counts and M) else None, status.data_ptr(),
+                                        aligned if M else None, nbytes, st), "sls_voxel_downsample")
+    return out, counts, status
+
+
+def _voxel_status(words, what: str) -> int:
+    """n_voxels from the three status words of one down-sample; ValueError where the cloud could not be served."""
+    n_voxels, n_nonfinite, n_big = (int(w) & 0xFFFFFFFF for w in words[:3])
+    if n_nonfinite:
+        raise ValueError(f"{what}: {n_nonfinite} points have a non-finite coordinate")
+    if n_big:
+        raise ValueError(f"{what}: {n_big} points lie more than 2^21 voxels from the cloud's minimum; the voxel size is too "
+                         "small for the cloud's extent")
+    return n_voxels
+
+
+def _check_voxel_size(voxel_size) -> float:
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
+        raise ValueError("voxel_size must be a finite number > 0")
+    return voxel_size
+
+
+def voxel_down_sample(points: torch.Tensor, voxel_size: float, return_counts: bool = False):
+    """Open3D's `voxel_down_sample` for points: one row per occupied voxel, the mean of the voxel's points — float64
+    sums, rounded to float32 once.  Voxel (ix, iy, iz) of a point is floor((p - (min - voxel_size / 2)) / voxel_size) per
+    axis in float64 (include/sls_cloud_math.h); the rows come in ascending order of ix | iy << 21 | iz << 42 (Open3D's
+    order is that of a hash map: unspecified).  The same cloud gives the same bits on every run.  `return_counts=True`
+    adds the number of points of every voxel, (n_voxels,) int32.  One host read (the status words).
+    ValueError: a non-finite coordinate, or a cloud wider than 2^21 voxels along an axis."""
+    points = _cloud(points, "points")
+    voxel_size = _check_voxel_size(voxel_size)
+    lib = _abi.lib()
+    with torch.cuda.device(points.device):
+        st = torch.cuda.current_stream(points.device).cuda_stream
+        out, counts, status = _voxel_enqueue(lib, points, voxel_size, return_counts, st)
+        n = _voxel_status(status.cpu().tolist(), "voxel_down_sample")      # the one host read
+    return (out[:n], counts[:n]) if return_counts else out[:n]
+
+
+def _mesh(vertices: torch.Tensor, faces: torch.Tensor):
+    vertices = _cloud(vertices, "vertices")
+    if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+        raise RuntimeError("faces must be a ROCm device tensor (libsls_hip.so); there is no CPU fallback")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype.is_floating_point:
+        raise ValueError("faces must be an integer tensor of shape (F,3)")
+    if faces.device != vertices.device:
+        raise ValueError("vertices and faces must live on the same device")
+    faces = faces.detach()
+    if faces.dtype != torch.int32:
+        faces = faces.to(torch.int32)
+    return vertices, faces.contiguous()
+
+
+def _mesh_enqueue(lib, vertices, faces, n: int, seed: int, crop_box, want_faces: bool, st):
+    """sls_mesh_sample without a host read: (points (n,3), face (n,) | None, status (4,) int32)."""
+    dev = vertices.device
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face = torch.empty((n,), dtype=torch.int32, device=dev) if want_faces else None
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    scratch, aligned, nbytes = _scratch_bytes(lib.sls_mesh_sample_scratch_bytes(V, F, n), dev)
+    _abi.check(lib.sls_mesh_sample(V, vertices.data_ptr() if V else None, F, faces.data_ptr() if F else None,
+                                   crop_box.data_ptr() if crop_box is not None else None, n, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   out.data_ptr() if n else None, face.data_ptr() if (want_faces and n) else None,
+                                   status.data_ptr(), aligned, nbytes, st), "sls_mesh_sample")
+    return out, face, status
+
+
+def _mesh_status(words, n: int) -> None:
+    written, n_bad, no_area = (int(w) & 0xFFFFFFFF for w in words[:3])
+    if n_bad:
+        raise ValueError(f"sample_mesh: {n_bad} faces have a vertex index outside the vertices")
+    if n and (no_area or written != n):
+        raise ValueError("sample_mesh: the mesh has no area to sample (no face, or every face is degenerate or cropped away)")
+
+
+def _crop_box(crop_box, device):
+    if crop_box is None:
+        return None
+    box = torch.as_tensor(crop_box, dtype=torch.float32).to(device).reshape(-1).contiguous()
+    if box.numel() != 6:
+        raise ValueError("crop_box must hold six numbers: min xyz, max xyz")
+    return box
+
+
+def sample_mesh(vertices: torch.Tensor, faces: torch.Tensor, n: int, seed: int = 0, crop_box=None, return_faces: bool = False):
+    """`n` points drawn uniformly from the surface of a triangle mesh — Open3D's `sample_points_uniformly` with a seeded,
+    defined random stream: sample i is a pure function of (mesh, crop box, seed, i), so a rerun gives the same cloud and
+    a longer draw starts with the shorter one.  A face is drawn in proportion to its float64 area, quantised to 2^-32 of
+    the largest area (smaller faces are never drawn); `crop_box` (six numbers or a device tensor: min xyz, max xyz)
+    keeps only the faces whose three vertices lie inside the closed box, as Open3D's `crop` does.  (n,3) float32, with
+    `return_faces=True` also the face of every point, (n,) int32.  One host read (the status words).
+    ValueError: a vertex index outside the vertices, or no face with area left."""
+    vertices, faces = _mesh(vertices, faces)
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must not be negative")
+    lib = _abi.lib()
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        out, face, status = _mesh_enqueue(lib, vertices, faces, n, seed, _crop_box(crop_box, dev), return_faces, st)
+        _mesh_status(status.cpu().tolist(), n)                              # the one host read
+    return (out, face) if return_faces else out
+
+
+def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, down_sample_res: float = 0.02,
+                   threshold: float = 0.2, truncation_acc: float = 0.5, truncation_com: float = 0.5,
+                   crop_to_reference: bool = False, mesh_sample_point: int = 10_000_000, seed: int = 0) -> dict:
+    """The reference's `evaluate_recon` (utils/eval_utils.py:67-154) for a reference cloud and an estimated mesh already
+    on the device, with its dictionary keys and units: sample `mesh_sample_point` points from the mesh, voxel-down-sample
+    both clouds at `down_sample_res` (skipped where that is <= 0, as in the reference), then the metric block of
+    `cloud_metrics`.  Two host reads in all: the status words of the sampling and of both down-samples together, then the
+    metric words.
+
+    `crop_to_reference` defaults to False ON PURPOSE: the reference calls `estimate_mesh.crop(reference_bbox)` and
+    discards what it returns (eval_utils.py:109; Open3D's crop does not work in place), so the numbers it publishes
+    are those of the UNCROPPED mesh.  True does what it intended: only the faces whose vertices all lie inside the
+    reference cloud's bounding box, padded by `down_sample_res` along z, are sampled (the box is computed on the device).
+    The sampling is seeded (`seed`), where the reference's is not: a rerun gives the same numbers."""
+    reference = _cloud(reference_points, "reference_points")
+    vertices, faces = _mesh(vertices, faces)
+    if reference.device != vertices.device:
+        raise ValueError("the reference cloud and the mesh must live on the same device")
+    if reference.shape[0] == 0:
+        raise ValueError("the reference cloud is empty")
+    n = int(mesh_sample_point)
+    if n < 1:
+        raise ValueError("mesh_sample_point must be at least 1")
+    res = float(down_sample_res)
+    down = res > 0.0
+    if down:
+        _check_voxel_size(res)
+    lib = _abi.lib()
+    dev = reference.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        box = None
+        if crop_to_reference:
+            pad = torch.tensor([0.0, 0.0, res], dtype=torch.float32, device=dev)
+            box = torch.cat([reference.amin(0) - pad, reference.amax(0) + pad]).contiguous()
+        estimate, _, status = _mesh_enqueue(lib, vertices, faces, n, seed, box, False, st)
+        if down:
+            estimate, _, status_e = _voxel_enqueue(lib, estimate, res, False, st)
+            reference, _, status_r = _voxel_enqueue(lib, reference, res, False, st)
+            status = torch.cat([status, status_e, status_r])
+        w = status.cpu().tolist()                                           # host read 1 of 2
+        _mesh_status(w[0:4], n)
+        if down:
+            estimate = estimate[:_voxel_status(w[4:8], "evaluate_recon: the sampled mesh")]
+            reference = reference[:_voxel_status(w[8:12], "evaluate_recon: the reference cloud")]
+    m = cloud_metrics(reference, estimate, threshold=threshold, truncation_acc=truncation_acc,
+                      truncation_com=truncation_com)                        # host read 2 of 2
+    return {
+        "MAE_accuracy (cm)": m["accuracy_m"] * 100, "MAE_completeness (cm)": m["completeness_m"] * 100,
+        "Chamfer_L1 (cm)": m["chamfer_l1_m"] * 100, "Precision [Accuracy] (%)": m["precision"] * 100.0,
+        "Recall [Completeness] (%)": m["recall"] * 100.0, "F-score (%)": m["fscore"] * 100.0,
+        "Inlier_threshold (m)": float(threshold), "Outlier_truncation_acc (m)": float(truncation_acc),
+        "Outlier_truncation_com (m)": float(truncation_com),
     }

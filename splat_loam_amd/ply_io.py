@@ -56,35 +56,40 @@ _KINDS = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "
           "uint16": "<u2", "char": "i1", "int8": "i1"}
 
 
-def _read_vertices(path):
-    """The `vertex` element of a binary little-endian PLY as a structured array, and its property names in file order.
-    Elements in front of it must be free of list properties (their size is not known from the header otherwise)."""
+def _parse_header(path):
+    """(file bytes, offset of the data, [[element, count, [(property, dtype | None for a list, header tokens)]]])"""
     with open(path, "rb") as f:
         blob = f.read()
     end = blob.index(b"end_header\n") + len(b"end_header\n")
     lines = blob[:end].decode("ascii").splitlines()
     if lines[0] != "ply" or "binary_little_endian" not in lines[1]:
         raise ValueError("only binary little-endian PLY is supported")
-    elements = []                                   # [name, count, [(property, dtype)]] in file order
+    elements = []                                   # in file order
     for ln in lines:
         tok = ln.split()
         if tok[:1] == ["element"]:
             elements.append([tok[1], int(tok[2]), []])
         elif tok[:1] == ["property"] and elements:
             if tok[1] == "list":
-                elements[-1][2].append((tok[-1], None))
+                elements[-1][2].append((tok[-1], None, tok))
             else:
-                elements[-1][2].append((tok[2], _KINDS[tok[1]]))
-    offset = end
+                elements[-1][2].append((tok[2], _KINDS[tok[1]], tok))
+    return blob, end, elements
+
+
+def _read_vertices(path):
+    """The `vertex` element of a binary little-endian PLY as a structured array, and its property names in file order.
+    Elements in front of it must be free of list properties (their size is not known from the header otherwise)."""
+    blob, offset, elements = _parse_header(path)
     for name, count, props in elements:
         if name == "vertex":
-            if any(kind is None for _, kind in props):
+            if any(kind is None for _, kind, _ in props):
                 raise ValueError("list properties on the vertex element are not supported")
-            rec = np.frombuffer(blob, dtype=np.dtype(props), count=count, offset=offset)
-            return rec, [p for p, _ in props]
-        if any(kind is None for _, kind in props):
+            rec = np.frombuffer(blob, dtype=np.dtype([(p, k) for p, k, _ in props]), count=count, offset=offset)
+            return rec, [p for p, _, _ in props]
+        if any(kind is None for _, kind, _ in props):
             raise ValueError(f"element {name} with list properties comes before the vertices")
-        offset += count * np.dtype(props).itemsize
+        offset += count * np.dtype([(p, k) for p, k, _ in props]).itemsize
     raise ValueError("no vertex element")
 
 
@@ -114,3 +119,54 @@ def load_point_cloud(path):
     points = np.stack([col("x"), col("y"), col("z")], 1)
     normals = np.stack([col("nx"), col("ny"), col("nz")], 1) if all(p in names for p in ("nx", "ny", "nz")) else None
     return points, normals
+
+
+def _xyz(path, rec, names):
+    for p in ("x", "y", "z"):
+        if p not in names:
+            raise ValueError(f"{path}: the vertex element has no property {p}")
+        if rec.dtype[p].kind != "f":
+            raise ValueError(f"{path}: property {p} is not float or double")
+    return np.stack([np.asarray(rec[p], dtype=np.float32) for p in ("x", "y", "z")], 1)
+
+
+def load_mesh(path):
+    """`(vertices (V,3) float32, faces (F,3) int32)` of a binary little-endian PLY triangle mesh, as Open3D writes one
+    (a Poisson reconstruction): a `vertex` element with `x y z` as float or double (other vertex properties are
+    skipped), then one `face` element whose only property is `list uchar int|uint vertex_indices` (or `vertex_index`).
+    Every face must be a triangle; an ASCII or big-endian file, a face with another vertex count or a face element with
+    further properties is refused with a ValueError.  Indices are not range-checked here (sls_mesh_sample counts the
+    faces that point outside the vertices); a uint index above 2^31 - 1 is refused."""
+    blob, offset, elements = _parse_header(path)
+    vertices = faces = None
+    for name, count, props in elements:
+        lists = [tok for _, kind, tok in props if kind is None]
+        if name == "face":
+            if len(props) != 1 or len(lists) != 1:
+                raise ValueError(f"{path}: the face element must hold exactly one list property")
+            tok = lists[0]
+            if len(tok) != 5 or tok[2] not in ("uchar", "uint8") or _KINDS.get(tok[3]) not in ("<i4", "<u4") or \
+                    tok[4] not in ("vertex_indices", "vertex_index"):
+                raise ValueError(f"{path}: unsupported face property `{' '.join(tok)}` (want list uchar int|uint vertex_indices)")
+            rec_t = np.dtype([("n", "u1"), ("i", _KINDS[tok[3]], (3,))])
+            if len(blob) - offset < count * rec_t.itemsize:
+                raise ValueError(f"{path}: the face data is shorter than {count} triangles")
+            rec = np.frombuffer(blob, dtype=rec_t, count=count, offset=offset)
+            if count and not np.all(rec["n"] == 3):       # (a quad shifts every later record: the counts stop being 3)
+                raise ValueError(f"{path}: only triangle meshes are supported (a face is not a triangle)")
+            idx = rec["i"]
+            if idx.dtype.kind == "u" and count and int(idx.max()) > 0x7FFFFFFF:
+                raise ValueError(f"{path}: a vertex index does not fit int32")
+            faces = np.ascontiguousarray(idx.astype(np.int32)).reshape(-1, 3)
+            break                                           # (what follows the faces is not needed)
+        if lists:
+            raise ValueError(f"{path}: element {name} with list properties comes before the faces")
+        rec_t = np.dtype([(p, k) for p, k, _ in props])
+        if name == "vertex":
+            vertices = _xyz(path, np.frombuffer(blob, dtype=rec_t, count=count, offset=offset), [p for p, _, _ in props])
+        offset += count * rec_t.itemsize
+    if vertices is None:
+        raise ValueError(f"{path}: no vertex element in front of the faces")
+    if faces is None:
+        raise ValueError(f"{path}: no face element")
+    return vertices, faces

@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""The reference's `evaluate_recon` (utils/eval_utils.py:67-154) for a reference point cloud and an estimated triangle
+mesh, on the device (splat_loam_amd.evaluation.evaluate_recon), one JSON line with the reference's keys and units:
+
+    python tools/eval_recon.py REFERENCE.ply MESH.ply [--down-sample-res 0.02] [--threshold 0.2] [--truncation-acc 0.5]
+                               [--truncation-com 0.5] [--mesh-sample-point 10000000] [--seed 0] [--crop-to-reference]
+
+REFERENCE.ply: binary little-endian PLY with `x y z` as float or double.  MESH.ply: binary little-endian PLY with a
+`vertex` element and one `face` element of triangles (`list uchar int vertex_indices`: what Open3D writes for a Poisson
+mesh).  The defaults are the reference's.  --crop-to-reference samples only the faces inside the reference cloud's
+bounding box (z padded by the voxel size): what the reference intended but does not do, so it is off by default."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch
+
+from splat_loam_amd import evaluation, ply_io
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("reference_ply")
+    ap.add_argument("mesh_ply")
+    ap.add_argument("--down-sample-res", type=float, default=0.02)
+    ap.add_argument("--threshold", type=float, default=0.2)
+    ap.add_argument("--truncation-acc", type=float, default=0.5)
+    ap.add_argument("--truncation-com", type=float, default=0.5)
+    ap.add_argument("--mesh-sample-point", type=int, default=10_000_000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--crop-to-reference", action="store_true")
+    ap.add_argument("--device", default="cuda")
+    a = ap.parse_args()
+    dev = torch.device(a.device)
+    reference = torch.from_numpy(ply_io.load_point_cloud(a.reference_ply)[0]).to(dev)
+    vertices, faces = ply_io.load_mesh(a.mesh_ply)
+    print(json.dumps(evaluation.evaluate_recon(
+        reference, torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev), down_sample_res=a.down_sample_res,
+        threshold=a.threshold, truncation_acc=a.truncation_acc, truncation_com=a.truncation_com,
+        crop_to_reference=a.crop_to_reference, mesh_sample_point=a.mesh_sample_point, seed=a.seed)))
+
+
+if __name__ == "__main__":
+    main()
