@@ -92,7 +92,7 @@ __device__ __forceinline__ uint32_t block_mask_of(const BlockMaskArgs &a, uint32
 // The list order inside a tile is the depth order of its surfels, so an instance's place in the sorted list is
 //     base[tile] + (instances of that tile emitted by earlier CHUNKS of depth positions) + (its rank inside its chunk),
 // all of which follow from a count table cnt[tile][chunk] over chunks of 1024 depth positions:
-//   1. the kernel that leaves the depth order — the repair's merge (resort_merge_kernel<true>), or gather_count_kernel
+//   1. the kernel that leaves the depth order — the repair's merge (resort_merge_kernel<true, *>), or gather_count_kernel
 //      after a from-scratch sort — gathers, per position, the surfel's emission record {rectangle, block box}, writes it
 //      to an array indexed by POSITION (the third kernel reads it coalesced) and counts its chunk's tiles in LDS:
 //      one column of the table;
@@ -708,21 +708,39 @@ __global__ __launch_bounds__(kResortThreads) void resort_sort_kernel(int N, cons
 // window b covers positions [b*W - W/2, b*W + W/2): second half of sorted window b-1, first half of b
 // Also produces level 1 of the scan of tiles_touched (the sums of the four aligned 256-blocks a
 // window covers), which saves the gather_block_sums launch.
-// PRE (a further repair round in ONE launch): `comp` is sorted inside every SHIFTED window (the previous round wrote the
-// merged pairs back, comp_out), so the two aligned windows b-1 and b this window straddles are two sorted halves each:
-// the workgroup merges both itself (10 stages each instead of the 55 of a sort; every aligned window is merged by the
-// two workgroups that need it), hands them over in LDS and goes on with its own window — the second half of b-1, the
-// first of b.  Every round lets a surfel travel another window, at one dependent launch per round.
-// comp_out: the merged (key, surfel) pairs by position, for the round that follows (in place where !PRE: a workgroup
-// reads and writes its own window only; another buffer where PRE: the neighbours read what this one would overwrite).
-template <bool DIRECT, bool PRE>
+//
+// ESC (a repair of `rounds` = k >= 2 rounds in ONE launch).  k global rounds are 2k - 1 levels of window merges over the
+// window-sorted `comp`: shifted, aligned, shifted, ..., shifted; level 1 alone is the repair of one round.  Write S_j for
+// shifted window j after level 1 and A_j for aligned sorted window j of `comp`.
+//   * What the 2k - 1 levels leave in the positions of S_b depends on S_{b-k+1} .. S_{b+k-1} only (every level widens
+//     the cone of dependence by half a window on either side), that is on A_{b-k} .. A_{b+k-1}.
+//   * Boundary j, between S_j and S_{j+1}, is IN ORDER when max S_j < min S_{j+1}.  Both follow from `comp` without any
+//     merge: max S_j = max(A_{j-1}[1023], A_j[511]), min S_{j+1} = min(A_j[512], A_{j+1}[0]).
+//   * If the 2k - 2 boundaries b-k+1 .. b+k-2 inside the cone are all in order, S_{b-k+1} .. S_{b+k-1} laid end to end are
+//     sorted: every merge of the levels 2 .. 2k-1 inside the cone gets two halves that are already in order and is the
+//     identity, so the positions of S_b hold after k rounds what they hold after level 1.  The workgroup merges its
+//     own window once and is done — what a one-round repair costs.
+//   * Otherwise the workgroup ESCALATES: it loads A_{b-k} .. A_{b+k-1} into LDS and runs the 2k - 1 levels on its cone
+//     itself, one window fewer per level, down to S_b (leaving out the merges that find their halves in order).  That
+//     is, element for element, what k global launches compute for these positions (positions in front of the order are
+//     padded with 0, behind its end with ~0, as there).
+// Either way every position receives exactly what k global rounds would have left there: the order, the edges and so
+// the verdict of resort_verify are those of k launches, at the price of one, and only the workgroups near a boundary
+// that is out of order pay for more than one merge.  (At k = 2 the test is the workgroup's own two boundaries.  From
+// k = 3 on those two alone would not do: a surfel can reach S_b through a neighbour whose FAR boundary was the one out
+// of order.)  Whatever a workgroup writes, resort_verify stays sound: every window written is strictly increasing and made
+// of pairs of `comp`, so strictly increasing edges mean N distinct pairs in increasing order — the exact order.
+// The decision is taken by wave 0 alone and published through LDS behind a barrier: the network has barriers, so
+// every thread of the workgroup must branch the same way.
+// Dynamic LDS: 2k windows of 8 KB for the cone (16 KB .. 64 KB); the one-round kernel (!ESC) asks for none.
+template <bool DIRECT, bool ESC>
 __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, const uint64_t *__restrict__ comp,
                                                                       uint32_t *__restrict__ order,
                                                                       uint64_t *__restrict__ edges,
                                                                       const uint32_t *__restrict__ tiles,
                                                                       uint32_t *__restrict__ block_sums, int GX,
                                                                       const uint2 *__restrict__ erec_box, DirectBin db,
-                                                                      uint64_t *comp_out)
+                                                                      int rounds)
 {
     // DIRECT: instead of level 1 of the scan, step 1 of the direct binning (above): the window is a chunk
     static_assert(kResortWindow == 1024 && kResortThreads == 512, "a 256-block of positions = two waves of pairs");
@@ -731,7 +749,7 @@ __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, con
     __shared__ uint32_t s_hist[DIRECT ? kDirectMaxBins : 1];
     __shared__ int s_diff[DIRECT ? kDirectMaxBins + 64 : 1];      // per tile row GX + 1 difference counts (count_rect_rows_diff)
     __shared__ int s_wide;
-    __shared__ uint64_t s_win[PRE ? 2 * kResortWindow : 1];
+    __shared__ int s_escalate;
     const bool use_diff = DIRECT && GX % 64 == 0 && db.bins % GX == 0 && db.bins / GX <= 64;
     if (DIRECT) {
         for (int d = threadIdx.x; d < db.bins; d += kResortThreads) s_hist[d] = 0u;   // (the network's barriers come before its use)
@@ -739,46 +757,65 @@ __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, con
         if (threadIdx.x == 0) s_wide = 0;
     }
     const int base = blockIdx.x * kResortWindow - kResortWindow / 2, o0 = 2 * (int)threadIdx.x;
-    uint64_t e[2];
-    if (PRE) {
-        uint64_t f[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int abase = ((int)blockIdx.x - 1 + a) * kResortWindow;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int pos = abase + bitonic_src(o0 + q);
-                const uint64_t c = comp[min(max(pos, 0), N - 1)];
-                f[a][q] = pos < 0 ? 0ull : (pos < N ? c : ~0ull);
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            bitonic_pairs<kResortWindow>(f[a][0], f[a][1], s_pairs);
-            s_win[a * kResortWindow + o0] = f[a][0];
-            s_win[a * kResortWindow + o0 + 1] = f[a][1];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int o = bitonic_src(o0 + q);        // position inside this (shifted) window
-            e[q] = o < kResortWindow / 2 ? s_win[kResortWindow / 2 + o] : s_win[kResortWindow + o - kResortWindow / 2];
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int pos = base + bitonic_src(o0 + q);
-            const uint64_t c = comp[min(max(pos, 0), N - 1)];
-            e[q] = pos < 0 ? 0ull : (pos < N ? c : ~0ull);
+    // element at position pos of the window-sorted pairs, padded on both sides of the order
+    auto pair_at = [&](int pos) -> uint64_t {
+        const uint64_t c = comp[min(max(pos, 0), N - 1)];
+        return pos < 0 ? 0ull : (pos < N ? c : ~0ull);
+    };
+    bool out_of_order = false;
+    if (ESC && (int)threadIdx.x < 2 * rounds - 2) {
+        // boundary j at position m: in order by definition where one side holds padding only
+        const int j = (int)blockIdx.x - (rounds - 1) + (int)threadIdx.x, m = j * kResortWindow + kResortWindow / 2;
+        if (m > 0 && m < N) {
+            const uint64_t l0 = pair_at(m - kResortWindow / 2 - 1), l1 = pair_at(m - 1);          // A_{j-1}[1023], A_j[511]
+            const uint64_t r0 = pair_at(m), r1 = pair_at(m + kResortWindow / 2);                  // A_j[512], A_{j+1}[0]
+            out_of_order = !(max(l0, l1) < min(r0, r1));
         }
     }
-    bitonic_pairs<kResortWindow>(e[0], e[1], s_pairs);
-    if (comp_out) {
+    uint64_t e[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int pos = base + o0 + q;
-            if (pos >= 0 && pos < N) comp_out[pos] = e[q];
+    for (int q = 0; q < 2; ++q) e[q] = pair_at(base + bitonic_src(o0 + q));
+    bool escalate = false;
+    if (ESC) {
+        if (threadIdx.x < 64) {
+            const bool any = __ballot(out_of_order) != 0ull;
+            if (threadIdx.x == 0) s_escalate = any ? 1 : 0;
         }
+        __syncthreads();
+        escalate = s_escalate != 0;            // (workgroup-uniform: one word, read behind the barrier)
+    }
+    if (ESC && escalate) {
+        extern __shared__ __attribute__((aligned(16))) uint64_t s_cone[];      // A_{b-k} .. A_{b+k-1}
+        const int nwin = 2 * rounds, cone0 = ((int)blockIdx.x - rounds) * kResortWindow;
+        for (int i = threadIdx.x; i < nwin * kResortWindow; i += kResortThreads) s_cone[i] = pair_at(cone0 + i);
+        __syncthreads();
+        // Every half window of the cone is sorted at all times (a merge leaves two sorted halves), so a merge is the
+        // identity exactly where the last pair of its first half does not lie above the first of its second: away from
+        // the boundaries that are out of order that is every merge behind level 1, and it is skipped.  The two words are
+        // read from LDS behind a barrier and made scalars: the same decision in every thread.
+        const auto word = [&](int i) -> uint64_t {
+            const uint64_t v = s_cone[i];
+            return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)v);
+        };
+        for (int level = 1; level < nwin; ++level) {
+            // odd levels merge the shifted windows, even levels the aligned ones; each level one window fewer on either end
+            const bool shifted = (level & 1) != 0;
+            const int first = level >> 1, last = nwin - 1 - first - (shifted ? 1 : 0);
+            for (int w = first; w <= last; ++w) {
+                const int off = w * kResortWindow + (shifted ? kResortWindow / 2 : 0);
+                if (word(off + kResortWindow / 2 - 1) <= word(off + kResortWindow / 2)) continue;      // (equal: padding)
+                uint64_t f0 = s_cone[off + bitonic_src(o0)], f1 = s_cone[off + bitonic_src(o0 + 1)];
+                bitonic_pairs<kResortWindow>(f0, f1, s_pairs);      // (its barriers separate these reads from the writes below)
+                s_cone[off + o0] = f0;
+                s_cone[off + o0 + 1] = f1;
+                __syncthreads();
+            }
+        }
+        // the workgroup's own window after k rounds, as the network would have left it in the registers
+        e[0] = s_cone[rounds * kResortWindow - kResortWindow / 2 + o0];
+        e[1] = s_cone[rounds * kResortWindow - kResortWindow / 2 + o0 + 1];
+    } else {
+        bitonic_pairs<kResortWindow>(e[0], e[1], s_pairs);
     }
     uint32_t v = 0;
     if (DIRECT) {
@@ -1483,7 +1520,7 @@ static int bits_for(uint32_t max_value)
 size_t order_scratch_bytes(int N)
 {
     const size_t n = (size_t)(N > 0 ? N : 1);
-    // (+ the repair's second pair buffer behind its window edges inside the sort's scratch: 8 n + 16 (n / 1024 + 3) bytes)
+    // (the repair's window edges live inside the sort's scratch: 16 (n / 1024 + 3) bytes)
     return sizeof(uint32_t) * (3 * n + (n + 255) / 256 + 64) + sort_scratch_bytes(n) + 16 + n / 32 + 128;
 }
 
@@ -1546,29 +1583,31 @@ int launch_depth_order_scan(const DepthOrderScan &a, hipStream_t st, ScanHandoff
         }
         const DirectBin no_db = { nullptr, nullptr, nullptr, 0, 0, 0 };
         const bool count_here = direct != nullptr && handoff != nullptr;
-        // the pairs of the rounds that follow ping-pong between comp and a second buffer behind the edges
-        uint64_t *comp2 = edges + 2 * (size_t)nB + 2;
-        // (the LAST merge counts: after it the order is final; every earlier one hands its merged pairs on)
-#define SLS_MERGE(PRE_, last_, in_, out_)                                                                                    \
-        do {                                                                                                                 \
-            if (count_here && (last_))                                                                                       \
-                hipLaunchKernelGGL((resort_merge_kernel<true, PRE_>), dim3(nB), dim3(kResortThreads), 0, st, N,               \
-                                   (const uint64_t *)(in_), order, edges, a.tiles, block_sums, a.GX, (const uint2 *)a.erec_box,      \
-                                   *direct, (uint64_t *)(out_));                                                              \
-            else                                                                                                             \
-                hipLaunchKernelGGL((resort_merge_kernel<false, PRE_>), dim3(nB), dim3(kResortThreads), 0, st, N,              \
-                                   (const uint64_t *)(in_), order, edges, a.tiles, block_sums, a.GX, (const uint2 *)a.erec_box,      \
-                                   no_db, (uint64_t *)(out_));                                                                \
-        } while (0)
-        SLS_MERGE(false, reuse_order <= 1, comp, reuse_order > 1 ? comp : nullptr);
-        SLS_LAUNCH_CHECK("resort_merge_kernel");
-        uint64_t *cin = comp, *cout = comp2;
-        for (int round = 1; round < reuse_order; ++round) {   // (reuse_order = 2: one more round, twice the reach)
-            const bool last = round + 1 == reuse_order;
-            SLS_MERGE(true, last, cin, last ? nullptr : cout);
-            SLS_LAUNCH_CHECK("resort_merge_kernel (further round)");
-            uint64_t *t = cin; cin = cout; cout = t;
+        // ONE merge launch whatever the number of rounds: beyond one round a workgroup runs the further rounds on its own
+        // neighbourhood, and only where a window boundary near it is out of order (resort_merge_kernel, ESC); its LDS
+        // grows with the rounds, so a one-round repair keeps the kernel without any
+        const int rounds = reuse_order;
+        if (rounds > 4) {
+            set_error("depth-order repair: at most 4 rounds (%d)", rounds);
+            return SLS_E_ARG;
         }
+        const size_t cone_bytes = rounds > 1 ? (size_t)2 * rounds * kResortWindow * sizeof(uint64_t) : 0;
+        static bool lds_allowed = false;
+        if (rounds > 1 && !lds_allowed) {       // (beyond the default limit at four rounds: 64 KB + the kernel's own)
+            const int most = 2 * 4 * kResortWindow * (int)sizeof(uint64_t);
+            SLS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(resort_merge_kernel<true, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, most));
+            SLS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(resort_merge_kernel<false, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, most));
+            lds_allowed = true;
+        }
+#define SLS_MERGE(DIRECT_, ESC_, db_)                                                                                        \
+        hipLaunchKernelGGL((resort_merge_kernel<DIRECT_, ESC_>), dim3(nB), dim3(kResortThreads), cone_bytes, st, N,          \
+                           (const uint64_t *)comp, order, edges, a.tiles, block_sums, a.GX, (const uint2 *)a.erec_box, db_,  \
+                           rounds)
+        if (count_here) { if (rounds > 1) SLS_MERGE(true, true, *direct); else SLS_MERGE(true, false, *direct); }
+        else { if (rounds > 1) SLS_MERGE(false, true, no_db); else SLS_MERGE(false, false, no_db); }
+        SLS_LAUNCH_CHECK("resort_merge_kernel");
 #undef SLS_MERGE
         if (count_here) {
             if (direct->nchunks != nB || direct->pos0 != -kResortWindow / 2) {

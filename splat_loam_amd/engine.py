@@ -295,7 +295,8 @@ class MappingEngine:
         how many positions a surfel travels for the same change of depth grows with the number of surfels: measured
         at 500 k surfels (4 / 12 / 48; looser values fail repairs, each costs a void iteration + a rebuild) and at
         170 k / 50 k (12 / 32 / 200 without a failure, -1.5 % / -2.5 % per iteration with the mapper's keyframe
-        sampling), hence the scale with 500 k / N, capped at 3.  A further repair round costs 9 us, the radix sort 90.
+        sampling), hence the scale with 500 k / N, capped at 3.  Further repair rounds run inside the one merge launch, where a window needs
+        them: under 1 us where it turns out that none does, 8-20 us where many do; the radix sort costs 90.
         (The four ages are plain attributes; what other values cost is in HISTORY.md #44, #50, #51.)"""
         scale = min(max(500000.0 / max(self.N, 1), 1.0), 3.0)
         self.max_order_age = int(4 * scale)
@@ -322,7 +323,7 @@ class MappingEngine:
                 torch.empty((self.N,), dtype=torch.int32, device=self.dev), camera,
                 torch.zeros((int(_abi.lib().sls_block_order_bytes(H, W)) // 4,), dtype=torch.int32, device=self.dev))
         # after a failed repair the following iterations repair with one more round (one more window of reach,
-        # +16 us); every `repair_span` iterations without a failure the number of rounds steps down again
+        # still one launch: HISTORY.md #83); every `repair_span` iterations without a failure the number of rounds steps down again
         if self._repair_rounds > 1 and self._enq >= self._repair_until:
             self._repair_rounds -= 1
             self._repair_until = self._enq + self.repair_span
