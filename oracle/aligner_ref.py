@@ -7,6 +7,12 @@ imported by the product).
 (slam/tracker.py:141-197).  The algorithm restated here is this repository's own
 specification; the functional tests (a known motion between two
 synthetic scans is recovered) anchor it, the GPU tests compare the HIP kernels with it.
+
+`normals` and `linearize` also run in float32 in the kernel's order of operations (dtype=np.float32): how far
+that restatement lies from float64 is the bar the kernel is held to.  `linearize(details=True)` reports every
+query pixel's decisions, `harden` uses them to give up the pixels near a threshold, so that what is left is
+associated identically in float32 and float64.  tests/aligner_autograd_ref.py holds the formulas below against
+an autograd formulation that shares none of them.
 """
 from __future__ import annotations
 
@@ -36,8 +42,11 @@ def cam_of(K, H, W):
     return dict(H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, wrap=wrap)
 
 
-def normals(cam, depth, points, depth_min):
-    """depth (H,W), points (H,W,3) -> normals (H,W,3); follows aligner_normals_kernel."""
+def normals(cam, depth, points, depth_min, dtype=np.float64):
+    """depth (H,W), points (H,W,3) -> normals (H,W,3); follows aligner_normals_kernel.
+    dtype=np.float32: every operation in float32 in the kernel's order (`_normals_in`)."""
+    if np.dtype(dtype) != np.float64:
+        return _normals_in(np.dtype(dtype).type, cam, depth, points, depth_min)
     H, W = cam["H"], cam["W"]
     d = np.asarray(depth, np.float64).reshape(H, W)
     p = np.asarray(points, np.float64).reshape(H, W, 3)
@@ -59,13 +68,76 @@ def normals(cam, depth, points, depth_min):
     return n
 
 
+def _normals_in(f, cam, depth, points, depth_min):
+    """The kernel's arithmetic operation by operation in the type `f` (the cross product by components, the
+    square root, ONE reciprocal and three products, the sign from the dot product with the point)."""
+    H, W = cam["H"], cam["W"]
+    d = np.asarray(depth, f).reshape(H, W)
+    p = np.asarray(points, f).reshape(H, W, 3)
+    ok = d > f(depth_min)
+    good = ok & np.roll(ok, -1, 0) & np.roll(ok, 1, 0) & np.roll(ok, -1, 1) & np.roll(ok, 1, 1)
+    good[0] = good[-1] = False
+    if not cam["wrap"]:
+        good[:, 0] = good[:, -1] = False
+    uu = np.roll(p, -1, 0) - np.roll(p, 1, 0)               # row r+1 minus row r-1
+    vv = np.roll(p, -1, 1) - np.roll(p, 1, 1)               # column c+1 minus column c-1
+    u0, u1, u2 = uu[..., 0], uu[..., 1], uu[..., 2]
+    v0, v1, v2 = vv[..., 0], vv[..., 1], vv[..., 2]
+    c0, c1, c2 = u1 * v2 - u2 * v1, u2 * v0 - u0 * v2, u0 * v1 - u1 * v0
+    ln = np.sqrt(c0 * c0 + c1 * c1 + c2 * c2)
+    good &= ln > f(1e-12)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = f(1.0) / ln
+        c0, c1, c2 = c0 * inv, c1 * inv, c2 * inv
+        s = np.where(c0 * p[..., 0] + c1 * p[..., 1] + c2 * p[..., 2] > f(0.0), f(-1.0), f(1.0))
+        n = np.stack([s * c0, s * c1, s * c2], -1)
+    n[~good] = 0
+    assert n.dtype == np.dtype(f)
+    return n
+
+
 def _huber(e, delta):
     a = np.abs(e)
     return np.where(a <= delta, 1.0, delta / np.maximum(a, 1e-300))
 
 
-def linearize(cam, prm: Params, ref_depth, ref_points, ref_normals, q_depth, q_points, T):
-    """Returns sys (30,): H upper triangle (21) | b (6) | chi2 | inliers | valid query pixels."""
+def _range_gradient(cam, depth_min, rdi, rr, cc):
+    """Central differences of the reference range image at (rr, cc): zero at a border (columns wrap on a
+    wrapping camera) and beside a depth <= depth_min.  Works in rdi's type."""
+    H, W = cam["H"], cam["W"]
+    cl, cr = cc - 1, cc + 1
+    if cam["wrap"]:
+        cl, cr = np.mod(cl, W), np.mod(cr, W)
+    inb = (cl >= 0) & (cr < W)
+    a, b = rdi[rr, np.clip(cl, 0, W - 1)], rdi[rr, np.clip(cr, 0, W - 1)]
+    gu = np.where(inb & (a > depth_min) & (b > depth_min), 0.5 * (b - a), 0.0)
+    inr = (rr > 0) & (rr < H - 1)
+    a, b = rdi[np.clip(rr - 1, 0, H - 1), cc], rdi[np.clip(rr + 1, 0, H - 1), cc]
+    gv = np.where(inr & (a > depth_min) & (b > depth_min), 0.5 * (b - a), 0.0)
+    return gu, gv
+
+
+def _spread(ok, values, fill=0.0):
+    out = np.full(ok.shape, fill, dtype=np.float64)
+    out[ok] = values
+    return out
+
+
+def linearize(cam, prm: Params, ref_depth, ref_points, ref_normals, q_depth, q_points, T, details=False,
+              dtype=np.float64):
+    """Returns sys (30,): H upper triangle (21) | b (6) | chi2 | inliers | valid query pixels.
+
+    details=True: returns (sys, det); det holds one entry per query pixel (float64 / int64 / bool arrays of
+    length H*W): `valid`, `ok` (inlier), `j` (target index, -1 where the projection left the image), `col` and
+    `row` (floor(u+1), floor(v+1) BEFORE wrapping), `u`, `v`, `rho`, `rxy`, `dr` (target depth), `has_n`,
+    `dist2`, `cosang` (NaN where j is -1), and for the inliers `e_g`, `e_r`, `gu`, `gv` (0 elsewhere; the last
+    three are given with range_weight == 0 too, where they do not enter the system); and `S_b` (6,), the sum of
+    |w J_ik e_i| over both terms: the scale of b, which is a cancelling sum.
+    dtype=np.float32: every per-pixel operation in float32 in the kernel's order, sums in float64
+    (`_linearize_in`); the default is the float64 arithmetic below."""
+    if np.dtype(dtype) != np.float64:
+        return _linearize_in(np.dtype(dtype).type, cam, prm, ref_depth, ref_points, ref_normals, q_depth, q_points,
+                             T, details)
     H, W = cam["H"], cam["W"]
     rd = np.asarray(ref_depth, np.float64).reshape(-1)
     rp = np.asarray(ref_points, np.float64).reshape(-1, 3)
@@ -84,55 +156,171 @@ def linearize(cam, prm: Params, ref_depth, ref_points, ref_normals, q_depth, q_p
     u, v = cam["fx"] * az + cam["cx"], cam["fy"] * el + cam["cy"]
     c = np.floor(u + 1.0).astype(np.int64)
     r = np.floor(v + 1.0).astype(np.int64)
+    col = c
     if cam["wrap"]:
         c = np.mod(c, W)
-    ok &= (c >= 0) & (c < W) & (r >= 0) & (r < H)
+    in_image = (c >= 0) & (c < W) & (r >= 0) & (r < H)
+    ok &= in_image
     j = np.where(ok, r * W + c, 0)
     dr = rd[j]
     n = rn[j]
-    ok &= (dr > prm.depth_min) & (dr <= prm.depth_max) & (np.abs(n).sum(1) > 0)
+    has_n = np.abs(n).sum(1) > 0
+    ok &= (dr > prm.depth_min) & (dr <= prm.depth_max) & has_n
     diff = p - rp[j]
     cosang = -(n * p).sum(1) / np.maximum(rho, 1e-300)
-    ok &= ((diff * diff).sum(1) <= prm.max_distance ** 2) & (cosang >= prm.min_cos_angle)
+    dist2 = (diff * diff).sum(1)
+    ok &= (dist2 <= prm.max_distance ** 2) & (cosang >= prm.min_cos_angle)
     sys = np.zeros(30)
     sys[29] = valid.sum()
     sys[28] = ok.sum()
+    det = None
+    if details:
+        seen = valid & (rho > prm.depth_min) & (rxy > 1e-6) & in_image       # the pixels whose j was looked up
+        nan = np.where(seen, 0.0, np.nan)
+        det = dict(valid=valid, ok=ok.copy(), j=np.where(seen, j, -1), col=col, row=r, u=u, v=v, rho=rho, rxy=rxy,
+                   dr=np.where(seen, dr, 0.0), has_n=seen & has_n, dist2=dist2 + nan, cosang=cosang + nan)
+        for k in ("e_g", "e_r", "gu", "gv"):
+            det[k] = np.zeros(ok.shape)
+        det["S_b"] = np.zeros(6)
     if not ok.any():
-        return sys
+        return (sys, det) if details else sys
 
     def add(J, e, w):
         Hm = (J * w[:, None]).T @ J
         sys[:21] += Hm[np.triu_indices(6)]
         sys[21:27] += (J * (w * e)[:, None]).sum(0)
         sys[27] += (w * e * e).sum()
+        if details:
+            det["S_b"] += np.abs(J * (w * e)[:, None]).sum(0)
 
     p_, n_, diff_ = p[ok], n[ok], diff[ok]
     e = (n_ * diff_).sum(1)
     J = np.concatenate([n_, np.cross(p_, n_)], 1)
     add(J, e, _huber(e, prm.huber_delta))
-    if prm.range_weight > 0.0:
+    if details:
+        det["e_g"] = _spread(ok, e)
+    if prm.range_weight > 0.0 or details:
         rdi = rd.reshape(H, W)
-        rr, cc = r[ok], c[ok]
-        cl, cr = cc - 1, cc + 1
-        if cam["wrap"]:
-            cl, cr = np.mod(cl, W), np.mod(cr, W)
-        inb = (cl >= 0) & (cr < W)
-        a, b = rdi[rr, np.clip(cl, 0, W - 1)], rdi[rr, np.clip(cr, 0, W - 1)]
-        gu = np.where(inb & (a > prm.depth_min) & (b > prm.depth_min), 0.5 * (b - a), 0.0)
-        inr = (rr > 0) & (rr < H - 1)
-        a, b = rdi[np.clip(rr - 1, 0, H - 1), cc], rdi[np.clip(rr + 1, 0, H - 1), cc]
-        gv = np.where(inr & (a > prm.depth_min) & (b > prm.depth_min), 0.5 * (b - a), 0.0)
+        gu, gv = _range_gradient(cam, prm.depth_min, rdi, r[ok], c[ok])
+        rhoo = np.sqrt(rho2[ok])
+        er = rhoo - dr[ok]
+        if details:
+            det["e_r"], det["gu"], det["gv"] = _spread(ok, er), _spread(ok, gu), _spread(ok, gv)
+    if prm.range_weight > 0.0:
         xo, yo, zo = p_[:, 0], p_[:, 1], p_[:, 2]
         rxy2o, rho2o = rxy2[ok], rho2[ok]
-        rxyo, rhoo = np.sqrt(rxy2o), np.sqrt(rho2o)
-        er = rhoo - dr[ok]
+        rxyo = np.sqrt(rxy2o)
         iu, iv = cam["fx"] / rxy2o, cam["fy"] / (rxyo * rho2o)
         g = np.stack([xo / rhoo - gu * (-yo * iu) - gv * (-xo * zo * iv),
                       yo / rhoo - gu * (xo * iu) - gv * (-yo * zo * iv),
                       zo / rhoo - gv * (rxy2o * iv)], 1)
         Jr = np.concatenate([g, np.cross(p_, g)], 1)
         add(Jr, er, prm.range_weight * _huber(er, prm.range_huber))
-    return sys
+    return (sys, det) if details else sys
+
+
+def _linearize_in(f, cam, prm, ref_depth, ref_points, ref_normals, q_depth, q_points, T, details):
+    """aligner_linearize_kernel operation by operation in the type `f`: the pose applied as three dot products,
+    1/rho then a product, the gates on f-typed parameters, Huber, w*J[a]*J[b], the two terms of a pixel added in
+    `f` as the thread's accumulator adds them; the sum over the pixels in float64 (the kernel's block reduction)."""
+    H, W = cam["H"], cam["W"]
+    rd = np.asarray(ref_depth, f).reshape(-1)
+    rp = np.asarray(ref_points, f).reshape(-1, 3)
+    rn = np.asarray(ref_normals, f).reshape(-1, 3)
+    qd = np.asarray(q_depth, f).reshape(-1)
+    qp = np.asarray(q_points, f).reshape(-1, 3)
+    Tf = np.asarray(T, f)
+    fx, fy, cx, cy = f(cam["fx"]), f(cam["fy"]), f(cam["cx"]), f(cam["cy"])
+    depth_min, depth_max = f(prm.depth_min), f(prm.depth_max)
+    one = f(1.0)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        valid = (qd > depth_min) & (qd <= depth_max)
+        px, py, pz = qp[:, 0], qp[:, 1], qp[:, 2]
+        x = Tf[0, 0] * px + Tf[0, 1] * py + Tf[0, 2] * pz + Tf[0, 3]
+        y = Tf[1, 0] * px + Tf[1, 1] * py + Tf[1, 2] * pz + Tf[1, 3]
+        z = Tf[2, 0] * px + Tf[2, 1] * py + Tf[2, 2] * pz + Tf[2, 3]
+        rxy2 = x * x + y * y
+        rho2 = rxy2 + z * z
+        rxy, rho = np.sqrt(rxy2), np.sqrt(rho2)
+        ok = valid & (rho > depth_min) & (rxy > f(1e-6))
+        az, el = np.arctan2(y, x), np.arctan2(z, rxy)
+        u, v = fx * az + cx, fy * el + cy
+        col = np.floor(u + one).astype(np.int64)
+        r = np.floor(v + one).astype(np.int64)
+        c = np.mod(col, W) if cam["wrap"] else col
+        in_image = (c >= 0) & (c < W) & (r >= 0) & (r < H)
+        ok &= in_image
+        seen = ok.copy()
+        j = np.where(ok, r * W + c, 0)
+        dr = rd[j]
+        n0, n1, n2 = rn[j, 0], rn[j, 1], rn[j, 2]
+        has_n = (n0 != 0) | (n1 != 0) | (n2 != 0)
+        ok &= (dr > depth_min) & (dr <= depth_max) & has_n
+        d0, d1, d2 = x - rp[j, 0], y - rp[j, 1], z - rp[j, 2]
+        dist2 = d0 * d0 + d1 * d1 + d2 * d2
+        inv_rho = one / rho
+        cosang = -(n0 * x + n1 * y + n2 * z) * inv_rho
+        ok &= (dist2 <= f(prm.max_distance) * f(prm.max_distance)) & (cosang >= f(prm.min_cos_angle))
+
+        def terms(J, e, w):
+            cols = [w * J[a] * J[b] for a in range(6) for b in range(a, 6)]
+            cols += [w * J[a] * e for a in range(6)]
+            cols.append(w * e * e)
+            return np.stack(cols, 1)
+
+        def huber(e, delta):
+            a = np.abs(e)
+            return np.where(a <= delta, one, delta / a)
+
+        e = n0 * d0 + n1 * d1 + n2 * d2
+        J = [n0, n1, n2, y * n2 - z * n1, z * n0 - x * n2, x * n1 - y * n0]
+        acc = terms(J, e, huber(e, f(prm.huber_delta)))
+        S = np.abs(acc[:, 21:27])
+        rdi = rd.reshape(H, W)
+        gu, gv = _range_gradient(cam, depth_min, rdi, np.clip(r, 0, H - 1), np.clip(c, 0, W - 1))
+        gu, gv = gu.astype(f), gv.astype(f)
+        er = rho - dr
+        if f(prm.range_weight) > 0:
+            wr = f(prm.range_weight) * huber(er, f(prm.range_huber))
+            iu, iv = fx / rxy2, fy / (rxy * rho2)
+            g0 = x * inv_rho - gu * (-y * iu) - gv * (-x * z * iv)
+            g1 = y * inv_rho - gu * (x * iu) - gv * (-y * z * iv)
+            g2 = z * inv_rho - gv * (rxy2 * iv)
+            Jr = [g0, g1, g2, y * g2 - z * g1, z * g0 - x * g2, x * g1 - y * g0]
+            acc_r = terms(Jr, er, wr)
+            S = S + np.abs(acc_r[:, 21:27])
+            acc = acc + acc_r
+    assert acc.dtype == np.dtype(f) and gu.dtype == np.dtype(f)
+    sys = np.zeros(30)
+    sys[:28] = acc[ok].astype(np.float64).sum(0)
+    sys[28], sys[29] = ok.sum(), valid.sum()
+    if not details:
+        return sys
+    g64 = lambda a, m: np.where(m, a.astype(np.float64), 0.0)
+    nan = np.where(seen, 0.0, np.nan)
+    det = dict(valid=valid, ok=ok, j=np.where(seen, j, -1), col=col, row=r, u=u.astype(np.float64),
+               v=v.astype(np.float64), rho=rho.astype(np.float64), rxy=rxy.astype(np.float64), dr=g64(dr, seen),
+               has_n=seen & has_n, dist2=dist2 + nan, cosang=cosang + nan, e_g=g64(e, ok), e_r=g64(er, ok),
+               gu=g64(gu, ok), gv=g64(gv, ok))
+    det["S_b"] = S[ok].astype(np.float64).sum(0)
+    return sys, det
+
+
+def harden(cam, prm: Params, ref_depth, ref_points, ref_normals, q_depth, q_points, T, px=0.02, rel=1e-3):
+    """-> (copy of q_depth, share of the valid query pixels removed).  The copy holds 0 at every valid query
+    pixel one of whose discrete decisions lies near its threshold in float64: u+1 or v+1 within `px` of an
+    integer, dist2 within 2*rel (relative) of max_distance^2, cosang within `rel` of min_cos_angle, rho within
+    `rel` of depth_min.  On what is left, float32 arithmetic takes every decision as float64 does."""
+    _, d = linearize(cam, prm, ref_depth, ref_points, ref_normals, q_depth, q_points, T, details=True)
+    near = lambda a: np.abs(a - np.round(a)) < px
+    md2 = prm.max_distance ** 2
+    with np.errstate(invalid="ignore"):
+        bad = near(d["u"] + 1.0) | near(d["v"] + 1.0) | (np.abs(d["rho"] - prm.depth_min) < rel)
+        bad |= (np.abs(d["dist2"] - md2) < 2.0 * rel * md2) | (np.abs(d["cosang"] - prm.min_cos_angle) < rel)
+    bad &= d["valid"]
+    out = np.array(q_depth, copy=True)
+    out.reshape(-1)[bad] = 0
+    return out, float(bad.sum()) / max(int(d["valid"].sum()), 1)
 
 
 def se3_exp(xi):
