@@ -770,6 +770,60 @@ int sls_mesh_sample(int V, const float *vertices, int F, const int32_t *faces, c
                     uint64_t seed, float *out_xyz, int32_t *out_face, uint32_t *out_status, void *scratch,
                     size_t scratch_bytes, void *stream);
 
+/* ---- a sparse TSDF volume: from rendered keyframes to a triangle mesh ------------------------------------------------
+ * include/sls_tsdf_math.h states every rule; DESIGN.md section 2, "TSDF volume".  A block is 8 x 8 x 8 voxels of edge
+ * voxel_size; block b (int32 x 3, every |b_a| < 2^20) covers origin + 8 voxel_size [b, b + 1); voxel
+ * l = x | y << 3 | z << 6 of block k lives at slot 512 k + l of the float32 arrays tsdf (normalised, in [-1, 1]) and
+ * weight.  The block list is kept in ascending order of kx | ky << 21 | kz << 42, k_a = b_a + 2^20.  origin3: three
+ * doubles on the HOST.  All three operations require voxel_size and trunc finite and > 0 and
+ * trunc + voxel_size <= 8 voxel_size.
+ *
+ * The blocks a point set names: for each of the M DEVICE points p every block the box [p - m, p + m] touches,
+ * m = trunc + voxel_size (at most three per axis); the unique ones in ascending key order as out_blocks (room for
+ * `capacity` rows of three int32: 27 M always suffices; rows from `capacity` on are not written, out_status[0] still
+ * counts them).
+ *   out_status (DEVICE, 4 words): [B, points with a non-finite coordinate, points with a block index outside
+ *       (-2^20, 2^20), 1]; a counted point names no block.
+ *   scratch: sls_tsdf_blocks_scratch_bytes(M) bytes (0 for M < 1 or M > SLS_TSDF_MAX_POINTS), 256-byte aligned.
+ * Keys, sort, head scan and compaction run in a fixed order (no floating-point atomics, no hash table): the same cloud
+ * gives the same array on every run.  M == 0 succeeds, writes [0, 0, 0, 1] to out_status when that is non-null and
+ * touches nothing else.  Before anything is enqueued: SLS_E_ARG for M < 0 or > SLS_TSDF_MAX_POINTS, a negative capacity,
+ * a null pointer, a bad voxel_size / trunc, misaligned scratch; SLS_E_SCRATCH for too little scratch. */
+#define SLS_TSDF_MAX_POINTS 67108864    /* 2^26: 27 candidate keys per point are sorted under 32-bit positions */
+#define SLS_TSDF_MAX_BLOCKS 524288      /* 2^19: a 2 GB volume; the triangle count stays below 2^32 */
+size_t sls_tsdf_blocks_scratch_bytes(int M);
+int sls_tsdf_blocks(int M, const float *xyz, double voxel_size, double trunc, const double *origin3, int capacity,
+                    int32_t *out_blocks, uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+
+/* One keyframe into the volume: one launch, no scratch, nothing read back.  allmap: the full seven planes of a
+ * rasterizer forward at cam->H x cam->W (planes 0, 1, 5, 6 are read); cam: Rvw / tvw map the VOLUME's frame to the view
+ * frame, fx, fy, cx, cy, wrap and near_cut as the forward had them (pix_offset is not read: the pixel of a voxel is
+ * floor(fx az + cx + 1), floor(fy el + cy + 1), the inverse of the half-pixel back-projection of sls_surface_samples).
+ * Per voxel, nearest pixel: valid iff !(alpha < min_opacity) && !(dist > max_depth_dist);
+ * depth = (1 - depth_ratio) D / alpha + depth_ratio median; sdf = depth - |q|; skipped below -trunc;
+ * tsdf <- (tsdf weight + min(1, sdf / trunc)) / (weight + 1), weight <- weight + 1.  Every voxel is owned by one thread
+ * and keyframes are ordered by the stream: the result is bit-reproducible and equals the header run on the host.
+ * B == 0 succeeds.  SLS_E_ARG before the launch: a null pointer, B < 0 or > SLS_TSDF_MAX_BLOCKS, a camera without
+ * pixels, a NaN threshold or depth_ratio, a bad voxel_size / trunc. */
+int sls_tsdf_integrate(const SlsCamera *cam, int B, const int32_t *blocks, float *tsdf, float *weight, const float *allmap,
+                       double voxel_size, double trunc, const double *origin3, float min_opacity, float max_depth_dist,
+                       float depth_ratio, void *stream);
+
+/* The zero surface as a triangle soup, marching tetrahedra over the Freudenthal split of every cube all of whose eight
+ * corners exist (a corner in an absent +x/+y/+z neighbour block does not) with weight >= min_weight.  Order: ascending
+ * block, ascending cube l, tetrahedron 0..5, triangle 0..1; normals point to the positive (free-space) side.
+ * Two calls.  count: counts[k] = the triangles of block k, prefix[k] = their exclusive prefix (B words each, DEVICE),
+ * out_status (DEVICE, 4 words) = [T, B, 0, 1]; the caller reads T and allocates.  emit: triangles (T x 3 x 3 floats)
+ * with every triangle at its prefixed position (in-workgroup scans, no atomics); T is the count call's total and
+ * nothing is written past it.  B == 0 succeeds (count writes [0, 0, 0, 1]); emit with T == 0 succeeds and launches
+ * nothing.  SLS_E_ARG before a launch: B < 0 or > SLS_TSDF_MAX_BLOCKS, a null pointer, a NaN min_weight, a bad
+ * voxel_size. */
+int sls_tsdf_extract_count(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
+                           uint32_t *counts, uint32_t *prefix, uint32_t *out_status, void *stream);
+int sls_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
+                          double voxel_size, const double *origin3, const uint32_t *prefix, uint32_t T, float *triangles_out,
+                          void *stream);
+
 /* visible[i] = 1 if surfel centre i survives the near cut (radii would be >0
  * unless it is off-image). */
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible,

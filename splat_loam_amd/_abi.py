@@ -167,6 +167,12 @@ _PROTOS = {
     "sls_voxel_downsample": (C.c_int, [C.c_int, _VP, C.c_double, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_mesh_sample_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "sls_mesh_sample": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_uint64, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_tsdf_blocks_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_tsdf_blocks": (C.c_int, [C.c_int, _VP, C.c_double, C.c_double, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_tsdf_integrate": (C.c_int, [C.POINTER(SlsCamera), C.c_int, _VP, _VP, _VP, _VP, C.c_double, C.c_double, _VP,
+                                     C.c_float, C.c_float, C.c_float, _VP]),
+    "sls_tsdf_extract_count": (C.c_int, [C.c_int, _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP]),
+    "sls_tsdf_extract_emit": (C.c_int, [C.c_int, _VP, _VP, _VP, C.c_float, C.c_double, _VP, _VP, C.c_uint32, _VP, _VP]),
     "sls_mark_visible": (C.c_int, [C.POINTER(SlsCamera), C.c_int, _VP, _VP, _VP]),
     "sls_aligner_workspace_bytes": (C.c_size_t, []),
     "sls_aligner_normals": (C.c_int, [C.POINTER(SlsCamera), _VP, _VP, C.c_float, _VP, _VP]),

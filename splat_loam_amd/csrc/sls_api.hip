@@ -518,6 +518,77 @@ int sls_mesh_sample(int V, const float *vertices, int F, const int32_t *faces, c
                               (hipStream_t)stream);
 }
 
+size_t sls_tsdf_blocks_scratch_bytes(int M) { return tsdf_blocks_scratch_bytes(M); }
+
+// voxel_size and trunc finite and > 0, and the margin trunc + voxel_size within one block
+static bool tsdf_grid_ok(double voxel_size, double trunc)
+{
+    return voxel_size > 0.0 && voxel_size <= DBL_MAX && trunc > 0.0 && trunc <= DBL_MAX && trunc + voxel_size <= 8.0 * voxel_size;
+}
+static bool tsdf_origin_ok(const double *o) { return o && fabs(o[0]) <= DBL_MAX && fabs(o[1]) <= DBL_MAX && fabs(o[2]) <= DBL_MAX; }
+
+int sls_tsdf_blocks(int M, const float *xyz, double voxel_size, double trunc, const double *origin3, int capacity,
+                    int32_t *out_blocks, uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(M >= 0 && M <= SLS_TSDF_MAX_POINTS, "M negative or above SLS_TSDF_MAX_POINTS");
+    SLS_REQUIRE(capacity >= 0, "negative capacity");
+    SLS_REQUIRE(tsdf_grid_ok(voxel_size, trunc), "voxel_size and trunc must be finite and > 0 with trunc + voxel_size <= 8 voxel_size");
+    SLS_REQUIRE(tsdf_origin_ok(origin3), "origin3 is null or not finite");
+    if (M == 0) {
+        if (out_status) {
+            SLS_HIP_CHECK(hipMemsetAsync(out_status, 0, 3 * sizeof(uint32_t), (hipStream_t)stream));
+            SLS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(out_status + 3), 1, 1, (hipStream_t)stream));
+        }
+        return SLS_OK;
+    }
+    SLS_REQUIRE(xyz && (out_blocks || capacity == 0) && out_status && scratch, "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < tsdf_blocks_scratch_bytes(M)) {
+        set_error("sls_tsdf_blocks: scratch too small: %zu < %zu", scratch_bytes, tsdf_blocks_scratch_bytes(M));
+        return SLS_E_SCRATCH;
+    }
+    return launch_tsdf_blocks(M, xyz, voxel_size, trunc, origin3, capacity, out_blocks, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_tsdf_integrate(const SlsCamera *cam, int B, const int32_t *blocks, float *tsdf, float *weight, const float *allmap,
+                       double voxel_size, double trunc, const double *origin3, float min_opacity, float max_depth_dist,
+                       float depth_ratio, void *stream)
+{
+    SLS_REQUIRE(cam, "null pointer");
+    SLS_REQUIRE(B >= 0 && B <= SLS_TSDF_MAX_BLOCKS, "B negative or above SLS_TSDF_MAX_BLOCKS");
+    SLS_REQUIRE(cam->H > 0 && cam->W > 0 && (uint64_t)cam->H * (uint64_t)cam->W <= 0x7FFFFFFFull, "bad image size");
+    SLS_REQUIRE(tsdf_grid_ok(voxel_size, trunc), "voxel_size and trunc must be finite and > 0 with trunc + voxel_size <= 8 voxel_size");
+    SLS_REQUIRE(tsdf_origin_ok(origin3), "origin3 is null or not finite");
+    SLS_REQUIRE(min_opacity == min_opacity && max_depth_dist == max_depth_dist && depth_ratio == depth_ratio, "NaN threshold");
+    if (B == 0) return SLS_OK;
+    SLS_REQUIRE(blocks && tsdf && weight && allmap, "null pointer");
+    return launch_tsdf_integrate(*cam, B, blocks, tsdf, weight, allmap, voxel_size, trunc, origin3, min_opacity, max_depth_dist,
+                                 depth_ratio, (hipStream_t)stream);
+}
+
+int sls_tsdf_extract_count(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
+                           uint32_t *counts, uint32_t *prefix, uint32_t *out_status, void *stream)
+{
+    SLS_REQUIRE(B >= 0 && B <= SLS_TSDF_MAX_BLOCKS, "B negative or above SLS_TSDF_MAX_BLOCKS");
+    SLS_REQUIRE(min_weight == min_weight, "NaN min_weight");
+    SLS_REQUIRE(out_status && (B == 0 || (blocks && tsdf && weight && counts && prefix)), "null pointer");
+    return launch_tsdf_extract_count(B, blocks, tsdf, weight, min_weight, counts, prefix, out_status, (hipStream_t)stream);
+}
+
+int sls_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
+                          double voxel_size, const double *origin3, const uint32_t *prefix, uint32_t T, float *triangles_out,
+                          void *stream)
+{
+    SLS_REQUIRE(B >= 0 && B <= SLS_TSDF_MAX_BLOCKS, "B negative or above SLS_TSDF_MAX_BLOCKS");
+    SLS_REQUIRE(min_weight == min_weight, "NaN min_weight");
+    SLS_REQUIRE(voxel_size > 0.0 && voxel_size <= DBL_MAX, "voxel_size is not a finite number > 0");
+    SLS_REQUIRE(tsdf_origin_ok(origin3), "origin3 is null or not finite");
+    if (B == 0 || T == 0u) return SLS_OK;
+    SLS_REQUIRE(blocks && tsdf && weight && prefix && triangles_out, "null pointer");
+    return launch_tsdf_extract_emit(B, blocks, tsdf, weight, min_weight, voxel_size, origin3, prefix, T, triangles_out,
+                                    (hipStream_t)stream);
+}
+
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible, void *stream)
 {
     SLS_REQUIRE(cam && N >= 0, "bad argument");

@@ -25,6 +25,7 @@
 #include <float.h>
 
 #include "sls_launch.hpp"
+#include "sls_scan.hpp"
 #include "../../include/sls_cloud_math.h"
 
 namespace sls {
@@ -50,44 +51,6 @@ __device__ __forceinline__ float cloud_ord2f(uint32_t o)
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
 }
 __device__ __forceinline__ bool cloud_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
-// exclusive scan of one value per thread over the workgroup's 256 threads (one use per kernel); *total: the sum of all
-template <typename T>
-__device__ __forceinline__ T cloud_block_scan(T v, T *s_wave, T *total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    T before = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < kCloudThreads / 64; ++j) {
-        const T t = s_wave[j];
-        before += j < wv ? t : (T)0;
-        tot += t;
-    }
-    *total = tot;
-    return before + incl - v;
-}
-
-// One workgroup: a[0 .. n) <- its exclusive scan, thread t owning ceil(n / 256) consecutive entries; returns the total
-template <typename T>
-__device__ __forceinline__ T cloud_scan_in_place(T *a, int n, T *s_wave)
-{
-    const int P = (n + kCloudThreads - 1) / kCloudThreads;
-    const int i0 = min((int)threadIdx.x * P, n), i1 = min(i0 + P, n);
-    T sum = 0;
-    for (int i = i0; i < i1; ++i) sum += a[i];
-    T total;
-    T run = cloud_block_scan<T>(sum, s_wave, &total);
-    for (int i = i0; i < i1; ++i) { const T v = a[i]; a[i] = run; run += v; }
-    return total;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // voxel down-sampling
@@ -177,7 +140,7 @@ __global__ __launch_bounds__(kCloudThreads) void voxel_heads_kernel(uint32_t M, 
     __shared__ uint32_t s_wave[kCloudThreads / 64];
     const uint32_t p0 = blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer;
     uint32_t total;
-    cloud_block_scan<uint32_t>((uint32_t)__popc(voxel_head_mask(M, keys, p0)), s_wave, &total);
+    block_scan<uint32_t, kCloudThreads>((uint32_t)__popc(voxel_head_mask(M, keys, p0)), s_wave, &total);
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
@@ -186,7 +149,7 @@ __global__ __launch_bounds__(kCloudThreads) void voxel_scan_kernel(uint32_t M, i
                                                                    uint32_t *__restrict__ status)
 {
     __shared__ uint32_t s_wave[kCloudThreads / 64];
-    const uint32_t nv = cloud_scan_in_place<uint32_t>(blk, nblk, s_wave);
+    const uint32_t nv = scan_in_place<uint32_t, kCloudThreads>(blk, blk, nblk, s_wave);
     if (threadIdx.x == 0) {
         hdr[VH_NVOX] = nv;
         seg_start[nv <= M ? nv : M] = M;       // (nv <= M always: a head per position at most)
@@ -202,7 +165,7 @@ __global__ __launch_bounds__(kCloudThreads) void voxel_segments_kernel(uint32_t 
     const uint32_t p0 = blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer;
     const uint32_t mask = voxel_head_mask(M, keys, p0);
     uint32_t total;
-    uint32_t id = blk[blockIdx.x] + cloud_block_scan<uint32_t>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kCloudThreads>((uint32_t)__popc(mask), s_wave, &total);
 #pragma unroll
     for (int j = 0; j < kCloudPer; ++j)
         if ((mask >> j) & 1u) {
@@ -395,7 +358,7 @@ __global__ __launch_bounds__(kCloudThreads) void mesh_weight_sums_kernel(uint32_
     const double amax = __longlong_as_double((long long)hdr[MH_AMAX]);
     unsigned long long w[kCloudPer], total;
     mesh_weights(F, area, amax, blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer, w);
-    cloud_block_scan<unsigned long long>((w[0] + w[1]) + (w[2] + w[3]), s_wave, &total);
+    block_scan<unsigned long long, kCloudThreads>((w[0] + w[1]) + (w[2] + w[3]), s_wave, &total);
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
@@ -404,7 +367,7 @@ __global__ __launch_bounds__(kCloudThreads) void mesh_scan_kernel(int nblk, unsi
                                                                   uint32_t *__restrict__ status)
 {
     __shared__ unsigned long long s_wave[kCloudThreads / 64];
-    const unsigned long long W = cloud_scan_in_place<unsigned long long>(blk, nblk, s_wave);
+    const unsigned long long W = scan_in_place<unsigned long long, kCloudThreads>(blk, blk, nblk, s_wave);
     if (threadIdx.x == 0) {
         hdr[MH_W] = W;
         const unsigned long long nbad = hdr[MH_BAD];
@@ -425,7 +388,7 @@ __global__ __launch_bounds__(kCloudThreads) void mesh_prefix_kernel(uint32_t F, 
     const uint32_t f0 = blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer;
     unsigned long long w[kCloudPer], total;
     mesh_weights(F, area, amax, f0, w);
-    unsigned long long run = blk[blockIdx.x] + cloud_block_scan<unsigned long long>((w[0] + w[1]) + (w[2] + w[3]), s_wave, &total);
+    unsigned long long run = blk[blockIdx.x] + block_scan<unsigned long long, kCloudThreads>((w[0] + w[1]) + (w[2] + w[3]), s_wave, &total);
 #pragma unroll
     for (int j = 0; j < kCloudPer; ++j) {
         run += w[j];

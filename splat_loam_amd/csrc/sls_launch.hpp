@@ -190,6 +190,18 @@ int launch_voxel_downsample(int M, const float *xyz, double voxel_size, float *o
 size_t mesh_sample_scratch_bytes(int V, int F, int n_samples);
 int launch_mesh_sample(int V, const float *vertices, int F, const int32_t *faces, const float *crop_box, int n_samples,
                        uint64_t seed, float *out_xyz, int32_t *out_face, uint32_t *out_status, void *scratch, hipStream_t st);
+// ---- sls_tsdf.hip (the arguments are checked by the caller, sls_api.hip) -------------------------------------------
+size_t tsdf_blocks_scratch_bytes(int M);
+int launch_tsdf_blocks(int M, const float *xyz, double voxel_size, double trunc, const double *origin, int capacity,
+                       int32_t *out_blocks, uint32_t *out_status, void *scratch, hipStream_t st);
+int launch_tsdf_integrate(const SlsCamera &cam, int B, const int32_t *blocks, float *tsdf, float *weight, const float *allmap,
+                          double voxel_size, double trunc, const double *origin, float min_opacity, float max_depth_dist,
+                          float depth_ratio, hipStream_t st);
+int launch_tsdf_extract_count(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
+                              uint32_t *counts, uint32_t *prefix, uint32_t *status, hipStream_t st);
+int launch_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
+                             double voxel_size, const double *origin, const uint32_t *prefix, uint32_t T, float *triangles,
+                             hipStream_t st);
 int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_raw, float smax, float pen,
                           const uint32_t *status_block, uint64_t *bitmap, hipStream_t st);
 int launch_adam(const SlsAdamGroup *groups, int ngroups, double beta1, double beta2, double eps, int64_t step,

@@ -9,6 +9,10 @@ csrc/sls_surface.hip): no boolean gather, no copy to the host, no host read — 
 device array that is read once at the end.  The reference draws with an unseeded `np.random.choice`; here the sample is
 a pure function of (allmap, thresholds, seed, frame id, kf_samples): DESIGN.md section 2, "Surface samples".
 
+`mesh_tsdf` makes a mesh here, without the Poisson solve: the same keyframes fused into a sparse TSDF volume around the
+sampled cloud and the zero surface extracted by marching tetrahedra (splat_loam_amd/tsdf.py; DESIGN.md section 2, "TSDF
+volume").
+
 `mesh_poisson` itself could not be run where this was written (Open3D is not installed there), so the sampling
 semantics are restated from reading postprocessing.py:161-188, not pinned by a reference-generated fixture; what it
 shares with `render()` (the maps, the back-projection) is pinned by goldens G1 / G2.
@@ -147,6 +151,34 @@ def _image_size(graph_dir: Path, image_height, image_width):
     return int(image_height), int(image_width)
 
 
+def _render_keyframes(graph_dir: Path, graph: dict, used: list, poses: list, H: int, W: int, dev):
+    """Yields (i, frame id, camera, the full (7,H,W) allmap) for the keyframes `used` ([(model index, frame id)], as
+    `frames_to_sample` lists them) with `poses[i]` their model_T_frame: renders each with the model it belongs to."""
+    from . import ply_io
+    from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+    from .scene import Camera, SurfelModel
+    frames = {int(fr["id"]): fr for fr in graph["frames"]}
+    zeros = {"d": torch.zeros((1, H, W), dtype=torch.float32, device=dev), "n": torch.zeros((3, H, W), dtype=torch.float32, device=dev),
+             "v": torch.zeros((1, H, W), dtype=torch.uint8, device=dev)}
+    loaded = (None, None)
+    for i, (mi, fid) in enumerate(used):
+        if loaded[0] != mi:                             # the frames of a model are consecutive: one load per model
+            raw = ply_io.load_ply(graph_dir / graph["models"][mi]["filename"])
+            gm = SurfelModel(*(np.array(raw[n]) for n in ("xyz", "scaling", "rotation", "opacity")), device=dev)   # (writable copies)
+            loaded = (mi, (gm.get_xyz.detach(), gm.get_opacity.detach(), gm.get_scaling.detach(), gm.get_rotation.detach()))
+        xyz, opac, scal, rot = loaded[1]
+        fr = frames[fid]
+        if int(fr["model_id"]) != int(graph["models"][mi]["id"]):
+            raise ValueError(f"frame {fid} is listed by model {graph['models'][mi]['id']} but belongs to model {fr['model_id']}")
+        fx, fy, cx, cy = (float(v) for v in fr["projmatrix"])
+        cam = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32), zeros["d"], zeros["n"], zeros["v"],
+                     world_T_lidar=poses[i], data_device=dev)
+        settings = GaussianRasterizationSettings(H, W, 1.0, cam.world_view_transform, cam.projection_matrix, lean_allmap=False)
+        _, allmap = GaussianRasterizer(raster_settings=settings)(means3D=xyz, means2D=xyz, opacities=opac, scales=scal,
+                                                                 rotations=rot)
+        yield i, fid, cam, allmap
+
+
 @torch.no_grad()
 def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int = 5000, min_opacity: float = 0.5,
                    max_depth_dist: float = 0.1, use_median_depth: bool = False, seed=None, device="cuda",
@@ -158,9 +190,7 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
     pixels: (frames used, kf_samples) int32, the selected row-major pixels, -1 in the rows of an empty keyframe, kept:
     which of the frames used contributed rows).  seed=None: torch.initial_seed().  Sample j of frame f depends on
     (seed, f, j) and the render alone — not on kf_interval or the order of processing."""
-    from . import ply_io, traj_io
-    from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
-    from .scene import Camera, SurfelModel
+    from . import traj_io
     path = Path(graph_dir_or_yaml)
     graph_file = path / "graph.yaml" if path.is_dir() else path
     graph_dir = graph_file.parent
@@ -188,24 +218,7 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
     Ms = np.stack([compose_cam_to_world(graph["models"][mi]["world_T_model"], v) for (mi, _), v in zip(used, views)]) \
         if F else np.zeros((0, 12), np.float32)
     Ms_dev = torch.from_numpy(np.ascontiguousarray(Ms)).to(dev)
-    zeros = {"d": torch.zeros((1, H, W), dtype=torch.float32, device=dev), "n": torch.zeros((3, H, W), dtype=torch.float32, device=dev),
-             "v": torch.zeros((1, H, W), dtype=torch.uint8, device=dev)}
-    loaded = (None, None)
-    for i, (mi, fid) in enumerate(used):
-        if loaded[0] != mi:                             # the frames of a model are consecutive: one load per model
-            raw = ply_io.load_ply(graph_dir / graph["models"][mi]["filename"])
-            gm = SurfelModel(*(np.array(raw[n]) for n in ("xyz", "scaling", "rotation", "opacity")), device=dev)   # (writable copies)
-            loaded = (mi, (gm.get_xyz.detach(), gm.get_opacity.detach(), gm.get_scaling.detach(), gm.get_rotation.detach()))
-        xyz, opac, scal, rot = loaded[1]
-        fr = frames[fid]
-        if int(fr["model_id"]) != int(graph["models"][mi]["id"]):
-            raise ValueError(f"frame {fid} is listed by model {graph['models'][mi]['id']} but belongs to model {fr['model_id']}")
-        fx, fy, cx, cy = (float(v) for v in fr["projmatrix"])
-        cam = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32), zeros["d"], zeros["n"], zeros["v"],
-                     world_T_lidar=poses[i], data_device=dev)
-        settings = GaussianRasterizationSettings(H, W, 1.0, cam.world_view_transform, cam.projection_matrix, lean_allmap=False)
-        _, allmap = GaussianRasterizer(raster_settings=settings)(means3D=xyz, means2D=xyz, opacities=opac, scales=scal,
-                                                                 rotations=rot)
+    for i, fid, cam, allmap in _render_keyframes(graph_dir, graph, used, poses, H, W, dev):
         sample_keyframe(allmap, cam, None, kf_samples=k, min_opacity=min_opacity, max_depth_dist=max_depth_dist,
                         use_median_depth=use_median_depth, seed=used_seed, frame_id=fid, cam_to_world=Ms_dev[i],
                         out=(points[i * k:(i + 1) * k], normals[i * k:(i + 1) * k], None if pixels is None else pixels[i],
@@ -220,3 +233,59 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
         return points, normals, {"frame_ids": [fid for _, fid in used], "n_valid": words[:, 0].astype(np.int64), "pixels": pixels,
                                  "kept": kept.copy(), "seed": used_seed}
     return points, normals
+
+
+@torch.no_grad()
+def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_interval: int = -1, kf_samples: int = 5000,
+              min_opacity: float = 0.5, max_depth_dist: float = 0.1, use_median_depth: bool = False, min_weight: float = 1.0,
+              seed=None, device="cuda", details: bool = False, image_height=None, image_width=None):
+    """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
+    frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
+
+    Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
+    its cloud: blocks of 8^3 voxels of edge `voxel_size`, truncation `trunc` (default 4 voxel_size).  Pass 2 renders every
+    keyframe that contributed samples again (the full allmap) and fuses it (`TsdfVolume.integrate`, nearest pixel, weight
+    1 per observation); then the zero surface of the voxels seen at least `min_weight` times is extracted.  Host reads:
+    those of `sample_surface`, one for the number of blocks, one for the number of triangles.  `details=True` adds
+    dict(blocks, volume_bytes, triangles, samples, frame_ids, stage_ms, volume: the TsdfVolume) and synchronises between the stages to time them."""
+    import time
+
+    from . import traj_io, tsdf
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("mesh_tsdf runs on a ROCm device; there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    voxel_size = float(voxel_size)
+    trunc = 4.0 * voxel_size if trunc is None else float(trunc)
+    stage_ms, t0 = {}, time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        if details:
+            torch.cuda.synchronize(dev)
+            stage_ms[name], t0 = (time.perf_counter() - t0) * 1e3, time.perf_counter()
+    points, _, det = sample_surface(graph_dir_or_yaml, kf_interval=kf_interval, kf_samples=kf_samples, min_opacity=min_opacity,
+                                    max_depth_dist=max_depth_dist, use_median_depth=use_median_depth, seed=seed, device=dev,
+                                    details=True, image_height=image_height, image_width=image_width)
+    lap("sample")
+    volume = tsdf.TsdfVolume(tsdf.allocate_blocks(points, voxel_size, trunc), voxel_size, trunc)
+    lap("allocate")
+    path = Path(graph_dir_or_yaml)
+    graph_file = path / "graph.yaml" if path.is_dir() else path
+    graph = traj_io.read_graph(graph_file)
+    H, W = _image_size(graph_file.parent, image_height, image_width)
+    used = [u for u, kept in zip(frames_to_sample(graph, kf_interval), det["kept"]) if kept]
+    frames = {int(fr["id"]): fr for fr in graph["frames"]}
+    poses = [_pose44(frames[fid]["model_T_frame"]) for _, fid in used]
+    for i, fid, cam, allmap in _render_keyframes(graph_file.parent, graph, used, poses, H, W, dev):
+        volume.integrate(allmap, cam, graph["models"][used[i][0]]["world_T_model"], min_opacity=min_opacity,
+                         max_depth_dist=max_depth_dist, depth_ratio=1.0 if use_median_depth else 0.0)
+    lap("integrate")
+    vertices, faces = volume.extract(min_weight=min_weight)
+    lap("extract")
+    if details:
+        return vertices, faces, {"blocks": int(volume.blocks.shape[0]), "volume_bytes": volume.nbytes, "triangles": int(faces.shape[0]),
+                                 "samples": int(points.shape[0]), "frame_ids": [fid for _, fid in used], "stage_ms": stage_ms,
+                                 "volume": volume}
+    return vertices, faces

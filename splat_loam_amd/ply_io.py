@@ -51,6 +51,27 @@ def save_point_cloud(path, points, normals) -> None:
         f.write(data.tobytes())
 
 
+def save_mesh(path, vertices, faces) -> None:
+    """A triangle mesh (`tsdf.TsdfVolume.extract`, `meshing.mesh_tsdf`) as binary little-endian PLY: a `vertex` element
+    with float32 `x y z`, then a `face` element with `list uchar int vertex_indices` — what `load_mesh` reads back bit for
+    bit, and the layout Open3D and MeshLab write for a plain triangle mesh."""
+    def host(a, dt):
+        return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=dt)
+    vertices, faces = host(vertices, np.float32).reshape(-1, 3), host(faces, np.int64).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() > 0x7FFFFFFF):
+        raise ValueError("a vertex index does not fit int32")
+    rec = np.empty(len(faces), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    rec["n"], rec["i"] = 3, faces
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(vertices)
+    header += "".join(f"property float {p}\n" for p in "xyz")
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(faces)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vertices.astype("<f4").tobytes())
+        f.write(rec.tobytes())
+
+
 _KINDS = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1",
           "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "short": "<i2", "int16": "<i2", "ushort": "<u2",
           "uint16": "<u2", "char": "i1", "int8": "i1"}

@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""From a results directory (graph.yaml, models/*.ply, optionally cfg.yaml) to a triangle mesh, on the device: the
+rendered depth of every keyframe fused into a sparse TSDF volume, the zero surface by marching tetrahedra
+(splat_loam_amd.meshing.mesh_tsdf; DESIGN.md section 2, "TSDF volume"):
+
+    python tools/mesh_tsdf.py RESULTS_DIR OUT.ply --voxel 0.1 [--trunc T] [--kf-interval N] [--kf-samples K]
+                              [--min-opacity A] [--max-depth-dist D] [--use-median-depth] [--min-weight W] [--weld]
+                              [--seed S] [--image-height H --image-width W]
+
+OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tools/eval_recon.py` takes as the estimate.
+Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from splat_loam_amd import meshing, ply_io, tsdf
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("results_dir")
+    ap.add_argument("out_ply")
+    ap.add_argument("--voxel", type=float, required=True, help="edge of a voxel in metres")
+    ap.add_argument("--trunc", type=float, default=None, help="truncation distance (default 4 voxels)")
+    ap.add_argument("--kf-interval", type=int, default=-1)
+    ap.add_argument("--kf-samples", type=int, default=5000)
+    ap.add_argument("--min-opacity", type=float, default=0.5)
+    ap.add_argument("--max-depth-dist", type=float, default=0.1)
+    ap.add_argument("--use-median-depth", action="store_true")
+    ap.add_argument("--min-weight", type=float, default=1.0)
+    ap.add_argument("--weld", action="store_true", help="merge bit-equal vertices before writing")
+    ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--image-height", type=int, default=None)
+    ap.add_argument("--image-width", type=int, default=None)
+    ap.add_argument("--device", default="cuda")
+    a = ap.parse_args()
+    vertices, faces, det = meshing.mesh_tsdf(a.results_dir, a.voxel, a.trunc, kf_interval=a.kf_interval, kf_samples=a.kf_samples,
+                                             min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist,
+                                             use_median_depth=a.use_median_depth, min_weight=a.min_weight, seed=a.seed,
+                                             device=a.device, details=True, image_height=a.image_height, image_width=a.image_width)
+    if a.weld:
+        vertices, faces = tsdf.weld_soup(vertices)
+    ply_io.save_mesh(a.out_ply, vertices, faces)
+    print(json.dumps({"blocks": det["blocks"], "volume_bytes": det["volume_bytes"], "triangles": det["triangles"],
+                      "vertices": int(vertices.shape[0]), "keyframes": len(det["frame_ids"]), "samples": det["samples"],
+                      "stage_ms": {k: round(v, 3) for k, v in det["stage_ms"].items()}, "out": a.out_ply}))
+
+
+if __name__ == "__main__":
+    main()
