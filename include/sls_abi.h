@@ -824,6 +824,56 @@ int sls_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const
                           double voxel_size, const double *origin3, const uint32_t *prefix, uint32_t T, float *triangles_out,
                           void *stream);
 
+/* ---- cleaning an extracted mesh: weld, clusters, selection, vertex normals ------------------------------------------
+ * include/sls_mesh_math.h states every rule; DESIGN.md section 2, "Mesh cleaning".  Every pointer is a DEVICE pointer;
+ * every scratch is 256-byte aligned and its size comes from the matching _scratch_bytes (0 for a size below 1 or above
+ * the limits).  A last status word of 1 means "written".  Outputs beyond the written count are left
+ * untouched.  Before anything is enqueued: SLS_E_ARG for a negative size, a size above the limits, a null pointer,
+ * misaligned scratch; SLS_E_SCRATCH for too little scratch.  A size of 0 succeeds and writes only the status words (when
+ * out_status is non-null).  No floating-point atomics anywhere: the same input gives the same bytes on every run.
+ *
+ * SLS_MESH_MAX_TRIANGLES: 3 T + 2, the largest edge / corner id, fits the sorter's u32 value and every row, vertex and
+ * triangle index fits int32. */
+#define SLS_MESH_MAX_TRIANGLES 536870912     /* 2^29 */
+#define SLS_MESH_MAX_VERTICES 1610612736     /* 3 x 2^29 */
+
+/* Weld: soup, n_rows x 3 float32 (n_rows <= 3 SLS_MESH_MAX_TRIANGLES).  Two rows are the same vertex iff their three words
+ * are equal as integers.  out_vertices (room for n_rows rows): the V unique rows in ascending lexicographic order of
+ * (x, y, z) as signed int32; out_index[r] (n_rows int32): the rank of row r; out_status (4 words) = [V, 0, 0, 1]. */
+size_t sls_mesh_weld_scratch_bytes(int n_rows);
+int sls_mesh_weld(int n_rows, const float *soup, float *out_vertices, int32_t *out_index, uint32_t *out_status, void *scratch,
+                  size_t scratch_bytes, void *stream);
+
+/* Clusters: faces, T x 3 int32 over V vertices (0 <= V <= SLS_MESH_MAX_VERTICES).  A triangle with two equal indices or an
+ * index outside [0, V) is degenerate: out_labels[t] = -1.  Non-degenerate triangles that share an undirected edge are
+ * joined; out_labels[t] (T int32) is the cluster of triangle t, clusters numbered in ascending order of their lowest
+ * triangle; out_counts[c] (room for T int32) the triangles of cluster c < C.
+ *   out_status (6 words) = [C, degenerate triangles (both kinds), those of them with an index outside [0, V), edges with
+ *   exactly one triangle, edges with more than two, 1]. */
+size_t sls_mesh_clusters_scratch_bytes(int T);
+int sls_mesh_clusters(int T, const int32_t *faces, int V, int32_t *out_labels, int32_t *out_counts, uint32_t *out_status,
+                      void *scratch, size_t scratch_bytes, void *stream);
+
+/* Selection: labels / counts / cluster_status as sls_mesh_clusters wrote them for these faces (C is read from
+ * cluster_status[0] on the device).  n_min = max(max(min_triangles, 0), the min(keep_clusters, C)-th largest count; 0 for
+ * keep_clusters <= 0); a triangle is kept iff its label is >= 0 and counts[label] >= n_min.  out_faces (room for T rows):
+ * the kept triangles in input order, re-indexed; out_vertices (room for V rows): the vertices they reference, in input
+ * order; out_vmap (V int32, may be null): the new index of every vertex, -1 for one that left.
+ *   out_status (4 words) = [V', T', n_min, 1].  V == 0 or T == 0 writes [0, 0, max(min_triangles, 0), 1] alone. */
+size_t sls_mesh_filter_scratch_bytes(int V, int T);
+int sls_mesh_filter(int V, const float *vertices, int T, const int32_t *faces, const int32_t *labels, const int32_t *counts,
+                    const uint32_t *cluster_status, int keep_clusters, int min_triangles, float *out_vertices,
+                    int32_t *out_faces, int32_t *out_vmap, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                    void *stream);
+
+/* Vertex normals: out_normals[v] (V x 3 float32) = the normalised sum, in ascending triangle index, of
+ * (p1 - p0) x (p2 - p0) over the non-degenerate triangles that reference v; zeros for a vertex without one or with a sum
+ * of zero or non-finite length.  Equals the header run on the host bit for bit.  Nothing is read back; V == 0 succeeds
+ * and writes nothing, T == 0 writes zeros. */
+size_t sls_mesh_vertex_normals_scratch_bytes(int V, int T);
+int sls_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
+                            size_t scratch_bytes, void *stream);
+
 /* visible[i] = 1 if surfel centre i survives the near cut (radii would be >0
  * unless it is off-image). */
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible,

@@ -173,6 +173,14 @@ _PROTOS = {
                                      C.c_float, C.c_float, C.c_float, _VP]),
     "sls_tsdf_extract_count": (C.c_int, [C.c_int, _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP]),
     "sls_tsdf_extract_emit": (C.c_int, [C.c_int, _VP, _VP, _VP, C.c_float, C.c_double, _VP, _VP, C.c_uint32, _VP, _VP]),
+    "sls_mesh_weld_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_mesh_weld": (C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_mesh_clusters_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_mesh_clusters": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_mesh_filter_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_mesh_filter": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_mesh_vertex_normals_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_mesh_vertex_normals": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_mark_visible": (C.c_int, [C.POINTER(SlsCamera), C.c_int, _VP, _VP, _VP]),
     "sls_aligner_workspace_bytes": (C.c_size_t, []),
     "sls_aligner_normals": (C.c_int, [C.POINTER(SlsCamera), _VP, _VP, C.c_float, _VP, _VP]),

@@ -589,6 +589,77 @@ int sls_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const
                                     (hipStream_t)stream);
 }
 
+size_t sls_mesh_weld_scratch_bytes(int n_rows) { return mesh_weld_scratch_bytes(n_rows); }
+size_t sls_mesh_clusters_scratch_bytes(int T) { return mesh_clusters_scratch_bytes(T); }
+size_t sls_mesh_filter_scratch_bytes(int V, int T) { return mesh_filter_scratch_bytes(V, T); }
+size_t sls_mesh_vertex_normals_scratch_bytes(int V, int T) { return mesh_normals_scratch_bytes(V, T); }
+
+// status words: `zeros` zeros, then `value` (optional), then the 1 that says "written"
+static int mesh_empty_status(uint32_t *out_status, int zeros, int has_value, uint32_t value, hipStream_t st)
+{
+    if (!out_status) return SLS_OK;
+    if (zeros) SLS_HIP_CHECK(hipMemsetAsync(out_status, 0, zeros * sizeof(uint32_t), st));
+    if (has_value) SLS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(out_status + zeros), (int)value, 1, st));
+    SLS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(out_status + zeros + has_value), 1, 1, st));
+    return SLS_OK;
+}
+
+#define SLS_MESH_SCRATCH(name, need)                                                        \
+    do {                                                                                    \
+        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");      \
+        if (scratch_bytes < (need)) {                                                       \
+            set_error(name ": scratch too small: %zu < %zu", scratch_bytes, (size_t)(need)); \
+            return SLS_E_SCRATCH;                                                           \
+        }                                                                                   \
+    } while (0)
+
+int sls_mesh_weld(int n_rows, const float *soup, float *out_vertices, int32_t *out_index, uint32_t *out_status, void *scratch,
+                  size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(n_rows >= 0 && (int64_t)n_rows <= 3 * (int64_t)SLS_MESH_MAX_TRIANGLES, "n_rows negative or above 3 SLS_MESH_MAX_TRIANGLES");
+    if (n_rows == 0) return mesh_empty_status(out_status, 3, 0, 0u, (hipStream_t)stream);
+    SLS_REQUIRE(soup && out_vertices && out_index && out_status && scratch, "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_weld", mesh_weld_scratch_bytes(n_rows));
+    return launch_mesh_weld(n_rows, soup, out_vertices, out_index, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_mesh_clusters(int T, const int32_t *faces, int V, int32_t *out_labels, int32_t *out_counts, uint32_t *out_status,
+                      void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    if (T == 0) return mesh_empty_status(out_status, 5, 0, 0u, (hipStream_t)stream);
+    SLS_REQUIRE(faces && out_labels && out_counts && out_status && scratch, "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_clusters", mesh_clusters_scratch_bytes(T));
+    return launch_mesh_clusters(T, faces, V, out_labels, out_counts, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_mesh_filter(int V, const float *vertices, int T, const int32_t *faces, const int32_t *labels, const int32_t *counts,
+                    const uint32_t *cluster_status, int keep_clusters, int min_triangles, float *out_vertices,
+                    int32_t *out_faces, int32_t *out_vmap, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                    void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    if (V == 0 || T == 0) return mesh_empty_status(out_status, 2, 1, min_triangles > 0 ? (uint32_t)min_triangles : 0u, (hipStream_t)stream);
+    SLS_REQUIRE(vertices && faces && labels && counts && cluster_status && out_vertices && out_faces && out_status && scratch,
+                "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_filter", mesh_filter_scratch_bytes(V, T));
+    return launch_mesh_filter(V, vertices, T, faces, labels, counts, cluster_status, keep_clusters, min_triangles, out_vertices,
+                              out_faces, out_vmap, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
+                            size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    if (V == 0) return SLS_OK;
+    SLS_REQUIRE(out_normals && (T == 0 || (vertices && faces && scratch)), "null pointer");
+    if (T > 0) SLS_MESH_SCRATCH("sls_mesh_vertex_normals", mesh_normals_scratch_bytes(V, T));
+    return launch_mesh_vertex_normals(V, vertices, T, faces, out_normals, scratch, (hipStream_t)stream);
+}
+
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible, void *stream)
 {
     SLS_REQUIRE(cam && N >= 0, "bad argument");

@@ -202,6 +202,20 @@ int launch_tsdf_extract_count(int B, const int32_t *blocks, const float *tsdf, c
 int launch_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
                              double voxel_size, const double *origin, const uint32_t *prefix, uint32_t T, float *triangles,
                              hipStream_t st);
+// ---- sls_mesh.hip (the arguments are checked by the caller, sls_api.hip) -------------------------------------------
+size_t mesh_weld_scratch_bytes(int64_t n_rows);
+int launch_mesh_weld(int n_rows, const float *soup, float *out_vertices, int32_t *out_index, uint32_t *out_status, void *scratch,
+                     hipStream_t st);
+size_t mesh_clusters_scratch_bytes(int T);
+int launch_mesh_clusters(int T, const int32_t *faces, int V, int32_t *out_labels, int32_t *out_counts, uint32_t *out_status,
+                         void *scratch, hipStream_t st);
+size_t mesh_filter_scratch_bytes(int V, int T);
+int launch_mesh_filter(int V, const float *vertices, int T, const int32_t *faces, const int32_t *labels, const int32_t *counts,
+                       const uint32_t *cluster_status, int keep_clusters, int min_triangles, float *out_vertices, int32_t *out_faces,
+                       int32_t *out_vmap, uint32_t *out_status, void *scratch, hipStream_t st);
+size_t mesh_normals_scratch_bytes(int V, int T);
+int launch_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
+                               hipStream_t st);
 int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_raw, float smax, float pen,
                           const uint32_t *status_block, uint64_t *bitmap, hipStream_t st);
 int launch_adam(const SlsAdamGroup *groups, int ngroups, double beta1, double beta2, double eps, int64_t step,

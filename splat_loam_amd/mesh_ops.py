@@ -1,0 +1,244 @@
+"""Cleaning an extracted mesh on the device: the last stage of graph.yaml -> mesh -> evaluate_recon.
+
+`weld` merges the bit-equal rows of a triangle soup (sls_mesh_weld: what `tsdf.weld_soup` does with `torch.unique`),
+`cluster_triangles` labels the edge-connected clusters of triangles and counts boundary and non-manifold edges
+(sls_mesh_clusters: union-find over triangles, driven by the sorted edge list), `keep_clusters` keeps the largest clusters
+and those above a floor of triangles and compacts the mesh (sls_mesh_filter: the post-processing of the 2DGS mesher),
+`vertex_normals` gives every vertex its area-weighted normal (sls_mesh_vertex_normals: Open3D's
+`compute_vertex_normals`), `clean_mesh` chains them.  include/sls_mesh_math.h states every rule, DESIGN.md section 2
+("Mesh cleaning") the contract, tests/mesh_ref.py restates it in NumPy.  Device tensors only; there is no CPU path.
+
+Host reads: `weld`, `cluster_triangles`, `keep_clusters` and `clean_mesh` one each (the status words, read once at the
+end: outputs are allocated at capacity and sliced), `vertex_normals` none.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _abi
+from .tsdf import _device_points, _stream
+
+MAX_TRIANGLES = 1 << 29              # SLS_MESH_MAX_TRIANGLES
+
+
+def _device_faces(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a ROCm device tensor (libsls_hip.so); there is no CPU fallback")
+    t = t.detach()
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be (T,3)")
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name} must be int32 or int64")
+    if t.shape[0] > MAX_TRIANGLES:
+        raise ValueError(f"{name} holds more than {MAX_TRIANGLES} triangles")
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    return t.contiguous()
+
+
+def _scratch(nbytes, dev):
+    """(the tensor that owns the bytes, a 256-byte aligned address inside it)"""
+    buf = torch.empty((int(nbytes) + 256,), dtype=torch.uint8, device=dev)
+    return buf, (buf.data_ptr() + 255) & ~255
+
+
+def _words(status):
+    return status.cpu().numpy().view(np.uint32)
+
+
+# ---- the launches: outputs at capacity, status words on the device, nothing read back --------------------------------
+def _weld_launch(rows, status):
+    """rows (N,3) float32 -> (vertices at capacity (N,3), index (N,) int32); status: 4 int32 words on the device."""
+    lib, dev, N = _abi.lib(), rows.device, int(rows.shape[0])
+    out = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    index = torch.empty((N,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.sls_mesh_weld_scratch_bytes(N))
+    keep, ptr = _scratch(nbytes, dev)
+    _abi.check(lib.sls_mesh_weld(N, rows.data_ptr(), out.data_ptr(), index.data_ptr(), status.data_ptr(), ptr, nbytes, _stream(dev)),
+               "sls_mesh_weld")
+    return out, index
+
+
+def _clusters_launch(faces, n_vertices, status):
+    """faces (T,3) int32 -> (labels (T,) int32, counts at capacity (T,) int32); status: 6 int32 words on the device."""
+    lib, dev, T = _abi.lib(), faces.device, int(faces.shape[0])
+    labels = torch.empty((T,), dtype=torch.int32, device=dev)
+    counts = torch.empty((T,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.sls_mesh_clusters_scratch_bytes(T))
+    keep, ptr = _scratch(nbytes, dev)
+    _abi.check(lib.sls_mesh_clusters(T, faces.data_ptr(), int(n_vertices), labels.data_ptr(), counts.data_ptr(), status.data_ptr(), ptr,
+                                     nbytes, _stream(dev)), "sls_mesh_clusters")
+    return labels, counts
+
+
+def _filter_launch(vertices, faces, labels, counts, cluster_status, keep, min_triangles, status):
+    """-> (vertices at capacity (V,3), faces at capacity (T,3), rows past the kept ones -1); status: 4 words."""
+    lib, dev, V, T = _abi.lib(), vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    out_v = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    out_f = torch.full((T, 3), -1, dtype=torch.int32, device=dev)
+    nbytes = int(lib.sls_mesh_filter_scratch_bytes(V, T))
+    hold, ptr = _scratch(nbytes, dev)
+    _abi.check(lib.sls_mesh_filter(V, vertices.data_ptr(), T, faces.data_ptr(), labels.data_ptr(), counts.data_ptr(),
+                                   cluster_status.data_ptr(), int(keep), int(min_triangles), out_v.data_ptr(), out_f.data_ptr(), None,
+                                   status.data_ptr(), ptr, nbytes, _stream(dev)), "sls_mesh_filter")
+    return out_v, out_f
+
+
+def _normals_launch(vertices, faces):
+    lib, dev, V, T = _abi.lib(), vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    nbytes = int(lib.sls_mesh_vertex_normals_scratch_bytes(V, T))
+    hold, ptr = _scratch(nbytes, dev)
+    _abi.check(lib.sls_mesh_vertex_normals(V, vertices.data_ptr(), T, faces.data_ptr(), out.data_ptr(), ptr, nbytes, _stream(dev)),
+               "sls_mesh_vertex_normals")
+    return out
+
+
+def _status(dev, n):
+    return torch.zeros((n,), dtype=torch.int32, device=dev)
+
+
+def _range_error(n):
+    return ValueError(f"{n} triangles hold a vertex index outside the vertices")
+
+
+def _cluster_details(w):
+    return {"clusters": int(w[0]), "degenerate": int(w[1]), "out_of_range": int(w[2]), "boundary_edges": int(w[3]),
+            "nonmanifold_edges": int(w[4])}
+
+
+# ---- the public calls ------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def weld_rows(rows: torch.Tensor):
+    """`(vertices (V,3) float32, index (N,) int32)`: the unique rows of (N,3) float32 device rows, compared as integers, in
+    ascending lexicographic order of (x, y, z) as signed int32, and the rank of every row.  One host read (V)."""
+    rows = _device_points(rows, "rows")
+    dev = rows.device
+    with torch.cuda.device(dev):
+        status = _status(dev, 4)
+        out, index = _weld_launch(rows, status)
+        V = int(_words(status)[0])                                  # the one host read
+    return out[:V], index
+
+
+@torch.no_grad()
+def weld(soup: torch.Tensor):
+    """A triangle soup (3T,3) with its bit-equal vertices merged: `(vertices (V,3) float32, faces (T,3) int32)`, exactly
+    what `tsdf.weld_soup` returns (-0.0 and 0.0 stay apart, NaN payloads are compared as bits), by three stable radix sorts
+    and a scan instead of `torch.unique`.  One host read (V)."""
+    soup = _device_points(soup, "soup")
+    if soup.shape[0] % 3:
+        raise ValueError("soup must be (3T,3)")
+    vertices, index = weld_rows(soup)
+    return vertices, index.view(soup.shape[0] // 3, 3)
+
+
+@torch.no_grad()
+def cluster_triangles(faces: torch.Tensor, n_vertices: int, details: bool = False):
+    """`(labels (T,) int32, cluster_count (C,) int32)`: the cluster of every triangle — triangles that share an undirected
+    edge are joined, clusters are numbered in ascending order of their lowest triangle, a triangle with a repeated index
+    carries -1 — and the triangles per cluster.  A face index outside [0, n_vertices) raises.  `details=True` adds
+    dict(clusters, degenerate, out_of_range, boundary_edges, nonmanifold_edges): a mesh with neither boundary nor
+    non-manifold edges is closed.  One host read (the status words)."""
+    faces = _device_faces(faces, "faces")
+    dev = faces.device
+    with torch.cuda.device(dev):
+        status = _status(dev, 8)
+        labels, counts = _clusters_launch(faces, int(n_vertices), status)
+        w = _words(status)                                          # the one host read
+    if w[2]:
+        raise _range_error(int(w[2]))
+    if details:
+        return labels, counts[:int(w[0])], _cluster_details(w)
+    return labels, counts[:int(w[0])]
+
+
+def _keep(vertices, faces, keep, min_triangles, details):
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        status = _status(dev, 16)
+        labels, counts = _clusters_launch(faces, int(vertices.shape[0]), status[0:8])
+        out_v, out_f = _filter_launch(vertices, faces, labels, counts, status[0:8], keep, min_triangles, status[8:12])
+        w = _words(status)                                          # the one host read
+    if w[2]:
+        raise _range_error(int(w[2]))
+    out_v, out_f = out_v[:int(w[8])], out_f[:int(w[9])]
+    if details:
+        d = _cluster_details(w)
+        d.update(cluster_count=counts[:int(w[0])], labels=labels, n_min=int(w[10]))
+        return out_v, out_f, d
+    return out_v, out_f
+
+
+@torch.no_grad()
+def keep_clusters(vertices: torch.Tensor, faces: torch.Tensor, keep_clusters: int = 1, min_triangles: int = 50, details: bool = False):
+    """The mesh with its small clusters dropped: `(vertices (V',3), faces (T',3) int32)`.  With
+    n_min = max(min_triangles, the triangles of the k-th largest cluster), k = min(keep_clusters, clusters), a triangle
+    stays iff it is non-degenerate and its cluster holds at least n_min triangles (ties at the threshold all stay);
+    `keep_clusters <= 0`: the floor alone, `min_triangles <= 0`: no floor.  Kept triangles and the vertices they reference
+    stay in input order.  `details=True` adds dict(clusters, cluster_count (a device tensor), labels, degenerate,
+    out_of_range, boundary_edges, nonmanifold_edges — all of the INPUT mesh — and n_min).  One host read."""
+    vertices = _device_points(vertices, "vertices")
+    faces = _device_faces(faces, "faces")
+    if faces.device != vertices.device:
+        raise ValueError("vertices and faces must live on the same device")
+    return _keep(vertices, faces, keep_clusters, min_triangles, details)
+
+
+@torch.no_grad()
+def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """(V,3) float32: per vertex the normalised sum of the un-normalised (area-weighted) normals (p1 - p0) x (p2 - p0) of
+    its triangles, summed in ascending triangle index in float32 — bit-reproducible, equal to the header on the host.
+    Triangles with a repeated or out-of-range index are skipped; a vertex without a triangle, or with a sum of zero or
+    non-finite length, gets zeros.  Nothing is read back."""
+    vertices = _device_points(vertices, "vertices")
+    faces = _device_faces(faces, "faces")
+    if faces.device != vertices.device:
+        raise ValueError("vertices and faces must live on the same device")
+    with torch.cuda.device(vertices.device):
+        return _normals_launch(vertices, faces)
+
+
+@torch.no_grad()
+def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True, keep_clusters: int = 1, min_triangles: int = 50,
+               normals: bool = True, details: bool = False):
+    """Weld, keep the largest clusters, compute vertex normals: `(vertices, faces)` or, with `normals`,
+    `(vertices, faces, normals)`; `details=True` appends the dict of `keep_clusters` (the statistics are those of the
+    welded mesh before the selection) plus `welded_vertices`.  `weld=True` merges the bit-equal rows of `vertices` and passes the faces
+    through their ranks: for a soup (`faces` = arange) that is `weld`.  `keep_clusters=None`: no selection.  One host read for
+    the whole chain: every stage runs at the capacity of its input (vertices beyond the welded count are referenced by
+    nothing, face rows beyond the kept count are -1 and skipped), and the outputs are sliced at the end."""
+    vertices = _device_points(vertices, "vertices")
+    faces = _device_faces(faces, "faces")
+    dev = vertices.device
+    if faces.device != dev:
+        raise ValueError("vertices and faces must live on the same device")
+    T = int(faces.shape[0])
+    select = keep_clusters is not None
+    with torch.cuda.device(dev):
+        status = _status(dev, 24)
+        status[0] = int(vertices.shape[0])                          # (without a weld: V as it came)
+        v, f = vertices, faces
+        if weld:
+            V = int(vertices.shape[0])
+            v, index = _weld_launch(vertices, status[0:4])
+            # the faces through the rank of every row (a gather: plumbing); a triangle with an index outside the vertices
+            # keeps one (-1) and is counted by the cluster stage
+            inside = ((faces >= 0) & (faces < V)).all(dim=1, keepdim=True)
+            f = torch.where(inside, index[faces.clamp(0, max(V - 1, 0)).long()], torch.full_like(faces, -1)) if V else \
+                torch.full_like(faces, -1)
+        labels, counts = _clusters_launch(f, int(v.shape[0]), status[8:16])
+        if select:
+            v, f = _filter_launch(v, f, labels, counts, status[8:16], keep_clusters, min_triangles, status[16:20])
+        n = _normals_launch(v, f) if normals else None
+        w = _words(status)                                          # the one host read
+    if w[10]:
+        raise _range_error(int(w[10]))
+    nv, nt = (int(w[16]), int(w[17])) if select else (int(w[0]), T)
+    out = (v[:nv], f[:nt]) + ((n[:nv],) if normals else ())
+    if details:
+        d = _cluster_details(w[8:])
+        d.update(cluster_count=counts[:int(w[8])], labels=labels, n_min=int(w[18]) if select else 0, welded_vertices=int(w[0]))
+        return out + (d,)
+    return out

@@ -238,9 +238,16 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
 @torch.no_grad()
 def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_interval: int = -1, kf_samples: int = 5000,
               min_opacity: float = 0.5, max_depth_dist: float = 0.1, use_median_depth: bool = False, min_weight: float = 1.0,
-              seed=None, device="cuda", details: bool = False, image_height=None, image_width=None):
+              seed=None, device="cuda", details: bool = False, image_height=None, image_width=None, keep_clusters=None,
+              min_triangles: int = 50, normals: bool = False):
     """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
     frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
+
+    `keep_clusters=K` (or `normals=True`) cleans the soup with `mesh_ops.clean_mesh`: bit-equal vertices welded, only the
+    K largest edge-connected clusters and those of at least `min_triangles` triangles kept (the floaters a fused LiDAR
+    volume leaves at depth discontinuities go), and with `normals=True` the return value is `(vertices, faces, normals)`
+    with area-weighted vertex normals.  One more host read; `details` gains `clean` (the statistics of `clean_mesh`) and
+    `stage_ms` a "clean" lap.  With the defaults nothing of this runs and the soup is returned as it always was.
 
     Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
     its cloud: blocks of 8^3 voxels of edge `voxel_size`, truncation `trunc` (default 4 voxel_size).  Pass 2 renders every
@@ -284,8 +291,17 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     lap("integrate")
     vertices, faces = volume.extract(min_weight=min_weight)
     lap("extract")
+    mesh, clean = (vertices, faces), None
+    if keep_clusters is not None or normals:
+        from . import mesh_ops
+        *mesh, clean = mesh_ops.clean_mesh(vertices, faces, weld=True, keep_clusters=keep_clusters, min_triangles=min_triangles,
+                                           normals=normals, details=True)
+        mesh = tuple(mesh)
+        lap("clean")
     if details:
-        return vertices, faces, {"blocks": int(volume.blocks.shape[0]), "volume_bytes": volume.nbytes, "triangles": int(faces.shape[0]),
-                                 "samples": int(points.shape[0]), "frame_ids": [fid for _, fid in used], "stage_ms": stage_ms,
-                                 "volume": volume}
-    return vertices, faces
+        det = {"blocks": int(volume.blocks.shape[0]), "volume_bytes": volume.nbytes, "triangles": int(faces.shape[0]),
+               "samples": int(points.shape[0]), "frame_ids": [fid for _, fid in used], "stage_ms": stage_ms, "volume": volume}
+        if clean is not None:
+            det["clean"] = clean
+        return mesh + (det,)
+    return mesh

@@ -51,19 +51,27 @@ def save_point_cloud(path, points, normals) -> None:
         f.write(data.tobytes())
 
 
-def save_mesh(path, vertices, faces) -> None:
+def save_mesh(path, vertices, faces, normals=None) -> None:
     """A triangle mesh (`tsdf.TsdfVolume.extract`, `meshing.mesh_tsdf`) as binary little-endian PLY: a `vertex` element
     with float32 `x y z`, then a `face` element with `list uchar int vertex_indices` — what `load_mesh` reads back bit for
-    bit, and the layout Open3D and MeshLab write for a plain triangle mesh."""
+    bit, and the layout Open3D and MeshLab write for a plain triangle mesh.  `normals` (V,3), e.g. of
+    `mesh_ops.vertex_normals`: the vertex element gains float32 `nx ny nz` (`load_point_cloud` returns them; `load_mesh`
+    skips them); without them the bytes are the same as ever."""
     def host(a, dt):
         return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=dt)
     vertices, faces = host(vertices, np.float32).reshape(-1, 3), host(faces, np.int64).reshape(-1, 3)
     if faces.size and (faces.min() < 0 or faces.max() > 0x7FFFFFFF):
         raise ValueError("a vertex index does not fit int32")
+    props = "xyz"
+    if normals is not None:
+        normals = host(normals, np.float32).reshape(-1, 3)
+        if normals.shape != vertices.shape:
+            raise ValueError("vertices and normals must have the same number of rows")
+        vertices, props = np.concatenate([vertices, normals], axis=1), ("x", "y", "z", "nx", "ny", "nz")
     rec = np.empty(len(faces), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
     rec["n"], rec["i"] = 3, faces
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(vertices)
-    header += "".join(f"property float {p}\n" for p in "xyz")
+    header += "".join(f"property float {p}\n" for p in props)
     header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(faces)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as f:

@@ -5,10 +5,15 @@ rendered depth of every keyframe fused into a sparse TSDF volume, the zero surfa
 
     python tools/mesh_tsdf.py RESULTS_DIR OUT.ply --voxel 0.1 [--trunc T] [--kf-interval N] [--kf-samples K]
                               [--min-opacity A] [--max-depth-dist D] [--use-median-depth] [--min-weight W] [--weld]
+                              [--keep-clusters K] [--min-triangles N] [--normals]
                               [--seed S] [--image-height H --image-width W]
 
 OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tools/eval_recon.py` takes as the estimate.
-Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage."""
+--keep-clusters K welds the soup and keeps only the K largest edge-connected clusters of triangles and those of at least
+--min-triangles triangles (`mesh_ops.clean_mesh`: the floaters go); --normals adds area-weighted vertex normals as
+`nx ny nz`.  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
+with a clean stage its statistics (of the welded mesh: clusters, degenerate triangles, boundary and non-manifold edges;
+n_min; the triangles kept)."""
 import argparse
 import json
 import os
@@ -33,21 +38,32 @@ def main():
     ap.add_argument("--use-median-depth", action="store_true")
     ap.add_argument("--min-weight", type=float, default=1.0)
     ap.add_argument("--weld", action="store_true", help="merge bit-equal vertices before writing")
+    ap.add_argument("--keep-clusters", type=int, default=None, help="weld, then keep the K largest clusters of triangles")
+    ap.add_argument("--min-triangles", type=int, default=50, help="... and every cluster of at least N triangles (with --keep-clusters)")
+    ap.add_argument("--normals", action="store_true", help="weld and write area-weighted vertex normals")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args()
-    vertices, faces, det = meshing.mesh_tsdf(a.results_dir, a.voxel, a.trunc, kf_interval=a.kf_interval, kf_samples=a.kf_samples,
-                                             min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist,
-                                             use_median_depth=a.use_median_depth, min_weight=a.min_weight, seed=a.seed,
-                                             device=a.device, details=True, image_height=a.image_height, image_width=a.image_width)
-    if a.weld:
+    *mesh, det = meshing.mesh_tsdf(a.results_dir, a.voxel, a.trunc, kf_interval=a.kf_interval, kf_samples=a.kf_samples,
+                                   min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist, use_median_depth=a.use_median_depth,
+                                   min_weight=a.min_weight, seed=a.seed, device=a.device, details=True, image_height=a.image_height,
+                                   image_width=a.image_width, keep_clusters=a.keep_clusters, min_triangles=a.min_triangles,
+                                   normals=a.normals)
+    vertices, faces, normals = mesh[0], mesh[1], (mesh[2] if a.normals else None)
+    if a.weld and "clean" not in det:
         vertices, faces = tsdf.weld_soup(vertices)
-    ply_io.save_mesh(a.out_ply, vertices, faces)
-    print(json.dumps({"blocks": det["blocks"], "volume_bytes": det["volume_bytes"], "triangles": det["triangles"],
-                      "vertices": int(vertices.shape[0]), "keyframes": len(det["frame_ids"]), "samples": det["samples"],
-                      "stage_ms": {k: round(v, 3) for k, v in det["stage_ms"].items()}, "out": a.out_ply}))
+    ply_io.save_mesh(a.out_ply, vertices, faces, normals=normals)
+    line = {"blocks": det["blocks"], "volume_bytes": det["volume_bytes"], "triangles": det["triangles"],
+            "vertices": int(vertices.shape[0]), "keyframes": len(det["frame_ids"]), "samples": det["samples"],
+            "stage_ms": {k: round(v, 3) for k, v in det["stage_ms"].items()}, "out": a.out_ply}
+    if "clean" in det:
+        line["clean"] = {k: det["clean"][k] for k in ("welded_vertices", "clusters", "degenerate", "boundary_edges", "nonmanifold_edges",
+                                                      "n_min")}
+        line["clean"]["triangles_kept"] = int(faces.shape[0])
+        line["clean"]["normals"] = bool(a.normals)
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":
