@@ -874,6 +874,25 @@ size_t sls_mesh_vertex_normals_scratch_bytes(int V, int T);
 int sls_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
                             size_t scratch_bytes, void *stream);
 
+/* Simplification by vertex clustering (include/sls_simplify_math.h states every rule; DESIGN.md section 2, "Mesh
+ * simplification").  The live vertices (those a non-degenerate triangle references) of one voxel of edge voxel_size become
+ * one vertex: their float64 mean (contraction 0) or the minimum of the voxel's error quadric, regularised towards that
+ * mean by `regularisation` times the quadric's trace (contraction 1).  Triangles are mapped to clusters, dropped when they
+ * collapse, rotated so that their smallest index comes first and de-duplicated (the lowest input index stays); kept
+ * triangles stay in input order, the surviving clusters leave in ascending voxel key.  out_vertices (room for V rows),
+ * out_faces (room for T rows), out_vmap (V int32, may be null): the output vertex of every input vertex, -1 for one that
+ * left.  The conventions of the mesh cleaning calls apply; additionally SLS_E_ARG for a voxel_size that is not finite and
+ * > 0, a contraction other than 0 or 1, a regularisation that is not finite and >= 0.  Face rows of -1 and unreferenced
+ * vertex rows take no part: the call runs behind sls_mesh_filter at capacity.  Equals the header run on the host bit for
+ * bit.
+ *   out_status (8 words) = [V', T', live vertices with a non-finite coordinate, live vertices with a voxel index >= 2^21
+ *   (not 0: the outputs are unspecified), collapsed triangles, duplicate triangles, quadric fallbacks to the mean, 1].
+ *   V == 0 or T == 0 writes [0, 0, 0, 0, 0, 0, 0, 1] and out_vmap = -1 alone. */
+size_t sls_mesh_simplify_scratch_bytes(int V, int T);
+int sls_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces, double voxel_size, int contraction,
+                      double regularisation, float *out_vertices, int32_t *out_faces, int32_t *out_vmap, uint32_t *out_status,
+                      void *scratch, size_t scratch_bytes, void *stream);
+
 /* visible[i] = 1 if surfel centre i survives the near cut (radii would be >0
  * unless it is off-image). */
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible,

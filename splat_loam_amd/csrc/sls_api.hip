@@ -36,7 +36,8 @@ DebugState &debug_state()
 // ---------------------------------------------------------------------------
 static const char *kTimerNames[T_COUNT] = {
     "preprocess_fwd", "scan", "emit_keys", "sort_hist", "sort_rowscan", "sort_scatter", "tile_ranges",
-    "render_fwd", "grec_memset", "render_bwd", "preprocess_bwd", "adam", "knn", "consumer", "resort", "bin_count", "bin_direct"
+    "render_fwd", "grec_memset", "render_bwd", "preprocess_bwd", "adam", "knn", "consumer", "resort", "bin_count", "bin_direct",
+    "simp_cluster", "simp_faces", "simp_corners", "simp_place"
 };
 constexpr int kTimerPool = 8192;
 struct TimerState {
@@ -593,6 +594,7 @@ size_t sls_mesh_weld_scratch_bytes(int n_rows) { return mesh_weld_scratch_bytes(
 size_t sls_mesh_clusters_scratch_bytes(int T) { return mesh_clusters_scratch_bytes(T); }
 size_t sls_mesh_filter_scratch_bytes(int V, int T) { return mesh_filter_scratch_bytes(V, T); }
 size_t sls_mesh_vertex_normals_scratch_bytes(int V, int T) { return mesh_normals_scratch_bytes(V, T); }
+size_t sls_mesh_simplify_scratch_bytes(int V, int T) { return mesh_simplify_scratch_bytes(V, T); }
 
 // status words: `zeros` zeros, then `value` (optional), then the 1 that says "written"
 static int mesh_empty_status(uint32_t *out_status, int zeros, int has_value, uint32_t value, hipStream_t st)
@@ -658,6 +660,25 @@ int sls_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *
     SLS_REQUIRE(out_normals && (T == 0 || (vertices && faces && scratch)), "null pointer");
     if (T > 0) SLS_MESH_SCRATCH("sls_mesh_vertex_normals", mesh_normals_scratch_bytes(V, T));
     return launch_mesh_vertex_normals(V, vertices, T, faces, out_normals, scratch, (hipStream_t)stream);
+}
+
+int sls_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces, double voxel_size, int contraction,
+                      double regularisation, float *out_vertices, int32_t *out_faces, int32_t *out_vmap, uint32_t *out_status,
+                      void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    SLS_REQUIRE(voxel_size > 0.0 && voxel_size <= DBL_MAX, "voxel_size must be finite and > 0");
+    SLS_REQUIRE(contraction == 0 || contraction == 1, "contraction must be 0 (average) or 1 (quadric)");
+    SLS_REQUIRE(regularisation >= 0.0 && regularisation <= DBL_MAX, "regularisation must be finite and >= 0");
+    if (V == 0 || T == 0) {                         // no triangle is kept: every vertex leaves
+        if (out_vmap && V > 0) SLS_HIP_CHECK(hipMemsetAsync(out_vmap, 0xFF, sizeof(int32_t) * (size_t)V, (hipStream_t)stream));
+        return mesh_empty_status(out_status, 7, 0, 0u, (hipStream_t)stream);
+    }
+    SLS_REQUIRE(vertices && faces && out_vertices && out_faces && out_status && scratch, "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_simplify", mesh_simplify_scratch_bytes(V, T));
+    return launch_mesh_simplify(V, vertices, T, faces, voxel_size, contraction, regularisation, out_vertices, out_faces, out_vmap,
+                                out_status, scratch, (hipStream_t)stream);
 }
 
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible, void *stream)

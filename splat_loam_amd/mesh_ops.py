@@ -5,11 +5,13 @@
 (sls_mesh_clusters: union-find over triangles, driven by the sorted edge list), `keep_clusters` keeps the largest clusters
 and those above a floor of triangles and compacts the mesh (sls_mesh_filter: the post-processing of the 2DGS mesher),
 `vertex_normals` gives every vertex its area-weighted normal (sls_mesh_vertex_normals: Open3D's
-`compute_vertex_normals`), `clean_mesh` chains them.  include/sls_mesh_math.h states every rule, DESIGN.md section 2
-("Mesh cleaning") the contract, tests/mesh_ref.py restates it in NumPy.  Device tensors only; there is no CPU path.
+`compute_vertex_normals`), `simplify_vertex_clustering` makes the mesh smaller (sls_mesh_simplify: Open3D's
+`simplify_vertex_clustering`, average or quadric contraction), `clean_mesh` chains them.  include/sls_mesh_math.h and
+include/sls_simplify_math.h state every rule, DESIGN.md section 2 ("Mesh cleaning", "Mesh simplification") the contract,
+tests/mesh_ref.py and tests/simplify_ref.py restate it in NumPy.  Device tensors only; there is no CPU path.
 
-Host reads: `weld`, `cluster_triangles`, `keep_clusters` and `clean_mesh` one each (the status words, read once at the
-end: outputs are allocated at capacity and sliced), `vertex_normals` none.
+Host reads: `weld`, `cluster_triangles`, `keep_clusters`, `simplify_vertex_clustering` and `clean_mesh` one each (the
+status words, read once at the end: outputs are allocated at capacity and sliced), `vertex_normals` none.
 """
 from __future__ import annotations
 
@@ -93,6 +95,47 @@ def _normals_launch(vertices, faces):
     _abi.check(lib.sls_mesh_vertex_normals(V, vertices.data_ptr(), T, faces.data_ptr(), out.data_ptr(), ptr, nbytes, _stream(dev)),
                "sls_mesh_vertex_normals")
     return out
+
+
+CONTRACTIONS = {"average": 0, "quadric": 1}
+
+
+def _simplify_args(voxel_size, contraction, regularisation):
+    if contraction not in CONTRACTIONS:
+        raise ValueError(f"contraction must be one of {sorted(CONTRACTIONS)}, not {contraction!r}")
+    voxel_size, regularisation = float(voxel_size), float(regularisation)
+    if not (np.isfinite(voxel_size) and voxel_size > 0):
+        raise ValueError("voxel_size must be finite and > 0")
+    if not (np.isfinite(regularisation) and regularisation >= 0):
+        raise ValueError("regularisation must be finite and >= 0")
+    return voxel_size, CONTRACTIONS[contraction], regularisation
+
+
+def _simplify_launch(vertices, faces, voxel_size, contraction, regularisation, status):
+    """-> (vertices at capacity (V,3), faces at capacity (T,3), rows past the kept ones -1, vmap (V,)); status: 8 words.
+    `contraction` is the integer of the C entry."""
+    lib, dev, V, T = _abi.lib(), vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    out_v = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    out_f = torch.full((T, 3), -1, dtype=torch.int32, device=dev)
+    vmap = torch.empty((V,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.sls_mesh_simplify_scratch_bytes(V, T))
+    hold, ptr = _scratch(nbytes, dev)
+    _abi.check(lib.sls_mesh_simplify(V, vertices.data_ptr(), T, faces.data_ptr(), float(voxel_size), int(contraction),
+                                     float(regularisation), out_v.data_ptr(), out_f.data_ptr(), vmap.data_ptr(), status.data_ptr(), ptr,
+                                     nbytes, _stream(dev)), "sls_mesh_simplify")
+    return out_v, out_f, vmap
+
+
+def _simplify_details(w):
+    return {"vertices": int(w[0]), "triangles": int(w[1]), "nonfinite": int(w[2]), "out_of_grid": int(w[3]), "collapsed": int(w[4]),
+            "duplicates": int(w[5]), "fallbacks": int(w[6])}
+
+
+def _simplify_errors(w, voxel_size):
+    if w[2]:
+        raise ValueError(f"{int(w[2])} vertices that a triangle references hold a non-finite coordinate")
+    if w[3]:
+        raise ValueError(f"{int(w[3])} vertices lie 2^21 voxels or more from the mesh's minimum: voxel_size {voxel_size} is too small")
 
 
 def _status(dev, n):
@@ -201,11 +244,48 @@ def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
+def simplify_vertex_clustering(vertices: torch.Tensor, faces: torch.Tensor, voxel_size: float, contraction: str = "average",
+                               regularisation: float = 1e-3, details: bool = False):
+    """The mesh with the vertices of every voxel of edge `voxel_size` merged into one: `(vertices (V',3), faces (T',3) int32)`
+    (Open3D's `simplify_vertex_clustering`).  Only vertices that a triangle with three different indices inside the vertices
+    references take part; the grid starts half a voxel below their minimum.  `contraction="average"` places a cluster at the
+    float64 mean of its vertices, `"quadric"` at the minimum of the cluster's error quadric (area-weighted plane distances
+    of every triangle with a corner in it), regularised towards that mean by `regularisation` times the quadric's trace — it
+    falls back to the mean where the solve is singular or would move the vertex by more than a voxel.  Triangles whose
+    corners do not fall into three different clusters leave, so do repeats of a kept triangle (the lowest input index stays;
+    the opposite orientation is another triangle); kept triangles stay in input order with their smallest index first, the
+    vertices leave in ascending voxel order.  A referenced vertex with a non-finite coordinate, or one 2^21 voxels or more
+    from the minimum, raises.  `details=True` appends dict(vertices, triangles, nonfinite, out_of_grid, collapsed,
+    duplicates, fallbacks, vmap — (V,) int32 on the device: the output vertex of every input vertex, -1 for one that left).
+    Bit-reproducible: equal to include/sls_simplify_math.h run on the host.  One host read (the status words)."""
+    vertices = _device_points(vertices, "vertices")
+    faces = _device_faces(faces, "faces")
+    dev = vertices.device
+    if faces.device != dev:
+        raise ValueError("vertices and faces must live on the same device")
+    voxel_size, code, regularisation = _simplify_args(voxel_size, contraction, regularisation)
+    with torch.cuda.device(dev):
+        status = _status(dev, 8)
+        out_v, out_f, vmap = _simplify_launch(vertices, faces, voxel_size, code, regularisation, status)
+        w = _words(status)                                          # the one host read
+    _simplify_errors(w, voxel_size)
+    out = (out_v[:int(w[0])], out_f[:int(w[1])])
+    if details:
+        d = _simplify_details(w)
+        d["vmap"] = vmap
+        return out + (d,)
+    return out
+
+
+@torch.no_grad()
 def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True, keep_clusters: int = 1, min_triangles: int = 50,
-               normals: bool = True, details: bool = False):
-    """Weld, keep the largest clusters, compute vertex normals: `(vertices, faces)` or, with `normals`,
+               normals: bool = True, details: bool = False, simplify: float = None, contraction: str = "average",
+               regularisation: float = 1e-3):
+    """Weld, keep the largest clusters, optionally simplify, compute vertex normals: `(vertices, faces)` or, with `normals`,
     `(vertices, faces, normals)`; `details=True` appends the dict of `keep_clusters` (the statistics are those of the
-    welded mesh before the selection) plus `welded_vertices`.  `weld=True` merges the bit-equal rows of `vertices` and passes the faces
+    welded mesh before the selection) plus `welded_vertices`.  `simplify=h` runs `simplify_vertex_clustering(h, contraction,
+    regularisation)` after the selection and before the normals (`details` then holds its dict under "simplify", with `vmap`
+    over the vertices at the selection's capacity); `simplify=None`: no such stage.  `weld=True` merges the bit-equal rows of `vertices` and passes the faces
     through their ranks: for a soup (`faces` = arange) that is `weld`.  `keep_clusters=None`: no selection.  One host read for
     the whole chain: every stage runs at the capacity of its input (vertices beyond the welded count are referenced by
     nothing, face rows beyond the kept count are -1 and skipped), and the outputs are sliced at the end."""
@@ -216,8 +296,10 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
         raise ValueError("vertices and faces must live on the same device")
     T = int(faces.shape[0])
     select = keep_clusters is not None
+    if simplify is not None:
+        simplify, code, regularisation = _simplify_args(simplify, contraction, regularisation)
     with torch.cuda.device(dev):
-        status = _status(dev, 24)
+        status = _status(dev, 32)
         status[0] = int(vertices.shape[0])                          # (without a weld: V as it came)
         v, f = vertices, faces
         if weld:
@@ -231,14 +313,21 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
         labels, counts = _clusters_launch(f, int(v.shape[0]), status[8:16])
         if select:
             v, f = _filter_launch(v, f, labels, counts, status[8:16], keep_clusters, min_triangles, status[16:20])
+        if simplify is not None:
+            v, f, vmap = _simplify_launch(v, f, simplify, code, regularisation, status[24:32])
         n = _normals_launch(v, f) if normals else None
         w = _words(status)                                          # the one host read
     if w[10]:
         raise _range_error(int(w[10]))
     nv, nt = (int(w[16]), int(w[17])) if select else (int(w[0]), T)
+    if simplify is not None:
+        _simplify_errors(w[24:], simplify)
+        nv, nt = int(w[24]), int(w[25])
     out = (v[:nv], f[:nt]) + ((n[:nv],) if normals else ())
     if details:
         d = _cluster_details(w[8:])
         d.update(cluster_count=counts[:int(w[8])], labels=labels, n_min=int(w[18]) if select else 0, welded_vertices=int(w[0]))
+        if simplify is not None:
+            d["simplify"] = dict(_simplify_details(w[24:]), vmap=vmap)
         return out + (d,)
     return out

@@ -239,7 +239,8 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
 def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_interval: int = -1, kf_samples: int = 5000,
               min_opacity: float = 0.5, max_depth_dist: float = 0.1, use_median_depth: bool = False, min_weight: float = 1.0,
               seed=None, device="cuda", details: bool = False, image_height=None, image_width=None, keep_clusters=None,
-              min_triangles: int = 50, normals: bool = False):
+              min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
+              regularisation: float = 1e-3):
     """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
     frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
 
@@ -247,7 +248,11 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     K largest edge-connected clusters and those of at least `min_triangles` triangles kept (the floaters a fused LiDAR
     volume leaves at depth discontinuities go), and with `normals=True` the return value is `(vertices, faces, normals)`
     with area-weighted vertex normals.  One more host read; `details` gains `clean` (the statistics of `clean_mesh`) and
-    `stage_ms` a "clean" lap.  With the defaults nothing of this runs and the soup is returned as it always was.
+    `stage_ms` a "clean" lap.  `simplify=h` (metres; a multiple of `voxel_size` is the natural choice) also runs the clean
+    stage and, after the selection, `mesh_ops.simplify_vertex_clustering(h, contraction, regularisation)`: the vertices of
+    every voxel of edge h become one, at their mean ("average") or at the minimum of the voxel's error quadric ("quadric");
+    `details["clean"]["simplify"]` holds its counts.  With the defaults nothing of this runs and the soup is returned as it
+    always was.
 
     Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
     its cloud: blocks of 8^3 voxels of edge `voxel_size`, truncation `trunc` (default 4 voxel_size).  Pass 2 renders every
@@ -292,10 +297,11 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     vertices, faces = volume.extract(min_weight=min_weight)
     lap("extract")
     mesh, clean = (vertices, faces), None
-    if keep_clusters is not None or normals:
+    if keep_clusters is not None or normals or simplify is not None:
         from . import mesh_ops
         *mesh, clean = mesh_ops.clean_mesh(vertices, faces, weld=True, keep_clusters=keep_clusters, min_triangles=min_triangles,
-                                           normals=normals, details=True)
+                                           normals=normals, details=True, simplify=simplify, contraction=contraction,
+                                           regularisation=regularisation)
         mesh = tuple(mesh)
         lap("clean")
     if details:

@@ -6,14 +6,17 @@ rendered depth of every keyframe fused into a sparse TSDF volume, the zero surfa
     python tools/mesh_tsdf.py RESULTS_DIR OUT.ply --voxel 0.1 [--trunc T] [--kf-interval N] [--kf-samples K]
                               [--min-opacity A] [--max-depth-dist D] [--use-median-depth] [--min-weight W] [--weld]
                               [--keep-clusters K] [--min-triangles N] [--normals]
+                              [--simplify RES [--contraction quadric] [--regularisation L]]
                               [--seed S] [--image-height H --image-width W]
 
 OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tools/eval_recon.py` takes as the estimate.
 --keep-clusters K welds the soup and keeps only the K largest edge-connected clusters of triangles and those of at least
 --min-triangles triangles (`mesh_ops.clean_mesh`: the floaters go); --normals adds area-weighted vertex normals as
-`nx ny nz`.  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
+`nx ny nz`; --simplify RES merges the vertices of every voxel of edge RES after the selection
+(`mesh_ops.simplify_vertex_clustering`: at their mean, or with --contraction quadric at the minimum of the voxel's error
+quadric).  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
 with a clean stage its statistics (of the welded mesh: clusters, degenerate triangles, boundary and non-manifold edges;
-n_min; the triangles kept)."""
+n_min; the triangles kept; the counts of the simplification)."""
 import argparse
 import json
 import os
@@ -41,6 +44,9 @@ def main():
     ap.add_argument("--keep-clusters", type=int, default=None, help="weld, then keep the K largest clusters of triangles")
     ap.add_argument("--min-triangles", type=int, default=50, help="... and every cluster of at least N triangles (with --keep-clusters)")
     ap.add_argument("--normals", action="store_true", help="weld and write area-weighted vertex normals")
+    ap.add_argument("--simplify", type=float, default=None, help="weld, then merge the vertices of every voxel of this edge (metres)")
+    ap.add_argument("--contraction", choices=("average", "quadric"), default="average", help="where a merged vertex goes (with --simplify)")
+    ap.add_argument("--regularisation", type=float, default=1e-3, help="pull of the quadric placement towards the mean (with --simplify)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -50,7 +56,7 @@ def main():
                                    min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist, use_median_depth=a.use_median_depth,
                                    min_weight=a.min_weight, seed=a.seed, device=a.device, details=True, image_height=a.image_height,
                                    image_width=a.image_width, keep_clusters=a.keep_clusters, min_triangles=a.min_triangles,
-                                   normals=a.normals)
+                                   normals=a.normals, simplify=a.simplify, contraction=a.contraction, regularisation=a.regularisation)
     vertices, faces, normals = mesh[0], mesh[1], (mesh[2] if a.normals else None)
     if a.weld and "clean" not in det:
         vertices, faces = tsdf.weld_soup(vertices)
@@ -63,6 +69,9 @@ def main():
                                                       "n_min")}
         line["clean"]["triangles_kept"] = int(faces.shape[0])
         line["clean"]["normals"] = bool(a.normals)
+        if "simplify" in det["clean"]:
+            line["clean"]["simplify"] = {k: v for k, v in det["clean"]["simplify"].items() if k != "vmap"}
+            line["clean"]["simplify"].update(voxel=a.simplify, contraction=a.contraction)
     print(json.dumps(line))
 
 
