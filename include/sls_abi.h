@@ -893,6 +893,32 @@ int sls_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces,
                       double regularisation, float *out_vertices, int32_t *out_faces, int32_t *out_vmap, uint32_t *out_status,
                       void *scratch, size_t scratch_bytes, void *stream);
 
+/* The edge graph of a mesh and smoothing over it (include/sls_smooth_math.h states every rule; DESIGN.md section 2, "Mesh
+ * smoothing").  sls_mesh_adjacency: the DISTINCT neighbours of every vertex in ascending index, in CSR form — out_offsets
+ * (V + 1 words; unsigned 32-bit values, which pass 2^31 only for T above 357 913 941), out_neighbours (room for 6 T int32,
+ * the first 2 E written, E = the distinct undirected edges), out_boundary[v] = 1 iff v is an end of an edge that exactly one
+ * non-degenerate triangle owns.  Degenerate triangles (sls_mesh_degenerate; rows of -1 too) take no part: the calls run
+ * behind sls_mesh_filter and sls_mesh_simplify at capacity.
+ * sls_mesh_smooth: `iterations` sweeps of method 0 (simple: Open3D's filter_smooth_simple), 1 (laplacian: steps of factor
+ * lambda) or 2 (taubin: a step of factor lambda, then one of factor mu, per iteration) with weights 0 (uniform) or 1
+ * (inverse distance); a vertex without a neighbour, and with fix_boundary a boundary vertex, is copied bit for bit.  The
+ * adjacency is built inside the scratch, the sweeps ping-pong between two float4 buffers of the scratch and the last one
+ * writes out_vertices (V x 3; iterations == 0 copies `vertices`); nothing is read back.  Every sum is float64 in a fixed
+ * order: equal to the header run on the host bit for bit.  The conventions of the mesh cleaning calls apply; additionally
+ * SLS_E_ARG for out_vertices == vertices, a negative `iterations`, an unknown method or weights, a lambda or mu that is not
+ * finite.
+ *   out_status (8 words) = [live vertices (those with a neighbour), E, boundary vertices, live vertices with a non-finite
+ *   coordinate (sls_mesh_smooth alone; not 0: out_vertices is unspecified), degenerate triangles (both kinds), those of
+ *   them with an index outside [0, V), the largest number of neighbours of a vertex, 1].
+ *   V == 0 or T == 0 writes [0, 0, 0, 0, 0, 0, 0, 1]; out_offsets and out_boundary are zeros, out_vertices = vertices. */
+size_t sls_mesh_adjacency_scratch_bytes(int V, int T);
+int sls_mesh_adjacency(int V, int T, const int32_t *faces, int32_t *out_offsets, int32_t *out_neighbours, uint8_t *out_boundary,
+                       uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+size_t sls_mesh_smooth_scratch_bytes(int V, int T);
+int sls_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces, int method, int weights, int iterations, double lambda,
+                    double mu, int fix_boundary, float *out_vertices, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                    void *stream);
+
 /* visible[i] = 1 if surfel centre i survives the near cut (radii would be >0
  * unless it is off-image). */
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible,

@@ -9,6 +9,7 @@
 
 #include "sls_consumer_dev.hpp"
 #include "sls_launch.hpp"
+#include "../../include/sls_smooth_math.h"
 
 namespace sls {
 
@@ -37,7 +38,7 @@ DebugState &debug_state()
 static const char *kTimerNames[T_COUNT] = {
     "preprocess_fwd", "scan", "emit_keys", "sort_hist", "sort_rowscan", "sort_scatter", "tile_ranges",
     "render_fwd", "grec_memset", "render_bwd", "preprocess_bwd", "adam", "knn", "consumer", "resort", "bin_count", "bin_direct",
-    "simp_cluster", "simp_faces", "simp_corners", "simp_place"
+    "simp_cluster", "simp_faces", "simp_corners", "simp_place", "smooth_adjacency", "smooth_step"
 };
 constexpr int kTimerPool = 8192;
 struct TimerState {
@@ -595,6 +596,8 @@ size_t sls_mesh_clusters_scratch_bytes(int T) { return mesh_clusters_scratch_byt
 size_t sls_mesh_filter_scratch_bytes(int V, int T) { return mesh_filter_scratch_bytes(V, T); }
 size_t sls_mesh_vertex_normals_scratch_bytes(int V, int T) { return mesh_normals_scratch_bytes(V, T); }
 size_t sls_mesh_simplify_scratch_bytes(int V, int T) { return mesh_simplify_scratch_bytes(V, T); }
+size_t sls_mesh_adjacency_scratch_bytes(int V, int T) { return mesh_adjacency_scratch_bytes(V, T); }
+size_t sls_mesh_smooth_scratch_bytes(int V, int T) { return mesh_smooth_scratch_bytes(V, T); }
 
 // status words: `zeros` zeros, then `value` (optional), then the 1 that says "written"
 static int mesh_empty_status(uint32_t *out_status, int zeros, int has_value, uint32_t value, hipStream_t st)
@@ -679,6 +682,46 @@ int sls_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces,
     SLS_MESH_SCRATCH("sls_mesh_simplify", mesh_simplify_scratch_bytes(V, T));
     return launch_mesh_simplify(V, vertices, T, faces, voxel_size, contraction, regularisation, out_vertices, out_faces, out_vmap,
                                 out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_mesh_adjacency(int V, int T, const int32_t *faces, int32_t *out_offsets, int32_t *out_neighbours, uint8_t *out_boundary,
+                       uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    if (V == 0 || T == 0) {                         // no edge: every row is empty
+        SLS_REQUIRE(V == 0 || (out_offsets && out_boundary), "null pointer");
+        if (out_offsets) SLS_HIP_CHECK(hipMemsetAsync(out_offsets, 0, sizeof(int32_t) * ((size_t)V + 1), (hipStream_t)stream));
+        if (V > 0) SLS_HIP_CHECK(hipMemsetAsync(out_boundary, 0, (size_t)V, (hipStream_t)stream));
+        return mesh_empty_status(out_status, 7, 0, 0u, (hipStream_t)stream);
+    }
+    SLS_REQUIRE(faces && out_offsets && out_neighbours && out_boundary && out_status && scratch, "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_adjacency", mesh_adjacency_scratch_bytes(V, T));
+    return launch_mesh_adjacency(V, T, faces, out_offsets, out_neighbours, out_boundary, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces, int method, int weights, int iterations, double lambda,
+                    double mu, int fix_boundary, float *out_vertices, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                    void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    SLS_REQUIRE(method == SLS_SMOOTH_SIMPLE || method == SLS_SMOOTH_LAPLACIAN || method == SLS_SMOOTH_TAUBIN,
+                "method must be 0 (simple), 1 (laplacian) or 2 (taubin)");
+    SLS_REQUIRE(weights == SLS_SMOOTH_UNIFORM || weights == SLS_SMOOTH_INVERSE_DISTANCE, "weights must be 0 (uniform) or 1 (inverse distance)");
+    SLS_REQUIRE(iterations >= 0, "iterations must be >= 0");
+    SLS_REQUIRE(fabs(lambda) <= DBL_MAX && fabs(mu) <= DBL_MAX, "lambda and mu must be finite");
+    SLS_REQUIRE(!(vertices && out_vertices == vertices), "out_vertices must not be vertices");
+    if (V == 0 || T == 0) {                         // no vertex is live: every one is copied
+        SLS_REQUIRE(V == 0 || (vertices && out_vertices), "null pointer");
+        if (V > 0)
+            SLS_HIP_CHECK(hipMemcpyAsync(out_vertices, vertices, 3 * sizeof(float) * (size_t)V, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return mesh_empty_status(out_status, 7, 0, 0u, (hipStream_t)stream);
+    }
+    SLS_REQUIRE(vertices && faces && out_vertices && out_status && scratch, "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_smooth", mesh_smooth_scratch_bytes(V, T));
+    return launch_mesh_smooth(V, vertices, T, faces, method, weights, iterations, lambda, mu, fix_boundary, out_vertices, out_status,
+                              scratch, (hipStream_t)stream);
 }
 
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible, void *stream)

@@ -40,6 +40,7 @@ enum TimerSlot {
     T_PREPROCESS_FWD = 0, T_SCAN, T_EMIT_KEYS, T_SORT_HIST, T_SORT_ROWSCAN, T_SORT_SCATTER, T_TILE_RANGES,
     T_RENDER_FWD, T_GREC_MEMSET, T_RENDER_BWD, T_PREPROCESS_BWD, T_ADAM, T_KNN, T_CONSUMER, T_RESORT, T_BIN_COUNT, T_BIN_DIRECT,
     T_SIMP_CLUSTER, T_SIMP_FACES, T_SIMP_CORNERS, T_SIMP_PLACE,     // sls_simplify.hip: groups of launches (its sorts: T_SORT_*)
+    T_SMOOTH_ADJACENCY, T_SMOOTH_STEP,                              // sls_smooth.hip: groups of launches (its sort: T_SORT_*)
     T_COUNT
 };
 // Debug / tuning switches (sls_debug_wave_cycles, sls_timing_*): ONE set per process, relaxed atomics — a backward

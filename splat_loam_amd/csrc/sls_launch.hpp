@@ -221,6 +221,14 @@ size_t mesh_simplify_scratch_bytes(int V, int T);
 int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces, double voxel_size, int contraction,
                          double regularisation, float *out_vertices, int32_t *out_faces, int32_t *out_vmap, uint32_t *out_status,
                          void *scratch, hipStream_t st);
+// ---- sls_smooth.hip (the arguments are checked by the caller, sls_api.hip) -----------------------------------------
+size_t mesh_adjacency_scratch_bytes(int V, int T);
+int launch_mesh_adjacency(int V, int T, const int32_t *faces, int32_t *out_offsets, int32_t *out_neighbours, uint8_t *out_boundary,
+                          uint32_t *out_status, void *scratch, hipStream_t st);
+size_t mesh_smooth_scratch_bytes(int V, int T);
+int launch_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces, int method, int weights, int iterations,
+                       double lambda, double mu, int fix_boundary, float *out_vertices, uint32_t *out_status, void *scratch,
+                       hipStream_t st);
 int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_raw, float smax, float pen,
                           const uint32_t *status_block, uint64_t *bitmap, hipStream_t st);
 int launch_adam(const SlsAdamGroup *groups, int ngroups, double beta1, double beta2, double eps, int64_t step,

@@ -6,12 +6,16 @@
 and those above a floor of triangles and compacts the mesh (sls_mesh_filter: the post-processing of the 2DGS mesher),
 `vertex_normals` gives every vertex its area-weighted normal (sls_mesh_vertex_normals: Open3D's
 `compute_vertex_normals`), `simplify_vertex_clustering` makes the mesh smaller (sls_mesh_simplify: Open3D's
-`simplify_vertex_clustering`, average or quadric contraction), `clean_mesh` chains them.  include/sls_mesh_math.h and
-include/sls_simplify_math.h state every rule, DESIGN.md section 2 ("Mesh cleaning", "Mesh simplification") the contract,
-tests/mesh_ref.py and tests/simplify_ref.py restate it in NumPy.  Device tensors only; there is no CPU path.
+`simplify_vertex_clustering`, average or quadric contraction), `vertex_adjacency` gives every vertex its distinct
+neighbours in CSR form and `smooth` moves every vertex towards them (sls_mesh_adjacency, sls_mesh_smooth: Open3D's
+`filter_smooth_taubin`, `filter_smooth_laplacian`, `filter_smooth_simple`), `clean_mesh` chains them.
+include/sls_mesh_math.h, include/sls_simplify_math.h and include/sls_smooth_math.h state every rule, DESIGN.md section 2
+("Mesh cleaning", "Mesh simplification", "Mesh smoothing") the contract, tests/mesh_ref.py, tests/simplify_ref.py and
+tests/smooth_ref.py restate it in NumPy.  Device tensors only; there is no CPU path.
 
-Host reads: `weld`, `cluster_triangles`, `keep_clusters`, `simplify_vertex_clustering` and `clean_mesh` one each (the
-status words, read once at the end: outputs are allocated at capacity and sliced), `vertex_normals` none.
+Host reads: `weld`, `cluster_triangles`, `keep_clusters`, `simplify_vertex_clustering`, `vertex_adjacency`, `smooth` and
+`clean_mesh` one each (the status words, read once at the end: outputs are allocated at capacity and sliced),
+`vertex_normals` none.
 """
 from __future__ import annotations
 
@@ -136,6 +140,47 @@ def _simplify_errors(w, voxel_size):
         raise ValueError(f"{int(w[2])} vertices that a triangle references hold a non-finite coordinate")
     if w[3]:
         raise ValueError(f"{int(w[3])} vertices lie 2^21 voxels or more from the mesh's minimum: voxel_size {voxel_size} is too small")
+
+
+SMOOTH_METHODS = {"simple": 0, "laplacian": 1, "taubin": 2}
+SMOOTH_WEIGHTS = {"uniform": 0, "inverse_distance": 1}
+
+
+def _smooth_args(iterations, method, weights, lambda_, mu):
+    if method not in SMOOTH_METHODS:
+        raise ValueError(f"method must be one of {sorted(SMOOTH_METHODS)}, not {method!r}")
+    if weights not in SMOOTH_WEIGHTS:
+        raise ValueError(f"weights must be one of {sorted(SMOOTH_WEIGHTS)}, not {weights!r}")
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 0:
+        raise ValueError("iterations must be an integer >= 0")
+    lambda_, mu = float(lambda_), float(mu)
+    if not (np.isfinite(lambda_) and np.isfinite(mu)):
+        raise ValueError("lambda_ and mu must be finite")
+    return int(iterations), SMOOTH_METHODS[method], SMOOTH_WEIGHTS[weights], lambda_, mu
+
+
+def _smooth_launch(vertices, faces, iterations, method, weights, lambda_, mu, fix_boundary, status):
+    """-> vertices (V,3): every row written; status: 8 words.  `method` and `weights` are the integers of the C entry."""
+    lib, dev, V, T = _abi.lib(), vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    nbytes = int(lib.sls_mesh_smooth_scratch_bytes(V, T))
+    hold, ptr = _scratch(nbytes, dev)
+    _abi.check(lib.sls_mesh_smooth(V, vertices.data_ptr(), T, faces.data_ptr(), int(method), int(weights), int(iterations), float(lambda_),
+                                   float(mu), int(bool(fix_boundary)), out.data_ptr(), status.data_ptr(), ptr, nbytes, _stream(dev)),
+               "sls_mesh_smooth")
+    return out
+
+
+def _smooth_details(w):
+    return {"live": int(w[0]), "edges": int(w[1]), "boundary": int(w[2]), "nonfinite": int(w[3]), "degenerate": int(w[4]),
+            "out_of_range": int(w[5]), "max_row": int(w[6])}
+
+
+def _smooth_errors(w, ranges=True):
+    if ranges and w[5]:
+        raise _range_error(int(w[5]))
+    if w[3]:
+        raise ValueError(f"{int(w[3])} vertices that a triangle references hold a non-finite coordinate")
 
 
 def _status(dev, n):
@@ -278,14 +323,78 @@ def simplify_vertex_clustering(vertices: torch.Tensor, faces: torch.Tensor, voxe
 
 
 @torch.no_grad()
+def vertex_adjacency(faces: torch.Tensor, n_vertices: int, details: bool = False):
+    """The edge graph of a mesh in CSR form, on the device: `(offsets (V+1,) int32, neighbours (2E,) int32, boundary (V,)
+    uint8)`.  `neighbours[offsets[v]:offsets[v+1]]` are the DISTINCT vertices that share an edge of a triangle with v, in
+    ascending index (a repeated triangle, the opposite orientation and a non-manifold edge add nothing twice);
+    `boundary[v]` is 1 iff v is an end of an edge that exactly one triangle owns.  Triangles with a repeated index (and rows
+    of -1) take no part; a face index outside [0, n_vertices) raises.  `details=True` adds dict(live, edges, boundary,
+    degenerate, out_of_range, max_row).  One host read (the status words, for E)."""
+    faces = _device_faces(faces, "faces")
+    dev, V, T = faces.device, int(n_vertices), int(faces.shape[0])
+    if V < 0:
+        raise ValueError("n_vertices must be >= 0")
+    lib = _abi.lib()
+    with torch.cuda.device(dev):
+        status = _status(dev, 8)
+        offsets = torch.empty((V + 1,), dtype=torch.int32, device=dev)
+        neighbours = torch.empty((6 * T,), dtype=torch.int32, device=dev)
+        boundary = torch.empty((V,), dtype=torch.uint8, device=dev)
+        nbytes = int(lib.sls_mesh_adjacency_scratch_bytes(V, T))
+        hold, ptr = _scratch(nbytes, dev)
+        _abi.check(lib.sls_mesh_adjacency(V, T, faces.data_ptr(), offsets.data_ptr(), neighbours.data_ptr(), boundary.data_ptr(),
+                                          status.data_ptr(), ptr, nbytes, _stream(dev)), "sls_mesh_adjacency")
+        w = _words(status)                                          # the one host read
+    if w[5]:
+        raise _range_error(int(w[5]))
+    out = (offsets, neighbours[:2 * int(w[1])], boundary)
+    if details:
+        d = _smooth_details(w)
+        del d["nonfinite"]                                          # (the call sees no positions)
+        return out + (d,)
+    return out
+
+
+@torch.no_grad()
+def smooth(vertices: torch.Tensor, faces: torch.Tensor, iterations: int, method: str = "taubin", weights: str = "inverse_distance",
+           lambda_: float = 0.5, mu: float = -0.53, fix_boundary: bool = False, details: bool = False):
+    """The vertices (V,3) float32 after `iterations` smoothing sweeps over the edge graph; the faces stay as they are.
+    `method="laplacian"`: every sweep moves a vertex by `lambda_` times the way to the weighted mean of its neighbours
+    (Open3D's `filter_smooth_laplacian`); `"taubin"`: a sweep with `lambda_`, then one with `mu` (negative: it undoes the
+    shrinkage; `filter_smooth_taubin`); `"simple"`: the mean of the vertex and its neighbours (`filter_smooth_simple`,
+    `weights` is not used).  `weights="inverse_distance"` weighs a neighbour by 1 / (distance + 1e-12), `"uniform"` by 1.
+    The neighbours are those of `vertex_adjacency`, the same for all sweeps; a vertex without one is copied bit for bit, and
+    with `fix_boundary` so is every boundary vertex.  A referenced vertex with a non-finite coordinate raises, so does a face
+    index outside the vertices.  `details=True` appends dict(live, edges, boundary, nonfinite, degenerate, out_of_range,
+    max_row).  Bit-reproducible (float64 sums in a fixed order, no atomics): equal to include/sls_smooth_math.h run on the
+    host.  One host read (the status words)."""
+    vertices = _device_points(vertices, "vertices")
+    faces = _device_faces(faces, "faces")
+    dev = vertices.device
+    if faces.device != dev:
+        raise ValueError("vertices and faces must live on the same device")
+    iterations, method, weights, lambda_, mu = _smooth_args(iterations, method, weights, lambda_, mu)
+    with torch.cuda.device(dev):
+        status = _status(dev, 8)
+        out = _smooth_launch(vertices, faces, iterations, method, weights, lambda_, mu, fix_boundary, status)
+        w = _words(status)                                          # the one host read
+    _smooth_errors(w)
+    return (out, _smooth_details(w)) if details else out
+
+
+@torch.no_grad()
 def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True, keep_clusters: int = 1, min_triangles: int = 50,
                normals: bool = True, details: bool = False, simplify: float = None, contraction: str = "average",
-               regularisation: float = 1e-3):
-    """Weld, keep the largest clusters, optionally simplify, compute vertex normals: `(vertices, faces)` or, with `normals`,
+               regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin",
+               smooth_weights: str = "inverse_distance", smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
+               fix_boundary: bool = False):
+    """Weld, keep the largest clusters, optionally simplify and smooth, compute vertex normals: `(vertices, faces)` or, with `normals`,
     `(vertices, faces, normals)`; `details=True` appends the dict of `keep_clusters` (the statistics are those of the
     welded mesh before the selection) plus `welded_vertices`.  `simplify=h` runs `simplify_vertex_clustering(h, contraction,
     regularisation)` after the selection and before the normals (`details` then holds its dict under "simplify", with `vmap`
-    over the vertices at the selection's capacity); `simplify=None`: no such stage.  `weld=True` merges the bit-equal rows of `vertices` and passes the faces
+    over the vertices at the selection's capacity); `simplify=None`: no such stage.  `smooth=n` runs `smooth(n, smooth_method,
+    smooth_weights, smooth_lambda, smooth_mu, fix_boundary)` after the simplification and before the normals (`details` then
+    holds its dict under "smooth"); `smooth=None`: no such stage.  `weld=True` merges the bit-equal rows of `vertices` and passes the faces
     through their ranks: for a soup (`faces` = arange) that is `weld`.  `keep_clusters=None`: no selection.  One host read for
     the whole chain: every stage runs at the capacity of its input (vertices beyond the welded count are referenced by
     nothing, face rows beyond the kept count are -1 and skipped), and the outputs are sliced at the end."""
@@ -298,8 +407,10 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
     select = keep_clusters is not None
     if simplify is not None:
         simplify, code, regularisation = _simplify_args(simplify, contraction, regularisation)
+    if smooth is not None:
+        smooth, s_method, s_weights, smooth_lambda, smooth_mu = _smooth_args(smooth, smooth_method, smooth_weights, smooth_lambda, smooth_mu)
     with torch.cuda.device(dev):
-        status = _status(dev, 32)
+        status = _status(dev, 40)
         status[0] = int(vertices.shape[0])                          # (without a weld: V as it came)
         v, f = vertices, faces
         if weld:
@@ -315,6 +426,8 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
             v, f = _filter_launch(v, f, labels, counts, status[8:16], keep_clusters, min_triangles, status[16:20])
         if simplify is not None:
             v, f, vmap = _simplify_launch(v, f, simplify, code, regularisation, status[24:32])
+        if smooth is not None:
+            v = _smooth_launch(v, f, smooth, s_method, s_weights, smooth_lambda, smooth_mu, fix_boundary, status[32:40])
         n = _normals_launch(v, f) if normals else None
         w = _words(status)                                          # the one host read
     if w[10]:
@@ -323,11 +436,15 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
     if simplify is not None:
         _simplify_errors(w[24:], simplify)
         nv, nt = int(w[24]), int(w[25])
+    if smooth is not None:
+        _smooth_errors(w[32:], ranges=False)                        # (rows of -1 beyond the kept triangles are no error here)
     out = (v[:nv], f[:nt]) + ((n[:nv],) if normals else ())
     if details:
         d = _cluster_details(w[8:])
         d.update(cluster_count=counts[:int(w[8])], labels=labels, n_min=int(w[18]) if select else 0, welded_vertices=int(w[0]))
         if simplify is not None:
             d["simplify"] = dict(_simplify_details(w[24:]), vmap=vmap)
+        if smooth is not None:
+            d["smooth"] = _smooth_details(w[32:])
         return out + (d,)
     return out

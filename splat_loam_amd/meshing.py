@@ -240,7 +240,8 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
               min_opacity: float = 0.5, max_depth_dist: float = 0.1, use_median_depth: bool = False, min_weight: float = 1.0,
               seed=None, device="cuda", details: bool = False, image_height=None, image_width=None, keep_clusters=None,
               min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
-              regularisation: float = 1e-3):
+              regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
+              smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False):
     """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
     frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
 
@@ -251,7 +252,10 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     `stage_ms` a "clean" lap.  `simplify=h` (metres; a multiple of `voxel_size` is the natural choice) also runs the clean
     stage and, after the selection, `mesh_ops.simplify_vertex_clustering(h, contraction, regularisation)`: the vertices of
     every voxel of edge h become one, at their mean ("average") or at the minimum of the voxel's error quadric ("quadric");
-    `details["clean"]["simplify"]` holds its counts.  With the defaults nothing of this runs and the soup is returned as it
+    `details["clean"]["simplify"]` holds its counts.  `smooth=n` also runs the clean stage and, before the normals, n sweeps
+    of `mesh_ops.smooth(n, smooth_method, smooth_weights, smooth_lambda, smooth_mu, fix_boundary)` over the edge graph
+    (Taubin by default: the terraces and the per-voxel jitter of a nearest-pixel fusion go, the faces stay);
+    `details["clean"]["smooth"]` holds its counts.  With the defaults nothing of this runs and the soup is returned as it
     always was.
 
     Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
@@ -297,11 +301,13 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     vertices, faces = volume.extract(min_weight=min_weight)
     lap("extract")
     mesh, clean = (vertices, faces), None
-    if keep_clusters is not None or normals or simplify is not None:
+    if keep_clusters is not None or normals or simplify is not None or smooth is not None:
         from . import mesh_ops
         *mesh, clean = mesh_ops.clean_mesh(vertices, faces, weld=True, keep_clusters=keep_clusters, min_triangles=min_triangles,
                                            normals=normals, details=True, simplify=simplify, contraction=contraction,
-                                           regularisation=regularisation)
+                                           regularisation=regularisation, smooth=smooth, smooth_method=smooth_method,
+                                           smooth_weights=smooth_weights, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
+                                           fix_boundary=fix_boundary)
         mesh = tuple(mesh)
         lap("clean")
     if details:

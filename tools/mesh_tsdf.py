@@ -7,6 +7,7 @@ rendered depth of every keyframe fused into a sparse TSDF volume, the zero surfa
                               [--min-opacity A] [--max-depth-dist D] [--use-median-depth] [--min-weight W] [--weld]
                               [--keep-clusters K] [--min-triangles N] [--normals]
                               [--simplify RES [--contraction quadric] [--regularisation L]]
+                              [--smooth N [--smooth-method laplacian] [--smooth-weights uniform] [--fix-boundary]]
                               [--seed S] [--image-height H --image-width W]
 
 OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tools/eval_recon.py` takes as the estimate.
@@ -14,9 +15,10 @@ OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tool
 --min-triangles triangles (`mesh_ops.clean_mesh`: the floaters go); --normals adds area-weighted vertex normals as
 `nx ny nz`; --simplify RES merges the vertices of every voxel of edge RES after the selection
 (`mesh_ops.simplify_vertex_clustering`: at their mean, or with --contraction quadric at the minimum of the voxel's error
-quadric).  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
+quadric); --smooth N runs N smoothing sweeps over the edge graph before the normals (`mesh_ops.smooth`: Taubin with
+inverse-distance weights unless told otherwise; --fix-boundary leaves the boundary vertices where they are).  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
 with a clean stage its statistics (of the welded mesh: clusters, degenerate triangles, boundary and non-manifold edges;
-n_min; the triangles kept; the counts of the simplification)."""
+n_min; the triangles kept; the counts of the simplification and of the smoothing)."""
 import argparse
 import json
 import os
@@ -47,6 +49,10 @@ def main():
     ap.add_argument("--simplify", type=float, default=None, help="weld, then merge the vertices of every voxel of this edge (metres)")
     ap.add_argument("--contraction", choices=("average", "quadric"), default="average", help="where a merged vertex goes (with --simplify)")
     ap.add_argument("--regularisation", type=float, default=1e-3, help="pull of the quadric placement towards the mean (with --simplify)")
+    ap.add_argument("--smooth", type=int, default=None, help="weld, then run N smoothing sweeps over the edge graph")
+    ap.add_argument("--smooth-method", choices=("taubin", "laplacian", "simple"), default="taubin", help="the sweep (with --smooth)")
+    ap.add_argument("--smooth-weights", choices=("inverse_distance", "uniform"), default="inverse_distance", help="neighbour weights (with --smooth)")
+    ap.add_argument("--fix-boundary", action="store_true", help="leave the boundary vertices where they are (with --smooth)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -56,7 +62,9 @@ def main():
                                    min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist, use_median_depth=a.use_median_depth,
                                    min_weight=a.min_weight, seed=a.seed, device=a.device, details=True, image_height=a.image_height,
                                    image_width=a.image_width, keep_clusters=a.keep_clusters, min_triangles=a.min_triangles,
-                                   normals=a.normals, simplify=a.simplify, contraction=a.contraction, regularisation=a.regularisation)
+                                   normals=a.normals, simplify=a.simplify, contraction=a.contraction, regularisation=a.regularisation,
+                                   smooth=a.smooth, smooth_method=a.smooth_method, smooth_weights=a.smooth_weights,
+                                   fix_boundary=a.fix_boundary)
     vertices, faces, normals = mesh[0], mesh[1], (mesh[2] if a.normals else None)
     if a.weld and "clean" not in det:
         vertices, faces = tsdf.weld_soup(vertices)
@@ -72,6 +80,9 @@ def main():
         if "simplify" in det["clean"]:
             line["clean"]["simplify"] = {k: v for k, v in det["clean"]["simplify"].items() if k != "vmap"}
             line["clean"]["simplify"].update(voxel=a.simplify, contraction=a.contraction)
+        if "smooth" in det["clean"]:
+            line["clean"]["smooth"] = dict(det["clean"]["smooth"], iterations=a.smooth, method=a.smooth_method, weights=a.smooth_weights,
+                                           fix_boundary=bool(a.fix_boundary))
     print(json.dumps(line))
 
 
