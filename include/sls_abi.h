@@ -919,6 +919,34 @@ int sls_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces, i
                     double mu, int fix_boundary, float *out_vertices, uint32_t *out_status, void *scratch, size_t scratch_bytes,
                     void *stream);
 
+/* Hole filling (include/sls_fill_math.h states every rule; DESIGN.md section 2, "Mesh hole filling").  Both calls take the
+ * mesh at capacity — V vertex rows, T face rows — and optionally in_counts, two device words [V_live, T_live] (each clamped
+ * to its capacity; null: V and T): rows beyond them are ignored, which lets the calls run behind sls_mesh_filter without a
+ * host read.  Degeneracy is judged against V_live.
+ * sls_mesh_boundary_loops: out_halfedges (room for 3 T pairs of int32): the B boundary half-edges (a, b) in ascending
+ * (a, b); out_loop (room for 3 T int32): the loop of every half-edge, -1 for an open one; out_loop_edges (room for T
+ * int32): the half-edges of every loop.  Loops are numbered in ascending order of their lowest vertex.
+ * sls_mesh_fill_holes: every loop of at most max_edges half-edges, with finite vertices and (max_size > 0) a bounding-box
+ * diagonal of at most max_size, is closed — a loop of three by one triangle, a longer one by a fan over its float64
+ * centroid.  out_vertices (cap_vertices x 3): the V_live rows, then the new vertices; out_faces (cap_triangles x 3): the
+ * T_live rows, then the new triangles, then rows of -1.  Where the needed rows exceed either capacity nothing is filled:
+ * the outputs are the live input, and status word 14 is 1.  Every sum is float64 in a fixed order: equal to the header run
+ * on the host bit for bit.  The conventions of the mesh cleaning calls apply; additionally SLS_E_ARG for max_edges < 3, a
+ * max_size that is not finite and >= 0, cap_vertices < V or cap_triangles < T, a capacity above the SLS_MESH_MAX_* limits,
+ * out_vertices == vertices or out_faces == faces.
+ *   out_status (16 words) = [V', T', B, loops, filled loops, loops skipped for max_edges, for max_size, for a non-finite
+ *   vertex, open half-edges, complex vertices, degenerate live triangles (both kinds), those of them with an index outside
+ *   the live vertices, needed vertices, needed triangles, overflow, 1]; sls_mesh_boundary_loops leaves words 0, 1, 4 to 7
+ *   and 12 to 14 at 0.  V == 0 or T == 0: no half-edge; words 10 and 11 are T_live where V == 0; the fill copies the live
+ *   rows and pads the faces. */
+size_t sls_mesh_boundary_loops_scratch_bytes(int V, int T);
+int sls_mesh_boundary_loops(int V, int T, const int32_t *faces, const uint32_t *in_counts, int32_t *out_halfedges, int32_t *out_loop,
+                            int32_t *out_loop_edges, uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+size_t sls_mesh_fill_holes_scratch_bytes(int V, int T);
+int sls_mesh_fill_holes(int V, const float *vertices, int T, const int32_t *faces, const uint32_t *in_counts, int max_edges,
+                        double max_size, int cap_vertices, float *out_vertices, int cap_triangles, int32_t *out_faces,
+                        uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+
 /* visible[i] = 1 if surfel centre i survives the near cut (radii would be >0
  * unless it is off-image). */
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible,

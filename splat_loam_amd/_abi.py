@@ -188,6 +188,11 @@ _PROTOS = {
     "sls_mesh_smooth_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_mesh_smooth": (C.c_int, [C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _VP, _VP, _VP,
                                   C.c_size_t, _VP]),
+    "sls_mesh_boundary_loops_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_mesh_boundary_loops": (C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_mesh_fill_holes_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_mesh_fill_holes": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_double, C.c_int, _VP, C.c_int, _VP, _VP, _VP, C.c_size_t,
+                                      _VP]),
     "sls_mark_visible": (C.c_int, [C.POINTER(SlsCamera), C.c_int, _VP, _VP, _VP]),
     "sls_aligner_workspace_bytes": (C.c_size_t, []),
     "sls_aligner_normals": (C.c_int, [C.POINTER(SlsCamera), _VP, _VP, C.c_float, _VP, _VP]),

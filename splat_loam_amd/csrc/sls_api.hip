@@ -598,6 +598,8 @@ size_t sls_mesh_vertex_normals_scratch_bytes(int V, int T) { return mesh_normals
 size_t sls_mesh_simplify_scratch_bytes(int V, int T) { return mesh_simplify_scratch_bytes(V, T); }
 size_t sls_mesh_adjacency_scratch_bytes(int V, int T) { return mesh_adjacency_scratch_bytes(V, T); }
 size_t sls_mesh_smooth_scratch_bytes(int V, int T) { return mesh_smooth_scratch_bytes(V, T); }
+size_t sls_mesh_boundary_loops_scratch_bytes(int V, int T) { return mesh_fill_scratch_bytes(V, T); }
+size_t sls_mesh_fill_holes_scratch_bytes(int V, int T) { return mesh_fill_scratch_bytes(V, T); }
 
 // status words: `zeros` zeros, then `value` (optional), then the 1 that says "written"
 static int mesh_empty_status(uint32_t *out_status, int zeros, int has_value, uint32_t value, hipStream_t st)
@@ -722,6 +724,42 @@ int sls_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces, i
     SLS_MESH_SCRATCH("sls_mesh_smooth", mesh_smooth_scratch_bytes(V, T));
     return launch_mesh_smooth(V, vertices, T, faces, method, weights, iterations, lambda, mu, fix_boundary, out_vertices, out_status,
                               scratch, (hipStream_t)stream);
+}
+
+int sls_mesh_boundary_loops(int V, int T, const int32_t *faces, const uint32_t *in_counts, int32_t *out_halfedges, int32_t *out_loop,
+                            int32_t *out_loop_edges, uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    if (V == 0 || T == 0)                           // no half-edge
+        return launch_mesh_fill_empty(V, nullptr, T, nullptr, in_counts, 0, nullptr, 0, nullptr, out_status, (hipStream_t)stream);
+    SLS_REQUIRE(faces && out_halfedges && out_loop && out_loop_edges && out_status && scratch, "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_boundary_loops", mesh_fill_scratch_bytes(V, T));
+    return launch_mesh_boundary_loops(V, T, faces, in_counts, out_halfedges, out_loop, out_loop_edges, out_status, scratch,
+                                      (hipStream_t)stream);
+}
+
+int sls_mesh_fill_holes(int V, const float *vertices, int T, const int32_t *faces, const uint32_t *in_counts, int max_edges,
+                        double max_size, int cap_vertices, float *out_vertices, int cap_triangles, int32_t *out_faces,
+                        uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(T >= 0 && T <= SLS_MESH_MAX_TRIANGLES, "T negative or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
+    SLS_REQUIRE(max_edges >= 3, "max_edges must be >= 3");
+    SLS_REQUIRE(max_size >= 0.0 && max_size <= DBL_MAX, "max_size must be finite and >= 0");
+    SLS_REQUIRE(cap_vertices >= V && cap_vertices <= SLS_MESH_MAX_VERTICES, "cap_vertices below V or above SLS_MESH_MAX_VERTICES");
+    SLS_REQUIRE(cap_triangles >= T && cap_triangles <= SLS_MESH_MAX_TRIANGLES, "cap_triangles below T or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(!(vertices && out_vertices == vertices), "out_vertices must not be vertices");
+    SLS_REQUIRE(!(faces && out_faces == faces), "out_faces must not be faces");
+    if (V == 0 || T == 0) {                         // no half-edge: the live rows are copied, the faces padded
+        SLS_REQUIRE((V == 0 || (vertices && out_vertices)) && (T == 0 || faces) && (cap_triangles == 0 || out_faces), "null pointer");
+        return launch_mesh_fill_empty(V, vertices, T, faces, in_counts, 1, out_vertices, cap_triangles, out_faces, out_status,
+                                      (hipStream_t)stream);
+    }
+    SLS_REQUIRE(vertices && faces && out_vertices && out_faces && out_status && scratch, "null pointer");
+    SLS_MESH_SCRATCH("sls_mesh_fill_holes", mesh_fill_scratch_bytes(V, T));
+    return launch_mesh_fill_holes(V, vertices, T, faces, in_counts, max_edges, max_size, cap_vertices, out_vertices, cap_triangles,
+                                  out_faces, out_status, scratch, (hipStream_t)stream);
 }
 
 int sls_mark_visible(const SlsCamera *cam, int N, const float *means3D, uint8_t *visible, void *stream)

@@ -229,6 +229,16 @@ size_t mesh_smooth_scratch_bytes(int V, int T);
 int launch_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces, int method, int weights, int iterations,
                        double lambda, double mu, int fix_boundary, float *out_vertices, uint32_t *out_status, void *scratch,
                        hipStream_t st);
+
+// ---- sls_fill.hip (the arguments are checked by the caller, sls_api.hip) -------------------------------------------
+size_t mesh_fill_scratch_bytes(int V, int T);
+int launch_mesh_boundary_loops(int V, int T, const int32_t *faces, const uint32_t *in_counts, int32_t *out_halfedges, int32_t *out_loop,
+                               int32_t *out_loop_edges, uint32_t *out_status, void *scratch, hipStream_t st);
+int launch_mesh_fill_holes(int V, const float *vertices, int T, const int32_t *faces, const uint32_t *in_counts, int max_edges,
+                           double max_size, int cap_vertices, float *out_vertices, int cap_triangles, int32_t *out_faces,
+                           uint32_t *out_status, void *scratch, hipStream_t st);
+int launch_mesh_fill_empty(int V, const float *vertices, int T, const int32_t *faces, const uint32_t *in_counts, int fills,
+                           float *out_vertices, int cap_triangles, int32_t *out_faces, uint32_t *out_status, hipStream_t st);
 int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_raw, float smax, float pen,
                           const uint32_t *status_block, uint64_t *bitmap, hipStream_t st);
 int launch_adam(const SlsAdamGroup *groups, int ngroups, double beta1, double beta2, double eps, int64_t step,

@@ -8,14 +8,18 @@ and those above a floor of triangles and compacts the mesh (sls_mesh_filter: the
 `compute_vertex_normals`), `simplify_vertex_clustering` makes the mesh smaller (sls_mesh_simplify: Open3D's
 `simplify_vertex_clustering`, average or quadric contraction), `vertex_adjacency` gives every vertex its distinct
 neighbours in CSR form and `smooth` moves every vertex towards them (sls_mesh_adjacency, sls_mesh_smooth: Open3D's
-`filter_smooth_taubin`, `filter_smooth_laplacian`, `filter_smooth_simple`), `clean_mesh` chains them.
-include/sls_mesh_math.h, include/sls_simplify_math.h and include/sls_smooth_math.h state every rule, DESIGN.md section 2
-("Mesh cleaning", "Mesh simplification", "Mesh smoothing") the contract, tests/mesh_ref.py, tests/simplify_ref.py and
-tests/smooth_ref.py restate it in NumPy.  Device tensors only; there is no CPU path.
+`filter_smooth_taubin`, `filter_smooth_laplacian`, `filter_smooth_simple`), `boundary_loops` lists the boundary half-edges
+of a mesh and the closed loops they form and `fill_holes` closes the small ones with a fan over their centroid
+(sls_mesh_boundary_loops, sls_mesh_fill_holes: no refinement, no fairing, and chains that meet at a non-manifold vertex
+stay open), `clean_mesh` chains them.
+include/sls_mesh_math.h, include/sls_simplify_math.h, include/sls_smooth_math.h and include/sls_fill_math.h state every
+rule, DESIGN.md section 2 ("Mesh cleaning", "Mesh simplification", "Mesh smoothing", "Mesh hole filling") the contract,
+tests/mesh_ref.py, tests/simplify_ref.py, tests/smooth_ref.py and tests/fill_ref.py restate it in NumPy.  Device tensors
+only; there is no CPU path.
 
-Host reads: `weld`, `cluster_triangles`, `keep_clusters`, `simplify_vertex_clustering`, `vertex_adjacency`, `smooth` and
-`clean_mesh` one each (the status words, read once at the end: outputs are allocated at capacity and sliced),
-`vertex_normals` none.
+Host reads: `weld`, `cluster_triangles`, `keep_clusters`, `simplify_vertex_clustering`, `vertex_adjacency`, `smooth`,
+`boundary_loops`, `fill_holes` and `clean_mesh` one each (the status words, read once at the end: outputs are allocated at
+capacity and sliced), `vertex_normals` none.
 """
 from __future__ import annotations
 
@@ -181,6 +185,56 @@ def _smooth_errors(w, ranges=True):
         raise _range_error(int(w[5]))
     if w[3]:
         raise ValueError(f"{int(w[3])} vertices that a triangle references hold a non-finite coordinate")
+
+
+FILL_STATUS = ("vertices", "triangles", "halfedges", "loops", "filled", "skipped_edges", "skipped_size", "skipped_nonfinite",
+               "open_halfedges", "complex_vertices", "degenerate", "out_of_range", "needed_vertices", "needed_triangles", "overflow")
+
+
+def _fill_args(max_edges, max_size, capacity):
+    if isinstance(max_edges, bool) or int(max_edges) != max_edges or max_edges < 3:
+        raise ValueError("max_edges must be an integer >= 3")
+    max_size = 0.0 if max_size is None else float(max_size)
+    if not (np.isfinite(max_size) and max_size >= 0):
+        raise ValueError("max_size must be finite and >= 0 (None or 0: no limit)")
+    capacity = float(capacity)
+    if not (np.isfinite(capacity) and capacity >= 0):
+        raise ValueError("capacity must be finite and >= 0")
+    return int(max_edges), max_size, capacity
+
+
+def _fill_room(V, T, capacity):
+    """(cap_vertices, cap_triangles): room for max(ceil(capacity T), 64) new triangles, and for the vertices they can bring —
+    a new vertex comes with at least four new triangles"""
+    cap_t = T + max(int(np.ceil(capacity * T)), 64)
+    return V + (cap_t - T) // 4 + 1, cap_t
+
+
+def _fill_launch(vertices, faces, in_counts, max_edges, max_size, capacity, status):
+    """-> (vertices at capacity (cap_v,3), faces at capacity (cap_t,3), rows past the written ones -1); status: 16 words.
+    `in_counts`: two int32 words on the device [V_live, T_live], or None."""
+    lib, dev, V, T = _abi.lib(), vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    cap_v, cap_t = _fill_room(V, T, capacity)
+    if cap_t > MAX_TRIANGLES:
+        raise ValueError(f"the room for {cap_t} triangles is above {MAX_TRIANGLES}")
+    out_v = torch.empty((cap_v, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((cap_t, 3), dtype=torch.int32, device=dev)
+    nbytes = int(lib.sls_mesh_fill_holes_scratch_bytes(V, T))
+    hold, ptr = _scratch(nbytes, dev)
+    _abi.check(lib.sls_mesh_fill_holes(V, vertices.data_ptr() if V else None, T, faces.data_ptr() if T else None,
+                                       in_counts.data_ptr() if in_counts is not None else None, int(max_edges), float(max_size), cap_v,
+                                       out_v.data_ptr(), cap_t, out_f.data_ptr(), status.data_ptr(), ptr if nbytes else None, nbytes,
+                                       _stream(dev)), "sls_mesh_fill_holes")
+    return out_v, out_f
+
+
+def _fill_details(w):
+    return {k: int(w[i]) for i, k in enumerate(FILL_STATUS)}
+
+
+def _fill_errors(w):
+    if w[14]:
+        raise ValueError(f"no room to fill the holes: {int(w[13])} triangles and {int(w[12])} vertices are needed; raise `capacity`")
 
 
 def _status(dev, n):
@@ -383,18 +437,89 @@ def smooth(vertices: torch.Tensor, faces: torch.Tensor, iterations: int, method:
 
 
 @torch.no_grad()
+def boundary_loops(faces: torch.Tensor, n_vertices: int, details: bool = False):
+    """The boundary of a mesh, on the device: `(halfedges (B,2) int32, loop (B,) int32, loop_edges (L,) int32)`.  A half-edge
+    a -> b of a triangle is a boundary half-edge iff exactly one triangle owns the undirected edge; they are listed in
+    ascending (a, b).  A vertex that exactly one of them leaves and exactly one enters is simple; chains through simple
+    vertices alone close into loops, numbered in ascending order of their lowest vertex: `loop[h]` is the loop of half-edge
+    h, -1 for an open one (a chain that touches a pinched vertex, a fin or a flipped triangle), `loop_edges[k]` the
+    half-edges of loop k.  Triangles with a repeated index (and rows of -1) take no part; a face index outside
+    [0, n_vertices) raises.  `details=True` adds dict(halfedges, loops, open_halfedges, complex_vertices, degenerate,
+    out_of_range).  One host read (the status words)."""
+    faces = _device_faces(faces, "faces")
+    dev, V, T = faces.device, int(n_vertices), int(faces.shape[0])
+    if V < 0:
+        raise ValueError("n_vertices must be >= 0")
+    lib = _abi.lib()
+    with torch.cuda.device(dev):
+        status = _status(dev, 16)
+        halfedges = torch.empty((3 * T, 2), dtype=torch.int32, device=dev)
+        loop = torch.empty((3 * T,), dtype=torch.int32, device=dev)
+        loop_edges = torch.empty((T,), dtype=torch.int32, device=dev)
+        nbytes = int(lib.sls_mesh_boundary_loops_scratch_bytes(V, T))
+        hold, ptr = _scratch(nbytes, dev)
+        _abi.check(lib.sls_mesh_boundary_loops(V, T, faces.data_ptr(), None, halfedges.data_ptr(), loop.data_ptr(), loop_edges.data_ptr(),
+                                               status.data_ptr(), ptr if nbytes else None, nbytes, _stream(dev)), "sls_mesh_boundary_loops")
+        w = _words(status)                                          # the one host read
+    if w[11]:
+        raise _range_error(int(w[11]))
+    B, L = int(w[2]), int(w[3])
+    out = (halfedges[:B], loop[:B], loop_edges[:L])
+    if details:
+        d = _fill_details(w)
+        return out + ({k: d[k] for k in ("halfedges", "loops", "open_halfedges", "complex_vertices", "degenerate", "out_of_range")},)
+    return out
+
+
+@torch.no_grad()
+def fill_holes(vertices: torch.Tensor, faces: torch.Tensor, max_edges: int = 64, max_size: float = None, capacity: float = 0.25,
+               details: bool = False):
+    """The mesh with its small holes closed: `(vertices (V',3), faces (T',3) int32)`.  Every loop of `boundary_loops` with at
+    most `max_edges` half-edges, finite vertices and (with `max_size`) an axis-aligned bounding box whose diagonal is at most
+    `max_size` is filled: a loop of three by one triangle, a longer one by a fan over a new vertex at the float64 mean of its
+    vertices, oriented like the triangles along the rim.  The input vertices and faces come first, unchanged; the new ones
+    follow in loop order.  It is a fan over a centroid and nothing more — no refinement, no fairing: a long or strongly
+    non-planar rim can fold the fan over itself, which is what the two limits are for (`smooth` afterwards evens out the
+    fans); open chains at complex vertices stay open.  The default of 64 edges is a judgement, not a measurement.
+    `capacity` is the room for new triangles as a share of T (at least 64 triangles); where it does not suffice the call
+    raises ValueError and names the triangles and vertices needed.  A face index outside the vertices raises.
+    `details=True` appends dict(vertices, triangles, halfedges, loops, filled, skipped_edges, skipped_size,
+    skipped_nonfinite, open_halfedges, complex_vertices, degenerate, out_of_range, needed_vertices, needed_triangles,
+    overflow).  Bit-reproducible (float64 sums in a fixed order, no float atomics): equal to include/sls_fill_math.h run on
+    the host.  One host read (the status words)."""
+    vertices = _device_points(vertices, "vertices")
+    faces = _device_faces(faces, "faces")
+    dev = vertices.device
+    if faces.device != dev:
+        raise ValueError("vertices and faces must live on the same device")
+    max_edges, max_size, capacity = _fill_args(max_edges, max_size, capacity)
+    with torch.cuda.device(dev):
+        status = _status(dev, 16)
+        out_v, out_f = _fill_launch(vertices, faces, None, max_edges, max_size, capacity, status)
+        w = _words(status)                                          # the one host read
+    if w[11]:
+        raise _range_error(int(w[11]))
+    _fill_errors(w)
+    out = (out_v[:int(w[0])], out_f[:int(w[1])])
+    return out + (_fill_details(w),) if details else out
+
+
+@torch.no_grad()
 def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True, keep_clusters: int = 1, min_triangles: int = 50,
                normals: bool = True, details: bool = False, simplify: float = None, contraction: str = "average",
                regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin",
                smooth_weights: str = "inverse_distance", smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
-               fix_boundary: bool = False):
-    """Weld, keep the largest clusters, optionally simplify and smooth, compute vertex normals: `(vertices, faces)` or, with `normals`,
+               fix_boundary: bool = False, fill_holes: int = None, fill_max_size: float = None, fill_capacity: float = 0.25):
+    """Weld, keep the largest clusters, optionally fill holes, simplify and smooth, compute vertex normals: `(vertices, faces)` or, with `normals`,
     `(vertices, faces, normals)`; `details=True` appends the dict of `keep_clusters` (the statistics are those of the
     welded mesh before the selection) plus `welded_vertices`.  `simplify=h` runs `simplify_vertex_clustering(h, contraction,
     regularisation)` after the selection and before the normals (`details` then holds its dict under "simplify", with `vmap`
     over the vertices at the selection's capacity); `simplify=None`: no such stage.  `smooth=n` runs `smooth(n, smooth_method,
     smooth_weights, smooth_lambda, smooth_mu, fix_boundary)` after the simplification and before the normals (`details` then
-    holds its dict under "smooth"); `smooth=None`: no such stage.  `weld=True` merges the bit-equal rows of `vertices` and passes the faces
+    holds its dict under "smooth"); `smooth=None`: no such stage.  `fill_holes=n` runs `fill_holes(max_edges=n, fill_max_size,
+    fill_capacity)` after the selection and before the simplification: its live counts are the device words of the earlier
+    stages, the later stages run at its capacity, `details` holds its dict under "fill", and too little room raises
+    ValueError; `fill_holes=None`: no such stage.  `weld=True` merges the bit-equal rows of `vertices` and passes the faces
     through their ranks: for a soup (`faces` = arange) that is `weld`.  `keep_clusters=None`: no selection.  One host read for
     the whole chain: every stage runs at the capacity of its input (vertices beyond the welded count are referenced by
     nothing, face rows beyond the kept count are -1 and skipped), and the outputs are sliced at the end."""
@@ -409,8 +534,10 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
         simplify, code, regularisation = _simplify_args(simplify, contraction, regularisation)
     if smooth is not None:
         smooth, s_method, s_weights, smooth_lambda, smooth_mu = _smooth_args(smooth, smooth_method, smooth_weights, smooth_lambda, smooth_mu)
+    if fill_holes is not None:
+        fill_holes, fill_max_size, fill_capacity = _fill_args(fill_holes, fill_max_size, fill_capacity)
     with torch.cuda.device(dev):
-        status = _status(dev, 40)
+        status = _status(dev, 56)
         status[0] = int(vertices.shape[0])                          # (without a weld: V as it came)
         v, f = vertices, faces
         if weld:
@@ -424,6 +551,12 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
         labels, counts = _clusters_launch(f, int(v.shape[0]), status[8:16])
         if select:
             v, f = _filter_launch(v, f, labels, counts, status[8:16], keep_clusters, min_triangles, status[16:20])
+        if fill_holes is not None:
+            if select:
+                live = status[16:18]                                # [V', T'] of the selection, on the device
+            else:
+                live = torch.stack([status[0], torch.tensor(T, dtype=torch.int32, device=dev)])
+            v, f = _fill_launch(v, f, live, fill_holes, fill_max_size, fill_capacity, status[40:56])
         if simplify is not None:
             v, f, vmap = _simplify_launch(v, f, simplify, code, regularisation, status[24:32])
         if smooth is not None:
@@ -433,6 +566,9 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
     if w[10]:
         raise _range_error(int(w[10]))
     nv, nt = (int(w[16]), int(w[17])) if select else (int(w[0]), T)
+    if fill_holes is not None:
+        _fill_errors(w[40:])
+        nv, nt = int(w[40]), int(w[41])
     if simplify is not None:
         _simplify_errors(w[24:], simplify)
         nv, nt = int(w[24]), int(w[25])
@@ -446,5 +582,7 @@ def clean_mesh(vertices: torch.Tensor, faces: torch.Tensor, *, weld: bool = True
             d["simplify"] = dict(_simplify_details(w[24:]), vmap=vmap)
         if smooth is not None:
             d["smooth"] = _smooth_details(w[32:])
+        if fill_holes is not None:
+            d["fill"] = _fill_details(w[40:])
         return out + (d,)
     return out

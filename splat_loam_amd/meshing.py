@@ -241,7 +241,8 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
               seed=None, device="cuda", details: bool = False, image_height=None, image_width=None, keep_clusters=None,
               min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
               regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
-              smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False):
+              smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False, fill_holes: int = None,
+              fill_max_size: float = None):
     """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
     frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
 
@@ -255,7 +256,9 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     `details["clean"]["simplify"]` holds its counts.  `smooth=n` also runs the clean stage and, before the normals, n sweeps
     of `mesh_ops.smooth(n, smooth_method, smooth_weights, smooth_lambda, smooth_mu, fix_boundary)` over the edge graph
     (Taubin by default: the terraces and the per-voxel jitter of a nearest-pixel fusion go, the faces stay);
-    `details["clean"]["smooth"]` holds its counts.  With the defaults nothing of this runs and the soup is returned as it
+    `details["clean"]["smooth"]` holds its counts.  `fill_holes=n` also runs the clean stage and, after the selection,
+    `mesh_ops.fill_holes(max_edges=n, max_size=fill_max_size)`: the closed boundary loops of at most n edges — what a voxel
+    no keyframe observed leaves — get a fan over their centroid; `details["clean"]["fill"]` holds its counts.  With the defaults nothing of this runs and the soup is returned as it
     always was.
 
     Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
@@ -301,13 +304,13 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     vertices, faces = volume.extract(min_weight=min_weight)
     lap("extract")
     mesh, clean = (vertices, faces), None
-    if keep_clusters is not None or normals or simplify is not None or smooth is not None:
+    if keep_clusters is not None or normals or simplify is not None or smooth is not None or fill_holes is not None:
         from . import mesh_ops
         *mesh, clean = mesh_ops.clean_mesh(vertices, faces, weld=True, keep_clusters=keep_clusters, min_triangles=min_triangles,
                                            normals=normals, details=True, simplify=simplify, contraction=contraction,
                                            regularisation=regularisation, smooth=smooth, smooth_method=smooth_method,
                                            smooth_weights=smooth_weights, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                                           fix_boundary=fix_boundary)
+                                           fix_boundary=fix_boundary, fill_holes=fill_holes, fill_max_size=fill_max_size)
         mesh = tuple(mesh)
         lap("clean")
     if details:

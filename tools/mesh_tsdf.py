@@ -8,6 +8,7 @@ rendered depth of every keyframe fused into a sparse TSDF volume, the zero surfa
                               [--keep-clusters K] [--min-triangles N] [--normals]
                               [--simplify RES [--contraction quadric] [--regularisation L]]
                               [--smooth N [--smooth-method laplacian] [--smooth-weights uniform] [--fix-boundary]]
+                              [--fill-holes 64 [--fill-max-size M]]
                               [--seed S] [--image-height H --image-width W]
 
 OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tools/eval_recon.py` takes as the estimate.
@@ -16,9 +17,11 @@ OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tool
 `nx ny nz`; --simplify RES merges the vertices of every voxel of edge RES after the selection
 (`mesh_ops.simplify_vertex_clustering`: at their mean, or with --contraction quadric at the minimum of the voxel's error
 quadric); --smooth N runs N smoothing sweeps over the edge graph before the normals (`mesh_ops.smooth`: Taubin with
-inverse-distance weights unless told otherwise; --fix-boundary leaves the boundary vertices where they are).  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
+inverse-distance weights unless told otherwise; --fix-boundary leaves the boundary vertices where they are); --fill-holes N
+closes the boundary loops of at most N edges (and a bounding-box diagonal of at most --fill-max-size) after the selection
+with a fan over their centroid (`mesh_ops.fill_holes`).  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
 with a clean stage its statistics (of the welded mesh: clusters, degenerate triangles, boundary and non-manifold edges;
-n_min; the triangles kept; the counts of the simplification and of the smoothing)."""
+n_min; the triangles kept; the counts of the hole filling, of the simplification and of the smoothing)."""
 import argparse
 import json
 import os
@@ -53,6 +56,8 @@ def main():
     ap.add_argument("--smooth-method", choices=("taubin", "laplacian", "simple"), default="taubin", help="the sweep (with --smooth)")
     ap.add_argument("--smooth-weights", choices=("inverse_distance", "uniform"), default="inverse_distance", help="neighbour weights (with --smooth)")
     ap.add_argument("--fix-boundary", action="store_true", help="leave the boundary vertices where they are (with --smooth)")
+    ap.add_argument("--fill-holes", type=int, default=None, help="weld, then fill the boundary loops of at most N edges")
+    ap.add_argument("--fill-max-size", type=float, default=None, help="... whose bounding box has at most this diagonal (with --fill-holes)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -64,7 +69,7 @@ def main():
                                    image_width=a.image_width, keep_clusters=a.keep_clusters, min_triangles=a.min_triangles,
                                    normals=a.normals, simplify=a.simplify, contraction=a.contraction, regularisation=a.regularisation,
                                    smooth=a.smooth, smooth_method=a.smooth_method, smooth_weights=a.smooth_weights,
-                                   fix_boundary=a.fix_boundary)
+                                   fix_boundary=a.fix_boundary, fill_holes=a.fill_holes, fill_max_size=a.fill_max_size)
     vertices, faces, normals = mesh[0], mesh[1], (mesh[2] if a.normals else None)
     if a.weld and "clean" not in det:
         vertices, faces = tsdf.weld_soup(vertices)
@@ -83,6 +88,8 @@ def main():
         if "smooth" in det["clean"]:
             line["clean"]["smooth"] = dict(det["clean"]["smooth"], iterations=a.smooth, method=a.smooth_method, weights=a.smooth_weights,
                                            fix_boundary=bool(a.fix_boundary))
+        if "fill" in det["clean"]:
+            line["clean"]["fill"] = dict(det["clean"]["fill"], max_edges=a.fill_holes, max_size=a.fill_max_size)
     print(json.dumps(line))
 
 
