@@ -22,17 +22,14 @@
 //   mesh_weight_sums / mesh_scan / mesh_prefix   w = floor(A / A_max 2^32), inclusive prefix C in chunks of 1024 faces
 //                               (64-bit integers: exact in any order), W and the status words
 //   mesh_sample                 a thread per sample: Philox words, t = mulhi64(., W), bisection of C, the point
-#include <float.h>
-
-#include "sls_launch.hpp"
+#include "sls_geom.hpp"
 #include "sls_scan.hpp"
 #include "../../include/sls_cloud_math.h"
 
 namespace sls {
 
 constexpr int kCloudThreads = 256;
-constexpr int kCloudPer = 4;                                 // consecutive items per thread of the chunked scans
-constexpr int kCloudChunk = kCloudThreads * kCloudPer;      // 1024
+using CloudChunks = Chunks<kCloudThreads, 4>;                // the chunked scans: 1024 items per workgroup
 constexpr uint32_t kVoxelLong = 64;                          // a voxel of more points is summed by 64 lanes
 constexpr int kVoxelKeyBits = 3 * SLS_VOXEL_INDEX_BITS;      // 63
 
@@ -40,17 +37,6 @@ constexpr int kVoxelKeyBits = 3 * SLS_VOXEL_INDEX_BITS;      // 63
 enum { VH_MIN = 0, VH_NONFINITE = 3, VH_BIG = 4, VH_COUNT = 5, VH_NVOX = 6 };
 // 64-bit hdr words of the mesh scratch
 enum { MH_AMAX = 0, MH_BAD = 1, MH_W = 2 };
-
-__device__ __forceinline__ uint32_t cloud_f2ord(float f)
-{   // monotone float -> uint mapping
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float cloud_ord2f(uint32_t o)
-{
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-__device__ __forceinline__ bool cloud_finite(float v) { return fabsf(v) <= FLT_MAX; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // voxel down-sampling
@@ -64,33 +50,7 @@ __global__ void voxel_init_kernel(uint32_t *hdr, uint32_t M)
 
 __global__ __launch_bounds__(kCloudThreads) void voxel_bbox_kernel(int M, const float *__restrict__ xyz, uint32_t *hdr)
 {
-    float mn[3] = { INFINITY, INFINITY, INFINITY };
-    uint32_t bad = 0u;
-    for (size_t i = (size_t)blockIdx.x * kCloudThreads + threadIdx.x; i < (size_t)M; i += (size_t)gridDim.x * kCloudThreads) {
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        if (cloud_finite(x) && cloud_finite(y) && cloud_finite(z)) {
-            mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-        } else {
-            bad += 1u;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) mn[k] = fminf(mn[k], __shfl_xor(mn[k], off, 64));
-        bad += __shfl_xor(bad, off, 64);
-    }
-    __shared__ uint32_t s_box[4];
-    if (threadIdx.x < 4) s_box[threadIdx.x] = threadIdx.x < 3 ? 0xFFFFFFFFu : 0u;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) atomicMin(&s_box[k], cloud_f2ord(mn[k]));
-        atomicAdd(&s_box[3], bad);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) atomicMin(&hdr[VH_MIN + threadIdx.x], s_box[threadIdx.x]);
-    else if (threadIdx.x == 3 && s_box[3]) atomicAdd(&hdr[VH_NONFINITE], s_box[3]);
+    bbox_min<kCloudThreads>((uint32_t)M, xyz, nullptr, hdr + VH_MIN, hdr + VH_NONFINITE);
 }
 
 __global__ __launch_bounds__(kCloudThreads) void voxel_keys_kernel(int M, const float *__restrict__ xyz, double voxel_size,
@@ -102,10 +62,10 @@ __global__ __launch_bounds__(kCloudThreads) void voxel_keys_kernel(int M, const 
     if (i < (size_t)M) {
         const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
         uint64_t key = 0u;
-        if (cloud_finite(x) && cloud_finite(y) && cloud_finite(z)) {    // (then the minima are finite too)
-            const double ox = sls_voxel_origin(cloud_ord2f(hdr[VH_MIN + 0]), voxel_size),
-                         oy = sls_voxel_origin(cloud_ord2f(hdr[VH_MIN + 1]), voxel_size),
-                         oz = sls_voxel_origin(cloud_ord2f(hdr[VH_MIN + 2]), voxel_size);
+        if (finite_f32(x) && finite_f32(y) && finite_f32(z)) {    // (then the minima are finite too)
+            const double ox = sls_voxel_origin(ord2f(hdr[VH_MIN + 0]), voxel_size),
+                         oy = sls_voxel_origin(ord2f(hdr[VH_MIN + 1]), voxel_size),
+                         oz = sls_voxel_origin(ord2f(hdr[VH_MIN + 2]), voxel_size);
             big = !sls_voxel_key(x, y, z, ox, oy, oz, voxel_size, &key);
         }
         keys[i] = key;
@@ -118,38 +78,20 @@ __global__ __launch_bounds__(kCloudThreads) void voxel_keys_kernel(int M, const 
 // the head flags of this thread's four consecutive sorted positions, as a bit mask
 __device__ __forceinline__ uint32_t voxel_head_mask(uint32_t M, const uint64_t *__restrict__ keys, uint32_t p0)
 {
-    uint32_t mask = 0u;
-    if (p0 < M) {
-        uint64_t prev = p0 ? keys[p0 - 1] : 0u;
-#pragma unroll
-        for (int j = 0; j < kCloudPer; ++j) {
-            const uint32_t p = p0 + (uint32_t)j;
-            if (p < M) {
-                const uint64_t k = keys[p];
-                if (p == 0u || k != prev) mask |= 1u << j;
-                prev = k;
-            }
-        }
-    }
-    return mask;
+    return CloudChunks::head_mask(M, p0, [&](uint32_t p) { return keys[p]; });
 }
 
 __global__ __launch_bounds__(kCloudThreads) void voxel_heads_kernel(uint32_t M, const uint64_t *__restrict__ keys,
                                                                     uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kCloudThreads / 64];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer;
-    uint32_t total;
-    block_scan<uint32_t, kCloudThreads>((uint32_t)__popc(voxel_head_mask(M, keys, p0)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    CloudChunks::total((uint32_t)__popc(voxel_head_mask(M, keys, CloudChunks::first())), blk);
 }
 
 __global__ __launch_bounds__(kCloudThreads) void voxel_scan_kernel(uint32_t M, int nblk, uint32_t *__restrict__ blk,
                                                                    uint32_t *__restrict__ hdr, uint32_t *__restrict__ seg_start,
                                                                    uint32_t *__restrict__ status)
 {
-    __shared__ uint32_t s_wave[kCloudThreads / 64];
-    const uint32_t nv = scan_in_place<uint32_t, kCloudThreads>(blk, blk, nblk, s_wave);
+    const uint32_t nv = CloudChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) {
         hdr[VH_NVOX] = nv;
         seg_start[nv <= M ? nv : M] = M;       // (nv <= M always: a head per position at most)
@@ -161,13 +103,11 @@ __global__ __launch_bounds__(kCloudThreads) void voxel_segments_kernel(uint32_t 
                                                                        const uint32_t *__restrict__ blk,
                                                                        uint32_t *__restrict__ seg_start)
 {
-    __shared__ uint32_t s_wave[kCloudThreads / 64];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer;
+    const uint32_t p0 = CloudChunks::first();
     const uint32_t mask = voxel_head_mask(M, keys, p0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kCloudThreads>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = CloudChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kCloudPer; ++j)
+    for (int j = 0; j < CloudChunks::kPer; ++j)
         if ((mask >> j) & 1u) {
             if (id < M) seg_start[id] = p0 + (uint32_t)j;       // (always: voxel ids are below the number of heads <= M)
             ++id;
@@ -209,19 +149,16 @@ __global__ __launch_bounds__(kCloudThreads) void voxel_sum_kernel(uint32_t M, co
         const int src = (int)__builtin_ctzll(longs);
         longs &= longs - 1ull;
         const uint32_t s0 = (uint32_t)__shfl((int)s, src, 64), e0 = (uint32_t)__shfl((int)e, src, 64);
-        double sx = 0.0, sy = 0.0, sz = 0.0;
+        double part[3] = { 0.0, 0.0, 0.0 };
         for (uint32_t p = s0 + (uint32_t)lane; p < e0; p += 64u) {
             const size_t i = min(order[p], M - 1u);
-            sx += (double)xyz[3 * i]; sy += (double)xyz[3 * i + 1]; sz += (double)xyz[3 * i + 2];
+            part[0] += (double)xyz[3 * i]; part[1] += (double)xyz[3 * i + 1]; part[2] += (double)xyz[3 * i + 2];
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {                // (a + b == b + a: every lane ends with the same bits)
-            sx += __shfl_xor(sx, off, 64); sy += __shfl_xor(sy, off, 64); sz += __shfl_xor(sz, off, 64);
-        }
+        xor_butterfly<3>(part);
         if (lane == src) {
-            out_xyz[3 * (size_t)v] = sls_voxel_centroid(sx, len);
-            out_xyz[3 * (size_t)v + 1] = sls_voxel_centroid(sy, len);
-            out_xyz[3 * (size_t)v + 2] = sls_voxel_centroid(sz, len);
+            out_xyz[3 * (size_t)v] = sls_voxel_centroid(part[0], len);
+            out_xyz[3 * (size_t)v + 1] = sls_voxel_centroid(part[1], len);
+            out_xyz[3 * (size_t)v + 2] = sls_voxel_centroid(part[2], len);
             if (out_count) out_count[v] = (int32_t)len;
         }
     }
@@ -239,22 +176,20 @@ struct VoxelScratch {
 
 static VoxelScratch voxel_layout(int M, void *base)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     VoxelScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
-    s.nblk = (int)(((size_t)M + kCloudChunk - 1) / kCloudChunk);
-    s.hdr = (uint32_t *)(p + off); off += al(16 * sizeof(uint32_t));
-    s.keys = (uint64_t *)(p + off); off += al(sizeof(uint64_t) * (size_t)M);
-    s.keys_tmp = (uint64_t *)(p + off); off += al(sizeof(uint64_t) * (size_t)M);
-    s.vals = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)M);
-    s.vals_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)M);
-    s.seg_start = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * ((size_t)M + 1));
-    s.blk = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)s.nblk);
-    s.sort = (void *)(p + off);
+    Arena a(base);
+    const size_t n = (size_t)M;
+    s.nblk = CloudChunks::count(n);
+    s.hdr = a.take<uint32_t>(16);
+    s.keys = a.take<uint64_t>(n);
+    s.keys_tmp = a.take<uint64_t>(n);
+    s.vals = a.take<uint32_t>(n);
+    s.vals_tmp = a.take<uint32_t>(n);
+    s.seg_start = a.take<uint32_t>(n + 1);
+    s.blk = a.take<uint32_t>((size_t)s.nblk);
     s.sort_bytes = sort_scratch_bytes((uint64_t)M);
-    off += al(s.sort_bytes);
-    s.total = off;
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total = a.off;
     return s;
 }
 
@@ -265,7 +200,7 @@ int launch_voxel_downsample(int M, const float *xyz, double voxel_size, float *o
 {
     const VoxelScratch s = voxel_layout(M, scratch);
     const uint32_t Mu = (uint32_t)M;
-    const int nb = (int)(((size_t)M + kCloudThreads - 1) / kCloudThreads);
+    const int nb = (int)grid_for((size_t)M, kCloudThreads).x;
     hipLaunchKernelGGL(voxel_init_kernel, dim3(1), dim3(64), 0, st, s.hdr, Mu);
     SLS_LAUNCH_CHECK("voxel_init_kernel");
     hipLaunchKernelGGL(voxel_bbox_kernel, dim3(nb < 1024 ? nb : 1024), dim3(kCloudThreads), 0, st, M, xyz, s.hdr);
@@ -341,10 +276,10 @@ __global__ __launch_bounds__(kCloudThreads) void mesh_area_kernel(int V, int F, 
 
 // the weights of this thread's four consecutive faces
 __device__ __forceinline__ void mesh_weights(uint32_t F, const double *__restrict__ area, double amax, uint32_t f0,
-                                             unsigned long long w[kCloudPer])
+                                             unsigned long long w[CloudChunks::kPer])
 {
 #pragma unroll
-    for (int j = 0; j < kCloudPer; ++j) {
+    for (int j = 0; j < CloudChunks::kPer; ++j) {
         const uint32_t f = f0 + (uint32_t)j;
         w[j] = f < F ? (unsigned long long)sls_mesh_weight(area[f], amax) : 0ull;
     }
@@ -354,20 +289,17 @@ __global__ __launch_bounds__(kCloudThreads) void mesh_weight_sums_kernel(uint32_
                                                                          const unsigned long long *__restrict__ hdr,
                                                                          unsigned long long *__restrict__ blk)
 {
-    __shared__ unsigned long long s_wave[kCloudThreads / 64];
     const double amax = __longlong_as_double((long long)hdr[MH_AMAX]);
-    unsigned long long w[kCloudPer], total;
-    mesh_weights(F, area, amax, blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer, w);
-    block_scan<unsigned long long, kCloudThreads>((w[0] + w[1]) + (w[2] + w[3]), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    unsigned long long w[CloudChunks::kPer];
+    mesh_weights(F, area, amax, CloudChunks::first(), w);
+    CloudChunks::total((w[0] + w[1]) + (w[2] + w[3]), blk);
 }
 
 __global__ __launch_bounds__(kCloudThreads) void mesh_scan_kernel(int nblk, unsigned long long *__restrict__ blk,
                                                                   unsigned long long *__restrict__ hdr, uint32_t n_samples,
                                                                   uint32_t *__restrict__ status)
 {
-    __shared__ unsigned long long s_wave[kCloudThreads / 64];
-    const unsigned long long W = scan_in_place<unsigned long long, kCloudThreads>(blk, blk, nblk, s_wave);
+    const unsigned long long W = CloudChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) {
         hdr[MH_W] = W;
         const unsigned long long nbad = hdr[MH_BAD];
@@ -383,14 +315,13 @@ __global__ __launch_bounds__(kCloudThreads) void mesh_prefix_kernel(uint32_t F, 
                                                                     const unsigned long long *__restrict__ blk,
                                                                     unsigned long long *__restrict__ C)
 {
-    __shared__ unsigned long long s_wave[kCloudThreads / 64];
     const double amax = __longlong_as_double((long long)hdr[MH_AMAX]);
-    const uint32_t f0 = blockIdx.x * (uint32_t)kCloudChunk + threadIdx.x * (uint32_t)kCloudPer;
-    unsigned long long w[kCloudPer], total;
+    const uint32_t f0 = CloudChunks::first();
+    unsigned long long w[CloudChunks::kPer];
     mesh_weights(F, area, amax, f0, w);
-    unsigned long long run = blk[blockIdx.x] + block_scan<unsigned long long, kCloudThreads>((w[0] + w[1]) + (w[2] + w[3]), s_wave, &total);
+    unsigned long long run = CloudChunks::rank((w[0] + w[1]) + (w[2] + w[3]), blk);
 #pragma unroll
-    for (int j = 0; j < kCloudPer; ++j) {
+    for (int j = 0; j < CloudChunks::kPer; ++j) {
         run += w[j];
         if (f0 + (uint32_t)j < F) C[f0 + (uint32_t)j] = run;    // inclusive
     }
@@ -436,16 +367,14 @@ struct MeshScratch {
 
 static MeshScratch mesh_layout(int F, void *base)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     MeshScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
-    s.nblk = (int)(((size_t)F + kCloudChunk - 1) / kCloudChunk);
-    s.hdr = (unsigned long long *)(p + off); off += al(8 * sizeof(uint64_t));
-    s.area = (double *)(p + off); off += al(sizeof(double) * (size_t)F);
-    s.C = (unsigned long long *)(p + off); off += al(sizeof(uint64_t) * (size_t)F);
-    s.blk = (unsigned long long *)(p + off); off += al(sizeof(uint64_t) * (size_t)s.nblk);
-    s.total = off;
+    Arena a(base);
+    s.nblk = CloudChunks::count((size_t)F);
+    s.hdr = a.take<unsigned long long>(8);
+    s.area = a.take<double>((size_t)F);
+    s.C = a.take<unsigned long long>((size_t)F);
+    s.blk = a.take<unsigned long long>((size_t)s.nblk);
+    s.total = a.off;
     return s;
 }
 
@@ -463,8 +392,7 @@ int launch_mesh_sample(int V, const float *vertices, int F, const int32_t *faces
     hipLaunchKernelGGL(mesh_init_kernel, dim3(1), dim3(64), 0, st, s.hdr);
     SLS_LAUNCH_CHECK("mesh_init_kernel");
     if (F > 0) {
-        const int nb = (int)(((size_t)F + kCloudThreads - 1) / kCloudThreads);
-        hipLaunchKernelGGL(mesh_area_kernel, dim3(nb), dim3(kCloudThreads), 0, st, V, F, vertices, faces, crop_box, s.area, s.hdr);
+        hipLaunchKernelGGL(mesh_area_kernel, grid_for((size_t)F, kCloudThreads), dim3(kCloudThreads), 0, st, V, F, vertices, faces, crop_box, s.area, s.hdr);
         SLS_LAUNCH_CHECK("mesh_area_kernel");
         hipLaunchKernelGGL(mesh_weight_sums_kernel, dim3(s.nblk), dim3(kCloudThreads), 0, st, Fu, (const double *)s.area,
                            (const unsigned long long *)s.hdr, s.blk);
@@ -476,7 +404,7 @@ int launch_mesh_sample(int V, const float *vertices, int F, const int32_t *faces
         hipLaunchKernelGGL(mesh_prefix_kernel, dim3(s.nblk), dim3(kCloudThreads), 0, st, Fu, (const double *)s.area,
                            (const unsigned long long *)s.hdr, (const unsigned long long *)s.blk, s.C);
         SLS_LAUNCH_CHECK("mesh_prefix_kernel");
-        hipLaunchKernelGGL(mesh_sample_kernel, dim3((nu + kCloudThreads - 1) / kCloudThreads), dim3(kCloudThreads), 0, st, (uint32_t)V,
+        hipLaunchKernelGGL(mesh_sample_kernel, grid_for(nu, kCloudThreads), dim3(kCloudThreads), 0, st, (uint32_t)V,
                            Fu, vertices, faces, (const unsigned long long *)s.C, (const unsigned long long *)s.hdr, nu, seed, out_xyz,
                            out_face);
         SLS_LAUNCH_CHECK("mesh_sample_kernel");

@@ -87,6 +87,24 @@ struct ScopedTimer {
         }                                            \
     } while (0)
 
+// A scratch buffer handed out array by array, every array 256-byte aligned; `off` ends as the bytes the layout needs.
+// With a null base it only counts (the *_scratch_bytes calls) and hands out null pointers.
+struct Arena {
+    char *base;
+    size_t off = 0;
+    explicit Arena(void *b) : base((char *)b) {}
+    template <typename T>
+    T *take(size_t count)
+    {
+        T *q = base ? (T *)(base + off) : nullptr;
+        off += (sizeof(T) * count + 255) & ~(size_t)255;
+        return q;
+    }
+};
+
+// the workgroups of `threads` threads that give n items a thread each
+inline dim3 grid_for(size_t n, int threads) { return dim3((unsigned)((n + (size_t)threads - 1) / (size_t)threads)); }
+
 // Device copy of the camera, passed by value as a kernel argument.
 struct DevCam {
     int H, W, wrap, GX, GY;

@@ -20,7 +20,7 @@
 //   scan + fill_decide          where every loop's vertex and triangles go; the needs against the room; the status
 //   fill_copy / fill_write      the live rows and the -1 padding; the fans (skipped on overflow: a device word)
 // The chunked scans (fill_totals / _blkscan / _apply) work in place over 2048 entries per workgroup.
-#include "sls_launch.hpp"
+#include "sls_geom.hpp"
 #include "sls_scan.hpp"
 #include "sls_unionfind.hpp"
 #include "../../include/sls_fill_math.h"
@@ -28,19 +28,13 @@
 namespace sls {
 
 constexpr int kFillThreads = 512;
-constexpr int kFillWaves = kFillThreads / 64;
-constexpr int kFillPer = 4;                                 // consecutive entries per thread of a chunked scan
-constexpr int kFillChunk = kFillThreads * kFillPer;         // 2048
+using FillChunks = Chunks<kFillThreads, 4>;                 // the chunked scans: 2048 entries per workgroup
 constexpr int kFillLongBlocks = 2048;                       // the long-loop kernel strides over the loops
 constexpr int kFillLongThreads = 256;
 
 // hdr words
 enum { FH_N3 = 0, FH_VL, FH_TL, FH_B, FH_LOOPS, FH_OPEN, FH_COMPLEX, FH_DEGENERATE, FH_RANGE, FH_FILLED, FH_SKIP_EDGES, FH_SKIP_SIZE,
        FH_SKIP_NONFINITE, FH_OVERFLOW, FH_NEW_V, FH_NEW_T, FH_WORDS };
-
-static size_t fill_al(size_t v) { return (v + 255) & ~(size_t)255; }
-static int fill_chunks(size_t n) { return (int)((n + kFillChunk - 1) / kFillChunk); }
-static dim3 fill_grid(size_t n) { return dim3((unsigned)((n + kFillThreads - 1) / kFillThreads)); }
 
 __global__ void fill_init_kernel(uint32_t *hdr, uint32_t n3, int V, int T, const uint32_t *__restrict__ in_counts)
 {
@@ -71,16 +65,7 @@ __global__ __launch_bounds__(kFillThreads) void fill_keys_kernel(int T, const in
             kb[3 * t + e] = (uint32_t)b;
         }
     }
-    const uint64_t md = __ballot(deg != 0), mr = __ballot(deg == 2);
-    if ((threadIdx.x & 63) == 0) {
-        if (md) atomicAdd(&hdr[FH_DEGENERATE], (uint32_t)__popcll(md));
-        if (mr) atomicAdd(&hdr[FH_RANGE], (uint32_t)__popcll(mr));
-    }
-}
-
-__device__ __forceinline__ uint64_t fill_pair(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb, uint32_t p)
-{
-    return ((uint64_t)sa[p] << 32) | (uint64_t)sb[p];
+    count_degenerate(deg, &hdr[FH_DEGENERATE], &hdr[FH_RANGE]);
 }
 
 // flag[p] = 1 iff the sorted pair at p is a boundary half-edge: alone in its run, and no (b, a) anywhere
@@ -93,12 +78,12 @@ __global__ __launch_bounds__(kFillThreads) void fill_mark_kernel(uint32_t n, con
     uint32_t is = 0u;
     if (a != b) {                                                   // (not the (0, 0) of a row that takes no part)
         const uint64_t k = ((uint64_t)a << 32) | b;
-        const bool alone = (p == 0 || fill_pair(sa, sb, (uint32_t)p - 1u) != k) && (p + 1 >= n || fill_pair(sa, sb, (uint32_t)p + 1u) != k);
+        const bool alone = (p == 0 || pair_key(sa, sb, (uint32_t)p - 1u) != k) && (p + 1 >= n || pair_key(sa, sb, (uint32_t)p + 1u) != k);
         if (alone) {
             const uint64_t target = ((uint64_t)b << 32) | a;
             uint32_t lo = 0u, hi = n;
-            while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (fill_pair(sa, sb, mid) < target) lo = mid + 1u; else hi = mid; }
-            is = (lo < n && fill_pair(sa, sb, lo) == target) ? 0u : 1u;
+            while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (pair_key(sa, sb, mid) < target) lo = mid + 1u; else hi = mid; }
+            is = (lo < n && pair_key(sa, sb, lo) == target) ? 0u : 1u;
         }
     }
     flag[p] = is;
@@ -108,47 +93,41 @@ __global__ __launch_bounds__(kFillThreads) void fill_mark_kernel(uint32_t n, con
 template <typename W>
 __global__ __launch_bounds__(kFillThreads) void fill_totals_kernel(uint32_t n, const W *__restrict__ arr, W *__restrict__ blk)
 {
-    __shared__ W s_wave[kFillWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kFillChunk + threadIdx.x * (uint32_t)kFillPer;
+    const uint32_t p0 = FillChunks::first();
     W sum = 0;
 #pragma unroll
-    for (int j = 0; j < kFillPer; ++j)
+    for (int j = 0; j < FillChunks::kPer; ++j)
         if (p0 + (uint32_t)j < n) sum += arr[p0 + (uint32_t)j];
-    W total;
-    block_scan<W, kFillThreads>(sum, s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    FillChunks::total(sum, blk);
 }
 
 template <typename W>
 __global__ __launch_bounds__(kFillThreads) void fill_blkscan_kernel(int nblk, W *blk, W *__restrict__ total)
 {
-    __shared__ W s_wave[kFillWaves];
-    const W sum = scan_in_place<W, kFillThreads>(blk, blk, nblk, s_wave);
+    const W sum = FillChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) *total = sum;
 }
 
 template <typename W>
 __global__ __launch_bounds__(kFillThreads) void fill_apply_kernel(uint32_t n, W *__restrict__ arr, const W *__restrict__ blk)
 {
-    __shared__ W s_wave[kFillWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kFillChunk + threadIdx.x * (uint32_t)kFillPer;
-    W v[kFillPer], sum = 0;
+    const uint32_t p0 = FillChunks::first();
+    W v[FillChunks::kPer], sum = 0;
 #pragma unroll
-    for (int j = 0; j < kFillPer; ++j) {
+    for (int j = 0; j < FillChunks::kPer; ++j) {
         v[j] = p0 + (uint32_t)j < n ? arr[p0 + (uint32_t)j] : (W)0;
         sum += v[j];
     }
-    W total;
-    W run = blk[blockIdx.x] + block_scan<W, kFillThreads>(sum, s_wave, &total);
+    W run = FillChunks::rank(sum, blk);
 #pragma unroll
-    for (int j = 0; j < kFillPer; ++j)
+    for (int j = 0; j < FillChunks::kPer; ++j)
         if (p0 + (uint32_t)j < n) { arr[p0 + (uint32_t)j] = run; run += v[j]; }
 }
 
 template <typename W>
 static int fill_scan(uint32_t n, W *arr, W *blk, W *total, hipStream_t st)
 {
-    const int nblk = fill_chunks(n);
+    const int nblk = FillChunks::count(n);
     hipLaunchKernelGGL((fill_totals_kernel<W>), dim3(nblk), dim3(kFillThreads), 0, st, n, (const W *)arr, blk);
     SLS_LAUNCH_CHECK("fill_totals_kernel");
     hipLaunchKernelGGL((fill_blkscan_kernel<W>), dim3(1), dim3(kFillThreads), 0, st, nblk, blk, total);
@@ -252,12 +231,7 @@ __global__ __launch_bounds__(kFillThreads) void fill_heads_kernel(uint32_t n, co
 {
     const size_t p = (size_t)blockIdx.x * kFillThreads + threadIdx.x;
     if (p >= n) return;
-    uint32_t is = 0u;
-    if (p < hdr[FH_B]) {
-        const uint32_t r = sr[p];
-        is = (r != n && (p == 0 || sr[p - 1] != r)) ? 1u : 0u;
-    }
-    flag[p] = is;
+    flag[p] = Chunks<kFillThreads, 1>::head_mask(hdr[FH_B], (uint32_t)p, [&](uint32_t q) { return sr[q]; }, n);     // (key n: open, no loop)
 }
 
 // rank: the exclusive scan of the head flags (hdr[FH_LOOPS]: their sum); ploop[p]: the loop of sorted position p or -1
@@ -358,11 +332,11 @@ __global__ __launch_bounds__(kFillLongThreads) void fill_verdict_long_kernel(Ver
             sls_fill_add(part, v);
         }
         finite = __all(finite);
+        xor_butterfly<3>(part);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                part[c] += __shfl_xor(part[c], off, 64);
                 const float l2 = __shfl_xor(lo[c], off, 64), h2 = __shfl_xor(hi[c], off, 64);
                 lo[c] = l2 < lo[c] ? l2 : lo[c];
                 hi[c] = h2 > hi[c] ? h2 : hi[c];
@@ -496,41 +470,35 @@ struct FillScratch {
 static FillScratch fill_layout(size_t V, size_t T, void *base)
 {
     FillScratch s;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *q = (char *)base + off; off += fill_al(bytes); return (void *)q; };
+    Arena a(base);
     const size_t n = 3 * T;
-    s.hdr = (uint32_t *)take(32 * sizeof(uint32_t));
-    s.total = (uint64_t *)take(sizeof(uint64_t));
-    for (int i = 0; i < 4; ++i) s.k[i] = (uint32_t *)take(sizeof(uint32_t) * n);
-    s.scan = (uint32_t *)take(sizeof(uint32_t) * n);
-    s.ha = (uint32_t *)take(sizeof(uint32_t) * n);
-    s.hb = (uint32_t *)take(sizeof(uint32_t) * n);
-    s.parent = (uint32_t *)take(sizeof(uint32_t) * n);
-    s.root = (uint32_t *)take(sizeof(uint32_t) * n);
-    s.ploop = (int32_t *)take(sizeof(int32_t) * n);
-    s.bad = (uint8_t *)take(n);
-    s.outdeg = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.indeg = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.first_out = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.loop_start = (uint32_t *)take(sizeof(uint32_t) * (T + 1));
-    s.verdict = (uint32_t *)take(sizeof(uint32_t) * T);
-    s.centroid = (float *)take(3 * sizeof(float) * T);
-    s.needs = (uint64_t *)take(sizeof(uint64_t) * T);
-    s.blk = (uint64_t *)take(sizeof(uint64_t) * (size_t)fill_chunks(n));
+    s.hdr = a.take<uint32_t>(32);
+    s.total = a.take<uint64_t>(1);
+    for (int i = 0; i < 4; ++i) s.k[i] = a.take<uint32_t>(n);
+    s.scan = a.take<uint32_t>(n);
+    s.ha = a.take<uint32_t>(n);
+    s.hb = a.take<uint32_t>(n);
+    s.parent = a.take<uint32_t>(n);
+    s.root = a.take<uint32_t>(n);
+    s.ploop = a.take<int32_t>(n);
+    s.bad = a.take<uint8_t>(n);
+    s.outdeg = a.take<uint32_t>(V);
+    s.indeg = a.take<uint32_t>(V);
+    s.first_out = a.take<uint32_t>(V);
+    s.loop_start = a.take<uint32_t>(T + 1);
+    s.verdict = a.take<uint32_t>(T);
+    s.centroid = a.take<float>(3 * T);
+    s.needs = a.take<uint64_t>(T);
+    s.blk = a.take<uint64_t>((size_t)FillChunks::count(n));
     s.sort_bytes = sort_scratch_bytes((uint64_t)n);
-    s.sort = take(s.sort_bytes);
-    s.total_bytes = off;
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total_bytes = a.off;
     return s;
-}
-
-static bool fill_sizes_ok(int V, int T)
-{
-    return V > 0 && T > 0 && T <= SLS_MESH_MAX_TRIANGLES && V <= SLS_MESH_MAX_VERTICES;
 }
 
 size_t mesh_fill_scratch_bytes(int V, int T)
 {
-    return fill_sizes_ok(V, T) ? fill_layout((size_t)V, (size_t)T, nullptr).total_bytes : 0;
+    return mesh_sizes_ok(V, T) ? fill_layout((size_t)V, (size_t)T, nullptr).total_bytes : 0;
 }
 
 // what both calls share: half-edges, loops, out_loop; afterwards s.k[*sorted] holds the sorted roots and s.k[*sorted + 1] the
@@ -542,41 +510,37 @@ static int fill_loops(int V, int T, const int32_t *faces, const uint32_t *in_cou
     const int bits = sls_mesh_index_bits(V);
     hipLaunchKernelGGL(fill_init_kernel, dim3(1), dim3(64), 0, st, s.hdr, n, V, T, in_counts);
     SLS_LAUNCH_CHECK("fill_init_kernel");
-    hipLaunchKernelGGL(fill_keys_kernel, fill_grid((size_t)T), dim3(kFillThreads), 0, st, T, faces, s.hdr, s.k[0], s.k[2]);
+    hipLaunchKernelGGL(fill_keys_kernel, grid_for((size_t)T, kFillThreads), dim3(kFillThreads), 0, st, T, faces, s.hdr, s.k[0], s.k[2]);
     SLS_LAUNCH_CHECK("fill_keys_kernel");
     uint32_t *a2[2] = { s.k[0], s.k[1] }, *b2[2] = { s.k[2], s.k[3] };
-    int which = 0;
-    int rc = radix_sort_pairs_u32(b2[0], a2[0], b2[1], a2[1], s.hdr + FH_N3, n, bits, s.sort, s.sort_bytes, &which, st);         // by b
+    int which = 0, cur = 0;
+    int rc = sort_pairs_ab(a2, b2, s.hdr + FH_N3, n, bits, s.sort, s.sort_bytes, &cur, st);
     if (rc) return rc;
-    int cur = which;
-    rc = radix_sort_pairs_u32(a2[cur], b2[cur], a2[cur ^ 1], b2[cur ^ 1], s.hdr + FH_N3, n, bits, s.sort, s.sort_bytes, &which, st);   // by a, stable
-    if (rc) return rc;
-    cur ^= which;
     const uint32_t *sa = a2[cur], *sb = b2[cur];
-    hipLaunchKernelGGL(fill_mark_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, sa, sb, s.scan);
+    hipLaunchKernelGGL(fill_mark_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, sa, sb, s.scan);
     SLS_LAUNCH_CHECK("fill_mark_kernel");
     rc = fill_scan<uint32_t>(n, s.scan, (uint32_t *)s.blk, s.hdr + FH_B, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(fill_compact_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, sa, sb, (const uint32_t *)s.scan,
+    hipLaunchKernelGGL(fill_compact_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, sa, sb, (const uint32_t *)s.scan,
                        (const uint32_t *)s.hdr, s.ha, s.hb, s.parent, out_halfedges);
     SLS_LAUNCH_CHECK("fill_compact_kernel");
     SLS_HIP_CHECK(hipMemsetAsync(s.outdeg, 0, sizeof(uint32_t) * (size_t)V, st));
     SLS_HIP_CHECK(hipMemsetAsync(s.indeg, 0, sizeof(uint32_t) * (size_t)V, st));
     SLS_HIP_CHECK(hipMemsetAsync(s.bad, 0, (size_t)n, st));
-    hipLaunchKernelGGL(fill_degrees_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, Vu, (const uint32_t *)s.hdr, (const uint32_t *)s.ha,
+    hipLaunchKernelGGL(fill_degrees_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, Vu, (const uint32_t *)s.hdr, (const uint32_t *)s.ha,
                        (const uint32_t *)s.hb, s.outdeg, s.indeg, s.first_out);
     SLS_LAUNCH_CHECK("fill_degrees_kernel");
-    hipLaunchKernelGGL(fill_union_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, Vu, (const uint32_t *)s.hdr, (const uint32_t *)s.hb,
+    hipLaunchKernelGGL(fill_union_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, Vu, (const uint32_t *)s.hdr, (const uint32_t *)s.hb,
                        (const uint32_t *)s.outdeg, (const uint32_t *)s.indeg, (const uint32_t *)s.first_out, s.parent);
     SLS_LAUNCH_CHECK("fill_union_kernel");
-    hipLaunchKernelGGL(fill_complex_kernel, fill_grid((size_t)V), dim3(kFillThreads), 0, st, Vu, (const uint32_t *)s.outdeg,
+    hipLaunchKernelGGL(fill_complex_kernel, grid_for((size_t)V, kFillThreads), dim3(kFillThreads), 0, st, Vu, (const uint32_t *)s.outdeg,
                        (const uint32_t *)s.indeg, s.hdr);
     SLS_LAUNCH_CHECK("fill_complex_kernel");
-    hipLaunchKernelGGL(fill_roots_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, Vu, (const uint32_t *)s.hdr, (const uint32_t *)s.parent,
+    hipLaunchKernelGGL(fill_roots_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, Vu, (const uint32_t *)s.hdr, (const uint32_t *)s.parent,
                        (const uint32_t *)s.ha, (const uint32_t *)s.hb, (const uint32_t *)s.outdeg, (const uint32_t *)s.indeg, s.root, s.bad);
     SLS_LAUNCH_CHECK("fill_roots_kernel");
     // the sorted pairs are spent: their four arrays hold the sort by root
-    hipLaunchKernelGGL(fill_rootkeys_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, s.hdr, (const uint32_t *)s.root, (const uint8_t *)s.bad,
+    hipLaunchKernelGGL(fill_rootkeys_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, s.hdr, (const uint32_t *)s.root, (const uint8_t *)s.bad,
                        s.k[0], s.k[1]);
     SLS_LAUNCH_CHECK("fill_rootkeys_kernel");
     rc = radix_sort_pairs_u32(s.k[0], s.k[1], s.k[2], s.k[3], s.hdr + FH_B, n, sls_mesh_index_bits((int32_t)n + 1), s.sort, s.sort_bytes,
@@ -584,11 +548,11 @@ static int fill_loops(int V, int T, const int32_t *faces, const uint32_t *in_cou
     if (rc) return rc;
     *sorted = which ? 2 : 0;
     const uint32_t *sr = s.k[*sorted], *sv = s.k[*sorted + 1];
-    hipLaunchKernelGGL(fill_heads_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, (const uint32_t *)s.hdr, sr, s.scan);
+    hipLaunchKernelGGL(fill_heads_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, (const uint32_t *)s.hdr, sr, s.scan);
     SLS_LAUNCH_CHECK("fill_heads_kernel");
     rc = fill_scan<uint32_t>(n, s.scan, (uint32_t *)s.blk, s.hdr + FH_LOOPS, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(fill_segments_kernel, fill_grid(n), dim3(kFillThreads), 0, st, n, (uint32_t)T, (const uint32_t *)s.hdr, sr, sv,
+    hipLaunchKernelGGL(fill_segments_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, n, (uint32_t)T, (const uint32_t *)s.hdr, sr, sv,
                        (const uint32_t *)s.scan, s.loop_start, s.ploop, out_loop);
     SLS_LAUNCH_CHECK("fill_segments_kernel");
     return SLS_OK;
@@ -601,7 +565,7 @@ int launch_mesh_boundary_loops(int V, int T, const int32_t *faces, const uint32_
     int sorted = 0;
     const int rc = fill_loops(V, T, faces, in_counts, out_halfedges, out_loop, s, &sorted, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(fill_lengths_kernel, fill_grid((size_t)T), dim3(kFillThreads), 0, st, (uint32_t)T, (const uint32_t *)s.hdr,
+    hipLaunchKernelGGL(fill_lengths_kernel, grid_for((size_t)T, kFillThreads), dim3(kFillThreads), 0, st, (uint32_t)T, (const uint32_t *)s.hdr,
                        (const uint32_t *)s.loop_start, out_loop_edges);
     SLS_LAUNCH_CHECK("fill_lengths_kernel");
     hipLaunchKernelGGL(fill_decide_kernel, dim3(1), dim3(64), 0, st, s.hdr, (const uint64_t *)s.total, 0u, 0u, 0, out_status);
@@ -622,7 +586,7 @@ int launch_mesh_fill_holes(int V, const float *vertices, int T, const int32_t *f
     v.n = n; v.V = (uint32_t)V; v.max_loops = (uint32_t)T; v.max_edges = (uint32_t)max_edges; v.max_size = max_size;
     v.loop_start = s.loop_start; v.sv = s.k[sorted + 1]; v.ha = s.ha; v.xyz = vertices;
     v.verdict = s.verdict; v.centroid = s.centroid; v.needs = s.needs;
-    hipLaunchKernelGGL(fill_verdict_short_kernel, fill_grid((size_t)T), dim3(kFillThreads), 0, st, v, s.hdr);
+    hipLaunchKernelGGL(fill_verdict_short_kernel, grid_for((size_t)T, kFillThreads), dim3(kFillThreads), 0, st, v, s.hdr);
     SLS_LAUNCH_CHECK("fill_verdict_short_kernel");
     const size_t long_blocks = ((size_t)T / (SLS_FILL_LONG + 1) + kFillLongThreads / 64) / (kFillLongThreads / 64);    // a long loop takes 65 half-edges at least
     hipLaunchKernelGGL(fill_verdict_long_kernel, dim3((unsigned)(long_blocks < (size_t)kFillLongBlocks ? long_blocks : (size_t)kFillLongBlocks)),
@@ -634,7 +598,7 @@ int launch_mesh_fill_holes(int V, const float *vertices, int T, const int32_t *f
                        (uint32_t)cap_triangles, 1, out_status);
     SLS_LAUNCH_CHECK("fill_decide_kernel");
     const size_t words = 3 * (size_t)(cap_triangles > V ? cap_triangles : V);
-    hipLaunchKernelGGL(fill_copy_kernel, fill_grid(words), dim3(kFillThreads), 0, st, (uint32_t)V, (uint32_t)T, (uint32_t)cap_triangles, 0u, 0u,
+    hipLaunchKernelGGL(fill_copy_kernel, grid_for(words, kFillThreads), dim3(kFillThreads), 0, st, (uint32_t)V, (uint32_t)T, (uint32_t)cap_triangles, 0u, 0u,
                        (const uint32_t *)s.hdr, (const uint32_t *)nullptr, (const uint32_t *)vertices, faces, (uint32_t *)out_vertices, out_faces);
     SLS_LAUNCH_CHECK("fill_copy_kernel");
     WriteArgs w;
@@ -642,7 +606,7 @@ int launch_mesh_fill_holes(int V, const float *vertices, int T, const int32_t *f
     w.hdr = s.hdr; w.loop_start = s.loop_start; w.sv = s.k[sorted + 1]; w.ha = s.ha; w.hb = s.hb; w.first_out = s.first_out;
     w.verdict = s.verdict; w.ploop = s.ploop; w.centroid = s.centroid; w.offsets = s.needs;
     w.out_vertices = out_vertices; w.out_faces = out_faces;
-    hipLaunchKernelGGL(fill_write_kernel, fill_grid(n), dim3(kFillThreads), 0, st, w);
+    hipLaunchKernelGGL(fill_write_kernel, grid_for(n, kFillThreads), dim3(kFillThreads), 0, st, w);
     SLS_LAUNCH_CHECK("fill_write_kernel");
     return SLS_OK;
 }
@@ -657,7 +621,7 @@ int launch_mesh_fill_empty(int V, const float *vertices, int T, const int32_t *f
     }
     const size_t words = 3 * (size_t)(cap_triangles > V ? cap_triangles : V);
     if (fills && words) {
-        hipLaunchKernelGGL(fill_copy_kernel, fill_grid(words), dim3(kFillThreads), 0, st, (uint32_t)V, (uint32_t)T, (uint32_t)cap_triangles,
+        hipLaunchKernelGGL(fill_copy_kernel, grid_for(words, kFillThreads), dim3(kFillThreads), 0, st, (uint32_t)V, (uint32_t)T, (uint32_t)cap_triangles,
                            (uint32_t)V, (uint32_t)T, (const uint32_t *)nullptr, in_counts, (const uint32_t *)vertices, faces,
                            (uint32_t *)out_vertices, out_faces);
         SLS_LAUNCH_CHECK("fill_copy_kernel");

@@ -27,7 +27,7 @@
 //                   compactions by chunked scans, no atomics.
 // sls_mesh_vertex_normals:  corners sorted by vertex (stable: ascending triangle within a vertex), then one thread per
 //                   vertex finds its run by bisection and sums the face normals in that order.  No float atomics.
-#include "sls_launch.hpp"
+#include "sls_geom.hpp"
 #include "sls_scan.hpp"
 #include "sls_unionfind.hpp"
 #include "../../include/sls_mesh_math.h"
@@ -35,16 +35,11 @@
 namespace sls {
 
 constexpr int kMeshThreads = 512;
-constexpr int kMeshWaves = kMeshThreads / 64;
-constexpr int kMeshPer = 4;                                 // consecutive positions per thread of a chunked scan
-constexpr int kMeshChunk = kMeshThreads * kMeshPer;         // 2048
+using MeshChunks = Chunks<kMeshThreads, 4>;                 // the chunked scans: 2048 positions per workgroup
 constexpr uint32_t kMeshNone = 0xFFFFFFFFu;                 // parent / root of a degenerate triangle
 
 enum { MH_COUNT = 0, MH_DEGENERATE = 1, MH_RANGE = 2, MH_BOUNDARY = 3, MH_NONMANIFOLD = 4, MH_NMIN = 5 };   // hdr words
 
-static size_t mesh_al(size_t v) { return (v + 255) & ~(size_t)255; }
-static int mesh_chunks(size_t n) { return (int)((n + kMeshChunk - 1) / kMeshChunk); }
-static dim3 mesh_grid(size_t n) { return dim3((unsigned)((n + kMeshThreads - 1) / kMeshThreads)); }
 
 __global__ void mesh_hdr_kernel(uint32_t *hdr, uint32_t n)
 {
@@ -65,47 +60,31 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_word_keys_kernel(uint32_t n
     if (!rows_in) rows_out[j] = r;
 }
 
+// the three words of a soup row: two rows differ unless they are the same vertex
+struct WeldRow {
+    uint32_t w[3];
+    __device__ __forceinline__ bool operator!=(const WeldRow &o) const { return !sls_mesh_same_row(w, o.w); }
+};
+
 // the head flags of this thread's four consecutive sorted positions, as a bit mask
 __device__ __forceinline__ uint32_t weld_head_mask(uint32_t n, const uint32_t *__restrict__ soup, const uint32_t *__restrict__ rows,
                                                    uint32_t p0)
 {
-    uint32_t mask = 0u;
-    if (p0 < n) {
-        uint32_t prev[3] = { 0u, 0u, 0u };
-        bool have = p0 > 0u;
-        if (have) {
-            const size_t r = rows[p0 - 1];
-            prev[0] = soup[3 * r]; prev[1] = soup[3 * r + 1]; prev[2] = soup[3 * r + 2];
-        }
-#pragma unroll
-        for (int j = 0; j < kMeshPer; ++j) {
-            const uint32_t p = p0 + (uint32_t)j;
-            if (p < n) {
-                const size_t r = rows[p];
-                const uint32_t cur[3] = { soup[3 * r], soup[3 * r + 1], soup[3 * r + 2] };
-                if (!have || !sls_mesh_same_row(cur, prev)) mask |= 1u << j;
-                prev[0] = cur[0]; prev[1] = cur[1]; prev[2] = cur[2];
-                have = true;
-            }
-        }
-    }
-    return mask;
+    return MeshChunks::head_mask(n, p0, [&](uint32_t p) {
+        const size_t r = rows[p];
+        return WeldRow{ { soup[3 * r], soup[3 * r + 1], soup[3 * r + 2] } };
+    });
 }
 
 __global__ __launch_bounds__(kMeshThreads) void weld_heads_kernel(uint32_t n, const uint32_t *__restrict__ soup,
                                                                   const uint32_t *__restrict__ rows, uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
-    uint32_t total;
-    block_scan<uint32_t, kMeshThreads>((uint32_t)__popc(weld_head_mask(n, soup, rows, p0)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    MeshChunks::total((uint32_t)__popc(weld_head_mask(n, soup, rows, MeshChunks::first())), blk);
 }
 
 __global__ __launch_bounds__(kMeshThreads) void weld_scan_kernel(int nblk, uint32_t *blk, uint32_t *__restrict__ status)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t nv = scan_in_place<uint32_t, kMeshThreads>(blk, blk, nblk, s_wave);
+    const uint32_t nv = MeshChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) { status[0] = nv; status[1] = 0u; status[2] = 0u; status[3] = 1u; }
 }
 
@@ -113,13 +92,11 @@ __global__ __launch_bounds__(kMeshThreads) void weld_write_kernel(uint32_t n, co
                                                                   const uint32_t *__restrict__ rows, const uint32_t *__restrict__ blk,
                                                                   uint32_t *__restrict__ out_vertices, int32_t *__restrict__ out_index)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
+    const uint32_t p0 = MeshChunks::first();
     const uint32_t mask = weld_head_mask(n, soup, rows, p0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kMeshThreads>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = MeshChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j) {
+    for (int j = 0; j < MeshChunks::kPer; ++j) {
         const uint32_t p = p0 + (uint32_t)j;
         if (p < n) {
             const size_t r = rows[p];
@@ -144,19 +121,17 @@ struct MeshSortScratch {
 static MeshSortScratch mesh_sort_layout(size_t n, void *base)
 {
     MeshSortScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
-    s.nblk = mesh_chunks(n);
-    s.hdr = (uint32_t *)(p + off); off += mesh_al(16 * sizeof(uint32_t));
-    s.keys = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * n);
-    s.keys_tmp = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * n);
-    s.vals = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * n);
-    s.vals_tmp = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * n);
-    s.blk = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * (size_t)s.nblk);
-    s.sort = (void *)(p + off);
+    Arena a(base);
+    s.nblk = MeshChunks::count(n);
+    s.hdr = a.take<uint32_t>(16);
+    s.keys = a.take<uint32_t>(n);
+    s.keys_tmp = a.take<uint32_t>(n);
+    s.vals = a.take<uint32_t>(n);
+    s.vals_tmp = a.take<uint32_t>(n);
+    s.blk = a.take<uint32_t>((size_t)s.nblk);
     s.sort_bytes = sort_scratch_bytes((uint64_t)n);
-    off += mesh_al(s.sort_bytes);
-    s.total = off;
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total = a.off;
     return s;
 }
 
@@ -176,7 +151,7 @@ int launch_mesh_weld(int n_rows, const float *soup, float *out_vertices, int32_t
     uint32_t *kb[2] = { s.keys, s.keys_tmp }, *vb[2] = { s.vals, s.vals_tmp };
     int cur = 0;
     for (int w = 2; w >= 0; --w) {                  // LSD over the words: z first
-        hipLaunchKernelGGL(mesh_word_keys_kernel, mesh_grid(n), dim3(kMeshThreads), 0, st, n, words, w,
+        hipLaunchKernelGGL(mesh_word_keys_kernel, grid_for(n, kMeshThreads), dim3(kMeshThreads), 0, st, n, words, w,
                            w == 2 ? (const uint32_t *)nullptr : (const uint32_t *)vb[cur], kb[cur], vb[cur]);
         SLS_LAUNCH_CHECK("mesh_word_keys_kernel");
         int which = 0;
@@ -215,11 +190,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_edges_kernel(int T, const i
         }
         parent[t] = d ? kMeshNone : (uint32_t)t;
     }
-    const uint64_t md = __ballot(d != 0), mr = __ballot(d == 2);
-    if ((threadIdx.x & 63) == 0) {
-        if (md) atomicAdd(&hdr[MH_DEGENERATE], (uint32_t)__popcll(md));
-        if (mr) atomicAdd(&hdr[MH_RANGE], (uint32_t)__popcll(mr));
-    }
+    count_degenerate(d, &hdr[MH_DEGENERATE], &hdr[MH_RANGE]);
 }
 
 __global__ __launch_bounds__(kMeshThreads) void mesh_union_kernel(uint32_t n, const uint64_t *__restrict__ keys,
@@ -249,11 +220,10 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_union_kernel(uint32_t n, co
 __global__ __launch_bounds__(kMeshThreads) void mesh_flatten_kernel(uint32_t T, const uint32_t *__restrict__ parent,
                                                                     uint32_t *__restrict__ root, uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
+    const uint32_t t0 = MeshChunks::first();
     uint32_t nroots = 0u;
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j) {
+    for (int j = 0; j < MeshChunks::kPer; ++j) {
         const uint32_t t = t0 + (uint32_t)j;
         if (t < T) {
             uint32_t x = parent[t];
@@ -265,16 +235,13 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_flatten_kernel(uint32_t T, 
             root[t] = x;
         }
     }
-    uint32_t total;
-    block_scan<uint32_t, kMeshThreads>(nroots, s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    MeshChunks::total(nroots, blk);
 }
 
 __global__ __launch_bounds__(kMeshThreads) void mesh_rootscan_kernel(int nblk, uint32_t *blk, const uint32_t *__restrict__ hdr,
                                                                      uint32_t *__restrict__ status)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t nc = scan_in_place<uint32_t, kMeshThreads>(blk, blk, nblk, s_wave);
+    const uint32_t nc = MeshChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) {
         status[0] = nc; status[1] = hdr[MH_DEGENERATE]; status[2] = hdr[MH_RANGE]; status[3] = hdr[MH_BOUNDARY];
         status[4] = hdr[MH_NONMANIFOLD]; status[5] = 1u;
@@ -286,18 +253,16 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_rank_kernel(uint32_t T, con
                                                                  const uint32_t *__restrict__ blk, uint32_t *__restrict__ dense,
                                                                  int32_t *__restrict__ counts)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
+    const uint32_t t0 = MeshChunks::first();
     uint32_t mask = 0u;
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j) {
+    for (int j = 0; j < MeshChunks::kPer; ++j) {
         const uint32_t t = t0 + (uint32_t)j;
         if (t < T && root[t] == t) mask |= 1u << j;
     }
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kMeshThreads>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = MeshChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j)
+    for (int j = 0; j < MeshChunks::kPer; ++j)
         if ((mask >> j) & 1u) {                     // (id < T: there are at most T roots, and counts holds T entries)
             dense[t0 + (uint32_t)j] = id;
             counts[id] = 0;
@@ -330,23 +295,21 @@ struct MeshClusterScratch {
 static MeshClusterScratch mesh_cluster_layout(size_t T, void *base)
 {
     MeshClusterScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
+    Arena a(base);
     const size_t n = 3 * T;
-    s.nblk = mesh_chunks(T);
-    s.hdr = (uint32_t *)(p + off); off += mesh_al(16 * sizeof(uint32_t));
-    s.keys = (uint64_t *)(p + off); off += mesh_al(sizeof(uint64_t) * n);
-    s.keys_tmp = (uint64_t *)(p + off); off += mesh_al(sizeof(uint64_t) * n);
-    s.vals = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * n);
-    s.vals_tmp = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * n);
-    s.parent = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * T);
-    s.root = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * T);
-    s.dense = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * T);
-    s.blk = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * (size_t)s.nblk);
-    s.sort = (void *)(p + off);
+    s.nblk = MeshChunks::count(T);
+    s.hdr = a.take<uint32_t>(16);
+    s.keys = a.take<uint64_t>(n);
+    s.keys_tmp = a.take<uint64_t>(n);
+    s.vals = a.take<uint32_t>(n);
+    s.vals_tmp = a.take<uint32_t>(n);
+    s.parent = a.take<uint32_t>(T);
+    s.root = a.take<uint32_t>(T);
+    s.dense = a.take<uint32_t>(T);
+    s.blk = a.take<uint32_t>((size_t)s.nblk);
     s.sort_bytes = sort_scratch_bytes((uint64_t)n);
-    off += mesh_al(s.sort_bytes);
-    s.total = off;
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total = a.off;
     return s;
 }
 
@@ -363,14 +326,14 @@ int launch_mesh_clusters(int T, const int32_t *faces, int V, int32_t *out_labels
     const int bits = sls_mesh_index_bits(V);
     hipLaunchKernelGGL(mesh_hdr_kernel, dim3(1), dim3(64), 0, st, s.hdr, n);
     SLS_LAUNCH_CHECK("mesh_hdr_kernel");
-    hipLaunchKernelGGL(mesh_edges_kernel, mesh_grid((size_t)T), dim3(kMeshThreads), 0, st, T, faces, V, bits, s.hdr, s.keys, s.vals,
+    hipLaunchKernelGGL(mesh_edges_kernel, grid_for((size_t)T, kMeshThreads), dim3(kMeshThreads), 0, st, T, faces, V, bits, s.hdr, s.keys, s.vals,
                        s.parent);
     SLS_LAUNCH_CHECK("mesh_edges_kernel");
     int which = 0;
     const int rc = radix_sort_pairs_u64(s.keys, s.vals, s.keys_tmp, s.vals_tmp, s.hdr + MH_COUNT, n, 2 * bits, s.sort, s.sort_bytes,
                                         &which, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(mesh_union_kernel, mesh_grid((size_t)n), dim3(kMeshThreads), 0, st, n,
+    hipLaunchKernelGGL(mesh_union_kernel, grid_for((size_t)n, kMeshThreads), dim3(kMeshThreads), 0, st, n,
                        (const uint64_t *)(which ? s.keys_tmp : s.keys), (const uint32_t *)(which ? s.vals_tmp : s.vals), s.parent, s.hdr);
     SLS_LAUNCH_CHECK("mesh_union_kernel");
     hipLaunchKernelGGL(mesh_flatten_kernel, dim3(s.nblk), dim3(kMeshThreads), 0, st, (uint32_t)T, (const uint32_t *)s.parent, s.root,
@@ -381,7 +344,7 @@ int launch_mesh_clusters(int T, const int32_t *faces, int V, int32_t *out_labels
     hipLaunchKernelGGL(mesh_rank_kernel, dim3(s.nblk), dim3(kMeshThreads), 0, st, (uint32_t)T, (const uint32_t *)s.root,
                        (const uint32_t *)s.blk, s.dense, out_counts);
     SLS_LAUNCH_CHECK("mesh_rank_kernel");
-    hipLaunchKernelGGL(mesh_label_kernel, mesh_grid((size_t)T), dim3(kMeshThreads), 0, st, (uint32_t)T, (const uint32_t *)s.root,
+    hipLaunchKernelGGL(mesh_label_kernel, grid_for((size_t)T, kMeshThreads), dim3(kMeshThreads), 0, st, (uint32_t)T, (const uint32_t *)s.root,
                        (const uint32_t *)s.dense, out_labels, out_counts);
     SLS_LAUNCH_CHECK("mesh_label_kernel");
     return SLS_OK;
@@ -396,7 +359,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_nmin_kernel(uint32_t T, con
                                                                  const int32_t *__restrict__ counts, int keep_clusters, int min_triangles,
                                                                  uint32_t *__restrict__ hdr)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
+    __shared__ uint32_t s_wave[kMeshThreads / 64];
     const uint32_t C = min(cluster_status[0], T);
     const uint32_t k = sls_mesh_keep_rank(keep_clusters, C);
     uint32_t lo = 0u;
@@ -422,7 +385,7 @@ __device__ __forceinline__ uint32_t mesh_kept_mask(uint32_t T, int V, uint32_t C
 {
     uint32_t mask = 0u;
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j) {
+    for (int j = 0; j < MeshChunks::kPer; ++j) {
         const uint32_t t = t0 + (uint32_t)j;
         if (t < T) {
             const int32_t l = labels[t];
@@ -438,42 +401,26 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_mark_kernel(uint32_t T, int
                                                                  const uint32_t *__restrict__ cluster_status, const uint32_t *__restrict__ hdr,
                                                                  uint32_t *vflag, uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
+    const uint32_t t0 = MeshChunks::first();
     const uint32_t mask = mesh_kept_mask(T, V, min(cluster_status[0], T), hdr[MH_NMIN], faces, labels, counts, t0);
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j)
+    for (int j = 0; j < MeshChunks::kPer; ++j)
         if ((mask >> j) & 1u) {
             const size_t t = t0 + (uint32_t)j;
             vflag[faces[3 * t]] = 1u; vflag[faces[3 * t + 1]] = 1u; vflag[faces[3 * t + 2]] = 1u;     // (every writer stores 1)
         }
-    uint32_t total;
-    block_scan<uint32_t, kMeshThreads>((uint32_t)__popc(mask), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
-}
-
-__device__ __forceinline__ uint32_t mesh_flag_mask(uint32_t V, const uint32_t *__restrict__ vflag, uint32_t v0)
-{
-    uint32_t mask = 0u;
-#pragma unroll
-    for (int j = 0; j < kMeshPer; ++j)
-        if (v0 + (uint32_t)j < V && vflag[v0 + (uint32_t)j]) mask |= 1u << j;
-    return mask;
+    MeshChunks::total((uint32_t)__popc(mask), blk);
 }
 
 __global__ __launch_bounds__(kMeshThreads) void mesh_vcount_kernel(uint32_t V, const uint32_t *__restrict__ vflag, uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t v0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
-    uint32_t total;
-    block_scan<uint32_t, kMeshThreads>((uint32_t)__popc(mesh_flag_mask(V, vflag, v0)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    MeshChunks::total((uint32_t)__popc(MeshChunks::flag_mask(V, vflag, MeshChunks::first())), blk);
 }
 
 __global__ __launch_bounds__(kMeshThreads) void mesh_filter_scan_kernel(int nblk_t, uint32_t *blk_t, int nblk_v, uint32_t *blk_v,
                                                                         const uint32_t *__restrict__ hdr, uint32_t *__restrict__ status)
 {
-    __shared__ uint32_t s_wave_t[kMeshWaves], s_wave_v[kMeshWaves];
+    __shared__ uint32_t s_wave_t[kMeshThreads / 64], s_wave_v[kMeshThreads / 64];
     const uint32_t nt = scan_in_place<uint32_t, kMeshThreads>(blk_t, blk_t, nblk_t, s_wave_t);
     const uint32_t nv = scan_in_place<uint32_t, kMeshThreads>(blk_v, blk_v, nblk_v, s_wave_v);
     if (threadIdx.x == 0) { status[0] = nv; status[1] = nt; status[2] = hdr[MH_NMIN]; status[3] = 1u; }
@@ -483,13 +430,11 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_vwrite_kernel(uint32_t V, c
                                                                    const uint32_t *__restrict__ blk, const uint32_t *__restrict__ vertices,
                                                                    uint32_t *__restrict__ out_vertices, int32_t *__restrict__ vmap)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t v0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
-    const uint32_t mask = mesh_flag_mask(V, vflag, v0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kMeshThreads>((uint32_t)__popc(mask), s_wave, &total);
+    const uint32_t v0 = MeshChunks::first();
+    const uint32_t mask = MeshChunks::flag_mask(V, vflag, v0);
+    uint32_t id = MeshChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j) {
+    for (int j = 0; j < MeshChunks::kPer; ++j) {
         const size_t v = v0 + (uint32_t)j;
         if (v < V) {
             if ((mask >> j) & 1u) {                 // (id < V: the output holds V rows)
@@ -508,13 +453,11 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_fwrite_kernel(uint32_t T, i
                                                                    const uint32_t *__restrict__ blk, const int32_t *__restrict__ vmap,
                                                                    int32_t *__restrict__ out_faces)
 {
-    __shared__ uint32_t s_wave[kMeshWaves];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kMeshChunk + threadIdx.x * (uint32_t)kMeshPer;
+    const uint32_t t0 = MeshChunks::first();
     const uint32_t mask = mesh_kept_mask(T, V, min(cluster_status[0], T), hdr[MH_NMIN], faces, labels, counts, t0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kMeshThreads>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = MeshChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kMeshPer; ++j)
+    for (int j = 0; j < MeshChunks::kPer; ++j)
         if ((mask >> j) & 1u) {                     // (id < T: the output holds T rows)
             const size_t t = t0 + (uint32_t)j;
             out_faces[3 * (size_t)id] = vmap[faces[3 * t]]; out_faces[3 * (size_t)id + 1] = vmap[faces[3 * t + 1]];
@@ -533,22 +476,20 @@ struct MeshFilterScratch {
 static MeshFilterScratch mesh_filter_layout(size_t V, size_t T, void *base)
 {
     MeshFilterScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
-    s.nblk_t = mesh_chunks(T); s.nblk_v = mesh_chunks(V);
-    s.hdr = (uint32_t *)(p + off); off += mesh_al(16 * sizeof(uint32_t));
-    s.vflag = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * V);
-    s.vmap = (int32_t *)(p + off); off += mesh_al(sizeof(int32_t) * V);
-    s.blk_t = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * (size_t)s.nblk_t);
-    s.blk_v = (uint32_t *)(p + off); off += mesh_al(sizeof(uint32_t) * (size_t)s.nblk_v);
-    s.total = off;
+    Arena a(base);
+    s.nblk_t = MeshChunks::count(T); s.nblk_v = MeshChunks::count(V);
+    s.hdr = a.take<uint32_t>(16);
+    s.vflag = a.take<uint32_t>(V);
+    s.vmap = a.take<int32_t>(V);
+    s.blk_t = a.take<uint32_t>((size_t)s.nblk_t);
+    s.blk_v = a.take<uint32_t>((size_t)s.nblk_v);
+    s.total = a.off;
     return s;
 }
 
 size_t mesh_filter_scratch_bytes(int V, int T)
 {
-    return (V > 0 && T > 0 && T <= SLS_MESH_MAX_TRIANGLES && V <= SLS_MESH_MAX_VERTICES) ? mesh_filter_layout((size_t)V, (size_t)T, nullptr).total
-                                                                                         : 0;
+    return mesh_sizes_ok(V, T) ? mesh_filter_layout((size_t)V, (size_t)T, nullptr).total : 0;
 }
 
 int launch_mesh_filter(int V, const float *vertices, int T, const int32_t *faces, const int32_t *labels, const int32_t *counts,
@@ -624,7 +565,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_normals_kernel(uint32_t V, 
 
 size_t mesh_normals_scratch_bytes(int V, int T)
 {
-    return (V > 0 && T > 0 && T <= SLS_MESH_MAX_TRIANGLES && V <= SLS_MESH_MAX_VERTICES) ? mesh_sort_layout(3 * (size_t)T, nullptr).total : 0;
+    return mesh_sizes_ok(V, T) ? mesh_sort_layout(3 * (size_t)T, nullptr).total : 0;
 }
 
 int launch_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
@@ -638,13 +579,13 @@ int launch_mesh_vertex_normals(int V, const float *vertices, int T, const int32_
     const uint32_t n = 3u * (uint32_t)T;
     hipLaunchKernelGGL(mesh_hdr_kernel, dim3(1), dim3(64), 0, st, s.hdr, n);
     SLS_LAUNCH_CHECK("mesh_hdr_kernel");
-    hipLaunchKernelGGL(mesh_corner_keys_kernel, mesh_grid((size_t)T), dim3(kMeshThreads), 0, st, T, faces, V, s.keys, s.vals);
+    hipLaunchKernelGGL(mesh_corner_keys_kernel, grid_for((size_t)T, kMeshThreads), dim3(kMeshThreads), 0, st, T, faces, V, s.keys, s.vals);
     SLS_LAUNCH_CHECK("mesh_corner_keys_kernel");
     int which = 0;
     const int rc = radix_sort_pairs_u32(s.keys, s.vals, s.keys_tmp, s.vals_tmp, s.hdr + MH_COUNT, n, sls_mesh_index_bits(V + 1), s.sort,
                                         s.sort_bytes, &which, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(mesh_normals_kernel, mesh_grid((size_t)V), dim3(kMeshThreads), 0, st, (uint32_t)V, n, vertices, faces,
+    hipLaunchKernelGGL(mesh_normals_kernel, grid_for((size_t)V, kMeshThreads), dim3(kMeshThreads), 0, st, (uint32_t)V, n, vertices, faces,
                        (const uint32_t *)(which ? s.keys_tmp : s.keys), (const uint32_t *)(which ? s.vals_tmp : s.vals), out_normals);
     SLS_LAUNCH_CHECK("mesh_normals_kernel");
     return SLS_OK;

@@ -1,5 +1,11 @@
-// sls_scan.hpp — workgroup-wide exclusive scans shared by sls_cloud.hip and sls_tsdf.hip: wave scans of 64 lanes, then
-// the wave sums through LDS.  Integer types only (the order of the additions then does not matter).
+// sls_scan.hpp — what the device geometry ops (sls_cloud, sls_tsdf, sls_mesh, sls_simplify, sls_smooth, sls_fill) share
+// of their scans.  block_scan / scan_in_place: workgroup-wide exclusive scans, wave scans of 64 lanes, then the wave sums
+// through LDS.  Chunks<THREADS, PER>: the chunked layer on top — an array is cut into chunks of THREADS * PER positions,
+// a workgroup per chunk, thread t owning PER consecutive positions — with the three launches of an ordered compaction:
+//   total      every workgroup's sum of its threads' values (popc of a head or flag mask, or any integer sum) -> blk[chunk]
+//   scan_totals  one workgroup: blk <- its exclusive scan, the caller's epilogue stores the grand total
+//   rank       the values recomputed: blk[chunk] + the scan inside the workgroup = this thread's rank in the whole array
+// Integer types only (the order of the additions then does not matter).
 #pragma once
 #include "sls_common.hpp"
 
@@ -44,5 +50,84 @@ __device__ __forceinline__ T scan_in_place(const T *in, T *out, int n, T *s_wave
     for (int i = i0; i < i1; ++i) { const T v = in[i]; out[i] = run; run += v; }
     return total;
 }
+
+// The chunk geometry and the per-chunk steps.  total / scan_totals / rank own their LDS wave array: one of them per kernel.
+template <int THREADS, int PER>
+struct Chunks {
+    static constexpr int kPer = PER, kChunk = THREADS * PER;
+
+    static int count(size_t n) { return (int)((n + kChunk - 1) / kChunk); }     // host: the chunks (= workgroups) of n positions
+    static __device__ __forceinline__ uint32_t first() { return blockIdx.x * (uint32_t)kChunk + threadIdx.x * (uint32_t)PER; }
+
+    // The head flags of the sorted positions p0 .. p0 + PER - 1 below n as a bit mask: a position whose key differs from its
+    // predecessor's (position 0 has none and is a head).  key(p) loads the key of position p: any type with != and a value
+    // initialisation.  A run of the key `reserved` has no head.
+    template <bool RESERVED, typename Load, typename K>
+    static __device__ __forceinline__ uint32_t head_mask_of(uint32_t n, uint32_t p0, Load key, K reserved)
+    {
+        uint32_t mask = 0u;
+        if (p0 < n) {
+            K prev = K();
+            if (p0) prev = key(p0 - 1u);
+#pragma unroll
+            for (int j = 0; j < PER; ++j) {
+                const uint32_t p = p0 + (uint32_t)j;
+                if (p < n) {
+                    const K k = key(p);
+                    if ((p == 0u || k != prev) && (!RESERVED || k != reserved)) mask |= 1u << j;
+                    prev = k;
+                }
+            }
+        }
+        return mask;
+    }
+    template <typename Load>
+    static __device__ __forceinline__ uint32_t head_mask(uint32_t n, uint32_t p0, Load key)
+    {
+        return head_mask_of<false>(n, p0, key, decltype(key(0u))());
+    }
+    template <typename Load, typename K>
+    static __device__ __forceinline__ uint32_t head_mask(uint32_t n, uint32_t p0, Load key, K reserved)
+    {
+        return head_mask_of<true>(n, p0, key, (decltype(key(0u)))reserved);
+    }
+
+    // the non-zero flags of the positions i0 .. i0 + PER - 1 below n as a bit mask
+    static __device__ __forceinline__ uint32_t flag_mask(uint32_t n, const uint32_t *__restrict__ flag, uint32_t i0)
+    {
+        uint32_t mask = 0u;
+#pragma unroll
+        for (int j = 0; j < PER; ++j)
+            if (i0 + (uint32_t)j < n && flag[i0 + (uint32_t)j]) mask |= 1u << j;
+        return mask;
+    }
+
+    // blk[this chunk] <- the sum of v over the workgroup
+    template <typename T>
+    static __device__ __forceinline__ void total(T v, T *__restrict__ blk)
+    {
+        __shared__ T s_wave[THREADS / 64];
+        T sum;
+        block_scan<T, THREADS>(v, s_wave, &sum);
+        if (threadIdx.x == 0) blk[blockIdx.x] = sum;
+    }
+
+    // one workgroup: out[0 .. nblk) <- the exclusive scan of the chunk totals in[0 .. nblk) (out may be in); returns their sum
+    template <typename T>
+    static __device__ __forceinline__ T scan_totals(const T *in, T *out, int nblk)
+    {
+        __shared__ T s_wave[THREADS / 64];
+        return scan_in_place<T, THREADS>(in, out, nblk, s_wave);
+    }
+
+    // the sum of v over every thread in front of this one in the whole array (blk: the scanned chunk totals)
+    template <typename T>
+    static __device__ __forceinline__ T rank(T v, const T *__restrict__ blk)
+    {
+        __shared__ T s_wave[THREADS / 64];
+        T sum;
+        return blk[blockIdx.x] + block_scan<T, THREADS>(v, s_wave, &sum);
+    }
+};
 
 }  // namespace sls

@@ -25,18 +25,14 @@
 //                               whole wave afterwards (lane l adds l, l + 64, ..., then a fixed xor butterfly)
 //   simp_status                 the eight status words
 // Timed (sls_timing_enable): the groups simp_cluster, simp_faces, simp_corners, simp_place; the sorts under sort_*.
-#include <float.h>
-
-#include "sls_launch.hpp"
+#include "sls_geom.hpp"
 #include "sls_scan.hpp"
 #include "../../include/sls_simplify_math.h"
 
 namespace sls {
 
 constexpr int kSimpThreads = 512;
-constexpr int kSimpWaves = kSimpThreads / 64;
-constexpr int kSimpPer = 4;                                 // consecutive positions per thread of a chunked scan
-constexpr int kSimpChunk = kSimpThreads * kSimpPer;         // 2048
+using SimpChunks = Chunks<kSimpThreads, 4>;                 // the chunked scans: 2048 positions per workgroup
 constexpr int kSimpPlaceThreads = 256;
 constexpr uint64_t kSimpNoKey = 1ull << 63;                 // the key of a vertex that belongs to no cluster
 constexpr int kSimpKeyBits = 64;
@@ -44,24 +40,6 @@ constexpr int kSimpKeyBits = 64;
 // hdr words
 enum { SH_MIN = 0, SH_NONFINITE = 3, SH_BIG = 4, SH_COLLAPSED = 5, SH_DUPLICATES = 6, SH_FALLBACKS = 7, SH_NV = 8, SH_NT = 9,
        SH_N3T = 10, SH_NC = 11, SH_VOUT = 12, SH_TOUT = 13 };
-
-static size_t simp_al(size_t v) { return (v + 255) & ~(size_t)255; }
-static int simp_chunks(size_t n) { return (int)((n + kSimpChunk - 1) / kSimpChunk); }
-static dim3 simp_grid(size_t n) { return dim3((unsigned)((n + kSimpThreads - 1) / kSimpThreads)); }
-
-__device__ __forceinline__ uint32_t simp_f2ord(float f)
-{   // monotone float -> uint mapping
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float simp_ord2f(uint32_t o)
-{
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-__device__ __forceinline__ bool simp_finite3(const float *__restrict__ xyz, size_t v)
-{
-    return sls_simplify_finite(xyz[3 * v]) && sls_simplify_finite(xyz[3 * v + 1]) && sls_simplify_finite(xyz[3 * v + 2]);
-}
 
 __global__ void simp_init_kernel(uint32_t *hdr, uint32_t V, uint32_t T)
 {
@@ -81,33 +59,7 @@ __global__ __launch_bounds__(kSimpThreads) void simp_mark_kernel(int T, const in
 __global__ __launch_bounds__(kSimpThreads) void simp_bbox_kernel(uint32_t V, const float *__restrict__ xyz,
                                                                  const uint32_t *__restrict__ vlive, uint32_t *hdr)
 {
-    float mn[3] = { INFINITY, INFINITY, INFINITY };
-    uint32_t bad = 0u;
-    for (size_t i = (size_t)blockIdx.x * kSimpThreads + threadIdx.x; i < (size_t)V; i += (size_t)gridDim.x * kSimpThreads) {
-        if (!vlive[i]) continue;
-        if (simp_finite3(xyz, i)) {
-            mn[0] = fminf(mn[0], xyz[3 * i]); mn[1] = fminf(mn[1], xyz[3 * i + 1]); mn[2] = fminf(mn[2], xyz[3 * i + 2]);
-        } else {
-            bad += 1u;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) mn[k] = fminf(mn[k], __shfl_xor(mn[k], off, 64));
-        bad += __shfl_xor(bad, off, 64);
-    }
-    __shared__ uint32_t s_box[4];
-    if (threadIdx.x < 4) s_box[threadIdx.x] = threadIdx.x < 3 ? 0xFFFFFFFFu : 0u;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) atomicMin(&s_box[k], simp_f2ord(mn[k]));
-        atomicAdd(&s_box[3], bad);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) atomicMin(&hdr[SH_MIN + threadIdx.x], s_box[threadIdx.x]);
-    else if (threadIdx.x == 3 && s_box[3]) atomicAdd(&hdr[SH_NONFINITE], s_box[3]);
+    bbox_min<kSimpThreads>(V, xyz, vlive, hdr + SH_MIN, hdr + SH_NONFINITE);
 }
 
 __global__ __launch_bounds__(kSimpThreads) void simp_keys_kernel(uint32_t V, const float *__restrict__ xyz,
@@ -118,10 +70,10 @@ __global__ __launch_bounds__(kSimpThreads) void simp_keys_kernel(uint32_t V, con
     bool big = false;
     if (i < (size_t)V) {
         uint64_t key = kSimpNoKey;
-        if (vlive[i] && simp_finite3(xyz, i)) {                 // (then the minima are finite too)
-            const double ox = sls_voxel_origin(simp_ord2f(hdr[SH_MIN + 0]), voxel_size),
-                         oy = sls_voxel_origin(simp_ord2f(hdr[SH_MIN + 1]), voxel_size),
-                         oz = sls_voxel_origin(simp_ord2f(hdr[SH_MIN + 2]), voxel_size);
+        if (vlive[i] && finite_row(xyz, i)) {                 // (then the minima are finite too)
+            const double ox = sls_voxel_origin(ord2f(hdr[SH_MIN + 0]), voxel_size),
+                         oy = sls_voxel_origin(ord2f(hdr[SH_MIN + 1]), voxel_size),
+                         oz = sls_voxel_origin(ord2f(hdr[SH_MIN + 2]), voxel_size);
             big = !sls_voxel_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ox, oy, oz, voxel_size, &key);
         }
         keys[i] = key;
@@ -134,37 +86,19 @@ __global__ __launch_bounds__(kSimpThreads) void simp_keys_kernel(uint32_t V, con
 // the head flags of this thread's four consecutive sorted positions, as a bit mask (the run of kSimpNoKey has one too)
 __device__ __forceinline__ uint32_t simp_head_mask(uint32_t V, const uint64_t *__restrict__ keys, uint32_t p0)
 {
-    uint32_t mask = 0u;
-    if (p0 < V) {
-        uint64_t prev = p0 ? keys[p0 - 1] : 0u;
-#pragma unroll
-        for (int j = 0; j < kSimpPer; ++j) {
-            const uint32_t p = p0 + (uint32_t)j;
-            if (p < V) {
-                const uint64_t k = keys[p];
-                if (p == 0u || k != prev) mask |= 1u << j;
-                prev = k;
-            }
-        }
-    }
-    return mask;
+    return SimpChunks::head_mask(V, p0, [&](uint32_t p) { return keys[p]; });
 }
 
 __global__ __launch_bounds__(kSimpThreads) void simp_vheads_kernel(uint32_t V, const uint64_t *__restrict__ keys, uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kSimpWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kSimpChunk + threadIdx.x * (uint32_t)kSimpPer;
-    uint32_t total;
-    block_scan<uint32_t, kSimpThreads>((uint32_t)__popc(simp_head_mask(V, keys, p0)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    SimpChunks::total((uint32_t)__popc(simp_head_mask(V, keys, SimpChunks::first())), blk);
 }
 
 // seg_start holds V + 1 entries: heads <= V
 __global__ __launch_bounds__(kSimpThreads) void simp_vscan_kernel(uint32_t V, int nblk, uint32_t *blk, const uint64_t *__restrict__ keys,
                                                                   uint32_t *__restrict__ hdr, uint32_t *__restrict__ seg_start)
 {
-    __shared__ uint32_t s_wave[kSimpWaves];
-    const uint32_t heads = scan_in_place<uint32_t, kSimpThreads>(blk, blk, nblk, s_wave);
+    const uint32_t heads = SimpChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) {
         const uint32_t h = heads <= V ? heads : V;              // (always: a head per position at most)
         seg_start[h] = V;
@@ -176,13 +110,11 @@ __global__ __launch_bounds__(kSimpThreads) void simp_vsegments_kernel(uint32_t V
                                                                       const uint32_t *__restrict__ order, const uint32_t *__restrict__ blk,
                                                                       uint32_t *__restrict__ seg_start, int32_t *__restrict__ cid)
 {
-    __shared__ uint32_t s_wave[kSimpWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kSimpChunk + threadIdx.x * (uint32_t)kSimpPer;
+    const uint32_t p0 = SimpChunks::first();
     const uint32_t mask = simp_head_mask(V, keys, p0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kSimpThreads>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = SimpChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kSimpPer; ++j) {
+    for (int j = 0; j < SimpChunks::kPer; ++j) {
         const uint32_t p = p0 + (uint32_t)j;
         if (p < V) {
             if ((mask >> j) & 1u) {
@@ -264,28 +196,15 @@ __global__ __launch_bounds__(kSimpThreads) void simp_dedupe_kernel(uint32_t T, u
 // ---------------------------------------------------------------------------------------------------------------------
 // the two ordered compactions
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t simp_flag_mask(uint32_t n, const uint32_t *__restrict__ flag, uint32_t i0)
-{
-    uint32_t mask = 0u;
-#pragma unroll
-    for (int j = 0; j < kSimpPer; ++j)
-        if (i0 + (uint32_t)j < n && flag[i0 + (uint32_t)j]) mask |= 1u << j;
-    return mask;
-}
-
 __global__ __launch_bounds__(kSimpThreads) void simp_count_kernel(uint32_t n, const uint32_t *__restrict__ flag, uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kSimpWaves];
-    const uint32_t i0 = blockIdx.x * (uint32_t)kSimpChunk + threadIdx.x * (uint32_t)kSimpPer;
-    uint32_t total;
-    block_scan<uint32_t, kSimpThreads>((uint32_t)__popc(simp_flag_mask(n, flag, i0)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    SimpChunks::total((uint32_t)__popc(SimpChunks::flag_mask(n, flag, SimpChunks::first())), blk);
 }
 
 __global__ __launch_bounds__(kSimpThreads) void simp_scan_kernel(int nblk_t, uint32_t *blk_t, int nblk_v, uint32_t *blk_v,
                                                                  uint32_t *__restrict__ hdr)
 {
-    __shared__ uint32_t s_wave_t[kSimpWaves], s_wave_v[kSimpWaves];
+    __shared__ uint32_t s_wave_t[kSimpThreads / 64], s_wave_v[kSimpThreads / 64];
     const uint32_t nt = scan_in_place<uint32_t, kSimpThreads>(blk_t, blk_t, nblk_t, s_wave_t);
     const uint32_t nv = scan_in_place<uint32_t, kSimpThreads>(blk_v, blk_v, nblk_v, s_wave_v);
     if (threadIdx.x == 0) { hdr[SH_VOUT] = nv; hdr[SH_TOUT] = nt; }
@@ -295,13 +214,11 @@ __global__ __launch_bounds__(kSimpThreads) void simp_scan_kernel(int nblk_t, uin
 __global__ __launch_bounds__(kSimpThreads) void simp_cnew_kernel(uint32_t V, const uint32_t *__restrict__ csurv,
                                                                  const uint32_t *__restrict__ blk, uint32_t *__restrict__ cnew)
 {
-    __shared__ uint32_t s_wave[kSimpWaves];
-    const uint32_t c0 = blockIdx.x * (uint32_t)kSimpChunk + threadIdx.x * (uint32_t)kSimpPer;
-    const uint32_t mask = simp_flag_mask(V, csurv, c0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kSimpThreads>((uint32_t)__popc(mask), s_wave, &total);
+    const uint32_t c0 = SimpChunks::first();
+    const uint32_t mask = SimpChunks::flag_mask(V, csurv, c0);
+    uint32_t id = SimpChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kSimpPer; ++j)
+    for (int j = 0; j < SimpChunks::kPer; ++j)
         if ((mask >> j) & 1u) cnew[c0 + (uint32_t)j] = id++;
 }
 
@@ -309,13 +226,11 @@ __global__ __launch_bounds__(kSimpThreads) void simp_fwrite_kernel(uint32_t T, u
                                                                    const uint32_t *__restrict__ blk, const int32_t *__restrict__ rf,
                                                                    const uint32_t *__restrict__ cnew, int32_t *__restrict__ out_faces)
 {
-    __shared__ uint32_t s_wave[kSimpWaves];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kSimpChunk + threadIdx.x * (uint32_t)kSimpPer;
-    const uint32_t mask = simp_flag_mask(T, kept, t0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kSimpThreads>((uint32_t)__popc(mask), s_wave, &total);
+    const uint32_t t0 = SimpChunks::first();
+    const uint32_t mask = SimpChunks::flag_mask(T, kept, t0);
+    uint32_t id = SimpChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kSimpPer; ++j)
+    for (int j = 0; j < SimpChunks::kPer; ++j)
         if ((mask >> j) & 1u) {                     // (id < T: the output holds T rows; a kept triple lies inside [0, V))
             const size_t t = t0 + (uint32_t)j;
 #pragma unroll
@@ -376,11 +291,7 @@ __device__ __forceinline__ void simp_segment_sums(uint32_t s, uint32_t e, bool a
 #pragma unroll
         for (int k = 0; k < N; ++k) part[k] = 0.0;
         for (uint32_t p = s0 + (uint32_t)lane; p < e0; p += 64u) add(p, part);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) part[k] += __shfl_xor(part[k], off, 64);
-        }
+        xor_butterfly<N>(part);
         if (lane == src) {
 #pragma unroll
             for (int k = 0; k < N; ++k) acc[k] = part[k];
@@ -474,43 +385,40 @@ struct SimplifyScratch {
 static SimplifyScratch simplify_layout(size_t V, size_t T, void *base)
 {
     SimplifyScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *q = p + off; off += simp_al(bytes); return (void *)q; };
-    s.nblk_v = simp_chunks(V); s.nblk_t = simp_chunks(T);
-    s.hdr = (uint32_t *)take(16 * sizeof(uint32_t));
-    s.vlive = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.vkeys = (uint64_t *)take(sizeof(uint64_t) * V);
-    s.vkeys_tmp = (uint64_t *)take(sizeof(uint64_t) * V);
-    s.vvals = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.vvals_tmp = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.seg_start = (uint32_t *)take(sizeof(uint32_t) * (V + 1));
-    s.cid = (int32_t *)take(sizeof(int32_t) * V);
-    s.vmap = (int32_t *)take(sizeof(int32_t) * V);
-    s.csurv = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.cnew = (uint32_t *)take(sizeof(uint32_t) * V);
-    s.rf = (int32_t *)take(3 * sizeof(int32_t) * T);
-    s.fkeys = (uint64_t *)take(sizeof(uint64_t) * T);
-    s.fkeys_tmp = (uint64_t *)take(sizeof(uint64_t) * T);
-    s.fvals = (uint32_t *)take(sizeof(uint32_t) * T);
-    s.fvals_tmp = (uint32_t *)take(sizeof(uint32_t) * T);
-    s.kept = (uint32_t *)take(sizeof(uint32_t) * T);
-    s.ckeys = (uint32_t *)take(3 * sizeof(uint32_t) * T);
-    s.ckeys_tmp = (uint32_t *)take(3 * sizeof(uint32_t) * T);
-    s.cvals = (uint32_t *)take(3 * sizeof(uint32_t) * T);
-    s.cvals_tmp = (uint32_t *)take(3 * sizeof(uint32_t) * T);
-    s.blk_v = (uint32_t *)take(sizeof(uint32_t) * (size_t)s.nblk_v);
-    s.blk_t = (uint32_t *)take(sizeof(uint32_t) * (size_t)s.nblk_t);
+    Arena a(base);
+    s.nblk_v = SimpChunks::count(V); s.nblk_t = SimpChunks::count(T);
+    s.hdr = a.take<uint32_t>(16);
+    s.vlive = a.take<uint32_t>(V);
+    s.vkeys = a.take<uint64_t>(V);
+    s.vkeys_tmp = a.take<uint64_t>(V);
+    s.vvals = a.take<uint32_t>(V);
+    s.vvals_tmp = a.take<uint32_t>(V);
+    s.seg_start = a.take<uint32_t>(V + 1);
+    s.cid = a.take<int32_t>(V);
+    s.vmap = a.take<int32_t>(V);
+    s.csurv = a.take<uint32_t>(V);
+    s.cnew = a.take<uint32_t>(V);
+    s.rf = a.take<int32_t>(3 * T);
+    s.fkeys = a.take<uint64_t>(T);
+    s.fkeys_tmp = a.take<uint64_t>(T);
+    s.fvals = a.take<uint32_t>(T);
+    s.fvals_tmp = a.take<uint32_t>(T);
+    s.kept = a.take<uint32_t>(T);
+    s.ckeys = a.take<uint32_t>(3 * T);
+    s.ckeys_tmp = a.take<uint32_t>(3 * T);
+    s.cvals = a.take<uint32_t>(3 * T);
+    s.cvals_tmp = a.take<uint32_t>(3 * T);
+    s.blk_v = a.take<uint32_t>((size_t)s.nblk_v);
+    s.blk_t = a.take<uint32_t>((size_t)s.nblk_t);
     s.sort_bytes = sort_scratch_bytes((uint64_t)(V > 3 * T ? V : 3 * T));
-    s.sort = take(s.sort_bytes);
-    s.total = off;
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total = a.off;
     return s;
 }
 
 size_t mesh_simplify_scratch_bytes(int V, int T)
 {
-    return (V > 0 && T > 0 && T <= SLS_MESH_MAX_TRIANGLES && V <= SLS_MESH_MAX_VERTICES) ? simplify_layout((size_t)V, (size_t)T, nullptr).total
-                                                                                         : 0;
+    return mesh_sizes_ok(V, T) ? simplify_layout((size_t)V, (size_t)T, nullptr).total : 0;
 }
 
 int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces, double voxel_size, int contraction,
@@ -527,13 +435,13 @@ int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *fac
     SLS_HIP_CHECK(hipMemsetAsync(s.csurv, 0, sizeof(uint32_t) * (size_t)V, st));
     hipLaunchKernelGGL(simp_init_kernel, dim3(1), dim3(64), 0, st, s.hdr, Vu, Tu);
     SLS_LAUNCH_CHECK("simp_init_kernel");
-    hipLaunchKernelGGL(simp_mark_kernel, simp_grid((size_t)T), dim3(kSimpThreads), 0, st, T, faces, V, s.vlive);
+    hipLaunchKernelGGL(simp_mark_kernel, grid_for((size_t)T, kSimpThreads), dim3(kSimpThreads), 0, st, T, faces, V, s.vlive);
     SLS_LAUNCH_CHECK("simp_mark_kernel");
-    const unsigned nbv = simp_grid((size_t)V).x;
+    const unsigned nbv = grid_for((size_t)V, kSimpThreads).x;
     hipLaunchKernelGGL(simp_bbox_kernel, dim3(nbv < 1024u ? nbv : 1024u), dim3(kSimpThreads), 0, st, Vu, vertices,
                        (const uint32_t *)s.vlive, s.hdr);
     SLS_LAUNCH_CHECK("simp_bbox_kernel");
-    hipLaunchKernelGGL(simp_keys_kernel, simp_grid((size_t)V), dim3(kSimpThreads), 0, st, Vu, vertices, (const uint32_t *)s.vlive,
+    hipLaunchKernelGGL(simp_keys_kernel, grid_for((size_t)V, kSimpThreads), dim3(kSimpThreads), 0, st, Vu, vertices, (const uint32_t *)s.vlive,
                        voxel_size, s.hdr, s.vkeys, s.vvals);
     SLS_LAUNCH_CHECK("simp_keys_kernel");
     tm_cluster.end_now();
@@ -552,7 +460,7 @@ int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *fac
     tm_segments.end_now();
 
     ScopedTimer tm_faces(T_SIMP_FACES, st);
-    hipLaunchKernelGGL(simp_faces_kernel, simp_grid((size_t)T), dim3(kSimpThreads), 0, st, T, faces, V, (const int32_t *)s.cid, s.hdr,
+    hipLaunchKernelGGL(simp_faces_kernel, grid_for((size_t)T, kSimpThreads), dim3(kSimpThreads), 0, st, T, faces, V, (const int32_t *)s.cid, s.hdr,
                        s.rf, s.fkeys, s.fvals);
     SLS_LAUNCH_CHECK("simp_faces_kernel");
     tm_faces.end_now();
@@ -562,7 +470,7 @@ int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *fac
     uint32_t *fv[2] = { s.fvals, s.fvals_tmp };
     int cur = which;
     ScopedTimer tm_face_keys(T_SIMP_FACES, st);
-    hipLaunchKernelGGL(simp_face_keys_kernel, simp_grid((size_t)T), dim3(kSimpThreads), 0, st, Tu, (const int32_t *)s.rf,
+    hipLaunchKernelGGL(simp_face_keys_kernel, grid_for((size_t)T, kSimpThreads), dim3(kSimpThreads), 0, st, Tu, (const int32_t *)s.rf,
                        (const uint32_t *)fv[cur], bits, fk[cur]);
     SLS_LAUNCH_CHECK("simp_face_keys_kernel");
     tm_face_keys.end_now();
@@ -570,7 +478,7 @@ int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *fac
     if (rc) return rc;
     cur ^= which;
     ScopedTimer tm_dedupe(T_SIMP_FACES, st);
-    hipLaunchKernelGGL(simp_dedupe_kernel, simp_grid((size_t)T), dim3(kSimpThreads), 0, st, Tu, Vu, (const int32_t *)s.rf,
+    hipLaunchKernelGGL(simp_dedupe_kernel, grid_for((size_t)T, kSimpThreads), dim3(kSimpThreads), 0, st, Tu, Vu, (const int32_t *)s.rf,
                        (const uint32_t *)fv[cur], s.kept, s.csurv, s.hdr);
     SLS_LAUNCH_CHECK("simp_dedupe_kernel");
 
@@ -586,7 +494,7 @@ int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *fac
     hipLaunchKernelGGL(simp_fwrite_kernel, dim3(s.nblk_t), dim3(kSimpThreads), 0, st, Tu, Vu, (const uint32_t *)s.kept,
                        (const uint32_t *)s.blk_t, (const int32_t *)s.rf, (const uint32_t *)s.cnew, out_faces);
     SLS_LAUNCH_CHECK("simp_fwrite_kernel");
-    hipLaunchKernelGGL(simp_vmap_kernel, simp_grid((size_t)V), dim3(kSimpThreads), 0, st, Vu, (const int32_t *)s.cid,
+    hipLaunchKernelGGL(simp_vmap_kernel, grid_for((size_t)V, kSimpThreads), dim3(kSimpThreads), 0, st, Vu, (const int32_t *)s.cid,
                        (const uint32_t *)s.csurv, (const uint32_t *)s.cnew, vmap);
     SLS_LAUNCH_CHECK("simp_vmap_kernel");
     tm_dedupe.end_now();
@@ -594,7 +502,7 @@ int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *fac
     const uint32_t *ckeys = s.ckeys, *cvals = s.cvals;
     if (contraction == 1) {
         ScopedTimer tm_corners(T_SIMP_CORNERS, st);
-        hipLaunchKernelGGL(simp_corner_keys_kernel, simp_grid((size_t)T), dim3(kSimpThreads), 0, st, T, faces, V, (const int32_t *)s.cid,
+        hipLaunchKernelGGL(simp_corner_keys_kernel, grid_for((size_t)T, kSimpThreads), dim3(kSimpThreads), 0, st, T, faces, V, (const int32_t *)s.cid,
                            s.ckeys, s.cvals);
         SLS_LAUNCH_CHECK("simp_corner_keys_kernel");
         tm_corners.end_now();
@@ -604,7 +512,7 @@ int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *fac
         if (which) { ckeys = s.ckeys_tmp; cvals = s.cvals_tmp; }
     }
     ScopedTimer tm_place(T_SIMP_PLACE, st);
-    hipLaunchKernelGGL(simp_place_kernel, dim3((Vu + kSimpPlaceThreads - 1) / kSimpPlaceThreads), dim3(kSimpPlaceThreads), 0, st, Vu, Tu,
+    hipLaunchKernelGGL(simp_place_kernel, grid_for(Vu, kSimpPlaceThreads), dim3(kSimpPlaceThreads), 0, st, Vu, Tu,
                        vertices, faces, order, (const uint32_t *)s.seg_start, (const uint32_t *)s.csurv, (const uint32_t *)s.cnew, ckeys,
                        cvals, contraction, regularisation, voxel_size, s.hdr, out_vertices);
     SLS_LAUNCH_CHECK("simp_place_kernel");

@@ -22,25 +22,20 @@
 //                               two float4 buffers of the scratch, the last sweep writes out_vertices
 //   adj_status                  the eight status words
 // Timed (sls_timing_enable): the groups smooth_adjacency and smooth_step; the sort under sort_*.
-#include "sls_launch.hpp"
+#include "sls_geom.hpp"
 #include "sls_scan.hpp"
 #include "../../include/sls_smooth_math.h"
 
 namespace sls {
 
 constexpr int kAdjThreads = 512;
-constexpr int kAdjWaves = kAdjThreads / 64;
-constexpr int kAdjPer = 4;                                  // consecutive positions per thread of a chunked scan
-constexpr int kAdjChunk = kAdjThreads * kAdjPer;            // 2048
+using AdjChunks = Chunks<kAdjThreads, 4>;                   // the chunked scan: 2048 positions per workgroup
 constexpr int kStepThreads = 256;
 constexpr int kLongMaxBlocks = 2048;                        // the long-row kernel strides over the list
 
 // hdr words
 enum { AH_N6 = 0, AH_HEADS, AH_LIVE, AH_BOUNDARY, AH_NONFINITE, AH_DEGENERATE, AH_RANGE, AH_MAXROW, AH_NLONG };
 
-static size_t adj_al(size_t v) { return (v + 255) & ~(size_t)255; }
-static int adj_chunks(size_t n) { return (int)((n + kAdjChunk - 1) / kAdjChunk); }
-static dim3 adj_grid(size_t n) { return dim3((unsigned)((n + kAdjThreads - 1) / kAdjThreads)); }
 // a row above 64 neighbours takes at least 65 of the 6 T directed keys, and there are at most V rows
 static size_t adj_long_cap(size_t V, size_t T) { const size_t c = 6 * T / (SLS_SMOOTH_LONG + 1) + 1; return c < V ? c : V; }
 
@@ -66,53 +61,25 @@ __global__ __launch_bounds__(kAdjThreads) void adj_keys_kernel(int T, const int3
             kb[6 * t + j] = (uint32_t)b;
         }
     }
-    const uint64_t md = __ballot(deg != 0), mr = __ballot(deg == 2);
-    if ((threadIdx.x & 63) == 0) {
-        if (md) atomicAdd(&hdr[AH_DEGENERATE], (uint32_t)__popcll(md));
-        if (mr) atomicAdd(&hdr[AH_RANGE], (uint32_t)__popcll(mr));
-    }
-}
-
-// the sorted pair at position p as one word: a in the high half (0: the pair of a degenerate triangle)
-__device__ __forceinline__ uint64_t adj_pair(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb, uint32_t p)
-{
-    return ((uint64_t)sa[p] << 32) | (uint64_t)sb[p];
+    count_degenerate(deg, &hdr[AH_DEGENERATE], &hdr[AH_RANGE]);
 }
 
 // the head flags of this thread's four consecutive sorted positions, as a bit mask: a pair that differs from its
-// predecessor (the zeros of the degenerate triangles come first and differ from nothing in front of them)
+// predecessor (the zeros of the degenerate triangles come first and form no run)
 __device__ __forceinline__ uint32_t adj_head_mask(uint32_t n, const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb, uint32_t p0)
 {
-    uint32_t mask = 0u;
-    if (p0 < n) {
-        uint64_t prev = p0 ? adj_pair(sa, sb, p0 - 1) : (uint64_t)0;
-#pragma unroll
-        for (int j = 0; j < kAdjPer; ++j) {
-            const uint32_t p = p0 + (uint32_t)j;
-            if (p < n) {
-                const uint64_t k = adj_pair(sa, sb, p);
-                if (k != prev) mask |= 1u << j;
-                prev = k;
-            }
-        }
-    }
-    return mask;
+    return AdjChunks::head_mask(n, p0, [&](uint32_t p) { return pair_key(sa, sb, p); }, 0u);
 }
 
 __global__ __launch_bounds__(kAdjThreads) void adj_heads_kernel(uint32_t n, const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb,
                                                                 uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kAdjWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kAdjChunk + threadIdx.x * (uint32_t)kAdjPer;
-    uint32_t total;
-    block_scan<uint32_t, kAdjThreads>((uint32_t)__popc(adj_head_mask(n, sa, sb, p0)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    AdjChunks::total((uint32_t)__popc(adj_head_mask(n, sa, sb, AdjChunks::first())), blk);
 }
 
 __global__ __launch_bounds__(kAdjThreads) void adj_scan_kernel(int nblk, uint32_t *blk, uint32_t *__restrict__ hdr)
 {
-    __shared__ uint32_t s_wave[kAdjWaves];
-    const uint32_t heads = scan_in_place<uint32_t, kAdjThreads>(blk, blk, nblk, s_wave);
+    const uint32_t heads = AdjChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) hdr[AH_HEADS] = heads;
 }
 
@@ -123,19 +90,17 @@ __global__ __launch_bounds__(kAdjThreads) void adj_write_kernel(uint32_t n, uint
                                                                 uint32_t *__restrict__ rank, int32_t *__restrict__ neighbours,
                                                                 uint8_t *boundary)
 {
-    __shared__ uint32_t s_wave[kAdjWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kAdjChunk + threadIdx.x * (uint32_t)kAdjPer;
+    const uint32_t p0 = AdjChunks::first();
     const uint32_t mask = adj_head_mask(n, sa, sb, p0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kAdjThreads>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = AdjChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kAdjPer; ++j) {
+    for (int j = 0; j < AdjChunks::kPer; ++j) {
         const uint32_t p = p0 + (uint32_t)j;
         if (p < n) {
             rank[p] = id;
             if ((mask >> j) & 1u) {
-                const uint64_t k = adj_pair(sa, sb, p);
-                const uint64_t next = p + 1u < n ? adj_pair(sa, sb, p + 1u) : (uint64_t)0;
+                const uint64_t k = pair_key(sa, sb, p);
+                const uint64_t next = p + 1u < n ? pair_key(sa, sb, p + 1u) : (uint64_t)0;
                 if (id < n) neighbours[id] = (int32_t)(uint32_t)k;  // (always: a head per position at most)
                 const uint32_t a = (uint32_t)(k >> 32);
                 if (next != k && a < V) boundary[a] = 1;            // (a < V always: the pair of a non-degenerate triangle)
@@ -274,11 +239,7 @@ __global__ __launch_bounds__(kStepThreads) void smooth_long_kernel(StepArgs a, c
         if (len <= (uint32_t)SLS_SMOOTH_LONG) continue;             // (never: the list holds long rows alone)
         double part[4] = { 0.0, 0.0, 0.0, 0.0 };
         for (uint32_t p = s + (uint32_t)lane; p < e; p += 64u) smooth_item(a, pi, p, part);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) part[k] += __shfl_xor(part[k], off, 64);
-        }
+        xor_butterfly<4>(part);
         if (lane == 0) {
             float o[3];
             smooth_result(a, pi, part, len, o);
@@ -297,23 +258,22 @@ struct AdjScratch {
     int nblk;
 };
 
-static AdjScratch adjacency_layout(size_t V, size_t T, char *base, size_t &off)
+static AdjScratch adjacency_layout(size_t V, size_t T, Arena &a)
 {
     AdjScratch s;
-    auto take = [&](size_t bytes) { char *q = base + off; off += adj_al(bytes); return (void *)q; };
     const size_t n6 = 6 * T;
-    s.nblk = adj_chunks(n6);
+    s.nblk = AdjChunks::count(n6);
     s.long_cap = adj_long_cap(V, T);
-    s.hdr = (uint32_t *)take(16 * sizeof(uint32_t));
-    s.ka = (uint32_t *)take(sizeof(uint32_t) * n6);
-    s.ka_tmp = (uint32_t *)take(sizeof(uint32_t) * n6);
-    s.kb = (uint32_t *)take(sizeof(uint32_t) * n6);
-    s.kb_tmp = (uint32_t *)take(sizeof(uint32_t) * n6);
-    s.blk = (uint32_t *)take(sizeof(uint32_t) * (size_t)s.nblk);
-    s.long_rows = (uint32_t *)take(sizeof(uint32_t) * s.long_cap);
+    s.hdr = a.take<uint32_t>(16);
+    s.ka = a.take<uint32_t>(n6);
+    s.ka_tmp = a.take<uint32_t>(n6);
+    s.kb = a.take<uint32_t>(n6);
+    s.kb_tmp = a.take<uint32_t>(n6);
+    s.blk = a.take<uint32_t>((size_t)s.nblk);
+    s.long_rows = a.take<uint32_t>(s.long_cap);
     s.sort_bytes = sort_scratch_bytes((uint64_t)n6);
-    s.sort = take(s.sort_bytes);
-    s.total = off;
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total = a.off;
     return s;
 }
 
@@ -329,32 +289,26 @@ struct SmoothScratch {
 static SmoothScratch smooth_layout(size_t V, size_t T, void *base)
 {
     SmoothScratch s;
-    size_t off = 0;
-    s.adj = adjacency_layout(V, T, (char *)base, off);
-    auto take = [&](size_t bytes) { char *q = (char *)base + off; off += adj_al(bytes); return (void *)q; };
-    s.offsets = (uint32_t *)take(sizeof(uint32_t) * (V + 1));
-    s.neighbours = (int32_t *)take(sizeof(int32_t) * 6 * T);
-    s.boundary = (uint8_t *)take(V);
-    s.ping = (float4 *)take(sizeof(float4) * V);
-    s.pong = (float4 *)take(sizeof(float4) * V);
-    s.total = off;
+    Arena a(base);
+    s.adj = adjacency_layout(V, T, a);
+    s.offsets = a.take<uint32_t>(V + 1);
+    s.neighbours = a.take<int32_t>(6 * T);
+    s.boundary = a.take<uint8_t>(V);
+    s.ping = a.take<float4>(V);
+    s.pong = a.take<float4>(V);
+    s.total = a.off;
     return s;
-}
-
-static bool smooth_sizes_ok(int V, int T)
-{
-    return V > 0 && T > 0 && T <= SLS_MESH_MAX_TRIANGLES && V <= SLS_MESH_MAX_VERTICES;
 }
 
 size_t mesh_adjacency_scratch_bytes(int V, int T)
 {
-    size_t off = 0;
-    return smooth_sizes_ok(V, T) ? adjacency_layout((size_t)V, (size_t)T, nullptr, off).total : 0;
+    Arena a(nullptr);
+    return mesh_sizes_ok(V, T) ? adjacency_layout((size_t)V, (size_t)T, a).total : 0;
 }
 
 size_t mesh_smooth_scratch_bytes(int V, int T)
 {
-    return smooth_sizes_ok(V, T) ? smooth_layout((size_t)V, (size_t)T, nullptr).total : 0;
+    return mesh_sizes_ok(V, T) ? smooth_layout((size_t)V, (size_t)T, nullptr).total : 0;
 }
 
 // offsets (V + 1), neighbours (capacity 6 T), boundary (V) and the hdr words; vertices may be null (no non-finite count)
@@ -363,21 +317,17 @@ static int adjacency_build(int V, int T, const int32_t *faces, const float *vert
 {
     const uint32_t Vu = (uint32_t)V, n6 = 6u * (uint32_t)T;
     const int bits = sls_mesh_index_bits(V);
-    int which = 0;
     ScopedTimer tm_keys(T_SMOOTH_ADJACENCY, st);
     SLS_HIP_CHECK(hipMemsetAsync(boundary, 0, (size_t)V, st));
     hipLaunchKernelGGL(adj_init_kernel, dim3(1), dim3(64), 0, st, s.hdr, n6);
     SLS_LAUNCH_CHECK("adj_init_kernel");
-    hipLaunchKernelGGL(adj_keys_kernel, adj_grid((size_t)T), dim3(kAdjThreads), 0, st, T, faces, V, s.hdr, s.ka, s.kb);
+    hipLaunchKernelGGL(adj_keys_kernel, grid_for((size_t)T, kAdjThreads), dim3(kAdjThreads), 0, st, T, faces, V, s.hdr, s.ka, s.kb);
     SLS_LAUNCH_CHECK("adj_keys_kernel");
     tm_keys.end_now();
     uint32_t *a2[2] = { s.ka, s.ka_tmp }, *b2[2] = { s.kb, s.kb_tmp };
-    int rc = radix_sort_pairs_u32(b2[0], a2[0], b2[1], a2[1], s.hdr + AH_N6, n6, bits, s.sort, s.sort_bytes, &which, st);    // by b
+    int cur = 0;
+    const int rc = sort_pairs_ab(a2, b2, s.hdr + AH_N6, n6, bits, s.sort, s.sort_bytes, &cur, st);
     if (rc) return rc;
-    int cur = which;
-    rc = radix_sort_pairs_u32(a2[cur], b2[cur], a2[cur ^ 1], b2[cur ^ 1], s.hdr + AH_N6, n6, bits, s.sort, s.sort_bytes, &which, st);   // by a, stable
-    if (rc) return rc;
-    cur ^= which;
     const uint32_t *sa = a2[cur], *sb = b2[cur];
     uint32_t *rank = a2[cur ^ 1];                                   // (the other copy is free: its room holds the ranks)
     ScopedTimer tm_rows(T_SMOOTH_ADJACENCY, st);
@@ -388,10 +338,10 @@ static int adjacency_build(int V, int T, const int32_t *faces, const float *vert
     hipLaunchKernelGGL(adj_write_kernel, dim3(s.nblk), dim3(kAdjThreads), 0, st, n6, Vu, sa, sb, (const uint32_t *)s.blk, rank,
                        neighbours, boundary);
     SLS_LAUNCH_CHECK("adj_write_kernel");
-    hipLaunchKernelGGL(adj_offsets_kernel, adj_grid((size_t)V + 1), dim3(kAdjThreads), 0, st, n6, Vu, sa, (const uint32_t *)rank,
+    hipLaunchKernelGGL(adj_offsets_kernel, grid_for((size_t)V + 1, kAdjThreads), dim3(kAdjThreads), 0, st, n6, Vu, sa, (const uint32_t *)rank,
                        (const uint32_t *)s.hdr, offsets);
     SLS_LAUNCH_CHECK("adj_offsets_kernel");
-    hipLaunchKernelGGL(adj_rows_kernel, adj_grid((size_t)V), dim3(kAdjThreads), 0, st, Vu, (const uint32_t *)offsets,
+    hipLaunchKernelGGL(adj_rows_kernel, grid_for((size_t)V, kAdjThreads), dim3(kAdjThreads), 0, st, Vu, (const uint32_t *)offsets,
                        (const uint8_t *)boundary, vertices, (uint32_t)s.long_cap, s.hdr, s.long_rows);
     SLS_LAUNCH_CHECK("adj_rows_kernel");
     return SLS_OK;
@@ -400,8 +350,8 @@ static int adjacency_build(int V, int T, const int32_t *faces, const float *vert
 int launch_mesh_adjacency(int V, int T, const int32_t *faces, int32_t *out_offsets, int32_t *out_neighbours, uint8_t *out_boundary,
                           uint32_t *out_status, void *scratch, hipStream_t st)
 {
-    size_t off = 0;
-    const AdjScratch s = adjacency_layout((size_t)V, (size_t)T, (char *)scratch, off);
+    Arena a(scratch);
+    const AdjScratch s = adjacency_layout((size_t)V, (size_t)T, a);
     const int rc = adjacency_build(V, T, faces, nullptr, (uint32_t *)out_offsets, out_neighbours, out_boundary, s, st);
     if (rc) return rc;
     hipLaunchKernelGGL(adj_status_kernel, dim3(1), dim3(64), 0, st, (const uint32_t *)s.hdr, out_status);
@@ -425,7 +375,7 @@ int launch_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces
         return SLS_OK;
     }
     ScopedTimer tm_step(T_SMOOTH_STEP, st);
-    const dim3 grid((Vu + kStepThreads - 1) / kStepThreads);
+    const dim3 grid = grid_for(Vu, kStepThreads);
     const size_t long_blocks = (s.adj.long_cap + kStepThreads / 64 - 1) / (kStepThreads / 64);
     const dim3 grid_long((unsigned)(long_blocks < (size_t)kLongMaxBlocks ? long_blocks : (size_t)kLongMaxBlocks));
     hipLaunchKernelGGL(smooth_pack_kernel, grid, dim3(kStepThreads), 0, st, Vu, vertices, s.ping);

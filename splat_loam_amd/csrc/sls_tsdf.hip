@@ -21,23 +21,17 @@
 //                               scans counts -> prefix, the total -> status.  emit: the workgroup's exclusive scan of
 //                               the cubes' counts (wave scans of 64 lanes, then the eight wave sums) fixes the position
 //                               of every triangle: ascending block, cube, tetrahedron, triangle.  No atomics.
-#include <float.h>
-
-#include "sls_launch.hpp"
+#include "sls_geom.hpp"
 #include "sls_scan.hpp"
 #include "../../include/sls_tsdf_math.h"
 
 namespace sls {
 
 constexpr int kTsdfThreads = SLS_TSDF_BLOCK_VOXELS;         // 512: a thread per voxel of a block
-constexpr int kTsdfWaves = kTsdfThreads / 64;
-constexpr int kTsdfPer = 4;                                 // consecutive sorted positions per thread of the head scan
-constexpr int kTsdfChunk = kTsdfThreads * kTsdfPer;         // 2048
+using TsdfChunks = Chunks<kTsdfThreads, 4>;                 // the head scan: chunks of 2048 sorted positions
 constexpr int kTsdfTile = 9 * 9 * 9;
 
 enum { TH_COUNT = 0, TH_NONFINITE = 1, TH_RANGE = 2 };      // hdr words of the block scratch
-
-__device__ __forceinline__ bool tsdf_finite(float v) { return fabsf(v) <= FLT_MAX; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // which blocks exist
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_keys_kernel(int M, const fl
         uint64_t k[SLS_TSDF_POINT_KEYS];
 #pragma unroll
         for (int j = 0; j < SLS_TSDF_POINT_KEYS; ++j) k[j] = 0u;
-        if (tsdf_finite(p[0]) && tsdf_finite(p[1]) && tsdf_finite(p[2])) range = !sls_tsdf_point_keys(p, g.origin, g.voxel_size, margin, k);
+        if (finite_f32(p[0]) && finite_f32(p[1]) && finite_f32(p[2])) range = !sls_tsdf_point_keys(p, g.origin, g.voxel_size, margin, k);
         else nonfinite = true;
 #pragma unroll
         for (int j = 0; j < SLS_TSDF_POINT_KEYS; ++j) {
@@ -75,39 +69,21 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_keys_kernel(int M, const fl
     }
 }
 
-// the head flags of this thread's four consecutive sorted positions, as a bit mask
+// the head flags of this thread's four consecutive sorted positions, as a bit mask (key 0: no block; the zeros sort to the front)
 __device__ __forceinline__ uint32_t tsdf_head_mask(uint32_t n, const uint64_t *__restrict__ keys, uint32_t p0)
 {
-    uint32_t mask = 0u;
-    if (p0 < n) {
-        uint64_t prev = p0 ? keys[p0 - 1] : 0u;
-#pragma unroll
-        for (int j = 0; j < kTsdfPer; ++j) {
-            const uint32_t p = p0 + (uint32_t)j;
-            if (p < n) {
-                const uint64_t k = keys[p];
-                if (k != 0u && k != prev) mask |= 1u << j;      // (key 0: no block; the zeros sort to the front)
-                prev = k;
-            }
-        }
-    }
-    return mask;
+    return TsdfChunks::head_mask(n, p0, [&](uint32_t p) { return keys[p]; }, 0u);
 }
 
 __global__ __launch_bounds__(kTsdfThreads) void tsdf_heads_kernel(uint32_t n, const uint64_t *__restrict__ keys, uint32_t *__restrict__ blk)
 {
-    __shared__ uint32_t s_wave[kTsdfWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kTsdfChunk + threadIdx.x * (uint32_t)kTsdfPer;
-    uint32_t total;
-    block_scan<uint32_t, kTsdfThreads>((uint32_t)__popc(tsdf_head_mask(n, keys, p0)), s_wave, &total);
-    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+    TsdfChunks::total((uint32_t)__popc(tsdf_head_mask(n, keys, TsdfChunks::first())), blk);
 }
 
 __global__ __launch_bounds__(kTsdfThreads) void tsdf_scan_kernel(int nblk, uint32_t *__restrict__ blk, const uint32_t *__restrict__ hdr,
                                                                  uint32_t *__restrict__ status)
 {
-    __shared__ uint32_t s_wave[kTsdfWaves];
-    const uint32_t nb = scan_in_place<uint32_t, kTsdfThreads>(blk, blk, nblk, s_wave);
+    const uint32_t nb = TsdfChunks::scan_totals(blk, blk, nblk);
     if (threadIdx.x == 0) {
         status[0] = nb; status[1] = hdr[TH_NONFINITE]; status[2] = hdr[TH_RANGE]; status[3] = 1u;
     }
@@ -117,13 +93,11 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_write_kernel(uint32_t n, co
                                                                   const uint32_t *__restrict__ blk, uint32_t capacity,
                                                                   int32_t *__restrict__ out_blocks)
 {
-    __shared__ uint32_t s_wave[kTsdfWaves];
-    const uint32_t p0 = blockIdx.x * (uint32_t)kTsdfChunk + threadIdx.x * (uint32_t)kTsdfPer;
+    const uint32_t p0 = TsdfChunks::first();
     const uint32_t mask = tsdf_head_mask(n, keys, p0);
-    uint32_t total;
-    uint32_t id = blk[blockIdx.x] + block_scan<uint32_t, kTsdfThreads>((uint32_t)__popc(mask), s_wave, &total);
+    uint32_t id = TsdfChunks::rank((uint32_t)__popc(mask), blk);
 #pragma unroll
-    for (int j = 0; j < kTsdfPer; ++j)
+    for (int j = 0; j < TsdfChunks::kPer; ++j)
         if ((mask >> j) & 1u) {
             if (id < capacity) {
                 int32_t b[3];
@@ -146,22 +120,19 @@ struct TsdfBlockScratch {
 
 static TsdfBlockScratch tsdf_block_layout(int M, void *base)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     TsdfBlockScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
+    Arena a(base);
     const size_t n = SLS_TSDF_POINT_KEYS * (size_t)M;
-    s.nblk = (int)((n + kTsdfChunk - 1) / kTsdfChunk);
-    s.hdr = (uint32_t *)(p + off); off += al(16 * sizeof(uint32_t));
-    s.keys = (uint64_t *)(p + off); off += al(sizeof(uint64_t) * n);
-    s.keys_tmp = (uint64_t *)(p + off); off += al(sizeof(uint64_t) * n);
-    s.vals = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * n);
-    s.vals_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * n);
-    s.blk = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)s.nblk);
-    s.sort = (void *)(p + off);
+    s.nblk = TsdfChunks::count(n);
+    s.hdr = a.take<uint32_t>(16);
+    s.keys = a.take<uint64_t>(n);
+    s.keys_tmp = a.take<uint64_t>(n);
+    s.vals = a.take<uint32_t>(n);
+    s.vals_tmp = a.take<uint32_t>(n);
+    s.blk = a.take<uint32_t>((size_t)s.nblk);
     s.sort_bytes = sort_scratch_bytes((uint64_t)n);
-    off += al(s.sort_bytes);
-    s.total = off;
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total = a.off;
     return s;
 }
 
@@ -176,7 +147,7 @@ int launch_tsdf_blocks(int M, const float *xyz, double voxel_size, double trunc,
     g.origin[0] = origin[0]; g.origin[1] = origin[1]; g.origin[2] = origin[2]; g.voxel_size = voxel_size;
     hipLaunchKernelGGL(tsdf_init_kernel, dim3(1), dim3(64), 0, st, s.hdr, n);
     SLS_LAUNCH_CHECK("tsdf_init_kernel");
-    hipLaunchKernelGGL(tsdf_keys_kernel, dim3((M + kTsdfThreads - 1) / kTsdfThreads), dim3(kTsdfThreads), 0, st, M, xyz, g,
+    hipLaunchKernelGGL(tsdf_keys_kernel, grid_for((size_t)M, kTsdfThreads), dim3(kTsdfThreads), 0, st, M, xyz, g,
                        trunc + voxel_size, s.hdr, s.keys, s.vals);
     SLS_LAUNCH_CHECK("tsdf_keys_kernel");
     int which = 0;
@@ -316,20 +287,15 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_count_kernel(TsdfExtractArg
 {
     __shared__ float s_t[kTsdfTile], s_w[kTsdfTile];
     __shared__ int s_nb[8];
-    __shared__ uint32_t s_wave[kTsdfWaves];
     float f[8], c0[3], c1[3];
     const bool observed = tsdf_cube_corners(a, (int)blockIdx.x, s_t, s_w, s_nb, f, c0, c1);
-    const uint32_t n = observed ? (uint32_t)sls_tsdf_cube(f, c0, c1, nullptr) : 0u;
-    uint32_t total;
-    block_scan<uint32_t, kTsdfThreads>(n, s_wave, &total);
-    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+    TsdfChunks::total(observed ? (uint32_t)sls_tsdf_cube(f, c0, c1, nullptr) : 0u, counts);
 }
 
 __global__ __launch_bounds__(kTsdfThreads) void tsdf_prefix_kernel(int B, const uint32_t *__restrict__ counts, uint32_t *__restrict__ prefix,
                                                                    uint32_t *__restrict__ status)
 {
-    __shared__ uint32_t s_wave[kTsdfWaves];
-    const uint32_t total = scan_in_place<uint32_t, kTsdfThreads>(counts, prefix, B, s_wave);
+    const uint32_t total = TsdfChunks::scan_totals(counts, prefix, B);
     if (threadIdx.x == 0) { status[0] = total; status[1] = (uint32_t)B; status[2] = 0u; status[3] = 1u; }
 }
 
@@ -338,12 +304,10 @@ __global__ __launch_bounds__(kTsdfThreads) void tsdf_emit_kernel(TsdfExtractArgs
 {
     __shared__ float s_t[kTsdfTile], s_w[kTsdfTile];
     __shared__ int s_nb[8];
-    __shared__ uint32_t s_wave[kTsdfWaves];
     float f[8], c0[3], c1[3];
     const bool observed = tsdf_cube_corners(a, (int)blockIdx.x, s_t, s_w, s_nb, f, c0, c1);
     const uint32_t n = observed ? (uint32_t)sls_tsdf_cube(f, c0, c1, nullptr) : 0u;
-    uint32_t total;
-    const uint32_t pos = prefix[blockIdx.x] + block_scan<uint32_t, kTsdfThreads>(n, s_wave, &total);
+    const uint32_t pos = TsdfChunks::rank(n, prefix);
     if (n == 0u || pos >= T || n > T - pos) return;     // (never past the array the caller sized from the count call)
     sls_tsdf_cube(f, c0, c1, triangles + 9 * (size_t)pos);
 }

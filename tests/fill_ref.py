@@ -15,7 +15,7 @@ from simplify_ref import segment_sum
 
 ROOT = mesh_ref.ROOT
 LONG = 64                       # SLS_FILL_LONG
-CHUNK = 2048                    # kFillChunk of csrc/sls_fill.hip: the entries one workgroup scans or compacts
+CHUNK = 2048                    # FillChunks::kChunk of csrc/sls_fill.hip: the entries one workgroup scans or compacts
 FILLED, SKIP_EDGES, SKIP_NONFINITE, SKIP_SIZE = 0, 1, 2, 3
 STATUS = ("vertices", "triangles", "halfedges", "loops", "filled", "skipped_edges", "skipped_size", "skipped_nonfinite",
           "open_halfedges", "complex_vertices", "degenerate", "out_of_range", "needed_vertices", "needed_triangles", "overflow")
@@ -434,7 +434,7 @@ MANY_CELLS = 79
 
 def many_loops():
     """every second square of every second row of a sheet of 159 x 159 squares left out: MANY_CELLS^2 = 6241 loops of 4
-    half-edges and the outer rim of 636, B = 25 600 — the loops and B are each more than three times kFillChunk = 2048, the
+    half-edges and the outer rim of 636, B = 25 600 — the loops and B are each more than three times FillChunks::kChunk = 2048, the
     entries one workgroup of every scan and compaction of sls_fill.hip handles (6241 > 3 x 2048 = 6144, B = 12.5 x 2048);
     25 600 vertices, 38 080 triangles"""
     n = 2 * MANY_CELLS + 2
@@ -522,6 +522,19 @@ def rings(sizes=(64, 65, 100), seed=5):
     return _f32(np.concatenate(vs)), _i32(np.concatenate(fs))
 
 
+STRIPS = (682, 683, 1365, 1366)     # 3 T = 2046, 2049, 4095, 4098 sorted pairs: either side of one and of two chunks of CHUNK entries
+
+
+def strip(T, seed=13):
+    """an open strip of T triangles of one orientation over T + 2 vertices on two rows with seeded noise: no hole, the rim
+    one loop of T + 2 half-edges (longer than every max_edges of settings(): found, never filled)"""
+    rng = np.random.default_rng(seed + T)
+    i = np.arange(T + 2)
+    v = np.stack([0.125 * i, 0.25 * (i % 2), 0.3 + 0.02 * rng.uniform(-1.0, 1.0, T + 2)], 1)
+    t = np.arange(T)
+    return _f32(v), _i32(np.stack([np.where(t % 2 == 0, t, t + 1), np.where(t % 2 == 0, t + 1, t), t + 2], 1))
+
+
 def cases():
     """name -> (vertices (V,3) float32, faces (T,3) int32, counts or None)"""
     nan = np.float32(np.nan)
@@ -544,6 +557,8 @@ def cases():
     out["nan_rim"] = (v, f, None)
     out["rings"] = rings() + (None,)                                                                    # loops of 64, 65 and 100, twice each
     out["many_loops"] = many_loops() + (None,)
+    for T in STRIPS:                                                                                    # the edges of the scans' chunks
+        out[f"strip_{T}"] = strip(T) + (None,)
     out["closed"] = (_f32(TET_V), _i32(TET_F), None)
     out["no_faces"] = (_f32(TET_V), _i32([]), None)
     out["no_vertices"] = (_f32([]), _i32([]), None)

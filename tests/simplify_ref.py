@@ -357,7 +357,7 @@ def status_words(stats):
 
 # ---- the case table --------------------------------------------------------------------------------------------------
 # One workgroup's share of every chunked pass: the sorter takes 1024 items per wave and 4096 per workgroup (11-bit digits),
-# the head / compaction scans take 2048 positions (kSimpChunk); a segment of more than 64 items is summed by 64 lanes.
+# the head / compaction scans take 2048 positions (SimpChunks::kChunk); a segment of more than 64 items is summed by 64 lanes.
 CHUNKS = {"sort_wave": 1024, "scan": 2048, "sort_workgroup": 4096}
 SIZED = sorted({n + d for n in CHUNKS.values() for d in (-1, 0, 1)} | {n + d - 2 for n in CHUNKS.values() for d in (-1, 0, 1)})
 

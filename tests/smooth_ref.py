@@ -307,6 +307,17 @@ def radii(v):
 
 
 SPHERE_NOISE = 0.02
+STRIPS = (341, 342, 682, 683)   # 6 T = 2046, 2052, 4092, 4098 directed pairs: either side of one and of two chunks of 2048 positions
+
+
+def strip(T, seed=13):
+    """an open strip of T triangles of one orientation over T + 2 vertices on two seeded irregular rows 0.25 apart: every
+    vertex lies on the rim, 6 T directed pairs with 2 (2 T + 1) heads"""
+    rng = np.random.default_rng(seed + T)
+    i = np.arange(T + 2)
+    v = np.stack([0.125 * i, 0.25 * (i % 2), np.zeros(T + 2)], 1) + rng.uniform(-0.05, 0.05, (T + 2, 3))
+    t = np.arange(T)
+    return _f32(v), _i32(np.stack([np.where(t % 2 == 0, t, t + 1), np.where(t % 2 == 0, t + 1, t), t + 2], 1))
 
 
 def cases():
@@ -333,6 +344,8 @@ def cases():
     out["coincident"] = (_f32([(0, 0, 0), (1, 0, 0), (1, 0, 0), (0.5, 1, 0.2), (0.5, -1, 0.1)]), _i32([(0, 1, 3), (1, 2, 3), (0, 4, 1), (1, 4, 2)]))
     out["nan_live"] = (_f32([(0, 0, 0), (1, 0, 0), (nan, 1, 0), (1, 1, 0.5)]), _i32([(0, 1, 2), (1, 3, 2)]))
     out["sphere_noisy"] = sphere(SPHERE_NOISE)
+    for T in STRIPS:                                                                                    # the edges of the scan's chunks
+        out[f"strip_{T}"] = strip(T)
     out["no_vertices"] = (_f32([]), _i32([]))
     out["no_faces"] = (_f32(tet_v), _i32([]))
     return out
