@@ -337,13 +337,18 @@ __device__ __forceinline__ int det_scale_exp(uint32_t own, uint32_t gex)
 
 // torch.optim.Adam update of one element (no weight decay, no amsgrad); shared by adam_kernel and
 // by the update fused into preprocess_bwd so that both produce the same bits.
+// The first moment is torch's lerp(m, g, w), w = 1 - beta1, in the form that is exact at its near end: m + (g - m) w for
+// w < 0.5 (every setting the project runs), g - (g - m) (1 - w) from 0.5 on.  The first form alone loses an ulp of g at
+// beta1 = 0, where the result is g itself: g - m rounds in the binade above g's and the sum lands beside g.
 struct AdamCoef {
-    float w1, b2, w2, eps, bc2_sqrt, bc1;   // 1-beta1, beta2, 1-beta2, eps, sqrt(1-beta2^t), 1-beta1^t
+    float w1, b2, w2, eps, bc2_sqrt, bc1;   // the lerp's factor, beta2, 1-beta2, eps, sqrt(1-beta2^t), 1-beta1^t
+    int from_g;                             // 0: m + (g - m) * w1, w1 = 1-beta1;  1: g + (g - m) * w1, w1 = -beta1
 };
 inline AdamCoef make_adam_coef(double beta1, double beta2, double eps, int64_t step)
 {
     AdamCoef c;
-    c.w1 = (float)(1.0 - beta1);
+    c.from_g = (float)(1.0 - beta1) >= 0.5f ? 1 : 0;
+    c.w1 = c.from_g ? -(float)beta1 : (float)(1.0 - beta1);
     c.b2 = (float)beta2;
     c.w2 = (float)(1.0 - beta2);
     c.eps = (float)eps;
@@ -353,7 +358,7 @@ inline AdamCoef make_adam_coef(double beta1, double beta2, double eps, int64_t s
 }
 __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, float step_size, const AdamCoef &a)
 {
-    m = m + (g - m) * a.w1;
+    m = (a.from_g ? g : m) + (g - m) * a.w1;
     v = v * a.b2 + (a.w2 * g) * g;
     // (hardware 1-ulp square root and reciprocals: an error of 1e-7 of the step, i.e. of lr-sized changes)
     const float denom = __builtin_amdgcn_sqrtf(v) * __builtin_amdgcn_rcpf(a.bc2_sqrt) + a.eps;
