@@ -364,14 +364,45 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     const float denom = __builtin_amdgcn_sqrtf(v) * __builtin_amdgcn_rcpf(a.bc2_sqrt) + a.eps;
     p = p - step_size * (m * __builtin_amdgcn_rcpf(denom));
 }
-// Adam fused into preprocess_bwd (one keyframe per step, sls_mapping_step): moments in the flat
-// [xyz 3N | opacity N | scaling 2N | rotation 4N] layout of the gradient bucket.
+// The surfel-layout Adam: moments in the flat [xyz 3N | opacity N | scaling 2N | rotation 4N] layout of the gradient
+// bucket, a learning rate per group.  ONE body for the update fused into the projection's backward (both kernels) and
+// the two exchange kernels: each caller moves the surfel's ten parameters and twenty moments its own way (the projection
+// from the registers it holds and with vector accesses, which need an even N and aligned buckets; the exchange kernels
+// element by element) and hands them over in registers, in the order xyz, opacity, scaling, rotation.
+struct SurfelAdam {
+    float *exp_avg, *exp_avg_sq;          // 10*N floats each
+    float lr[4];                          // xyz, opacity, scaling, rotation
+    AdamCoef c;
+};
+inline SurfelAdam make_surfel_adam(float *exp_avg, float *exp_avg_sq, float lr_xyz, float lr_opacity, float lr_scaling,
+                                   float lr_rotation, double beta1, double beta2, double eps, int64_t step)
+{
+    return SurfelAdam{ exp_avg, exp_avg_sq, { lr_xyz, lr_opacity, lr_scaling, lr_rotation }, make_adam_coef(beta1, beta2, eps, step) };
+}
+// where surfel i's four groups start in a flat bucket of n surfels
+__device__ __forceinline__ void surfel_offsets(size_t n, size_t i, size_t (&off)[4])
+{
+    off[0] = 3 * i; off[1] = 3 * n + i; off[2] = 4 * n + 2 * i; off[3] = 6 * n + 4 * i;
+}
+__device__ __forceinline__ void surfel_step_sizes(const SurfelAdam &a, float (&st)[4])
+{
+    const float ibc1 = __builtin_amdgcn_rcpf(a.c.bc1);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) st[q] = a.lr[q] * ibc1;
+}
+__device__ __forceinline__ void adam_surfel(float (&p)[10], const float (&g)[10], float (&m)[10], float (&v)[10], const SurfelAdam &a)
+{
+    float st[4];
+    surfel_step_sizes(a, st);
+#pragma unroll
+    for (int k = 0; k < 10; ++k) adam_one(p[k], g[k], m[k], v[k], st[k < 3 ? 0 : k < 4 ? 1 : k < 6 ? 2 : 3], a.c);
+}
+// What the projection's backward takes besides its arrays (one keyframe per step, sls_mapping_step): Adam fused into it
+// and the iteration's closing duties.
 struct AdamFuse {
     int enabled, write_grads;
     int clear_grec;                       // zero every gradient record after reading it (ready for the next iteration)
-    AdamCoef c;
-    float lr_xyz, lr_opacity, lr_scaling, lr_rotation;
-    float *exp_avg, *exp_avg_sq;          // 10*N floats each
+    SurfelAdam adam;
     const uint32_t *skip_flag;            // the iteration's overflow word: non-zero -> no update
     // optional: the iteration's status block (8 words, complete before this last kernel starts) is
     // copied to a host-visible mirror by thread 0, which saves the device->host copy kernel

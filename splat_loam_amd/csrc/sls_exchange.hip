@@ -20,7 +20,6 @@
 // every rank: SlsMappingConfig.union_bitmap); step 5 then only touches the union (part = 2).
 // Every rank ends with bit-identical parameters: the collective's result is identical everywhere and the update
 // is a pure function of it.  Results equal the dense all-reduce path's to the bit (same operands per element).
-#include <string.h>
 
 #include "sls_launch.hpp"
 
@@ -173,11 +172,34 @@ int launch_touched_bitmap(int N, const uint8_t *touched, const float *scaling_ra
 }
 
 struct SparseAdamArgs {
-    float *xyz, *opacity, *scaling, *rotation;
-    float *exp_avg, *exp_avg_sq;          // flat buckets [xyz 3N | opacity N | scaling 2N | rotation 4N]
-    float lr_xyz, lr_opacity, lr_scaling, lr_rotation;
-    AdamCoef c;
+    float *par[4];                        // xyz, opacity, scaling, rotation
+    SurfelAdam adam;
 };
+
+// Adam on surfel i of n with the gradient g, element by element (sls_adam_step_sparse and _union take any N and any
+// alignment).  Every load before the first store: parameters, moments and the gradient's row alias as far as the compiler
+// can tell, and interleaved with the stores they became four dependent round trips — 15 us for a union of 58 k surfels.
+__device__ __forceinline__ void sparse_adam_surfel(const SparseAdamArgs &a, size_t n, size_t i, const float (&g)[10])
+{
+    constexpr int kW[4] = { 3, 1, 2, 4 }, kG[4] = { 0, 3, 4, 6 };
+    float *const par[4] = { a.par[0] + 3 * i, a.par[1] + i, a.par[2] + 2 * i, a.par[3] + 4 * i };
+    size_t off[4];
+    surfel_offsets(n, i, off);
+    float p[10], m[10], v[10];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < kW[q]; ++k) {
+            p[kG[q] + k] = par[q][k]; m[kG[q] + k] = a.adam.exp_avg[off[q] + k]; v[kG[q] + k] = a.adam.exp_avg_sq[off[q] + k];
+        }
+    adam_surfel(p, g, m, v, a.adam);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < kW[q]; ++k) {
+            par[q][k] = p[kG[q] + k]; a.adam.exp_avg[off[q] + k] = m[kG[q] + k]; a.adam.exp_avg_sq[off[q] + k] = v[kG[q] + k];
+        }
+}
 
 // torch.optim.Adam on every surfel; the gradient comes from the reduced compact buffer (union surfels) or is zero.
 // Skipped as a whole when the group voided the iteration; the last kernel of the iteration: mirrors the status.
@@ -205,32 +227,7 @@ __global__ __launch_bounds__(256) void exchange_adam_kernel(int N, SparseAdamArg
 #pragma unroll
         for (int k = 0; k < 10; ++k) g[k] = s[k];
     }
-    const size_t n = (size_t)N, ix = 3 * (size_t)i, io = 3 * n + i, is = 4 * n + 2 * (size_t)i, ir = 6 * n + 4 * (size_t)i;
-    float *M = a.exp_avg, *V = a.exp_avg_sq;
-    const float ibc1 = __builtin_amdgcn_rcpf(a.c.bc1);
-    const float st_x = a.lr_xyz * ibc1, st_o = a.lr_opacity * ibc1, st_s = a.lr_scaling * ibc1, st_r = a.lr_rotation * ibc1;
-    float p, m, v;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        p = a.xyz[ix + k]; m = M[ix + k]; v = V[ix + k];
-        adam_one(p, g[k], m, v, st_x, a.c);
-        a.xyz[ix + k] = p; M[ix + k] = m; V[ix + k] = v;
-    }
-    p = a.opacity[i]; m = M[io]; v = V[io];
-    adam_one(p, g[3], m, v, st_o, a.c);
-    a.opacity[i] = p; M[io] = m; V[io] = v;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        p = a.scaling[2 * (size_t)i + k]; m = M[is + k]; v = V[is + k];
-        adam_one(p, g[4 + k], m, v, st_s, a.c);
-        a.scaling[2 * (size_t)i + k] = p; M[is + k] = m; V[is + k] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        p = a.rotation[4 * (size_t)i + k]; m = M[ir + k]; v = V[ir + k];
-        adam_one(p, g[6 + k], m, v, st_r, a.c);
-        a.rotation[4 * (size_t)i + k] = p; M[ir + k] = m; V[ir + k] = v;
-    }
+    sparse_adam_surfel(a, (size_t)N, (size_t)i, g);
 }
 
 // The same update for the union ONLY, a thread per SLOT: surfel = index[slot] (written next to the row by the projection's
@@ -245,34 +242,11 @@ __global__ __launch_bounds__(256) void exchange_adam_union_kernel(uint32_t capac
     if (slot == 0 && status_mirror) mirror_status_block(status_block, status_mirror);
     if (status_block[1] != 0u) return;        // void: the verdict of the group or an exchange buffer too small
     if (slot >= min(capacity, status_block[7])) return;
-    const size_t i = index[slot];
-    const size_t off[4] = { 3 * i, 3 * n + i, 4 * n + 2 * i, 6 * n + 4 * i };     // the surfel's place in the flat buckets
-    float *const par[4] = { a.xyz + 3 * i, a.opacity + i, a.scaling + 2 * i, a.rotation + 4 * i };
-    constexpr int kW[4] = { 3, 1, 2, 4 }, kG[4] = { 0, 3, 4, 6 };
     const float *row = compact + (size_t)slot * 10;
-    // every load first (parameters, moments and the row alias as far as the compiler can tell: interleaved with the stores
-    // they became four dependent round trips — 15 us for 58 k surfels)
-    float g[10], p[10], m[10], v[10];
+    float g[10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) g[k] = row[k];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int k = 0; k < kW[q]; ++k) {
-            p[kG[q] + k] = par[q][k]; m[kG[q] + k] = a.exp_avg[off[q] + k]; v[kG[q] + k] = a.exp_avg_sq[off[q] + k];
-        }
-    const float ibc1 = __builtin_amdgcn_rcpf(a.c.bc1);
-    const float stp[4] = { a.lr_xyz * ibc1, a.lr_opacity * ibc1, a.lr_scaling * ibc1, a.lr_rotation * ibc1 };
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int k = 0; k < kW[q]; ++k) adam_one(p[kG[q] + k], g[kG[q] + k], m[kG[q] + k], v[kG[q] + k], stp[q], a.c);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int k = 0; k < kW[q]; ++k) {
-            par[q][k] = p[kG[q] + k]; a.exp_avg[off[q] + k] = m[kG[q] + k]; a.exp_avg_sq[off[q] + k] = v[kG[q] + k];
-        }
+    sparse_adam_surfel(a, n, (size_t)index[slot], g);
 }
 
 }  // namespace sls
@@ -324,12 +298,8 @@ int sls_adam_step_sparse(int N, float *xyz, float *opacity, float *scaling, floa
                     exp_avg && exp_avg_sq && status_dev,
                 "bad argument");
     SLS_REQUIRE(step >= 1, "step is 1-based");
-    SparseAdamArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = xyz; a.opacity = opacity; a.scaling = scaling; a.rotation = rotation;
-    a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
-    a.lr_xyz = lr_xyz; a.lr_opacity = lr_opacity; a.lr_scaling = lr_scaling; a.lr_rotation = lr_rotation;
-    a.c = make_adam_coef(beta1, beta2, eps, step);
+    const SparseAdamArgs a{ { xyz, opacity, scaling, rotation },
+                            make_surfel_adam(exp_avg, exp_avg_sq, lr_xyz, lr_opacity, lr_scaling, lr_rotation, beta1, beta2, eps, step) };
     ScopedTimer tm(T_ADAM, (hipStream_t)stream);
     hipLaunchKernelGGL(exchange_adam_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, a, union_bitmap,
                        word_prefix, compact_reduced, (const uint32_t *)status_dev, (uint32_t *)status_mirror, part);
@@ -346,12 +316,8 @@ int sls_adam_step_union(int N, float *xyz, float *opacity, float *scaling, float
                     exp_avg && exp_avg_sq && status_dev,
                 "bad argument");
     SLS_REQUIRE(step >= 1, "step is 1-based");
-    SparseAdamArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = xyz; a.opacity = opacity; a.scaling = scaling; a.rotation = rotation;
-    a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
-    a.lr_xyz = lr_xyz; a.lr_opacity = lr_opacity; a.lr_scaling = lr_scaling; a.lr_rotation = lr_rotation;
-    a.c = make_adam_coef(beta1, beta2, eps, step);
+    const SparseAdamArgs a{ { xyz, opacity, scaling, rotation },
+                            make_surfel_adam(exp_avg, exp_avg_sq, lr_xyz, lr_opacity, lr_scaling, lr_rotation, beta1, beta2, eps, step) };
     ScopedTimer tm(T_ADAM, (hipStream_t)stream);
     hipLaunchKernelGGL(exchange_adam_union_kernel, dim3((capacity + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, capacity,
                        (size_t)N, a, compact_index, compact_reduced, (const uint32_t *)status_dev, (uint32_t *)status_mirror);

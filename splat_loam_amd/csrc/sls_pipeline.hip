@@ -619,10 +619,8 @@ static void fill_step_fuse(AdamFuse &af, const SlsMappingConfig *cfg, SlsMapping
     if (!cfg->apply_adam || !aligned) return;
     af.enabled = 1;
     af.write_grads = cfg->keep_grads;
-    af.c = make_adam_coef(cfg->beta1, cfg->beta2, cfg->eps, adam_step);
-    af.lr_xyz = cfg->lr_xyz; af.lr_opacity = cfg->lr_opacity;
-    af.lr_scaling = cfg->lr_scaling; af.lr_rotation = cfg->lr_rotation;
-    af.exp_avg = exp_avg; af.exp_avg_sq = exp_avg_sq;
+    af.adam = make_surfel_adam(exp_avg, exp_avg_sq, cfg->lr_xyz, cfg->lr_opacity, cfg->lr_scaling, cfg->lr_rotation, cfg->beta1,
+                               cfg->beta2, cfg->eps, adam_step);
 }
 
 // ... and elsewhere (odd N or unaligned moments) the separate optimiser kernel over the flat bucket's four groups

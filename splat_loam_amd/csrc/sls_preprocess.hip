@@ -568,9 +568,7 @@ __device__ __forceinline__ void pose_finish(const PoseOut &po, int G, int nb)
 }
 
 // The chain of one gradient record (g0..g3) through one camera: dL/d(mean, activated scale before the modifier's
-// product, opacity, normalised rotation), for the batched kernel below: the arithmetic of preprocess_bwd_kernel,
-// which keeps its own copy inline (as a shared function the compiler allocates that kernel's registers
-// differently, and its code is to stay as it is)
+// product, opacity, normalised rotation); with POSE the six pose terms too.  Both projection backward kernels call it.
 template <bool POSE>
 __device__ __forceinline__ void chain_grad_record(const DevCam &cam, const SurfelGeom &g, const float4 q, const float4 g0,
                                                   const float4 g1, const float4 g2, const float4 g3, float *dm, float2 &ds,
@@ -626,6 +624,122 @@ __device__ __forceinline__ void chain_grad_record(const DevCam &cam, const Surfe
     dq.w = 2.0f * (-2.0f * z * G0[0] - r * G1[0] + x * G2[0] + r * G0[1] - 2.0f * z * G1[1] + y * G2[1] + x * G0[2] + y * G1[2]);
 }
 
+// ---- the other stages the two projection backward kernels share: one body each ---------------------------------------
+// The publisher's loss sums.  The tile backward's blocks left their pixels' loss terms (three arrays of n floats, n a
+// multiple of 16): every thread a strided share of 16-byte loads (all in flight at once), then the wave; the block's four
+// waves meet in s_loss.  Reached by ALL 256 threads; a barrier, then loss_publish by one of them.
+__device__ __forceinline__ void loss_wave_sums(const float *partials, int n, float (&s_loss)[3][4])
+{
+    const int n4 = n / 4;
+    float t[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 *src = reinterpret_cast<const float4 *>(partials + (size_t)k * n);
+#pragma unroll 8
+        for (int b = threadIdx.x; b < n4; b += 256) {
+            const float4 v = src[b];
+            t[k] += (v.x + v.y) + (v.z + v.w);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        t[0] += __shfl_down(t[0], off, 64); t[1] += __shfl_down(t[1], off, 64); t[2] += __shfl_down(t[2], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_loss[0][threadIdx.x >> 6] = t[0]; s_loss[1][threadIdx.x >> 6] = t[1]; s_loss[2][threadIdx.x >> 6] = t[2]; }
+}
+// ... the iteration's three sums and the pixel-loss total, in a fixed order: words 2..5 of the keyframe's status block
+__device__ __forceinline__ void loss_publish(const float (&s_loss)[3][4], const float *w, uint32_t *st)
+{
+    float r[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r[k] = (s_loss[k][0] + s_loss[k][1]) + (s_loss[k][2] + s_loss[k][3]);
+    st[2] = __float_as_uint(r[0]); st[3] = __float_as_uint(r[1]); st[4] = __float_as_uint(r[2]);
+    st[5] = __float_as_uint(r[0] * w[0] + w[1] * r[1] + w[2] * r[2]);
+}
+
+// Deterministic accumulation: sum k of surfel i's record is its fixed-point accumulator scaled back by 2^(ex - 166) — ex
+// the exponent of the exact maximum in the two-pass scheme (det_max_exp), the predicted one in the one-pass scheme —
+// and cleared where read if `clear` (a one-launch iteration that follows finds the accumulators at zero)
+__device__ __forceinline__ int det_max_exp(const uint32_t *det_max, int i, int k) { return (int)((det_max[(size_t)i * 16 + k] >> 23) & 0xFFu); }
+__device__ __forceinline__ float det_take_sum(long long *det_acc, int i, int k, int ex, bool clear)
+{
+    const long long acc = det_acc[(size_t)i * 16 + k];
+    if (clear) det_acc[(size_t)i * 16 + k] = 0;
+    return (float)ldexp((double)acc, ex - 166);
+}
+// The scale the keyframe's NEXT iteration will use for surfel i's sixteen sums (never from a void iteration's sums: the
+// caller's test), and with det_gex the fields' defaults: raised by two-pass iterations only (a one-pass iteration reads them)
+__device__ __forceinline__ void det_predict_next(const float (&gv)[16], uint8_t *det_prev, uint32_t *det_gex, int i)
+{
+    uint32_t pw[4];
+#pragma unroll
+    for (int w4 = 0; w4 < 4; ++w4) {
+        pw[w4] = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) pw[w4] |= det_predict(gv[4 * w4 + b]) << (8 * b);
+    }
+    reinterpret_cast<uint4 *>(det_prev)[i] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
+    if (!det_gex) return;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t pe = (pw[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+        if (pe > det_gex[k]) atomicMax(&det_gex[k], pe);
+    }
+}
+
+// d/ds of pen * relu(max(s.x, s.y) - smax); torch.max picks the first index on ties
+__device__ __forceinline__ void reg_grad(const RegArgs &ra, const float2 s, float2 &ds)
+{
+    if (ra.pen == 0.0f) return;
+    const bool first = s.x >= s.y;
+    if ((first ? s.x : s.y) >= ra.smax) { if (first) ds.x += ra.pen; else ds.y += ra.pen; }
+}
+// from gradients w.r.t. the activated values (s, o, q = activate(raw)) to gradients w.r.t. the raw parameters
+__device__ __forceinline__ void activations_bwd(const float2 s, const float o, const float4 q_in, const float4 q, float2 &ds,
+                                                float &dop, float4 &dq)
+{
+    ds.x *= s.x; ds.y *= s.y;                                   // exp backward
+    dop *= o * (1.0f - o);                                      // sigmoid backward
+    const float nrm = fsqrt(q_in.x * q_in.x + q_in.y * q_in.y + q_in.z * q_in.z + q_in.w * q_in.w);
+    const float inv = frcp(fmaxf(nrm, 1e-12f));                 // F.normalize backward
+    const float dd = dq.x * q.x + dq.y * q.y + dq.z * q.z + dq.w * q.w;
+    dq.x = (dq.x - dd * q.x) * inv; dq.y = (dq.y - dd * q.y) * inv;
+    dq.z = (dq.z - dd * q.z) * inv; dq.w = (dq.w - dd * q.w) * inv;
+}
+__device__ __forceinline__ bool any_nonzero(const float *dm, const float dop, const float2 ds, const float4 dq)
+{
+    return dm[0] != 0.0f || dm[1] != 0.0f || dm[2] != 0.0f || dop != 0.0f || ds.x != 0.0f || ds.y != 0.0f ||
+           dq.x != 0.0f || dq.y != 0.0f || dq.z != 0.0f || dq.w != 0.0f;
+}
+// Adam at once, on the values the thread holds: the gradients never travel through HBM and no optimiser launch reads the
+// parameters again.  The moments of scaling and rotation with float2 / float4 accesses: 4N + 2i and 6N + 4i floats are
+// 8- resp. 16-byte aligned whenever the bucket is 16-byte aligned and N is even (fill_step_fuse: elsewhere the separate
+// optimiser kernel runs).
+__device__ __forceinline__ void fused_adam_surfel(const SurfelAdam &a, int N, int i, const float *m, const float o_in,
+                                                  const float2 s_in, const float4 q_in, const float *dm, const float dop,
+                                                  const float2 ds, const float4 dq, float *means, float *opac, float2 *scales,
+                                                  float4 *rots)
+{
+    size_t off[4];
+    surfel_offsets((size_t)N, (size_t)i, off);
+    float *M = a.exp_avg, *V = a.exp_avg_sq;
+    float2 *Ms = reinterpret_cast<float2 *>(M + off[2]), *Vs = reinterpret_cast<float2 *>(V + off[2]);
+    float4 *Mq = reinterpret_cast<float4 *>(M + off[3]), *Vq = reinterpret_cast<float4 *>(V + off[3]);
+    const float2 ms = *Ms, vs = *Vs;
+    const float4 mq = *Mq, vq = *Vq;
+    float p[10] = { m[0], m[1], m[2], o_in, s_in.x, s_in.y, q_in.x, q_in.y, q_in.z, q_in.w };
+    const float g[10] = { dm[0], dm[1], dm[2], dop, ds.x, ds.y, dq.x, dq.y, dq.z, dq.w };
+    float mm[10] = { M[off[0]], M[off[0] + 1], M[off[0] + 2], M[off[1]], ms.x, ms.y, mq.x, mq.y, mq.z, mq.w };
+    float vv[10] = { V[off[0]], V[off[0] + 1], V[off[0] + 2], V[off[1]], vs.x, vs.y, vq.x, vq.y, vq.z, vq.w };
+    adam_surfel(p, g, mm, vv, a);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { means[3 * i + k] = p[k]; M[off[0] + k] = mm[k]; V[off[0] + k] = vv[k]; }
+    opac[i] = p[3]; M[off[1]] = mm[3]; V[off[1]] = vv[3];
+    scales[i] = make_float2(p[4], p[5]); *Ms = make_float2(mm[4], mm[5]); *Vs = make_float2(vv[4], vv[5]);
+    rots[i] = make_float4(p[6], p[7], p[8], p[9]);
+    *Mq = make_float4(mm[6], mm[7], mm[8], mm[9]); *Vq = make_float4(vv[6], vv[7], vv[8], vv[9]);
+}
+
 // With ra.raw the inputs are raw parameters, the activations are re-applied here
 // and the outputs are gradients w.r.t. the RAW parameters (exp / sigmoid /
 // normalize backward + the scale regulariser's gradient), opacity needed too.
@@ -651,34 +765,10 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
     const int n_pub = af.publisher ? 1 : 0, n_ord = af.order_out ? 8 : 0;
     if ((int)blockIdx.x < n_pub) {
         if (af.loss_partials) {
-            // the tile backward's blocks left their pixels' loss terms (three arrays of n_loss_partials floats, a multiple
-            // of 16): the iteration's three sums and the pixel-loss total, in a fixed order — every thread a strided
-            // share of 16-byte loads (all in flight at once), then the wave, then the block's four waves
             __shared__ float s_loss[3][4];
-            const int n4 = af.n_loss_partials / 4;
-            float t[3] = { 0.0f, 0.0f, 0.0f };
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float4 *src = reinterpret_cast<const float4 *>(af.loss_partials + (size_t)k * af.n_loss_partials);
-#pragma unroll 8
-                for (int b = threadIdx.x; b < n4; b += 256) {
-                    const float4 v = src[b];
-                    t[k] += (v.x + v.y) + (v.z + v.w);
-                }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                t[0] += __shfl_down(t[0], off, 64); t[1] += __shfl_down(t[1], off, 64); t[2] += __shfl_down(t[2], off, 64);
-            }
-            if ((threadIdx.x & 63) == 0) { s_loss[0][threadIdx.x >> 6] = t[0]; s_loss[1][threadIdx.x >> 6] = t[1]; s_loss[2][threadIdx.x >> 6] = t[2]; }
+            loss_wave_sums(af.loss_partials, af.n_loss_partials, s_loss);
             __syncthreads();
-            if (threadIdx.x == 0) {
-                float r[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) r[k] = (s_loss[k][0] + s_loss[k][1]) + (s_loss[k][2] + s_loss[k][3]);
-                af.status_src[2] = __float_as_uint(r[0]); af.status_src[3] = __float_as_uint(r[1]); af.status_src[4] = __float_as_uint(r[2]);
-                af.status_src[5] = __float_as_uint(r[0] * af.loss_w[0] + af.loss_w[1] * r[1] + af.loss_w[2] * r[2]);
-            }
+            if (threadIdx.x == 0) loss_publish(s_loss, af.loss_w, af.status_src);
         }
         if (threadIdx.x == 0) {
             if (af.reg_accum) {   // the regulariser was summed in the workspace: publish it, leave zero for the next iteration
@@ -741,37 +831,12 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
             }
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
-                int ex;
-                if (af.det_onepass) {
-                    const uint32_t pb = (prev[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                    ex = det_scale_exp(pb, af.det_gex[k]);
-                } else {
-                    ex = (int)((af.det_max[(size_t)i * 16 + k] >> 23) & 0xFFu);
-                }
-                const long long acc = af.det_acc[(size_t)i * 16 + k];
-                gv[k] = (float)ldexp((double)acc, ex - 166);
-                // (cleared where read: a one-launch iteration that follows finds the accumulators at zero)
-                if (af.det_onepass || af.clear_grec) const_cast<long long *>(af.det_acc)[(size_t)i * 16 + k] = 0;
+                const int ex = af.det_onepass ? det_scale_exp((prev[k >> 2] >> (8 * (k & 3))) & 0xFFu, af.det_gex[k])
+                                              : det_max_exp(af.det_max, i, k);
+                gv[k] = det_take_sum(const_cast<long long *>(af.det_acc), i, k, ex, af.det_onepass || af.clear_grec);
             }
-            if (af.det_prev && (!af.status_src || af.status_src[1] == 0u)) {
-                // the scale the keyframe's NEXT iteration will use (never from a void iteration's sums)
-                uint32_t pw[4];
-#pragma unroll
-                for (int w4 = 0; w4 < 4; ++w4) {
-                    pw[w4] = 0u;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) pw[w4] |= det_predict(gv[4 * w4 + b]) << (8 * b);
-                }
-                reinterpret_cast<uint4 *>(af.det_prev)[i] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
-                if (!af.det_onepass && af.det_gex) {
-                    // the fields' defaults: raised by two-pass iterations only (a one-pass iteration reads them)
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const uint32_t pe = (pw[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                        if (pe > af.det_gex[k]) atomicMax(&af.det_gex[k], pe);
-                    }
-                }
-            }
+            if (af.det_prev && (!af.status_src || af.status_src[1] == 0u))
+                det_predict_next(gv, af.det_prev, af.det_onepass ? nullptr : af.det_gex, i);
             g0 = make_float4(gv[0], gv[1], gv[2], gv[3]); g1 = make_float4(gv[4], gv[5], gv[6], gv[7]);
             g2 = make_float4(gv[8], gv[9], gv[10], gv[11]); g3 = make_float4(gv[12], gv[13], gv[14], gv[15]);
         } else {
@@ -782,72 +847,12 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
             const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             grec[(size_t)i * 4 + 0] = z; grec[(size_t)i * 4 + 1] = z; grec[(size_t)i * 4 + 2] = z; grec[(size_t)i * 4 + 3] = z;
         }
-        const float gHu[3] = { g0.x, g0.y, g0.z }, gHv[3] = { g1.x, g1.y, g1.z }, gn[3] = { g2.x, g2.y, g2.z };
-        const float gnpv = g0.w, grhoc = g1.w, go = g2.w, Su = g3.x, Sv = g3.y, gcpx = g3.z, gcpy = g3.w;
-        float dc[3];
-        const float irho = frcp(g.rho), isu = frcp(g.su), isv = frcp(g.sv);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dc[k] = g.p[k] * irho;
-        float dp[3], dA[3], dB[3], t1[3], t2[3];
-        cross3(g.p, gHu, dA); cross3(gHu, g.A, t1);
-        cross3(g.p, gHv, dB); cross3(gHv, g.B, t2);
-        float dTu[3], dTv[3], dTn[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            dp[k] = t1[k] + t2[k];
-            dTv[k] = g.sig * dA[k] * isu;
-            dTu[k] = -g.sig * dB[k] * isv;
-        }
-        const float dsu = -dot3(dA, g.A) * isu, dsv = -dot3(dB, g.B) * isv;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            dTn[k] = g.sig * (gn[k] + gnpv * g.p[k]);
-            dp[k] += gnpv * g.n[k];
-            dp[k] += grhoc * dc[k];
-        }
-        float gdc[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gdc[k] = -(Su * g.Hu[k] + Sv * g.Hv[k]);
-        const float gd = dot3(gdc, dc);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dp[k] += (gdc[k] - gd * dc[k]) * irho;
-        if (g.rxy2 > 1e-30f) {
-            const float gaz = gcpx * cam.fx, gel = gcpy * cam.fy;
-            const float irxy2 = frcp(g.rxy2), irr = frcp(g.rxy * g.rho2), irho2 = irho * irho;
-            dp[0] += gaz * (-g.p[1] * irxy2) + gel * (-g.p[2] * g.p[0] * irr);
-            dp[1] += gaz * (g.p[0] * irxy2) + gel * (-g.p[2] * g.p[1] * irr);
-            dp[2] += gel * (g.rxy * irho2);
-        }
-        if constexpr (POSE) pose_terms(g, dp, dTu, dTv, dTn, pg);
-        matTvec(cam.R, dp, dm);
-        ds = make_float2(cam.mod * dsu, cam.mod * dsv);
-        dop = go;
-        float G0[3], G1[3], G2[3];
-        matTvec(cam.R, dTu, G0); matTvec(cam.R, dTv, G1); matTvec(cam.R, dTn, G2);
-        const float r = q.x, x = q.y, y = q.z, z = q.w;
-        // G[i][j] = dL/dR_ij, column j in {tu, tv, tn}: Gj[i]
-        dq.x = 2.0f * (-z * G1[0] + y * G2[0] + z * G0[1] - x * G2[1] - y * G0[2] + x * G1[2]);
-        dq.y = 2.0f * (y * G1[0] + z * G2[0] + y * G0[1] - 2.0f * x * G1[1] - r * G2[1] + z * G0[2] + r * G1[2] - 2.0f * x * G2[2]);
-        dq.z = 2.0f * (-2.0f * y * G0[0] + x * G1[0] + r * G2[0] + x * G0[1] + z * G2[1] - r * G0[2] + z * G1[2] - 2.0f * y * G2[2]);
-        dq.w = 2.0f * (-2.0f * z * G0[0] - r * G1[0] + x * G2[0] + r * G0[1] - 2.0f * z * G1[1] + y * G2[1] + x * G0[2] + y * G1[2]);
+        chain_grad_record<POSE>(cam, g, q, g0, g1, g2, g3, dm, ds, dop, dq, pg);
     }
-    if (ra.pen != 0.0f) {   // d/ds of pen * relu(max(s.x, s.y) - smax); torch.max picks the first index on ties
-        const bool first = s.x >= s.y;
-        if ((first ? s.x : s.y) >= ra.smax) { if (first) ds.x += ra.pen; else ds.y += ra.pen; }
-    }
-    if (ra.raw) {
-        ds.x *= s.x; ds.y *= s.y;                                   // exp backward
-        dop *= o * (1.0f - o);                                      // sigmoid backward
-        const float nrm = fsqrt(q_in.x * q_in.x + q_in.y * q_in.y + q_in.z * q_in.z + q_in.w * q_in.w);
-        const float inv = frcp(fmaxf(nrm, 1e-12f));                 // F.normalize backward
-        const float dd = dq.x * q.x + dq.y * q.y + dq.z * q.z + dq.w * q.w;
-        dq.x = (dq.x - dd * q.x) * inv; dq.y = (dq.y - dd * q.y) * inv;
-        dq.z = (dq.z - dd * q.z) * inv; dq.w = (dq.w - dd * q.w) * inv;
-    }
+    reg_grad(ra, s, ds);
+    if (ra.raw) activations_bwd(s, o, q_in, q, ds, dop, dq);
     if (af.grad_bitmap) {   // which surfels have anything to exchange (one 64-bit word per wave)
-        const bool nz = dm[0] != 0.0f || dm[1] != 0.0f || dm[2] != 0.0f || dop != 0.0f || ds.x != 0.0f || ds.y != 0.0f ||
-                        dq.x != 0.0f || dq.y != 0.0f || dq.z != 0.0f || dq.w != 0.0f;
-        const uint64_t bal = __ballot(nz);
+        const uint64_t bal = __ballot(any_nonzero(dm, dop, ds, dq));
         if ((threadIdx.x & 63) == 0) af.grad_bitmap[i >> 6] = bal;
     }
     if (af.gchunk) {
@@ -886,40 +891,10 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(
             if constexpr (POSE) goto pose_reduce; else return;
         }
         // (the early bitmap is a superset of the non-zero gradients by construction: say so if it ever is not)
-        if (dm[0] != 0.0f || dm[1] != 0.0f || dm[2] != 0.0f || dop != 0.0f || ds.x != 0.0f || ds.y != 0.0f ||
-            dq.x != 0.0f || dq.y != 0.0f || dq.z != 0.0f || dq.w != 0.0f)
-            if (af.status_src) atomicOr(af.status_src + 1, 32u);
+        if (af.status_src && any_nonzero(dm, dop, ds, dq)) atomicOr(af.status_src + 1, 32u);
     }
-    if (af.enabled && *af.skip_flag == 0u) {
-        // moments in the bucket layout [xyz 3N | opacity N | scaling 2N | rotation 4N]
-        const size_t n = (size_t)N, ix = 3 * (size_t)i, io = 3 * n + i, is = 4 * n + 2 * (size_t)i, ir = 6 * n + 4 * (size_t)i;
-        float *M = af.exp_avg, *V = af.exp_avg_sq;
-        float p, mm, vv;
-        const float ibc1 = frcp(af.c.bc1);
-        const float st_x = af.lr_xyz * ibc1, st_o = af.lr_opacity * ibc1;
-        const float st_s = af.lr_scaling * ibc1, st_r = af.lr_rotation * ibc1;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            p = m[k]; mm = M[ix + k]; vv = V[ix + k];
-            adam_one(p, dm[k], mm, vv, st_x, af.c);
-            means[3 * i + k] = p; M[ix + k] = mm; V[ix + k] = vv;
-        }
-        p = o_in; mm = M[io]; vv = V[io];
-        adam_one(p, dop, mm, vv, st_o, af.c);
-        opac[i] = p; M[io] = mm; V[io] = vv;
-        float2 ps = s_in, ms = *reinterpret_cast<float2 *>(M + is), vs = *reinterpret_cast<float2 *>(V + is);
-        adam_one(ps.x, ds.x, ms.x, vs.x, st_s, af.c);
-        adam_one(ps.y, ds.y, ms.y, vs.y, st_s, af.c);
-        scales[i] = ps; *reinterpret_cast<float2 *>(M + is) = ms; *reinterpret_cast<float2 *>(V + is) = vs;
-        // (4N + 2i and 6N + 4i floats: 8- resp. 16-byte aligned whenever the bucket is 16-byte aligned and N is even;
-        //  the launcher falls back to the separate optimiser kernel otherwise)
-        float4 pq = q_in, mq = *reinterpret_cast<float4 *>(M + ir), vq = *reinterpret_cast<float4 *>(V + ir);
-        adam_one(pq.x, dq.x, mq.x, vq.x, st_r, af.c);
-        adam_one(pq.y, dq.y, mq.y, vq.y, st_r, af.c);
-        adam_one(pq.z, dq.z, mq.z, vq.z, st_r, af.c);
-        adam_one(pq.w, dq.w, mq.w, vq.w, st_r, af.c);
-        rots[i] = pq; *reinterpret_cast<float4 *>(M + ir) = mq; *reinterpret_cast<float4 *>(V + ir) = vq;
-    }
+    if (af.enabled && *af.skip_flag == 0u)
+        fused_adam_surfel(af.adam, N, i, m, o_in, s_in, q_in, dm, dop, ds, dq, means, opac, scales, rots);
     }
 pose_reduce:
     if constexpr (POSE) {
@@ -949,27 +924,10 @@ __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, B
     if (blockIdx.x == 0) {
         __shared__ float s_loss[SLS_MAX_BATCH][3][4];
         if (bf.n_loss_partials > 0) {
-            const int n4 = bf.n_loss_partials / 4;
 #pragma unroll
             for (int g = 0; g < SLS_MAX_BATCH; ++g) {
                 if (g >= bf.G) break;
-                float t[3] = { 0.0f, 0.0f, 0.0f };
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float4 *src = reinterpret_cast<const float4 *>(bf.kf[g].loss_partials + (size_t)k * bf.n_loss_partials);
-#pragma unroll 8
-                    for (int b = threadIdx.x; b < n4; b += 256) {
-                        const float4 v = src[b];
-                        t[k] += (v.x + v.y) + (v.z + v.w);
-                    }
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    t[0] += __shfl_down(t[0], off, 64); t[1] += __shfl_down(t[1], off, 64); t[2] += __shfl_down(t[2], off, 64);
-                }
-                if ((threadIdx.x & 63) == 0) {
-                    s_loss[g][0][threadIdx.x >> 6] = t[0]; s_loss[g][1][threadIdx.x >> 6] = t[1]; s_loss[g][2][threadIdx.x >> 6] = t[2];
-                }
+                loss_wave_sums(bf.kf[g].loss_partials, bf.n_loss_partials, s_loss[g]);
             }
             __syncthreads();
         }
@@ -980,14 +938,7 @@ __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, B
             for (int g = 0; g < SLS_MAX_BATCH; ++g) {
                 if (g >= bf.G) break;
                 uint32_t *st = bf.kf[g].status;
-                if (bf.n_loss_partials > 0) {      // (as the one-keyframe publisher: the same sums in the same order)
-                    float r[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) r[k] = (s_loss[g][k][0] + s_loss[g][k][1]) + (s_loss[g][k][2] + s_loss[g][k][3]);
-                    const float* w = bf.kf[g].loss_w;
-                    st[2] = __float_as_uint(r[0]); st[3] = __float_as_uint(r[1]); st[4] = __float_as_uint(r[2]);
-                    st[5] = __float_as_uint(r[0] * w[0] + w[1] * r[1] + w[2] * r[2]);
-                }
+                if (bf.n_loss_partials > 0) loss_publish(s_loss[g], bf.kf[g].loss_w, st);
                 R = max(R, st[0]);
                 bits |= st[1];
 #pragma unroll
@@ -1060,28 +1011,8 @@ __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, B
         if (kf.det_acc) {
             float gv[16];
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int ex = (int)((kf.det_max[(size_t)i * 16 + k] >> 23) & 0xFFu);
-                gv[k] = (float)ldexp((double)kf.det_acc[(size_t)i * 16 + k], ex - 166);
-                kf.det_acc[(size_t)i * 16 + k] = 0;
-            }
-            if (kf.det_prev && skip == 0u) {
-                uint32_t pw[4];
-#pragma unroll
-                for (int w4 = 0; w4 < 4; ++w4) {
-                    pw[w4] = 0u;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) pw[w4] |= det_predict(gv[4 * w4 + b]) << (8 * b);
-                }
-                reinterpret_cast<uint4 *>(kf.det_prev)[i] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
-                if (kf.det_gex) {
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const uint32_t pe = (pw[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                        if (pe > kf.det_gex[k]) atomicMax(&kf.det_gex[k], pe);
-                    }
-                }
-            }
+            for (int k = 0; k < 16; ++k) gv[k] = det_take_sum(kf.det_acc, i, k, det_max_exp(kf.det_max, i, k), true);
+            if (kf.det_prev && skip == 0u) det_predict_next(gv, kf.det_prev, kf.det_gex, i);
             g0 = make_float4(gv[0], gv[1], gv[2], gv[3]); g1 = make_float4(gv[4], gv[5], gv[6], gv[7]);
             g2 = make_float4(gv[8], gv[9], gv[10], gv[11]); g3 = make_float4(gv[12], gv[13], gv[14], gv[15]);
         } else {
@@ -1099,52 +1030,16 @@ __global__ __launch_bounds__(256) void preprocess_bwd_batch_kernel(RegArgs ra, B
         dop += dopk;
         dq.x += dqk.x; dq.y += dqk.y; dq.z += dqk.z; dq.w += dqk.w;
     }
-    if (ra.pen != 0.0f) {   // the regulariser once, as preprocess_bwd_kernel
-        const bool first = s.x >= s.y;
-        if ((first ? s.x : s.y) >= ra.smax) { if (first) ds.x += ra.pen; else ds.y += ra.pen; }
-    }
-    ds.x *= s.x; ds.y *= s.y;
-    dop *= o * (1.0f - o);
-    {
-        const float nrm = fsqrt(q_in.x * q_in.x + q_in.y * q_in.y + q_in.z * q_in.z + q_in.w * q_in.w);
-        const float inv = frcp(fmaxf(nrm, 1e-12f));
-        const float dd = dq.x * q.x + dq.y * q.y + dq.z * q.z + dq.w * q.w;
-        dq.x = (dq.x - dd * q.x) * inv; dq.y = (dq.y - dd * q.y) * inv;
-        dq.z = (dq.z - dd * q.z) * inv; dq.w = (dq.w - dd * q.w) * inv;
-    }
+    reg_grad(ra, s, ds);               // (the regulariser once)
+    activations_bwd(s, o, q_in, q, ds, dop, dq);
     if (!af.enabled || af.write_grads) {
         dmeans[3 * i] = dm[0]; dmeans[3 * i + 1] = dm[1]; dmeans[3 * i + 2] = dm[2];
         dscales[i] = ds;
         drots[i] = dq;
         dopac[i] = dop;
     }
-    if (af.enabled && skip == 0u) {
-        const size_t n = (size_t)N, ix = 3 * (size_t)i, io = 3 * n + i, is = 4 * n + 2 * (size_t)i, ir = 6 * n + 4 * (size_t)i;
-        float *M = af.exp_avg, *V = af.exp_avg_sq;
-        float p, mm, vv;
-        const float ibc1 = frcp(af.c.bc1);
-        const float st_x = af.lr_xyz * ibc1, st_o = af.lr_opacity * ibc1;
-        const float st_s = af.lr_scaling * ibc1, st_r = af.lr_rotation * ibc1;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            p = m[k]; mm = M[ix + k]; vv = V[ix + k];
-            adam_one(p, dm[k], mm, vv, st_x, af.c);
-            means[3 * i + k] = p; M[ix + k] = mm; V[ix + k] = vv;
-        }
-        p = o_in; mm = M[io]; vv = V[io];
-        adam_one(p, dop, mm, vv, st_o, af.c);
-        opac[i] = p; M[io] = mm; V[io] = vv;
-        float2 ps = s_in, ms = *reinterpret_cast<float2 *>(M + is), vs = *reinterpret_cast<float2 *>(V + is);
-        adam_one(ps.x, ds.x, ms.x, vs.x, st_s, af.c);
-        adam_one(ps.y, ds.y, ms.y, vs.y, st_s, af.c);
-        scales[i] = ps; *reinterpret_cast<float2 *>(M + is) = ms; *reinterpret_cast<float2 *>(V + is) = vs;
-        float4 pq = q_in, mq = *reinterpret_cast<float4 *>(M + ir), vq = *reinterpret_cast<float4 *>(V + ir);
-        adam_one(pq.x, dq.x, mq.x, vq.x, st_r, af.c);
-        adam_one(pq.y, dq.y, mq.y, vq.y, st_r, af.c);
-        adam_one(pq.z, dq.z, mq.z, vq.z, st_r, af.c);
-        adam_one(pq.w, dq.w, mq.w, vq.w, st_r, af.c);
-        rots[i] = pq; *reinterpret_cast<float4 *>(M + ir) = mq; *reinterpret_cast<float4 *>(V + ir) = vq;
-    }
+    if (af.enabled && skip == 0u)
+        fused_adam_surfel(af.adam, N, i, m, o_in, s_in, q_in, dm, dop, ds, dq, means, opac, scales, rots);
     }
 pose_reduce:
     if constexpr (POSE) {

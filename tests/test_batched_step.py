@@ -175,6 +175,30 @@ def test_g1_is_step_bit_for_bit(device):
     assert _same(_state(ea, ma), _state(eb, mb))
 
 
+@pytest.mark.parametrize("N", [258, 4999], ids=["two_workgroups", "odd_n_fallback"])
+def test_g1_is_step_bit_for_bit_with_pose_and_kept_grads(device, N):
+    """The same equality through the chain, the pose rows and the Adam tail together, at the smallest sizes that cross a
+    workgroup (258: Adam fused into the projection's backward) and take the separate optimiser kernel (4999, odd):
+    state, gradient bucket and pose row after each of three iterations."""
+    H, W = RAGGED["H"], RAGGED["W"]
+    scene = _scene(N, H, W)
+    cam_a, cam_b = _cameras(scene, 1, device)[0], _cameras(scene, 1, device)[0]
+    ea, ma = _engine(scene, device, deterministic=True)
+    eb, mb = _engine(scene, device, deterministic=True)
+    ea.keep_grads = eb.keep_grads = True
+    for s in range(3):
+        sa = ea.step(cam_a, pose_grad=True)
+        sb = eb.step_batch([cam_b], pose_grad=True)
+        assert not sa["overflow"] and not sb["overflow"], s
+        assert sa["sums"] == sb["sums"] == sb["keyframes"][0]["sums"], s
+        assert torch.equal(ea.grads[:-2], eb.grads[:-2]), f"iteration {s}: gradient bucket"
+        assert ea.grads[:-2].abs().max().item() > 0.0, f"iteration {s}: no gradient"
+        assert ea.pose_grad.shape == (6,) and eb.pose_grad.shape == (1, 6)
+        assert torch.equal(ea.pose_grad, eb.pose_grad[0]), f"iteration {s}: pose row"
+        assert _same(_state(ea, ma), _state(eb, mb)), f"iteration {s}: parameters or moments"
+    assert ea.t == eb.t == 3
+
+
 def test_deterministic_batches_are_reproducible(device):
     N, H, W, G = C5["N"], C5["H"], C5["W"], C5["G"]
     scene = _scene(N, H, W)
