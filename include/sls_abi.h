@@ -731,6 +731,53 @@ int sls_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz
 int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
                  void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- the k nearest neighbours, outlier removal ---------------------------------------------------------------------
+ * sls_nn_query with k answers per query (include/sls_outlier_math.h): query q's list is the min(k, Mt) smallest keys
+ * (bits(d2) << 32 | original target index) over ALL targets, ascending — nearer first, then the lower index; a target
+ * that is the query's own copy is a target like any other (d2 = 0).  Exact, bit for bit.
+ *   out_dist2 [Mq * k] floats, out_index [Mq * k] int32 (row q: its list; slots beyond Mt: +inf and -1),
+ *   out_mean [Mq] doubles: (sum in list order of (double)sqrtf(d2_j)) / min(k, Mt).
+ * Each of the three may be null and is then skipped.  1 <= k <= SLS_NN_K_MAX.  Where query_xyz == target_xyz and
+ * Mq == Mt the cloud's own index serves as the sorted query set.
+ *   scratch: sls_nn_k_scratch_bytes(Mt, Mq, k) bytes (0 for Mt < 1, Mq < 0 or k outside [1, SLS_NN_K_MAX]), 256-byte
+ *       aligned; never below sls_nn_scratch_bytes(Mt, Mq).
+ * Mq == 0 succeeds and writes nothing.  Before anything is enqueued: SLS_E_ARG for Mt < 1, Mq < 0, k out of range, a
+ * null target_xyz / query_xyz / scratch, scratch that is not 256-byte aligned; SLS_E_SCRATCH for too little scratch. */
+#ifndef SLS_NN_K_MAX
+#define SLS_NN_K_MAX 32     /* (include/sls_outlier_math.h defines the same) */
+#endif
+size_t sls_nn_k_scratch_bytes(int Mt, int Mq, int k);
+int sls_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,
+                   double *out_mean, void *scratch, size_t scratch_bytes, void *stream);
+/* Outlier removal of a cloud of M points, one call each, nothing read back inside it (include/sls_outlier_math.h).
+ * Statistical — Open3D's remove_statistical_outlier(nb_neighbors = k, std_ratio) as restated there (Open3D is not a
+ * dependency): mean_i = out_mean of the cloud's self-query at k, so the point itself is one of its k;
+ *   cloud_mean = sum{mean_i > 0} mean_i / M, std = sqrt(sum{mean_i > 0} (mean_i - cloud_mean)^2 / (M - 1)),
+ *   thr = cloud_mean + std_ratio * std; point i is kept iff mean_i > 0 && mean_i < thr.
+ * So a point whose k - 1 nearest others are exact copies of it is removed, k = 1 removes everything and M = 1 removes
+ * the point (thr is NaN).  The sums are float64, in a fixed order, no atomics: the same input, the same bits.
+ * Radius — point i is kept iff more than nb_points points, itself included, have d2 <= radius * radius (a float32
+ * product): 0 <= nb_points <= SLS_NN_K_MAX - 1.
+ *   normals (optional, M x 3): rows that travel with their points into out_normals.
+ *   out_xyz, out_normals (M x 3 floats), out_index (M int32: the original row): room for M rows each, the kept rows in
+ *       ascending original index, the rows from `kept` on not written.  Each may be null and is then skipped
+ *       (out_normals must be null when normals is).
+ *   out_status (DEVICE, SLS_OUTLIER_STATUS_WORDS 64-bit words): [kept, points with a mean that is not > 0, bits of
+ *       the doubles cloud_mean, std, thr, M, 0, 0]; the radius filter writes [kept, 0, 0, 0, 0, M, 0, 0].
+ *   scratch: sls_outlier_scratch_bytes(M, k) bytes, k = nb_points + 1 for the radius filter (0 for M < 1 or k outside
+ *       [1, SLS_NN_K_MAX]), 256-byte aligned; never below sls_nn_k_scratch_bytes(M, M, k).
+ * M == 0 succeeds, zeroes out_status when that is non-null and touches nothing else.  Before anything is enqueued:
+ * SLS_E_ARG for M < 0, k or nb_points out of range, a std_ratio or radius that is not a finite number > 0, a null xyz /
+ * out_status / scratch, out_normals without normals, misaligned scratch; SLS_E_SCRATCH for too little scratch. */
+#define SLS_OUTLIER_STATUS_WORDS 8
+size_t sls_outlier_scratch_bytes(int M, int k);
+int sls_outlier_statistical(int M, const float *xyz, const float *normals, int k, double std_ratio, float *out_xyz,
+                            float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, size_t scratch_bytes,
+                            void *stream);
+int sls_outlier_radius(int M, const float *xyz, const float *normals, int nb_points, float radius, float *out_xyz,
+                       float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, size_t scratch_bytes,
+                       void *stream);
+
 /* ---- voxel down-sampling and mesh sampling (what evaluate_recon does before its metric block) -----------------------
  * Open3D's voxel_down_sample for points only, restated (include/sls_cloud_math.h): every point gets the voxel
  * (ix, iy, iz), i_a = floor(((double)p_a - o_a) / voxel_size), o_a = (double)min_a - 0.5 * voxel_size, packed into the

@@ -163,6 +163,11 @@ _PROTOS = {
     "sls_nn_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_nn_query": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_nn_stats": (C.c_int, [C.c_int, _VP, C.c_float, C.c_float, C.c_int, _VP, _VP, C.c_size_t, _VP]),
+    "sls_nn_k_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sls_nn_query_k": (C.c_int, [C.c_int, _VP, C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_outlier_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_outlier_statistical": (C.c_int, [C.c_int, _VP, _VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_outlier_radius": (C.c_int, [C.c_int, _VP, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_voxel_scratch_bytes": (C.c_size_t, [C.c_int]),
     "sls_voxel_downsample": (C.c_int, [C.c_int, _VP, C.c_double, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_mesh_sample_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -478,6 +478,76 @@ int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, i
     return launch_nn_stats(M, dist2, truncation, threshold, include_truncated, out_stats, scratch, (hipStream_t)stream);
 }
 
+size_t sls_nn_k_scratch_bytes(int Mt, int Mq, int k) { return nn_k_scratch_bytes(Mt, Mq, k); }
+
+int sls_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,
+                   double *out_mean, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(Mt >= 1, "Mt < 1: the target cloud is empty");
+    SLS_REQUIRE(Mq >= 0, "negative Mq");
+    SLS_REQUIRE(k >= 1 && k <= SLS_NN_K_MAX, "k outside [1, SLS_NN_K_MAX]");
+    if (Mq == 0) return SLS_OK;
+    SLS_REQUIRE(target_xyz && query_xyz && scratch, "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < nn_k_scratch_bytes(Mt, Mq, k)) {
+        set_error("sls_nn_query_k: scratch too small: %zu < %zu", scratch_bytes, nn_k_scratch_bytes(Mt, Mq, k));
+        return SLS_E_SCRATCH;
+    }
+    return launch_nn_query_k(Mt, target_xyz, Mq, query_xyz, k, out_dist2, out_index, out_mean, nullptr, scratch, (hipStream_t)stream);
+}
+
+size_t sls_outlier_scratch_bytes(int M, int k) { return outlier_scratch_bytes(M, k); }
+
+// what the two filters check alike, behind their own parameter
+static int outlier_check(const char *who, int M, const float *xyz, const float *normals, int k, float *out_normals,
+                         uint64_t *out_status, void *scratch, size_t scratch_bytes, void *stream, bool *done)
+{
+    *done = true;
+    if (M == 0) {
+        if (out_status) SLS_HIP_CHECK(hipMemsetAsync(out_status, 0, SLS_OUTLIER_STATUS_WORDS * sizeof(uint64_t), (hipStream_t)stream));
+        return SLS_OK;
+    }
+    if (!(xyz && out_status && scratch)) { set_error("%s: null pointer", who); return SLS_E_ARG; }
+    if (out_normals && !normals) { set_error("%s: out_normals without normals", who); return SLS_E_ARG; }
+    if (((uintptr_t)scratch & 255u) != 0) { set_error("%s: scratch not 256-byte aligned", who); return SLS_E_ARG; }
+    if (scratch_bytes < outlier_scratch_bytes(M, k)) {
+        set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, outlier_scratch_bytes(M, k));
+        return SLS_E_SCRATCH;
+    }
+    *done = false;
+    return SLS_OK;
+}
+
+int sls_outlier_statistical(int M, const float *xyz, const float *normals, int k, double std_ratio, float *out_xyz,
+                            float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, size_t scratch_bytes,
+                            void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE(k >= 1 && k <= SLS_NN_K_MAX, "k outside [1, SLS_NN_K_MAX]");
+    SLS_REQUIRE(std_ratio > 0.0 && std_ratio <= DBL_MAX, "std_ratio is not a finite number > 0");
+    bool done;
+    const int rc = outlier_check("sls_outlier_statistical", M, xyz, normals, k, out_normals, out_status, scratch, scratch_bytes,
+                                 stream, &done);
+    if (rc || done) return rc;
+    return launch_outlier_statistical(M, xyz, normals, k, std_ratio, out_xyz, out_normals, out_index, out_status, scratch,
+                                      (hipStream_t)stream);
+}
+
+int sls_outlier_radius(int M, const float *xyz, const float *normals, int nb_points, float radius, float *out_xyz,
+                       float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, size_t scratch_bytes,
+                       void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE(nb_points >= 0 && nb_points <= SLS_NN_K_MAX - 1, "nb_points outside [0, SLS_NN_K_MAX - 1]");
+    SLS_REQUIRE(radius > 0.0f && radius <= FLT_MAX, "radius is not a finite number > 0");
+    bool done;
+    const int rc = outlier_check("sls_outlier_radius", M, xyz, normals, nb_points + 1, out_normals, out_status, scratch,
+                                 scratch_bytes, stream, &done);
+    if (rc || done) return rc;
+    return launch_outlier_radius(M, xyz, normals, nb_points, radius, out_xyz, out_normals, out_index, out_status, scratch,
+                                 (hipStream_t)stream);
+}
+
 size_t sls_voxel_scratch_bytes(int M) { return voxel_scratch_bytes(M); }
 
 int sls_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,

@@ -17,6 +17,7 @@
 
 #include "sls_launch.hpp"
 #include "../../include/sls_nn_math.h"
+#include "../../include/sls_outlier_math.h"
 
 namespace sls {
 
@@ -665,6 +666,236 @@ int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_
                        s.t.boxes, s.t.subboxes, which ? s.t.keys_tmp : s.t.keys, Mq, s.qpts,
                        qwhich ? s.qkeys_tmp : s.qkeys, out_dist2, out_index);
     SLS_LAUNCH_CHECK("nn_query_kernel");
+    return SLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sls_nn_query_k: the k nearest targets of every query (include/sls_outlier_math.h) — nn_query_kernel with the single
+// packed best replaced by a per-lane ascending list of K keys in registers (K = 4, 8, 16 or 32, the smallest >= k; every
+// index into it is a compile-time constant after unrolling) and the pruning bound by the lane's k-th best distance, +inf
+// until k targets are held.  The K - k slots in front are filled with the key 0, which nothing beats: the k real entries
+// then live in list[K - k .. K) and list[K - 1] is the k-th best whatever k is.  What keeps the search exact is kept:
+// every gap test is <= with the 0.99999 slack, and a candidate enters the list on a comparison of WHOLE keys.  Unlike a
+// minimum, a list counts what it meets: every target is presented exactly once (the sweep visits every box once, a short
+// last run is padded with SLS_NN_KEY_NONE, which never enters).  No cross-workgroup communication, no waiting, every loop
+// bounded by the box count.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int K>
+__device__ __forceinline__ void nnk_scan32(const float4 *s_run, const float4 me, uint64_t (&list)[K])
+{
+#pragma clang loop unroll_count(K <= 8 ? 4 : 1)
+    for (int j = 0; j < kKnnSub; ++j) {
+        const float4 p = s_run[j];
+        const uint64_t key = sls_nn_key(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), __float_as_uint(p.w));
+        if (key < list[K - 1]) sls_knn_insert(list, K, key);
+    }
+}
+
+// a run's point for the LDS stage: beyond Mt a point nothing is near to, d2 = +inf and index 0xFFFFFFFF = SLS_NN_KEY_NONE
+__device__ __forceinline__ float4 nnk_point(const float4 *__restrict__ pts, int i, int Mt)
+{
+    return i < Mt ? pts[i] : make_float4(1.0e30f, 1.0e30f, 1.0e30f, __uint_as_float(0xFFFFFFFFu));
+}
+
+template <int K>
+__global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, const float4 *__restrict__ pts,
+                                                        const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                        const uint32_t *__restrict__ tkeys, int Mq,
+                                                        const float4 *__restrict__ qpts, const uint32_t *__restrict__ qkeys, int k,
+                                                        float *__restrict__ out_dist2, int32_t *__restrict__ out_index,
+                                                        double *__restrict__ out_mean, uint64_t *__restrict__ out_last_key)
+{
+    constexpr int kSubs = kKnnBox / kKnnSub;
+    __shared__ float4 s_run[kKnnSub];                   // wave-private: the workgroup IS one wave
+    __shared__ uint32_t s_box[64];
+    __shared__ uint32_t s_sub[64 * kSubs];
+    const int lane = threadIdx.x;
+    const int q0 = blockIdx.x * 64, q = q0 + lane;      // (the grid has ceil(Mq / 64) waves: q0 < Mq)
+    const bool live = q < Mq;
+    const float4 me = qpts[live ? q : Mq - 1];
+    const int nsub = (Mt + kKnnSub - 1) / kKnnSub;
+    const int first = K - k;                            // (the launcher guarantees K / 2 < k <= K, or k <= K = 4)
+    uint64_t list[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) list[j] = j < first ? 0ull : SLS_NN_KEY_NONE;
+    auto bound = [&]() -> float { return sls_nn_key_dist2(list[K - 1]); };
+
+    int start_box;
+    {
+        const uint32_t code = qkeys[q0];
+        int lo = 0, hi = Mt;                            // lower bound in tkeys[0, Mt): at most 31 halvings
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (tkeys[mid] < code) lo = mid + 1; else hi = mid;
+        }
+        start_box = __builtin_amdgcn_readfirstlane(min(lo, Mt - 1) / kKnnBox);
+    }
+
+    // a. the runs of the starting box: a first bound
+    for (int t = 0; t < kSubs; ++t) {
+        const int sb = start_box * kSubs + t;
+        if (sb >= nsub) break;
+        __builtin_amdgcn_wave_barrier();
+        if (lane < kKnnSub) s_run[lane] = nnk_point(pts, sb * kKnnSub + lane, Mt);
+        __syncthreads();
+        nnk_scan32<K>(s_run, me, list);
+    }
+
+    // bounding box of the wave's queries, and of its 8 groups of 8 consecutive ones (dead lanes: empty)
+    auto rl = [](float v, int i) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), i)); };
+    float4 gmn = live ? me : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f);
+    float4 gmx = live ? me : make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) {
+        gmn.x = fminf(gmn.x, __shfl_xor(gmn.x, off, 64)); gmn.y = fminf(gmn.y, __shfl_xor(gmn.y, off, 64));
+        gmn.z = fminf(gmn.z, __shfl_xor(gmn.z, off, 64));
+        gmx.x = fmaxf(gmx.x, __shfl_xor(gmx.x, off, 64)); gmx.y = fmaxf(gmx.y, __shfl_xor(gmx.y, off, 64));
+        gmx.z = fmaxf(gmx.z, __shfl_xor(gmx.z, off, 64));
+    }
+    float4 wmn = gmn, wmx = gmx;
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+        wmn.x = fminf(wmn.x, __shfl_xor(wmn.x, off, 64)); wmn.y = fminf(wmn.y, __shfl_xor(wmn.y, off, 64));
+        wmn.z = fminf(wmn.z, __shfl_xor(wmn.z, off, 64));
+        wmx.x = fmaxf(wmx.x, __shfl_xor(wmx.x, off, 64)); wmx.y = fmaxf(wmx.y, __shfl_xor(wmx.y, off, 64));
+        wmx.z = fmaxf(wmx.z, __shfl_xor(wmx.z, off, 64));
+    }
+
+    // b. the outward sweep over chunks of 64 boxes, as in nn_query_kernel (the bound is the lane's k-th best distance)
+    const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;
+    for (int it = 0; it < nchunks; ++it) {
+        int chunk;
+        {
+            const int near = min(c0, nchunks - 1 - c0);
+            if (it <= 2 * near) chunk = c0 + ((it & 1) ? (it + 1) / 2 : -(it / 2));
+            else chunk = (c0 < nchunks - 1 - c0) ? it : nchunks - 1 - it;
+        }
+        float gB = live ? bound() : 0.0f;
+        gB = fmaxf(gB, __shfl_xor(gB, 1, 64)); gB = fmaxf(gB, __shfl_xor(gB, 2, 64)); gB = fmaxf(gB, __shfl_xor(gB, 4, 64));
+        const float B2 = wave_max(gB);
+        auto reaches = [&](const float4 bmn, const float4 bmx) -> bool {
+            if (!(box_gap2(wmn, wmx, bmn, bmx) * 0.99999f <= B2)) return false;
+            bool r = false;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const float4 mn = make_float4(rl(gmn.x, 8 * g), rl(gmn.y, 8 * g), rl(gmn.z, 8 * g), 0.0f);
+                const float4 mx = make_float4(rl(gmx.x, 8 * g), rl(gmx.y, 8 * g), rl(gmx.z, 8 * g), 0.0f);
+                r = r || (box_gap2(mn, mx, bmn, bmx) * 0.99999f <= rl(gB, 8 * g));
+            }
+            return r;
+        };
+        const int b = chunk * 64 + lane;
+        bool c = false;
+        if (b < nboxes && b != start_box) c = reaches(boxes[2 * b], boxes[2 * b + 1]);
+        const uint64_t cm = __ballot(c);
+        const int nb = __builtin_popcountll(cm);
+        if (nb == 0) continue;
+        __builtin_amdgcn_wave_barrier();
+        if (c) s_box[__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u))] = (uint32_t)b;
+        __syncthreads();
+        int ns = 0;                                     // <= 8 * nb <= 512 = the size of s_sub
+        for (int g = 0; g < nb; g += 8) {
+            const int slot = g + (lane >> 3);
+            bool cs = false;
+            uint32_t sb = 0;
+            if (slot < nb) {
+                sb = s_box[slot] * kSubs + (uint32_t)(lane & 7);
+                if ((int)sb < nsub) cs = reaches(subboxes[2 * (size_t)sb], subboxes[2 * (size_t)sb + 1]);
+            }
+            const uint64_t sm = __ballot(cs);
+            if (cs) s_sub[ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u))] = sb;
+            ns += __builtin_popcountll(sm);
+        }
+        __syncthreads();
+        // c. the listed runs, 64 at a time: can one still enter (or tie into) ANY query's list?  Then its 32 points go
+        //    through LDS
+        for (int base = 0; base < ns; base += 64) {
+            const int nk = min(64, ns - base);
+            const uint32_t sbl = s_sub[base + min(lane, nk - 1)];
+            const float4 mnl = subboxes[2 * (size_t)sbl], mxl = subboxes[2 * (size_t)sbl + 1];
+            const float qb2 = live ? bound() : -1.0f;
+            bool need = false;
+            for (int qi = 0; qi < 64; ++qi) {
+                const float4 qp = make_float4(rl(me.x, qi), rl(me.y, qi), rl(me.z, qi), 0.0f);
+                need = need || (box_gap2(qp, qp, mnl, mxl) * 0.99999f <= rl(qb2, qi));
+            }
+            uint64_t todo = __ballot(need && lane < nk);
+            auto fetch = [&](int i) -> float4 {         // lanes 0..31: the points of candidate i
+                return nnk_point(pts, __builtin_amdgcn_readlane((int)sbl, i) * kKnnSub + (lane & (kKnnSub - 1)), Mt);
+            };
+            float4 pre = make_float4(0, 0, 0, 0);
+            if (todo) pre = fetch(__builtin_ctzll(todo));
+            while (todo) {
+                todo &= todo - 1;
+                const float4 cur = pre;
+                if (todo) pre = fetch(__builtin_ctzll(todo));
+                __builtin_amdgcn_wave_barrier();
+                if (lane < kKnnSub) s_run[lane] = cur;
+                __syncthreads();
+                nnk_scan32<K>(s_run, me, list);
+            }
+        }
+    }
+    if (live) {
+        const size_t i = __float_as_uint(me.w);
+        if (out_dist2 || out_index) {
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (j >= first) {
+                    const size_t o = i * (size_t)k + (size_t)(j - first);
+                    if (out_dist2) out_dist2[o] = sls_nn_key_dist2(list[j]);
+                    if (out_index) out_index[o] = (int32_t)sls_nn_key_index(list[j]);      // (SLS_NN_KEY_NONE: -1)
+                }
+        }
+        if (out_mean) out_mean[i] = sls_knn_mean(list, K, first, min(k, Mt));
+        if (out_last_key) out_last_key[i] = list[K - 1];
+    }
+}
+
+size_t nn_k_scratch_bytes(int Mt, int Mq, int k)
+{
+    return (k >= 1 && k <= SLS_NN_K_MAX) ? nn_scratch_bytes(Mt, Mq) : 0;
+}
+
+int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,
+                      double *out_mean, uint64_t *out_last_key, void *scratch, hipStream_t st)
+{
+    const NnScratch s = nn_layout(Mt, Mq, scratch);
+    const int key_bits = knn_key_bits(Mt);
+    ScopedTimer tm(T_KNN, st);
+    int which = 0, qwhich = 0;
+    int rc = knn_build(Mt, target_xyz, s.t, key_bits, (uint32_t)Mq, st, &which);
+    if (rc) return rc;
+    const uint32_t *tkeys = which ? s.t.keys_tmp : s.t.keys;
+    const float4 *qpts = s.t.pts;
+    const uint32_t *qkeys = tkeys;
+    // a cloud queried by itself is its own sorted query set; any other one goes through the target's cube and the sorter
+    if (!(query_xyz == target_xyz && Mq == Mt)) {
+        hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, s.t.bbox, s.qkeys, s.qvals,
+                           key_bits);
+        SLS_LAUNCH_CHECK("knn_morton_kernel");
+        rc = radix_sort_pairs_u32(s.qkeys, s.qvals, s.qkeys_tmp, s.qvals_tmp, s.t.bbox + 7, (uint32_t)Mq, key_bits, s.t.sort,
+                                  s.t.sort_bytes, &qwhich, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(nn_gather_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz,
+                           qwhich ? s.qvals_tmp : s.qvals, s.qpts);
+        SLS_LAUNCH_CHECK("nn_gather_kernel");
+        qpts = s.qpts;
+        qkeys = qwhich ? s.qkeys_tmp : s.qkeys;
+    }
+    const dim3 grid((Mq + 63) / 64);
+    const int nboxes = (Mt + kKnnBox - 1) / kKnnBox;
+#define SLS_NNK_LAUNCH(KK)                                                                                                    \
+    hipLaunchKernelGGL(nn_query_k_kernel<KK>, grid, dim3(64), 0, st, Mt, nboxes, s.t.pts, s.t.boxes, s.t.subboxes, tkeys, Mq, \
+                       qpts, qkeys, k, out_dist2, out_index, out_mean, out_last_key)
+    switch (sls_knn_list_length(k)) {
+    case 4: SLS_NNK_LAUNCH(4); break;
+    case 8: SLS_NNK_LAUNCH(8); break;
+    case 16: SLS_NNK_LAUNCH(16); break;
+    default: SLS_NNK_LAUNCH(32); break;
+    }
+#undef SLS_NNK_LAUNCH
+    SLS_LAUNCH_CHECK("nn_query_k_kernel");
     return SLS_OK;
 }
 

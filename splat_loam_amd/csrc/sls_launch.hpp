@@ -183,6 +183,16 @@ int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_
                     void *scratch, hipStream_t st);
 int launch_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
                     void *scratch, hipStream_t st);
+// the k nearest (sls_knn.hip).  Every output may be null; out_last_key: the k-th key of every query's list
+size_t nn_k_scratch_bytes(int Mt, int Mq, int k);
+int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,
+                      double *out_mean, uint64_t *out_last_key, void *scratch, hipStream_t st);
+// ---- sls_outlier.hip (the arguments are checked by the caller, sls_api.hip) ----------------------------------------
+size_t outlier_scratch_bytes(int M, int k);
+int launch_outlier_statistical(int M, const float *xyz, const float *normals, int k, double std_ratio, float *out_xyz,
+                               float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st);
+int launch_outlier_radius(int M, const float *xyz, const float *normals, int nb_points, float radius, float *out_xyz,
+                          float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st);
 // ---- sls_cloud.hip (the arguments are checked by the caller, sls_api.hip) ------------------------------------------
 size_t voxel_scratch_bytes(int M);
 int launch_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,

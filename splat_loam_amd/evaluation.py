@@ -70,6 +70,144 @@ def nearest(target: torch.Tensor, query: torch.Tensor, return_index: bool = True
         return _query(lib, target, query, return_index, scratch, st)
 
 
+NN_K_MAX = 32      # SLS_NN_K_MAX (include/sls_abi.h)
+
+
+def _check_k(k, name: str, lo: int = 1, hi: int = NN_K_MAX) -> int:
+    if isinstance(k, bool) or int(k) != k or not lo <= int(k) <= hi:
+        raise ValueError(f"{name} must be an integer in [{lo}, {hi}]")
+    return int(k)
+
+
+def nearest_k(target: torch.Tensor, query: torch.Tensor, k: int, return_index: bool = True):
+    """For every row of `query` (Mq,3) its `k` nearest rows of `target` (Mt,3), 1 <= k <= 32:
+    `(dist2 (Mq,k) float32, index (Mq,k) int32)`, or `(dist2, None)` with `return_index=False`.  Row q is sorted by
+    (dist2, index): nearer first, the lower target row first among equal distances, bit for bit
+    (include/sls_outlier_math.h); with Mt < k the slots from Mt on hold +inf and -1.  A target that is the query's own
+    copy is a target like any other: querying a cloud by itself gives every point itself first, at distance 0.
+    `nearest_k(k=1)` equals `nearest`.  As for `nearest`, the coordinates must be finite: they are not checked, and what
+    a row with a NaN or an infinity gets, or gives to others, is unspecified (every access stays inside the buffers)."""
+    target, query = _cloud(target, "target"), _cloud(query, "query")
+    k = _check_k(k, "k")
+    if query.device != target.device:
+        raise ValueError("target and query must live on the same device")
+    if target.shape[0] == 0:
+        raise ValueError("the target cloud is empty")
+    Mt, Mq = int(target.shape[0]), int(query.shape[0])
+    lib = _abi.lib()
+    dev = target.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        dist2 = torch.empty((Mq, k), dtype=torch.float32, device=dev)
+        index = torch.empty((Mq, k), dtype=torch.int32, device=dev) if return_index else None
+        if Mq:
+            _, aligned, nbytes = _scratch_bytes(lib.sls_nn_k_scratch_bytes(Mt, Mq, k), dev)
+            _abi.check(lib.sls_nn_query_k(Mt, target.data_ptr(), Mq, query.data_ptr(), k, dist2.data_ptr(),
+                                          index.data_ptr() if return_index else None, None, aligned, nbytes, st), "sls_nn_query_k")
+    return dist2, index
+
+
+def _normals(normals, points: torch.Tensor):
+    if normals is None:
+        return None
+    normals = _cloud(normals, "normals")
+    if normals.shape != points.shape or normals.device != points.device:
+        raise ValueError("normals must have the shape and the device of points")
+    return normals
+
+
+def _outlier_enqueue(lib, call, name: str, points, normals, k: int, args: tuple, st):
+    """One filter call without a host read: (rows (M,3), normals (M,3) | None, index (M,) int32, status (8,) int64)."""
+    M = int(points.shape[0])
+    dev = points.device
+    out = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    out_n = torch.empty((M, 3), dtype=torch.float32, device=dev) if normals is not None else None
+    index = torch.empty((M,), dtype=torch.int32, device=dev)
+    status = torch.empty((8,), dtype=torch.int64, device=dev)
+    _, aligned, nbytes = _scratch_bytes(lib.sls_outlier_scratch_bytes(M, k), dev)
+    _abi.check(call(M, points.data_ptr() if M else None, normals.data_ptr() if (normals is not None and M) else None, *args,
+                    out.data_ptr() if M else None, out_n.data_ptr() if (out_n is not None and M) else None,
+                    index.data_ptr() if M else None, status.data_ptr(), aligned if M else None, nbytes, st), name)
+    return out, out_n, index, status
+
+
+def _outlier_result(out, out_n, index, words, has_normals: bool, return_index: bool, details: bool):
+    bits = lambda v: struct.unpack("<d", struct.pack("<q", v))[0]
+    kept = int(words[0])
+    res = [out[:kept]]
+    if has_normals:
+        res.append(out_n[:kept])
+    if return_index:
+        res.append(index[:kept])
+    if details:
+        res.append({"kept": kept, "removed": int(words[5]) - kept, "zero_mean": int(words[1]), "cloud_mean": bits(words[2]),
+                    "std": bits(words[3]), "threshold": bits(words[4])})
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def _check_stat_args(nb_neighbors, std_ratio) -> tuple[int, float]:
+    k = _check_k(nb_neighbors, "nb_neighbors")
+    std_ratio = float(std_ratio)
+    if not (std_ratio > 0.0 and math.isfinite(std_ratio)):
+        raise ValueError("std_ratio must be a finite number > 0")
+    return k, std_ratio
+
+
+def remove_statistical_outlier(points: torch.Tensor, nb_neighbors: int = 20, std_ratio: float = 2.0, normals=None,
+                               return_index: bool = False, details: bool = False):
+    """Open3D's `remove_statistical_outlier`, restated (include/sls_outlier_math.h; Open3D is not a dependency and the
+    rule is pinned against a NumPy restatement, tests/outlier_ref.py, not against Open3D itself).  mean_i is the mean
+    distance of point i to its `nb_neighbors` nearest points, ITSELF INCLUDED (at distance 0: the cloud is queried
+    by itself): float32 roots of the exact neighbour list of `nearest_k`, summed in float64.
+    With n = M: cloud_mean = sum{mean_i > 0} mean_i / n, std = sqrt(sum{mean_i > 0} (mean_i - cloud_mean)^2 / (n - 1)),
+    and point i is kept iff mean_i > 0 and mean_i < cloud_mean + std_ratio * std.  Three consequences: a point whose
+    nb_neighbors - 1 nearest others are exact copies of it is removed; nb_neighbors = 1 removes everything; a cloud of
+    one point loses it.  One native call (sls_outlier_statistical), fixed-order float64 sums — the same cloud gives the
+    same bits on every run — and one host read (the status words).
+
+    Returns the kept rows in their original order, (kept,3) float32; then, in this order, the kept rows of `normals`
+    where given, with `return_index=True` their original row numbers (kept,) int32, with `details=True` a dict: kept,
+    removed, zero_mean (points with mean 0), cloud_mean, std, threshold.  1 <= nb_neighbors <= 32, std_ratio > 0.
+    As for `nearest`, the coordinates must be finite: they are not checked, and a NaN or an infinity makes the result
+    unspecified (every access stays inside the buffers)."""
+    points = _cloud(points, "points")
+    k, std_ratio = _check_stat_args(nb_neighbors, std_ratio)
+    normals = _normals(normals, points)
+    lib = _abi.lib()
+    with torch.cuda.device(points.device):
+        st = torch.cuda.current_stream(points.device).cuda_stream
+        out, out_n, index, status = _outlier_enqueue(lib, lib.sls_outlier_statistical, "sls_outlier_statistical", points, normals,
+                                                     k, (k, std_ratio), st)
+        words = status.cpu().tolist()                                       # the one host read
+    return _outlier_result(out, out_n, index, words, normals is not None, return_index, details)
+
+
+def remove_radius_outlier(points: torch.Tensor, nb_points: int, radius: float, normals=None, return_index: bool = False,
+                          details: bool = False):
+    """Keep the points with MORE than `nb_points` points, themselves included, within `radius`: d2 <= radius * radius,
+    one float32 product, d2 the exact float32 expression of `nearest`.  This is the project's rule; whether Open3D's
+    `remove_radius_outlier` puts its boundary at < or <= was not verified.  0 <= nb_points <= 31, radius > 0.  One
+    native call (sls_outlier_radius), one host read.  Returns as `remove_statistical_outlier`; the details hold kept
+    and removed.  Coordinates must be finite, as there."""
+    points = _cloud(points, "points")
+    nb = _check_k(nb_points, "nb_points", 0, NN_K_MAX - 1)
+    radius = float(radius)
+    if not (radius > 0.0 and math.isfinite(radius) and radius <= 3.0e38):
+        raise ValueError("radius must be a finite number > 0")
+    normals = _normals(normals, points)
+    lib = _abi.lib()
+    with torch.cuda.device(points.device):
+        st = torch.cuda.current_stream(points.device).cuda_stream
+        out, out_n, index, status = _outlier_enqueue(lib, lib.sls_outlier_radius, "sls_outlier_radius", points, normals, nb + 1,
+                                                     (nb, radius), st)
+        words = status.cpu().tolist()                                       # the one host read
+    res = _outlier_result(out, out_n, index, words, normals is not None, return_index, details)
+    if details:
+        for key in ("zero_mean", "cloud_mean", "std", "threshold"):
+            res[-1].pop(key)                                                # (the statistical filter's words)
+    return res
+
+
 def crop_union_mask(reference: torch.Tensor, estimate: torch.Tensor, threshold_dist: float = 1.2) -> torch.Tensor:
     """bool (Mref,): the reference points with an estimate point nearer than `threshold_dist` — `crop_union`
     (eval_utils.py:202-250) after its mesh sampling; `estimate` is the merged cloud of all methods.  The comparison is

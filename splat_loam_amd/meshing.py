@@ -179,18 +179,33 @@ def _render_keyframes(graph_dir: Path, graph: dict, used: list, poses: list, H: 
         yield i, fid, cam, allmap
 
 
+def _check_outlier(outlier_nb, outlier_std):
+    """None, or (nb_neighbors, std_ratio) checked as evaluation.remove_statistical_outlier checks them — before any work."""
+    if outlier_nb is None:
+        return None
+    from . import evaluation
+    return evaluation._check_stat_args(outlier_nb, outlier_std)
+
+
 @torch.no_grad()
 def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int = 5000, min_opacity: float = 0.5,
                    max_depth_dist: float = 0.1, use_median_depth: bool = False, seed=None, device="cuda",
-                   details: bool = False, image_height=None, image_width=None):
+                   details: bool = False, image_height=None, image_width=None, outlier_nb=None, outlier_std: float = 2.0):
     """`mesh_poisson`'s steps 1-4 (postprocessing.py:122-190) over a results directory (`graph.yaml`, `models/*.ply`,
     optionally `cfg.yaml` for the image size): returns (points (M,3), normals (M,3)), float32 device tensors in keyframe
     order, `kf_samples` rows per keyframe that has a valid pixel (the reference raises on one that has none; here it
     contributes no rows).  `details=True` adds dict(frame_ids: the frames used, n_valid: their counts of valid pixels,
     pixels: (frames used, kf_samples) int32, the selected row-major pixels, -1 in the rows of an empty keyframe, kept:
     which of the frames used contributed rows).  seed=None: torch.initial_seed().  Sample j of frame f depends on
-    (seed, f, j) and the render alone — not on kf_interval or the order of processing."""
+    (seed, f, j) and the render alone — not on kf_interval or the order of processing.
+
+    `outlier_nb=k` filters the merged cloud with `evaluation.remove_statistical_outlier(k, outlier_std)`: what the
+    reference's `remove_statistical_outlier(nb_neighbors=20, std_ratio=2.0)` (postprocessing.py:192) meant to do, at its
+    place in the sequence — the reference discards that call's result.  One more host read; the rows keep their order
+    and `details` gains `outlier` (the filter's statistics and `index`, the surviving rows of the unfiltered cloud).
+    The default None leaves the cloud as it always was, to the bit."""
     from . import traj_io
+    outlier = _check_outlier(outlier_nb, outlier_std)
     path = Path(graph_dir_or_yaml)
     graph_file = path / "graph.yaml" if path.is_dir() else path
     graph_dir = graph_file.parent
@@ -229,9 +244,18 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
         idx = torch.from_numpy(np.flatnonzero(kept)).to(dev)
         points = points.view(F, k, 3).index_select(0, idx).reshape(-1, 3)
         normals = normals.view(F, k, 3).index_select(0, idx).reshape(-1, 3)
+    outlier_det = None
+    if outlier is not None:
+        from . import evaluation
+        points, normals, index, outlier_det = evaluation.remove_statistical_outlier(points, outlier[0], outlier[1], normals=normals,
+                                                                                    return_index=True, details=True)
+        outlier_det["index"] = index
     if details:
-        return points, normals, {"frame_ids": [fid for _, fid in used], "n_valid": words[:, 0].astype(np.int64), "pixels": pixels,
-                                 "kept": kept.copy(), "seed": used_seed}
+        det = {"frame_ids": [fid for _, fid in used], "n_valid": words[:, 0].astype(np.int64), "pixels": pixels,
+               "kept": kept.copy(), "seed": used_seed}
+        if outlier_det is not None:
+            det["outlier"] = outlier_det
+        return points, normals, det
     return points, normals
 
 
@@ -242,7 +266,7 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
               min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
               regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
               smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False, fill_holes: int = None,
-              fill_max_size: float = None):
+              fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0):
     """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
     frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
 
@@ -261,6 +285,10 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     no keyframe observed leaves — get a fan over their centroid; `details["clean"]["fill"]` holds its counts.  With the defaults nothing of this runs and the soup is returned as it
     always was.
 
+    `outlier_nb=k` (with `outlier_std`) goes to `sample_surface`: the samples that name the TSDF blocks are the filtered
+    ones, so a block that only stray samples at a depth discontinuity would have named is never allocated;
+    `details["outlier"]` holds the filter's statistics.  Default None: off.
+
     Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
     its cloud: blocks of 8^3 voxels of edge `voxel_size`, truncation `trunc` (default 4 voxel_size).  Pass 2 renders every
     keyframe that contributed samples again (the full allmap) and fuses it (`TsdfVolume.integrate`, nearest pixel, weight
@@ -270,6 +298,7 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     import time
 
     from . import traj_io, tsdf
+    _check_outlier(outlier_nb, outlier_std)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("mesh_tsdf runs on a ROCm device; there is no CPU fallback")
@@ -286,8 +315,10 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
             stage_ms[name], t0 = (time.perf_counter() - t0) * 1e3, time.perf_counter()
     points, _, det = sample_surface(graph_dir_or_yaml, kf_interval=kf_interval, kf_samples=kf_samples, min_opacity=min_opacity,
                                     max_depth_dist=max_depth_dist, use_median_depth=use_median_depth, seed=seed, device=dev,
-                                    details=True, image_height=image_height, image_width=image_width)
+                                    details=True, image_height=image_height, image_width=image_width, outlier_nb=outlier_nb,
+                                    outlier_std=outlier_std)
     lap("sample")
+    outlier = det.get("outlier")
     volume = tsdf.TsdfVolume(tsdf.allocate_blocks(points, voxel_size, trunc), voxel_size, trunc)
     lap("allocate")
     path = Path(graph_dir_or_yaml)
@@ -318,5 +349,7 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
                "samples": int(points.shape[0]), "frame_ids": [fid for _, fid in used], "stage_ms": stage_ms, "volume": volume}
         if clean is not None:
             det["clean"] = clean
+        if outlier is not None:
+            det["outlier"] = outlier
         return mesh + (det,)
     return mesh

@@ -9,6 +9,7 @@ rendered depth of every keyframe fused into a sparse TSDF volume, the zero surfa
                               [--simplify RES [--contraction quadric] [--regularisation L]]
                               [--smooth N [--smooth-method laplacian] [--smooth-weights uniform] [--fix-boundary]]
                               [--fill-holes 64 [--fill-max-size M]]
+                              [--outlier-nb 20 [--outlier-std 2.0]]
                               [--seed S] [--image-height H --image-width W]
 
 OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tools/eval_recon.py` takes as the estimate.
@@ -19,7 +20,8 @@ OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tool
 quadric); --smooth N runs N smoothing sweeps over the edge graph before the normals (`mesh_ops.smooth`: Taubin with
 inverse-distance weights unless told otherwise; --fix-boundary leaves the boundary vertices where they are); --fill-holes N
 closes the boundary loops of at most N edges (and a bounding-box diagonal of at most --fill-max-size) after the selection
-with a fan over their centroid (`mesh_ops.fill_holes`).  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
+with a fan over their centroid (`mesh_ops.fill_holes`); --outlier-nb K filters the surface samples that name the volume's
+blocks (`evaluation.remove_statistical_outlier(K, --outlier-std)`: what the reference's mesh_poisson meant to do).  Prints one JSON line: blocks, bytes of the volume (4 KB per block), triangles, milliseconds per stage, and
 with a clean stage its statistics (of the welded mesh: clusters, degenerate triangles, boundary and non-manifold edges;
 n_min; the triangles kept; the counts of the hole filling, of the simplification and of the smoothing)."""
 import argparse
@@ -58,6 +60,8 @@ def main():
     ap.add_argument("--fix-boundary", action="store_true", help="leave the boundary vertices where they are (with --smooth)")
     ap.add_argument("--fill-holes", type=int, default=None, help="weld, then fill the boundary loops of at most N edges")
     ap.add_argument("--fill-max-size", type=float, default=None, help="... whose bounding box has at most this diagonal (with --fill-holes)")
+    ap.add_argument("--outlier-nb", type=int, default=None, help="statistical outlier removal of the surface samples: neighbours (1..32)")
+    ap.add_argument("--outlier-std", type=float, default=2.0, help="... and the threshold in standard deviations (with --outlier-nb)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -69,7 +73,8 @@ def main():
                                    image_width=a.image_width, keep_clusters=a.keep_clusters, min_triangles=a.min_triangles,
                                    normals=a.normals, simplify=a.simplify, contraction=a.contraction, regularisation=a.regularisation,
                                    smooth=a.smooth, smooth_method=a.smooth_method, smooth_weights=a.smooth_weights,
-                                   fix_boundary=a.fix_boundary, fill_holes=a.fill_holes, fill_max_size=a.fill_max_size)
+                                   fix_boundary=a.fix_boundary, fill_holes=a.fill_holes, fill_max_size=a.fill_max_size,
+                                   outlier_nb=a.outlier_nb, outlier_std=a.outlier_std)
     vertices, faces, normals = mesh[0], mesh[1], (mesh[2] if a.normals else None)
     if a.weld and "clean" not in det:
         vertices, faces = tsdf.weld_soup(vertices)
@@ -77,6 +82,8 @@ def main():
     line = {"blocks": det["blocks"], "volume_bytes": det["volume_bytes"], "triangles": det["triangles"],
             "vertices": int(vertices.shape[0]), "keyframes": len(det["frame_ids"]), "samples": det["samples"],
             "stage_ms": {k: round(v, 3) for k, v in det["stage_ms"].items()}, "out": a.out_ply}
+    if "outlier" in det:
+        line["outlier"] = dict({k: v for k, v in det["outlier"].items() if k != "index"}, nb_neighbors=a.outlier_nb, std_ratio=a.outlier_std)
     if "clean" in det:
         line["clean"] = {k: det["clean"][k] for k in ("welded_vertices", "clusters", "degenerate", "boundary_edges", "nonmanifold_edges",
                                                       "n_min")}

@@ -4,8 +4,10 @@ reconstruction takes — the reference's `run.py mesh` up to the Poisson solve (
 
     python tools/sample_surface.py RESULTS_DIR OUT.ply [--kf-interval N] [--kf-samples K] [--min-opacity A]
                                    [--max-depth-dist D] [--use-median-depth] [--seed S] [--image-height H --image-width W]
+                                   [--outlier-nb 20 [--outlier-std 2.0]]
 
-OUT.ply holds float32 `x y z nx ny nz`; elsewhere: `o3d.io.read_point_cloud(OUT.ply)` and
+--outlier-nb K filters the merged cloud with `evaluation.remove_statistical_outlier(K, --outlier-std)`: the call the
+reference makes at this place (postprocessing.py:192) and whose result it discards.  OUT.ply holds float32 `x y z nx ny nz`; elsewhere: `o3d.io.read_point_cloud(OUT.ply)` and
 `o3d.geometry.TriangleMesh.create_from_point_cloud_poisson(pcd, depth=...)` (INTEGRATION.md).
 
     python tools/sample_surface.py --probe [--probe-out FILE.json]
@@ -134,6 +136,8 @@ def main():
     ap.add_argument("--min-opacity", type=float, default=0.5)
     ap.add_argument("--max-depth-dist", type=float, default=0.1)
     ap.add_argument("--use-median-depth", action="store_true")
+    ap.add_argument("--outlier-nb", type=int, default=None, help="statistical outlier removal of the merged cloud: neighbours (1..32)")
+    ap.add_argument("--outlier-std", type=float, default=2.0, help="... and the threshold in standard deviations (with --outlier-nb)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -149,11 +153,13 @@ def main():
     pts, nrm, det = meshing.sample_surface(a.results_dir, kf_interval=a.kf_interval, kf_samples=a.kf_samples,
                                            min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist,
                                            use_median_depth=a.use_median_depth, seed=a.seed, device=a.device, details=True,
-                                           image_height=a.image_height, image_width=a.image_width)
+                                           image_height=a.image_height, image_width=a.image_width, outlier_nb=a.outlier_nb,
+                                           outlier_std=a.outlier_std)
     ply_io.save_point_cloud(a.out_ply, pts, nrm)
     empty = [f for f, kept in zip(det["frame_ids"], det["kept"]) if not kept]
     print(f"{pts.shape[0]} oriented points from {int(det['kept'].sum())} of {len(det['frame_ids'])} keyframes "
-          f"(seed {det['seed']}) -> {a.out_ply}" + (f"; no valid pixel in frames {empty}" if empty else ""))
+          f"(seed {det['seed']}) -> {a.out_ply}" + (f"; no valid pixel in frames {empty}" if empty else "") +
+          (f"; {det['outlier']['removed']} outliers removed (threshold {det['outlier']['threshold']:.4f} m)" if "outlier" in det else ""))
 
 
 if __name__ == "__main__":
