@@ -778,6 +778,37 @@ int sls_outlier_radius(int M, const float *xyz, const float *normals, int nb_poi
                        float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, size_t scratch_bytes,
                        void *stream);
 
+/* ---- normals of a cloud by PCA --------------------------------------------------------------------------------------
+ * Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn = k)) followed by
+ * orient_normals_towards_camera_location(viewpoint), restated in include/sls_normals_math.h (Open3D is not a dependency).
+ * One call, nothing read back inside it, no float atomics: the cloud's self-query at k writes every point's list into the
+ * scratch, one more kernel — a thread per point — takes the prefix of the list with d2 <= radius * radius (a float32
+ * product; the point itself is its first entry) as the neighbourhood, n_i points, and from it
+ *   n_i >= 3: the float64 mean and covariance in list order, a cyclic Jacobi eigen-solve (+ - * / and sqrt only), the
+ *             eigenvector of the smallest eigenvalue, normalised, flipped towards the viewpoint, rounded to float32;
+ *   n_i <  3: unit(viewpoint - p), or (0, 0, 1) where that is the zero vector.
+ * The same input gives the same bits on every run, and the bits of the header compiled for the host.
+ *   k: 1 <= k <= SLS_NORMALS_NN_MAX (beyond SLS_NN_K_MAX the search takes two passes: the 32 nearest, then the k - 32
+ *       nearest beyond the 32nd key; only this call reaches them).
+ *   radius: finite and > 0, or +inf: the k nearest whatever their distance.
+ *   viewpoint3: three floats in HOST memory, read before the call returns.
+ *   out_normals [M * 3] floats; out_count [M] int32: n_i; out_eigenvalues [M * 3] floats, ascending, zeros where
+ *       n_i < 3.  The last two may be null and are then skipped.
+ *   scratch: sls_cloud_normals_scratch_bytes(M, k) bytes (0 for M < 1 or k outside [1, SLS_NORMALS_NN_MAX]), 256-byte
+ *       aligned, a multiple of 256, monotone in M and k; never below sls_nn_scratch_bytes(M, M) + 8 * M * k (the rows) + 8 * M.
+ *       On return (in stream order) it holds every point's list as sls_nn_query_k writes it: with up(v) = v rounded up to
+ *       a multiple of 256, out_dist2 [M * k] floats at byte up(sls_nn_scratch_bytes(M, M)) and out_index [M * k] int32 at
+ *       up(4 * M * k) bytes behind that.
+ * M == 0 succeeds and touches nothing.  Before anything is enqueued: SLS_E_ARG for M < 0, k out of range, a radius that is
+ * NaN or not > 0, a null xyz / viewpoint3 / out_normals / scratch, misaligned scratch; SLS_E_SCRATCH for too little
+ * scratch.  Coordinates must be finite (not checked; every access stays inside the buffers). */
+#ifndef SLS_NORMALS_NN_MAX
+#define SLS_NORMALS_NN_MAX 64   /* (include/sls_normals_math.h defines the same) */
+#endif
+size_t sls_cloud_normals_scratch_bytes(int M, int k);
+int sls_cloud_normals(int M, const float *xyz, int k, float radius, const float *viewpoint3, float *out_normals,
+                      int32_t *out_count, float *out_eigenvalues, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- voxel down-sampling and mesh sampling (what evaluate_recon does before its metric block) -----------------------
  * Open3D's voxel_down_sample for points only, restated (include/sls_cloud_math.h): every point gets the voxel
  * (ix, iy, iz), i_a = floor(((double)p_a - o_a) / voxel_size), o_a = (double)min_a - 0.5 * voxel_size, packed into the

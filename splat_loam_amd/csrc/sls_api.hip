@@ -493,7 +493,7 @@ int sls_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_x
         set_error("sls_nn_query_k: scratch too small: %zu < %zu", scratch_bytes, nn_k_scratch_bytes(Mt, Mq, k));
         return SLS_E_SCRATCH;
     }
-    return launch_nn_query_k(Mt, target_xyz, Mq, query_xyz, k, out_dist2, out_index, out_mean, nullptr, scratch, (hipStream_t)stream);
+    return launch_nn_query_k(Mt, target_xyz, Mq, query_xyz, k, SLS_NN_K_MAX, out_dist2, out_index, out_mean, nullptr, scratch, (hipStream_t)stream);
 }
 
 size_t sls_outlier_scratch_bytes(int M, int k) { return outlier_scratch_bytes(M, k); }
@@ -546,6 +546,25 @@ int sls_outlier_radius(int M, const float *xyz, const float *normals, int nb_poi
     if (rc || done) return rc;
     return launch_outlier_radius(M, xyz, normals, nb_points, radius, out_xyz, out_normals, out_index, out_status, scratch,
                                  (hipStream_t)stream);
+}
+
+size_t sls_cloud_normals_scratch_bytes(int M, int k) { return cloud_normals_scratch_bytes(M, k); }
+
+int sls_cloud_normals(int M, const float *xyz, int k, float radius, const float *viewpoint3, float *out_normals,
+                      int32_t *out_count, float *out_eigenvalues, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE(k >= 1 && k <= SLS_NORMALS_NN_MAX, "k outside [1, SLS_NORMALS_NN_MAX]");
+    SLS_REQUIRE(radius > 0.0f, "radius is not a number > 0 (+inf: the k nearest at any distance)");
+    if (M == 0) return SLS_OK;
+    SLS_REQUIRE(xyz && viewpoint3 && out_normals && scratch, "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < cloud_normals_scratch_bytes(M, k)) {
+        set_error("sls_cloud_normals: scratch too small: %zu < %zu", scratch_bytes, cloud_normals_scratch_bytes(M, k));
+        return SLS_E_SCRATCH;
+    }
+    return launch_cloud_normals(M, xyz, k, radius, viewpoint3, out_normals, out_count, out_eigenvalues, scratch,
+                                (hipStream_t)stream);
 }
 
 size_t sls_voxel_scratch_bytes(int M) { return voxel_scratch_bytes(M); }

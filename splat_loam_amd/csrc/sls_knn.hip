@@ -679,15 +679,21 @@ int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_
 // minimum, a list counts what it meets: every target is presented exactly once (the sweep visits every box once, a short
 // last run is padded with SLS_NN_KEY_NONE, which never enters).  No cross-workgroup communication, no waiting, every loop
 // bounded by the box count.
+// Beyond k = 32 (sls_cloud_normals alone, up to SLS_NORMALS_NN_MAX = 64) the list is found in TWO passes of the same kernel:
+// the 32 nearest, whose last key L goes to a per-query buffer; then, with SECOND set, the k - 32 nearest among the targets
+// with key > L — a key names its target, so those are exactly the targets the first pass did not list — written behind the
+// first 32 of the row.  The second pass prunes by its own list alone (+inf until k - 32 such targets are held), which is
+// all exactness needs.  A 64-long register list was tried first: it compiled to 256 VGPRs + 40 AGPRs without scratch, 1 wave
+// per SIMD, and gave wrong lists on the device (3 % of the rows of a 1500-point cloud missed a neighbour); not shipped.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ void nnk_scan32(const float4 *s_run, const float4 me, uint64_t (&list)[K])
+template <int K, bool SECOND>
+__device__ __forceinline__ void nnk_scan32(const float4 *s_run, const float4 me, uint64_t (&list)[K], const uint64_t floor_key)
 {
 #pragma clang loop unroll_count(K <= 8 ? 4 : 1)
     for (int j = 0; j < kKnnSub; ++j) {
         const float4 p = s_run[j];
         const uint64_t key = sls_nn_key(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), __float_as_uint(p.w));
-        if (key < list[K - 1]) sls_knn_insert(list, K, key);
+        if (key < list[K - 1] && (!SECOND || key > floor_key)) sls_knn_insert(list, K, key);
     }
 }
 
@@ -697,13 +703,15 @@ __device__ __forceinline__ float4 nnk_point(const float4 *__restrict__ pts, int 
     return i < Mt ? pts[i] : make_float4(1.0e30f, 1.0e30f, 1.0e30f, __uint_as_float(0xFFFFFFFFu));
 }
 
-template <int K>
+// stride: the floats (int32s) between two queries' rows of out_dist2 (out_index); floor_keys: SECOND only, by original index
+template <int K, bool SECOND>
 __global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, const float4 *__restrict__ pts,
                                                         const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
                                                         const uint32_t *__restrict__ tkeys, int Mq,
                                                         const float4 *__restrict__ qpts, const uint32_t *__restrict__ qkeys, int k,
                                                         float *__restrict__ out_dist2, int32_t *__restrict__ out_index,
-                                                        double *__restrict__ out_mean, uint64_t *__restrict__ out_last_key)
+                                                        double *__restrict__ out_mean, uint64_t *__restrict__ out_last_key,
+                                                        int stride, const uint64_t *__restrict__ floor_keys)
 {
     constexpr int kSubs = kKnnBox / kKnnSub;
     __shared__ float4 s_run[kKnnSub];                   // wave-private: the workgroup IS one wave
@@ -719,6 +727,7 @@ __global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, cons
 #pragma unroll
     for (int j = 0; j < K; ++j) list[j] = j < first ? 0ull : SLS_NN_KEY_NONE;
     auto bound = [&]() -> float { return sls_nn_key_dist2(list[K - 1]); };
+    const uint64_t floor_key = SECOND ? floor_keys[__float_as_uint(me.w)] : 0ull;
 
     int start_box;
     {
@@ -738,7 +747,7 @@ __global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, cons
         __builtin_amdgcn_wave_barrier();
         if (lane < kKnnSub) s_run[lane] = nnk_point(pts, sb * kKnnSub + lane, Mt);
         __syncthreads();
-        nnk_scan32<K>(s_run, me, list);
+        nnk_scan32<K, SECOND>(s_run, me, list, floor_key);
     }
 
     // bounding box of the wave's queries, and of its 8 groups of 8 consecutive ones (dead lanes: empty)
@@ -832,7 +841,7 @@ __global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, cons
                 __builtin_amdgcn_wave_barrier();
                 if (lane < kKnnSub) s_run[lane] = cur;
                 __syncthreads();
-                nnk_scan32<K>(s_run, me, list);
+                nnk_scan32<K, SECOND>(s_run, me, list, floor_key);
             }
         }
     }
@@ -842,7 +851,7 @@ __global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, cons
 #pragma unroll
             for (int j = 0; j < K; ++j)
                 if (j >= first) {
-                    const size_t o = i * (size_t)k + (size_t)(j - first);
+                    const size_t o = i * (size_t)stride + (size_t)(j - first);
                     if (out_dist2) out_dist2[o] = sls_nn_key_dist2(list[j]);
                     if (out_index) out_index[o] = (int32_t)sls_nn_key_index(list[j]);      // (SLS_NN_KEY_NONE: -1)
                 }
@@ -857,9 +866,13 @@ size_t nn_k_scratch_bytes(int Mt, int Mq, int k)
     return (k >= 1 && k <= SLS_NN_K_MAX) ? nn_scratch_bytes(Mt, Mq) : 0;
 }
 
-int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,
-                      double *out_mean, uint64_t *out_last_key, void *scratch, hipStream_t st)
+int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, int k_max, float *out_dist2,
+                      int32_t *out_index, double *out_mean, uint64_t *out_last_key, void *scratch, hipStream_t st)
 {
+    if (k < 1 || k > k_max || k_max > 2 * SLS_NN_K_MAX || (k > SLS_NN_K_MAX && (out_mean || !out_last_key))) {
+        set_error("launch_nn_query_k: k = %d outside [1, %d], or beyond %d with a mean or without the key buffer", k, k_max, SLS_NN_K_MAX);
+        return SLS_E_ARG;
+    }
     const NnScratch s = nn_layout(Mt, Mq, scratch);
     const int key_bits = knn_key_bits(Mt);
     ScopedTimer tm(T_KNN, st);
@@ -885,14 +898,29 @@ int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *quer
     }
     const dim3 grid((Mq + 63) / 64);
     const int nboxes = (Mt + kKnnBox - 1) / kKnnBox;
-#define SLS_NNK_LAUNCH(KK)                                                                                                    \
-    hipLaunchKernelGGL(nn_query_k_kernel<KK>, grid, dim3(64), 0, st, Mt, nboxes, s.t.pts, s.t.boxes, s.t.subboxes, tkeys, Mq, \
-                       qpts, qkeys, k, out_dist2, out_index, out_mean, out_last_key)
-    switch (sls_knn_list_length(k)) {
-    case 4: SLS_NNK_LAUNCH(4); break;
-    case 8: SLS_NNK_LAUNCH(8); break;
-    case 16: SLS_NNK_LAUNCH(16); break;
-    default: SLS_NNK_LAUNCH(32); break;
+#define SLS_NNK_LAUNCH(KK, SECOND, kk, d2, idx, mean, last, floor)                                                            \
+    hipLaunchKernelGGL((nn_query_k_kernel<KK, SECOND>), grid, dim3(64), 0, st, Mt, nboxes, s.t.pts, s.t.boxes, s.t.subboxes,  \
+                       tkeys, Mq, qpts, qkeys, kk, d2, idx, mean, last, k, floor)
+    if (k <= SLS_NN_K_MAX) {
+        switch (sls_knn_list_length(k)) {
+        case 4: SLS_NNK_LAUNCH(4, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
+        case 8: SLS_NNK_LAUNCH(8, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
+        case 16: SLS_NNK_LAUNCH(16, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
+        default: SLS_NNK_LAUNCH(32, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
+        }
+    } else {
+        // two passes (see above): the 32 nearest and their last key, then the k - 32 nearest beyond that key
+        const int k2 = k - SLS_NN_K_MAX;
+        float *d2_b = out_dist2 ? out_dist2 + SLS_NN_K_MAX : nullptr;
+        int32_t *idx_b = out_index ? out_index + SLS_NN_K_MAX : nullptr;
+        SLS_NNK_LAUNCH(32, false, SLS_NN_K_MAX, out_dist2, out_index, nullptr, out_last_key, nullptr);
+        SLS_LAUNCH_CHECK("nn_query_k_kernel");
+        switch (sls_knn_list_length(k2)) {
+        case 4: SLS_NNK_LAUNCH(4, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
+        case 8: SLS_NNK_LAUNCH(8, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
+        case 16: SLS_NNK_LAUNCH(16, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
+        default: SLS_NNK_LAUNCH(32, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
+        }
     }
 #undef SLS_NNK_LAUNCH
     SLS_LAUNCH_CHECK("nn_query_k_kernel");

@@ -183,16 +183,24 @@ int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_
                     void *scratch, hipStream_t st);
 int launch_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
                     void *scratch, hipStream_t st);
-// the k nearest (sls_knn.hip).  Every output may be null; out_last_key: the k-th key of every query's list
+// the k nearest (sls_knn.hip).  Every output may be null; out_last_key: the k-th key of every query's list.  k_max: the
+// caller's own limit, SLS_NN_K_MAX everywhere but in sls_normals.hip (SLS_NORMALS_NN_MAX = 2 * SLS_NN_K_MAX).  Beyond
+// SLS_NN_K_MAX the list is found in two passes: out_mean must be null and out_last_key [Mq] must be given — it carries the
+// 32nd key from the first pass to the second and holds that key afterwards.  The scratch does not depend on k:
+// nn_scratch_bytes(Mt, Mq)
 size_t nn_k_scratch_bytes(int Mt, int Mq, int k);
-int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,
-                      double *out_mean, uint64_t *out_last_key, void *scratch, hipStream_t st);
+int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, int k_max, float *out_dist2,
+                      int32_t *out_index, double *out_mean, uint64_t *out_last_key, void *scratch, hipStream_t st);
 // ---- sls_outlier.hip (the arguments are checked by the caller, sls_api.hip) ----------------------------------------
 size_t outlier_scratch_bytes(int M, int k);
 int launch_outlier_statistical(int M, const float *xyz, const float *normals, int k, double std_ratio, float *out_xyz,
                                float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st);
 int launch_outlier_radius(int M, const float *xyz, const float *normals, int nb_points, float radius, float *out_xyz,
                           float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st);
+// ---- sls_normals.hip (the arguments are checked by the caller, sls_api.hip; viewpoint3: host memory) ---------------
+size_t cloud_normals_scratch_bytes(int M, int k);
+int launch_cloud_normals(int M, const float *xyz, int k, float radius, const float *viewpoint3, float *out_normals,
+                         int32_t *out_count, float *out_eigenvalues, void *scratch, hipStream_t st);
 // ---- sls_cloud.hip (the arguments are checked by the caller, sls_api.hip) ------------------------------------------
 size_t voxel_scratch_bytes(int M);
 int launch_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,

@@ -205,7 +205,7 @@ int launch_outlier_statistical(int M, const float *xyz, const float *normals, in
                                float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st)
 {
     const OutlierScratch s = outlier_layout(M, k, scratch);
-    int rc = launch_nn_query_k(M, xyz, M, xyz, k, nullptr, nullptr, (double *)s.vals, nullptr, s.nn, st);
+    int rc = launch_nn_query_k(M, xyz, M, xyz, k, SLS_NN_K_MAX, nullptr, nullptr, (double *)s.vals, nullptr, s.nn, st);
     if (rc) return rc;
     int nblocks = (M + kOutThreads - 1) / kOutThreads;
     if (nblocks > kOutMaxBlocks) nblocks = kOutMaxBlocks;
@@ -229,7 +229,7 @@ int launch_outlier_radius(int M, const float *xyz, const float *normals, int nb_
                           float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st)
 {
     const OutlierScratch s = outlier_layout(M, nb_points + 1, scratch);
-    const int rc = launch_nn_query_k(M, xyz, M, xyz, nb_points + 1, nullptr, nullptr, nullptr, s.vals, s.nn, st);
+    const int rc = launch_nn_query_k(M, xyz, M, xyz, nb_points + 1, SLS_NN_K_MAX, nullptr, nullptr, nullptr, s.vals, s.nn, st);
     if (rc) return rc;
     return outlier_compact<true>(M, s, radius, xyz, normals, out_xyz, out_normals, out_index, out_status, st);
 }

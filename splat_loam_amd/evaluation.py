@@ -18,6 +18,7 @@ together) and the reference's error map, which it does not implement either.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import struct
 
@@ -105,6 +106,68 @@ def nearest_k(target: torch.Tensor, query: torch.Tensor, k: int, return_index: b
             _abi.check(lib.sls_nn_query_k(Mt, target.data_ptr(), Mq, query.data_ptr(), k, dist2.data_ptr(),
                                           index.data_ptr() if return_index else None, None, aligned, nbytes, st), "sls_nn_query_k")
     return dist2, index
+
+
+NORMALS_NN_MAX = 64     # SLS_NORMALS_NN_MAX (include/sls_abi.h)
+
+
+def _check_normals_args(radius, max_nn, viewpoint) -> tuple[float, int, tuple[float, float, float]]:
+    k = _check_k(max_nn, "max_nn", 1, NORMALS_NN_MAX)
+    radius = math.inf if radius is None else float(radius)
+    if not radius > 0.0 or (radius > 3.0e38 and radius != math.inf):
+        raise ValueError("radius must be a number > 0 that float32 holds, or None for the max_nn nearest at any distance")
+    view = tuple(float(v) for v in viewpoint)
+    if len(view) != 3 or not all(math.isfinite(v) for v in view):
+        raise ValueError("viewpoint must be three finite numbers")
+    return radius, k, view
+
+
+def estimate_normals(points: torch.Tensor, radius=0.5, max_nn: int = 30, viewpoint=(0.0, 0.0, 0.0), return_details: bool = False):
+    """Open3D's `estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))` followed by
+    `orient_normals_towards_camera_location(viewpoint)`, restated (include/sls_normals_math.h; Open3D is not a dependency
+    and the rule is pinned against a NumPy restatement, tests/normals_ref.py, not against Open3D itself).  The
+    neighbourhood of point i is the part of its `max_nn` nearest points, ITSELF INCLUDED, with d2 <= radius * radius (one
+    float32 product; `radius=None`: the `max_nn` nearest whatever their distance), n_i points from the exact list of
+    `nearest_k`.  With n_i >= 3 the normal is the eigenvector of the smallest eigenvalue of the float64 covariance (cyclic
+    Jacobi, + - * / and sqrt only, fixed order), flipped towards `viewpoint`; with n_i < 3 it is unit(viewpoint - p) — the
+    reference's default -unit(point) for a viewpoint at the origin — or (0, 0, 1) for a point at the viewpoint.
+
+    Returns `normals` (M,3) float32; with `return_details=True` `(normals, count (M,) int32 = n_i, eigenvalues (M,3)
+    float32, ascending, zeros where n_i < 3)`.  1 <= max_nn <= 64.  One native call (sls_cloud_normals), no host read, no
+    float atomics: the same cloud gives the same bits on every run, and the bits of the header compiled for the host.
+    Device float32 (M,3) only; the coordinates must be finite (not checked; every access stays inside the buffers)."""
+    res = _estimate_normals(points, radius, max_nn, viewpoint, return_details, False)
+    return res if return_details else res[0]
+
+
+def _estimate_normals(points, radius, max_nn, viewpoint, details: bool, lists: bool):
+    """estimate_normals' call: (normals,), + (count, eigenvalues) with `details`, + (dist2 (M,k), index (M,k)) with `lists`
+    — every point's neighbour list as `nearest_k` returns it, for max_nn up to 64, copied out of the scratch, where
+    sls_cloud_normals leaves the rows (include/sls_abi.h).  For tests and tools/normals_bench.py."""
+    points = _cloud(points, "points")
+    radius, k, view = _check_normals_args(radius, max_nn, viewpoint)
+    M = int(points.shape[0])
+    lib = _abi.lib()
+    dev = points.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        normals = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        count = torch.empty((M,), dtype=torch.int32, device=dev) if details else None
+        eig = torch.empty((M, 3), dtype=torch.float32, device=dev) if details else None
+        rows = (torch.empty((M, k), dtype=torch.float32, device=dev), torch.empty((M, k), dtype=torch.int32, device=dev)) if lists else ()
+        if M:
+            buf, aligned, nbytes = _scratch_bytes(lib.sls_cloud_normals_scratch_bytes(M, k), dev)
+            view3 = (ctypes.c_float * 3)(*view)                   # host memory, read before the call returns
+            _abi.check(lib.sls_cloud_normals(M, points.data_ptr(), k, radius, ctypes.addressof(view3), normals.data_ptr(),
+                                             count.data_ptr() if details else None, eig.data_ptr() if details else None,
+                                             aligned, nbytes, st), "sls_cloud_normals")
+            if lists:
+                up = lambda v: (v + 255) & ~255
+                a = aligned - buf.data_ptr() + up(int(lib.sls_nn_scratch_bytes(M, M)))
+                b = a + up(4 * M * k)
+                rows = (buf[a:a + 4 * M * k].view(torch.float32).view(M, k).clone(),
+                        buf[b:b + 4 * M * k].view(torch.int32).view(M, k).clone())
+    return (normals,) + ((count, eig) if details else ()) + tuple(rows)
 
 
 def _normals(normals, points: torch.Tensor):

@@ -95,12 +95,27 @@ class DeviceProjector:
 
         proj = DeviceProjector(H, W, depth_min, depth_max)
         out = proj.scan_to_images(cloud_cuda)     # dict like scan_to_images(), device tensors; K (3,3) on device
+
+    normals="radial" (the default) writes the reference's default normals, -unit(point).  normals="pca" is the
+    reference's `preprocessing.enable_normal_estimation` (scene/preprocessing.py:85-118): the points inside the depth
+    window (depth_min, depth_max] alone form a cloud, `evaluation.estimate_normals(radius=normal_radius,
+    max_nn=normal_max_nn, viewpoint=origin)` gives them normals (a point with fewer than three neighbours within the
+    radius keeps -unit(point)), and the normals image is gathered from those through `lut`; empty pixels stay 0.  lut,
+    range_image and valid are the "radial" ones.  Selecting the in-window points is a boolean selection whose size the
+    host must learn before the next launch can be sized, so "pca" costs ONE host synchronisation per scan and gives up
+    the "no host synchronisation" property above; everything else stays on the device.
     """
 
     def __init__(self, H: int, W: int, depth_min: float = 0.5, depth_max: float = 100.0,
-                 full_azimuth_threshold_deg: float = 300.0, device="cuda:0"):
+                 full_azimuth_threshold_deg: float = 300.0, device="cuda:0", normals: str = "radial",
+                 normal_radius: float = 0.5, normal_max_nn: int = 50):
         import torch
-        from . import _abi
+        from . import _abi, evaluation
+        if normals not in ("radial", "pca"):
+            raise ValueError('normals must be "radial" or "pca"')
+        self.normals = normals
+        if normals == "pca":                                    # checked before any work
+            self.normal_radius, self.normal_max_nn, _ = evaluation._check_normals_args(normal_radius, normal_max_nn, (0.0, 0.0, 0.0))
         self.H, self.W = int(H), int(W)
         self.depth_min, self.depth_max = float(depth_min), float(depth_max)
         self.thr = float(full_azimuth_threshold_deg)
@@ -155,8 +170,28 @@ class DeviceProjector:
                                                     self._stream()), "sls_projector_project")
         return lut, rng, nrm, valid.view(torch.bool)
 
+    def pca_normals_image(self, cloud, lut, valid):
+        """normals_image (H,W,3) of normals="pca" for a projected scan: estimate_normals over the in-window points,
+        scattered back to the scan's rows and gathered through lut; 0 at empty pixels.  One host synchronisation."""
+        import torch
+        from . import evaluation
+        cloud = self._cloud(cloud)
+        x, y, z = cloud[:, 0], cloud[:, 1], cloud[:, 2]
+        rng = (x * x + y * y + z * z).sqrt()                    # float32, the projection kernel's own expression
+        lo, hi = torch.tensor([self.depth_min, self.depth_max], dtype=torch.float32, device=cloud.device)
+        inside = (rng > lo) & (rng <= hi)                       # (float32 against float32, as there)
+        rows = torch.nonzero(inside).squeeze(1)                 # the host synchronisation: the selection's size
+        radius = None if math.isinf(self.normal_radius) else self.normal_radius
+        est = evaluation.estimate_normals(cloud[rows], radius, self.normal_max_nn, (0.0, 0.0, 0.0))
+        per_point = torch.zeros_like(cloud)
+        per_point[rows] = est
+        image = per_point[lut.long().clamp_(min=0).view(-1)].view(self.H, self.W, 3)
+        return torch.where(valid.unsqueeze(-1), image, torch.zeros_like(image))
+
     def scan_to_images(self, cloud):
         intr = self.intrinsics(cloud)
         lut, rng, nrm, valid = self.project(cloud, intr)
+        if self.normals == "pca":
+            nrm = self.pca_normals_image(cloud, lut, valid)
         return dict(K=intr[:9].view(3, 3), vfov=intr[9], hfov=intr[10], range_image=rng, normals_image=nrm,
                     valid=valid, lut=lut)
