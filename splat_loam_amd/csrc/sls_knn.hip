@@ -7,33 +7,21 @@
 //   2. wave64 LSD radix sort of (code, index) — the sorter of sls_sort.hip;
 //   3. points gathered in curve order (float4: xyz + original index) and
 //      axis-aligned boxes over runs of 256 consecutive points;
-//   4. one wave per 64 consecutive points, one lane per point: the own box first for a
-//      tight bound, then boxes / their 32-point sub-boxes whose gap to the wave's points
-//      beats the wave's worst third-best are listed (64 tests per step), and each listed
-//      sub-box is staged through LDS if it can still improve some lane's own bound.
+//   4. one wave per 64 consecutive points, one lane per point: the own box first for a tight bound, then the sweep
+//      (knn_sweep below) over the other boxes; the two-cloud searches (sls_nn_query, sls_nn_query_k) run it too.
 // Squared distances use the fixed expression fma(dz,dz,fma(dy,dy,dx*dx)), so
 // the result is reproducible bit for bit by a CPU brute force.
 #include <float.h>
 
-#include "sls_launch.hpp"
+#include "sls_geom.hpp"
 #include "../../include/sls_nn_math.h"
 #include "../../include/sls_outlier_math.h"
 
 namespace sls {
 
 constexpr int kKnnBox = 256;
-constexpr int kKnnSub = 32;    // points per sub-box (8 per box)
-
-__device__ __forceinline__ uint32_t f2ord(float f)
-{   // monotone float -> uint mapping
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o)
-{
-    const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-    return __uint_as_float(u);
-}
+constexpr int kKnnSub = 32;    // points per sub-box
+constexpr int kKnnSubs = kKnnBox / kKnnSub;     // 8 sub-boxes per box
 
 __global__ void knn_init_bbox_kernel(uint32_t *bbox, uint32_t M, uint32_t M2)
 {
@@ -124,83 +112,88 @@ __global__ __launch_bounds__(256) void knn_morton_kernel(int M, const float *__r
     vals[i] = (uint32_t)i;
 }
 
+// a bounding box (mn, mx) grown to hold another one
+__device__ __forceinline__ void box_join(float4 &mn, float4 &mx, const float4 omn, const float4 omx)
+{
+    mn = make_float4(fminf(mn.x, omn.x), fminf(mn.y, omn.y), fminf(mn.z, omn.z), 0.0f);
+    mx = make_float4(fmaxf(mx.x, omx.x), fmaxf(mx.y, omx.y), fmaxf(mx.z, omx.z), 0.0f);
+}
+
+// ... by the box of the lane `off` away: one step of a butterfly
+__device__ __forceinline__ void box_merge(float4 &mn, float4 &mx, int off)
+{
+    box_join(mn, mx, make_float4(__shfl_xor(mn.x, off, 64), __shfl_xor(mn.y, off, 64), __shfl_xor(mn.z, off, 64), 0.0f),
+             make_float4(__shfl_xor(mx.x, off, 64), __shfl_xor(mx.y, off, 64), __shfl_xor(mx.z, off, 64), 0.0f));
+}
+
 __global__ __launch_bounds__(256) void knn_gather_boxes_kernel(int M, const float *__restrict__ xyz,
                                                                const uint32_t *__restrict__ sorted_idx,
                                                                float4 *__restrict__ pts, float4 *__restrict__ boxes,
                                                                float4 *__restrict__ subboxes)
 {
     // one block per box of kKnnBox == blockDim.x points
-    __shared__ float s_mn[4][3], s_mx[4][3];
+    __shared__ float4 s_mn[4], s_mx[4];
     const int j = blockIdx.x * kKnnBox + threadIdx.x;
-    float mn[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, mx[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+    float4 mn = make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f), mx = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
     if (j < M) {
         const uint32_t i = sorted_idx[j];
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        pts[j] = make_float4(x, y, z, __uint_as_float(i));
-        mn[0] = mx[0] = x; mn[1] = mx[1] = y; mn[2] = mx[2] = z;
+        mn = mx = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
+        pts[j] = make_float4(mn.x, mn.y, mn.z, __uint_as_float(i));
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], off, 64));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], off, 64));
-        }
-    }
+    for (int off = 16; off > 0; off >>= 1) box_merge(mn, mx, off);
     if ((threadIdx.x & (kKnnSub - 1)) == 0) {   // tight boxes over runs of 32 points (empty run: min > max)
-        const size_t sb = (size_t)blockIdx.x * (kKnnBox / kKnnSub) + threadIdx.x / kKnnSub;
-        subboxes[2 * sb] = make_float4(mn[0], mn[1], mn[2], 0.0f);
-        subboxes[2 * sb + 1] = make_float4(mx[0], mx[1], mx[2], 0.0f);
+        const size_t sb = (size_t)blockIdx.x * kKnnSubs + threadIdx.x / kKnnSub;
+        subboxes[2 * sb] = mn;
+        subboxes[2 * sb + 1] = mx;
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        mn[k] = fminf(mn[k], __shfl_xor(mn[k], 32, 64));
-        mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], 32, 64));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 3; ++k) { s_mn[wave][k] = mn[k]; s_mx[wave][k] = mx[k]; }
+    box_merge(mn, mx, 32);
+    if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6] = mn; s_mx[threadIdx.x >> 6] = mx; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 0; k < 3; ++k)
-            for (int w = 1; w < 4; ++w) { s_mn[0][k] = fminf(s_mn[0][k], s_mn[w][k]); s_mx[0][k] = fmaxf(s_mx[0][k], s_mx[w][k]); }
-        boxes[2 * blockIdx.x] = make_float4(s_mn[0][0], s_mn[0][1], s_mn[0][2], 0.0f);
-        boxes[2 * blockIdx.x + 1] = make_float4(s_mx[0][0], s_mx[0][1], s_mx[0][2], 0.0f);
+    if (threadIdx.x == 0) {                     // (its own box is wave 0's)
+        for (int w = 1; w < 4; ++w) box_join(mn, mx, s_mn[w], s_mx[w]);
+        boxes[2 * blockIdx.x] = mn;
+        boxes[2 * blockIdx.x + 1] = mx;
     }
 }
 
-__device__ __forceinline__ void best3_update(float d2, float &b0, float &b1, float &b2)
-{   // insertion into the sorted triple b0 <= b1 <= b2, branch-free (nested ifs end up as an indexed
-    // stack array here: scratch traffic in the innermost loop)
-    const float u0 = fmaxf(b0, d2);
-    b0 = fminf(b0, d2);
-    const float u1 = fmaxf(b1, u0);
-    b1 = fminf(b1, u0);
-    b2 = fminf(b2, u1);
-}
+// ---------------------------------------------------------------------------------------------------------------------
+// The sweep: the ONE exact spatial search of all three query kernels.  One WAVE per 64 curve-consecutive queries (lane =
+// query), the workgroup IS the wave: no workgroup waits on another, every loop is bounded by the box count.  A kernel sets
+// up its queries and a SEARCH (what a lane keeps of the targets it is shown), scans one box for a first bound (its own, or
+// the one a binary search names) and calls knn_sweep for the others:
+//   1. chunks of 64 boxes (256 points each), outwards from the scanned box, so the bounds shrink early;
+//   2. lane = box: a box is listed if its gap to the wave's bounding box beats the wave's worst bound AND its gap to the box
+//      of one of the 8 groups of 8 consecutive queries beats that group's worst bound (one bound for all 64 would be ruined
+//      by a single isolated query, or by a sparse stretch of the curve whose box swallows the dense regions in between);
+//   3. the listed boxes' sub-boxes (32 points; even a Hilbert run of 256 is loose) pass the same test, 8 boxes per step,
+//      lane = (box slot, sub-box), into a wave-private LDS list;
+//   4. 64 listed sub-boxes at a time, lane = candidate: the point-to-box gap against EACH query's own bound (broadcast
+//      with v_readlane); a run that can still matter to one goes through LDS to all lanes, the next one fetched meanwhile.
+// A search supplies bound(), the squared distance beyond which a target cannot matter to the lane (+inf while anything
+// would); scan(s_run), which shows it 32 staged targets; pad(pts, r0), the point that fills a short last run from r0 on.
+// Exact whatever the search, because
+//   * every gap test is `gap * 0.99999f <= bound`: equality passes, a gap never exceeds the distance to a point inside the
+//     box (float subtraction, fma and max are monotone) and bounds only shrink, so a target that could enter or tie with
+//     what a lane holds — an equally near one of lower index in another box — is always shown to it;
+//   * sweep_chunk permutes the chunks and a run is listed once: no target is shown twice, which a search that COUNTS what
+//     it meets (the list) needs, and one shown for another lane's sake lies beyond this lane's bound;
+//   * each pad() changes nothing, for the reason given there.
+// ---------------------------------------------------------------------------------------------------------------------
+struct KnnIndex {           // a cloud in curve order (knn_build)
+    int M, nboxes;
+    const float4 *__restrict__ pts, *__restrict__ boxes, *__restrict__ subboxes;
+    __device__ __forceinline__ int nsub() const { return (M + kKnnSub - 1) / kKnnSub; }
+};
 
-// One WAVE per 64 curve-consecutive query points (lane = point), no block barriers: every wave runs
-// its own search at its own pace and 8 of them share a SIMD.
-//   a. the 8 runs of 32 points of the own box (256 points): a tight third-best b2 per lane;
-//   b. boxes (256 points) are tested 64 at a time, lane = box: gap between the box and the bounding
-//      box of each group of 8 consecutive query points against that group's worst b2 (isolated
-//      points and sparse stretches of the curve must not widen everybody's search); for the survivors the
-//      8 sub-boxes (32 points, much tighter: even a Hilbert run of 256 is loose) are tested the same
-//      way, 8 boxes per step; surviving sub-boxes go to a wave-private LDS list.  Chunks of 64 boxes
-//      are visited outwards from the own box, so b2 shrinks early;
-//   c. every listed sub-box is re-tested per lane against the lane's own b2 (point-to-box gap);
-//      if any lane can still improve, its 32 points go through LDS (broadcast reads) to all lanes.
-// All bounds are conservative (relative slack 1e-5), so the result is the exact 3-NN.
-template <bool SELF>
-__device__ __forceinline__ void knn_scan32(const float4 *s_run, const float4 me, int self, float &b0, float &b1, float &b2)
+struct SweepLds {           // wave-private: 2 816 bytes
+    float4 run[kKnnSub];
+    uint32_t box[64], sub[64 * kKnnSubs];
+};
+
+__device__ __forceinline__ float rl(float v, int k)
 {
-#pragma unroll 8
-    for (int k = 0; k < kKnnSub; ++k) {
-        const float4 p = s_run[k];
-        const float dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
-        const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-        best3_update((SELF && k == self) ? FLT_MAX : d2, b0, b1, b2);
-    }
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
 }
 
 __device__ __forceinline__ float box_gap2(const float4 amn, const float4 amx, const float4 bmn, const float4 bmx)
@@ -211,23 +204,186 @@ __device__ __forceinline__ float box_gap2(const float4 amn, const float4 amx, co
     return fmaf(gz, gz, fmaf(gy, gy, gx * gx));
 }
 
-__device__ __forceinline__ float wave_max(float v)
+// the conservative test of every level: relative slack 1e-5, and equality passes
+__device__ __forceinline__ bool within(float gap2, float bound) { return gap2 * 0.99999f <= bound; }
+
+// bounding boxes of the 8 groups of 8 consecutive queries (dead lanes: empty), valid in every lane of the group
+__device__ __forceinline__ void group_boxes(bool live, const float4 me, float4 &gmn, float4 &gmx)
 {
+    gmn = live ? me : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f);
+    gmx = live ? me : make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
+    for (int off = 1; off < 8; off <<= 1) box_merge(gmn, gmx, off);
 }
+
+// chunks outwards from c0: c0, c0+1, c0-1, c0+2, ... while both sides exist, then the rest of the longer side
+__device__ __forceinline__ int sweep_chunk(int it, int c0, int nchunks)
+{
+    const int near = min(c0, nchunks - 1 - c0);            // both sides available for 2*near steps
+    if (it <= 2 * near) return c0 + ((it & 1) ? (it + 1) / 2 : -(it / 2));
+    return (c0 < nchunks - 1 - c0) ? it : nchunks - 1 - it;
+}
+
+// Ballot compaction: the lanes with `keep` write v to dst in lane order; the count of them.
+__device__ __forceinline__ int wave_compact(bool keep, uint32_t v, uint32_t *dst)
+{
+    const uint64_t m = __ballot(keep);
+    if (keep) dst[__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = v;
+    return __builtin_popcountll(m);
+}
+
+// point `lane & 31` of run sb for the LDS stage; LOW: loaded by lanes 0..31 alone, the ones that stage it
+template <bool LOW, class Search>
+__device__ __forceinline__ float4 run_point(const KnnIndex &ix, int sb, const Search &s)
+{
+    const int r0 = sb * kKnnSub, i = r0 + ((int)threadIdx.x & (kKnnSub - 1));
+    if (LOW && threadIdx.x >= kKnnSub) return make_float4(0, 0, 0, 0);
+    return i < ix.M ? ix.pts[i] : s.pad(ix.pts, r0);
+}
+
+// a run's 32 points -> LDS, for every lane to scan
+__device__ __forceinline__ void stage(SweepLds &lds, const float4 p)
+{
+    __builtin_amdgcn_wave_barrier();
+    if (threadIdx.x < kKnnSub) lds.run[threadIdx.x] = p;
+    __syncthreads();
+}
+
+template <class Search>
+__device__ __forceinline__ void knn_sweep(const KnnIndex &ix, const int start_box, const bool live, const float4 me,
+                                          const float4 wmn, const float4 wmx, const float4 gmn, const float4 gmx, Search &s,
+                                          SweepLds &lds)
+{
+    const int lane = threadIdx.x, nboxes = ix.nboxes, nsub = ix.nsub();   // start_box: scanned by the caller, skipped here
+    const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;
+    for (int it = 0; it < nchunks; ++it) {
+        // the worst bound of my group of 8, and of the wave
+        float gB = live ? s.bound() : 0.0f;
+        gB = fmaxf(gB, __shfl_xor(gB, 1, 64)); gB = fmaxf(gB, __shfl_xor(gB, 2, 64)); gB = fmaxf(gB, __shfl_xor(gB, 4, 64));
+        float B2 = gB;
+#pragma unroll
+        for (int off = 8; off < 64; off <<= 1) B2 = fmaxf(B2, __shfl_xor(B2, off, 64));
+        auto reaches = [&](const float4 bmn, const float4 bmx) -> bool {
+            if (!within(box_gap2(wmn, wmx, bmn, bmx), B2)) return false;
+            bool r = false;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const float4 mn = make_float4(rl(gmn.x, 8 * g), rl(gmn.y, 8 * g), rl(gmn.z, 8 * g), 0.0f);
+                const float4 mx = make_float4(rl(gmx.x, 8 * g), rl(gmx.y, 8 * g), rl(gmx.z, 8 * g), 0.0f);
+                r = r || within(box_gap2(mn, mx, bmn, bmx), rl(gB, 8 * g));
+            }
+            return r;
+        };
+        // 2. the chunk's boxes, lane = box
+        const int b = sweep_chunk(it, c0, nchunks) * 64 + lane;
+        bool c = false;
+        if (b < nboxes && b != start_box) c = reaches(ix.boxes[2 * b], ix.boxes[2 * b + 1]);
+        __builtin_amdgcn_wave_barrier();
+        const int nb = wave_compact(c, (uint32_t)b, lds.box);
+        if (nb == 0) continue;
+        __syncthreads();
+        // 3. their sub-boxes, 8 boxes per step
+        int ns = 0;                                     // <= 8 * nb <= 512 = the size of lds.sub
+        for (int g = 0; g < nb; g += 8) {
+            const int slot = g + (lane >> 3);
+            bool cs = false;
+            uint32_t sb = 0;
+            if (slot < nb) {
+                sb = lds.box[slot] * kKnnSubs + (uint32_t)(lane & 7);
+                if ((int)sb < nsub) cs = reaches(ix.subboxes[2 * (size_t)sb], ix.subboxes[2 * (size_t)sb + 1]);
+            }
+            ns += wave_compact(cs, sb, lds.sub + ns);
+        }
+        __syncthreads();
+        // 4. the listed runs, 64 at a time
+        for (int base = 0; base < ns; base += 64) {
+            const int nk = min(64, ns - base);
+            const uint32_t sbl = lds.sub[base + min(lane, nk - 1)];
+            const float4 mnl = ix.subboxes[2 * (size_t)sbl], mxl = ix.subboxes[2 * (size_t)sbl + 1];
+            const float qb2 = live ? s.bound() : -1.0f;
+            bool need = false;
+            for (int qi = 0; qi < 64; ++qi) {
+                const float4 qp = make_float4(rl(me.x, qi), rl(me.y, qi), rl(me.z, qi), 0.0f);
+                need = need || within(box_gap2(qp, qp, mnl, mxl), rl(qb2, qi));
+            }
+            uint64_t todo = __ballot(need && lane < nk);
+            float4 pre = make_float4(0, 0, 0, 0);
+            if (todo) pre = run_point<false>(ix, __builtin_amdgcn_readlane((int)sbl, __builtin_ctzll(todo)), s);
+            while (todo) {
+                todo &= todo - 1;
+                const float4 cur = pre;
+                if (todo) pre = run_point<false>(ix, __builtin_amdgcn_readlane((int)sbl, __builtin_ctzll(todo)), s);
+                stage(lds, cur);
+                s.scan(lds.run);
+            }
+        }
+    }
+}
+
+// The body of both nn_* kernels behind their set-up, the queries being ANOTHER cloud's: the start box is the one holding
+// the first target whose code is not below the wave's first code; its runs give a first bound; the wave's box is a
+// reduction over its own queries.
+template <class Search>
+__device__ __forceinline__ void nn_search(const KnnIndex &ix, const uint32_t *__restrict__ tkeys, const uint32_t code,
+                                          const bool live, const float4 me, Search &s, SweepLds &lds)
+{
+    int lo = 0, hi = ix.M;                              // lower bound in tkeys[0, M): at most 31 halvings
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (tkeys[mid] < code) lo = mid + 1; else hi = mid;
+    }
+    const int start_box = __builtin_amdgcn_readfirstlane(min(lo, ix.M - 1) / kKnnBox);
+    for (int t = 0; t < kKnnSubs; ++t) {
+        const int sb = start_box * kKnnSubs + t;
+        if (sb >= ix.nsub()) break;
+        stage(lds, run_point<true>(ix, sb, s));
+        s.scan(lds.run);
+    }
+    float4 gmn, gmx;
+    group_boxes(live, me, gmn, gmx);
+    float4 wmn = gmn, wmx = gmx;
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) box_merge(wmn, wmx, off);
+    knn_sweep(ix, start_box, live, me, wmn, wmx, gmn, gmx, s, lds);
+}
+
+// sls_knn_dist2: the three smallest squared distances to OTHER points of the same cloud
+__device__ __forceinline__ void best3_update(float d2, float &b0, float &b1, float &b2)
+{   // insertion into the sorted triple b0 <= b1 <= b2, branch-free (nested ifs end up as an indexed
+    // stack array here: scratch traffic in the innermost loop)
+    const float u0 = fmaxf(b0, d2);
+    b0 = fminf(b0, d2);
+    const float u1 = fmaxf(b1, u0);
+    b1 = fminf(b1, u0);
+    b2 = fminf(b2, u1);
+}
+
+struct Best3Search {
+    const float4 me;
+    float b0, b1, b2;
+    __device__ __forceinline__ float bound() const { return b2; }
+    // a far point: its d2 overflows to +inf, which lowers no entry of the triple
+    __device__ __forceinline__ float4 pad(const float4 *, int) const { return make_float4(1.0e30f, 1.0e30f, 1.0e30f, 0.0f); }
+    // SELF: the lane's own point, at s_run[self], is left out
+    template <bool SELF = false>
+    __device__ __forceinline__ void scan(const float4 *s_run, int self = -1)
+    {
+#pragma unroll 8
+        for (int k = 0; k < kKnnSub; ++k) {
+            const float4 p = s_run[k];
+            const float d2 = sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z);
+            best3_update((SELF && k == self) ? FLT_MAX : d2, b0, b1, b2);
+        }
+    }
+};
 
 __global__ __launch_bounds__(64) void knn_query_kernel(int M, int nboxes, const float4 *__restrict__ pts,
                                                        const float4 *__restrict__ boxes,
                                                        const float4 *__restrict__ subboxes, float *__restrict__ out, uint32_t Mq)
 {
-    constexpr int kSubs = kKnnBox / kKnnSub;            // 8 sub-boxes per box
-    __shared__ float4 s_run[kKnnSub];                   // wave-private: the workgroup IS one wave
-    __shared__ uint32_t s_box[64];
-    __shared__ uint32_t s_sub[64 * kSubs];
-    const int lane = threadIdx.x;
-    const int q = blockIdx.x * 64 + lane;
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { M, nboxes, pts, boxes, subboxes };
+    const int q = blockIdx.x * 64 + threadIdx.x;
     const float4 me = pts[q < M ? q : M - 1];
     // Mq < M (sls_knn_dist2_first): only the points whose ORIGINAL index is below Mq are queries — Mapper.densify asks
     // for the new surfels' distances among new + existing centres (slam/mapper.py:109-117) and drops the rest.  A wave
@@ -235,129 +391,24 @@ __global__ __launch_bounds__(64) void knn_query_kernel(int M, int nboxes, const 
     const bool live = q < M && __float_as_uint(me.w) < Mq;
     if (!__ballot(live)) return;
     const int own_box = (blockIdx.x * 64) / kKnnBox, own_sub0 = (blockIdx.x * 64) / kKnnSub;   // my runs: own_sub0, +1
-    const int nsub = (M + kKnnSub - 1) / kKnnSub;
-    float b0 = FLT_MAX, b1 = FLT_MAX, b2 = FLT_MAX;
+    const int nsub = ix.nsub();
+    Best3Search s = { me, FLT_MAX, FLT_MAX, FLT_MAX };
 
-    auto stage = [&](int sb) {      // 32 points of run sb -> LDS (far-away sentinels beyond M)
-        __builtin_amdgcn_wave_barrier();
-        if (lane < kKnnSub) {
-            const int k = sb * kKnnSub + lane;
-            s_run[lane] = k < M ? pts[k] : make_float4(1.0e30f, 1.0e30f, 1.0e30f, 0.0f);
-        }
-        __syncthreads();
-    };
-
-    // a. own box: my two runs first, then the other six
-    for (int t = 0; t < kSubs; ++t) {
-        const int sb = own_box * kSubs + ((t + (own_sub0 % kSubs)) % kSubs);
+    // the own box for a first bound: my two runs, then the other six; every lane leaves itself out
+    for (int t = 0; t < kKnnSubs; ++t) {
+        const int sb = own_box * kKnnSubs + ((t + (own_sub0 % kKnnSubs)) % kKnnSubs);
         if (sb >= nsub) continue;
-        stage(sb);
-        const int self = (live && (q / kKnnSub) == sb) ? (q % kKnnSub) : -1;
-        knn_scan32<true>(s_run, me, self, b0, b1, b2);
+        stage(lds, run_point<true>(ix, sb, s));
+        s.scan<true>(lds.run, (live && (q / kKnnSub) == sb) ? (q % kKnnSub) : -1);
     }
 
-    // bounding box of the wave's own points
+    // the wave's bounding box is that of its two runs (dead and non-query lanes included), the groups' are of live lanes
     float4 wmn = subboxes[2 * (size_t)own_sub0], wmx = subboxes[2 * (size_t)own_sub0 + 1];
-    if (own_sub0 + 1 < nsub) {
-        const float4 mn1 = subboxes[2 * (size_t)(own_sub0 + 1)], mx1 = subboxes[2 * (size_t)(own_sub0 + 1) + 1];
-        wmn = make_float4(fminf(wmn.x, mn1.x), fminf(wmn.y, mn1.y), fminf(wmn.z, mn1.z), 0.0f);
-        wmx = make_float4(fmaxf(wmx.x, mx1.x), fmaxf(wmx.y, mx1.y), fmaxf(wmx.z, mx1.z), 0.0f);
-    }
-
-    // bounding boxes of the 8 groups of 8 consecutive points (dead lanes: empty)
-    auto rl = [](float v, int k) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k)); };
-    float4 gmn = live ? me : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f);
-    float4 gmx = live ? me : make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
-#pragma unroll
-    for (int off = 1; off < 8; off <<= 1) {
-        gmn.x = fminf(gmn.x, __shfl_xor(gmn.x, off, 64)); gmn.y = fminf(gmn.y, __shfl_xor(gmn.y, off, 64));
-        gmn.z = fminf(gmn.z, __shfl_xor(gmn.z, off, 64));
-        gmx.x = fmaxf(gmx.x, __shfl_xor(gmx.x, off, 64)); gmx.y = fmaxf(gmx.y, __shfl_xor(gmx.y, off, 64));
-        gmx.z = fmaxf(gmx.z, __shfl_xor(gmx.z, off, 64));
-    }
-    const int nchunks = (nboxes + 63) / 64, c0 = own_box / 64;
-    for (int it = 0; it < nchunks; ++it) {
-        // chunks outwards from the own one: c0, c0+1, c0-1, c0+2, ... (those inside [0, nchunks))
-        int chunk;
-        {
-            const int near = min(c0, nchunks - 1 - c0);            // both sides available for 2*near steps
-            if (it <= 2 * near) chunk = c0 + ((it & 1) ? (it + 1) / 2 : -(it / 2));
-            else chunk = (c0 < nchunks - 1 - c0) ? it : nchunks - 1 - it;
-        }
-        // Which boxes can reach the wave?  One bound for all 64 points would be ruined by a single isolated
-        // point (its b2 can be 1000 x the others') or by a sparse stretch of the curve (a bounding box that
-        // swallows the dense regions in between), so the wave is split into 8 groups of 8 consecutive points:
-        // a box is a candidate if its gap to a group's bounding box beats that group's worst b2.
-        float gB = live ? b2 : 0.0f;
-        gB = fmaxf(gB, __shfl_xor(gB, 1, 64)); gB = fmaxf(gB, __shfl_xor(gB, 2, 64)); gB = fmaxf(gB, __shfl_xor(gB, 4, 64));
-        const float B2 = wave_max(gB);
-        auto reaches = [&](const float4 bmn, const float4 bmx) -> bool {
-            if (!(box_gap2(wmn, wmx, bmn, bmx) * 0.99999f <= B2)) return false;
-            bool r = false;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const float4 mn = make_float4(rl(gmn.x, 8 * g), rl(gmn.y, 8 * g), rl(gmn.z, 8 * g), 0.0f);
-                const float4 mx = make_float4(rl(gmx.x, 8 * g), rl(gmx.y, 8 * g), rl(gmx.z, 8 * g), 0.0f);
-                r = r || (box_gap2(mn, mx, bmn, bmx) * 0.99999f <= rl(gB, 8 * g));
-            }
-            return r;
-        };
-        const int b = chunk * 64 + lane;
-        bool c = false;
-        if (b < nboxes && b != own_box) c = reaches(boxes[2 * b], boxes[2 * b + 1]);
-        const uint64_t cm = __ballot(c);
-        const int nb = __builtin_popcountll(cm);
-        if (nb == 0) continue;
-        __builtin_amdgcn_wave_barrier();
-        if (c) s_box[__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u))] = (uint32_t)b;
-        __syncthreads();
-        // their sub-boxes, 8 boxes per step: lane = (box slot, sub-box)
-        int ns = 0;
-        for (int g = 0; g < nb; g += 8) {
-            const int slot = g + (lane >> 3);
-            bool cs = false;
-            uint32_t sb = 0;
-            if (slot < nb) {
-                sb = s_box[slot] * kSubs + (uint32_t)(lane & 7);
-                if ((int)sb < nsub) cs = reaches(subboxes[2 * (size_t)sb], subboxes[2 * (size_t)sb + 1]);
-            }
-            const uint64_t sm = __ballot(cs);
-            if (cs) s_sub[ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u))] = sb;
-            ns += __builtin_popcountll(sm);
-        }
-        __syncthreads();
-        // c. 64 listed sub-boxes at a time, lane = candidate: the exact test — can it improve ANY of the 64
-        //    query points? — runs for all 64 candidates at once (the queries are broadcast with v_readlane);
-        //    the survivors are scanned one after the other, the next one's points are fetched meanwhile.
-        for (int base = 0; base < ns; base += 64) {
-            const int nk = min(64, ns - base);
-            const uint32_t sbl = s_sub[base + min(lane, nk - 1)];
-            const float4 mnl = subboxes[2 * (size_t)sbl], mxl = subboxes[2 * (size_t)sbl + 1];
-            const float qb2 = live ? b2 : -1.0f;
-            bool need = false;
-            for (int qi = 0; qi < 64; ++qi) {
-                const float4 qp = make_float4(rl(me.x, qi), rl(me.y, qi), rl(me.z, qi), 0.0f);
-                need = need || (box_gap2(qp, qp, mnl, mxl) * 0.99999f <= rl(qb2, qi));
-            }
-            uint64_t todo = __ballot(need && lane < nk);
-            auto fetch = [&](int k) -> float4 {     // lanes 0..31: the points of candidate k (sentinels beyond M)
-                const int i = __builtin_amdgcn_readlane((int)sbl, k) * kKnnSub + (lane & (kKnnSub - 1));
-                return i < M ? pts[i] : make_float4(1.0e30f, 1.0e30f, 1.0e30f, 0.0f);
-            };
-            float4 pre = make_float4(0, 0, 0, 0);
-            if (todo) pre = fetch(__builtin_ctzll(todo));
-            while (todo) {
-                todo &= todo - 1;
-                const float4 cur = pre;
-                if (todo) pre = fetch(__builtin_ctzll(todo));
-                __builtin_amdgcn_wave_barrier();
-                if (lane < kKnnSub) s_run[lane] = cur;
-                __syncthreads();
-                knn_scan32<false>(s_run, me, -1, b0, b1, b2);    // (a lane that did not need it cannot be changed by it)
-            }
-        }
-    }
-    if (live) out[__float_as_uint(me.w)] = (b0 + b1 + b2) / 3.0f;
+    if (own_sub0 + 1 < nsub) box_join(wmn, wmx, subboxes[2 * (size_t)own_sub0 + 2], subboxes[2 * (size_t)own_sub0 + 3]);
+    float4 gmn, gmx;
+    group_boxes(live, me, gmn, gmx);
+    knn_sweep(ix, own_box, live, me, wmn, wmx, gmn, gmx, s, lds);
+    if (live) out[__float_as_uint(me.w)] = (s.b0 + s.b1 + s.b2) / 3.0f;
 }
 
 // scratch layout (all 256-byte aligned)
@@ -370,29 +421,27 @@ struct KnnScratch {
     size_t sort_bytes, total;
 };
 
-static KnnScratch knn_layout(int M, void *base)
+// sort_items: what the sorter's scratch, the last piece, is sized for
+static KnnScratch knn_layout(int M, void *base, int sort_items)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nboxes = (size_t)((M + kKnnBox - 1) / kKnnBox);
+    Arena a(base);
     KnnScratch s;
-    char *p = (char *)base;
-    size_t off = 0;
-    const int nboxes = (M + kKnnBox - 1) / kKnnBox;
-    s.bbox = (uint32_t *)(p + off); off += al(8 * sizeof(uint32_t));
-    s.keys = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)M);
-    s.keys_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)M);
-    s.vals = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)M);
-    s.vals_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)M);
-    s.pts = (float4 *)(p + off); off += al(sizeof(float4) * (size_t)M);
-    s.boxes = (float4 *)(p + off); off += al(sizeof(float4) * 2 * (size_t)nboxes);
-    s.subboxes = (float4 *)(p + off); off += al(sizeof(float4) * 2 * (size_t)nboxes * (kKnnBox / kKnnSub));
-    s.sort = (void *)(p + off);
-    s.sort_bytes = sort_scratch_bytes((uint64_t)M);
-    off += al(s.sort_bytes);
-    s.total = off;
+    s.bbox = a.take<uint32_t>(8);
+    s.keys = a.take<uint32_t>((size_t)M);
+    s.keys_tmp = a.take<uint32_t>((size_t)M);
+    s.vals = a.take<uint32_t>((size_t)M);
+    s.vals_tmp = a.take<uint32_t>((size_t)M);
+    s.pts = a.take<float4>((size_t)M);
+    s.boxes = a.take<float4>(2 * nboxes);
+    s.subboxes = a.take<float4>(2 * nboxes * kKnnSubs);
+    s.sort_bytes = sort_scratch_bytes((uint64_t)sort_items);
+    s.sort = a.take<char>(s.sort_bytes);
+    s.total = a.off;
     return s;
 }
 
-size_t knn_scratch_bytes(int M) { return M > 0 ? knn_layout(M, nullptr).total : 0; }
+size_t knn_scratch_bytes(int M) { return M > 0 ? knn_layout(M, nullptr, M).total : 0; }
 
 // The front half of both searches: bounding cube, Hilbert codes, sort, points in curve order, boxes and sub-boxes.
 // M2: the item count of a second sort that follows (bbox[7]).  *which: where the sorted (code, index) pairs ended up.
@@ -420,7 +469,7 @@ static int knn_key_bits(int M) { return M <= 200000 ? 21 : 30; }
 
 int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratch_bytes, hipStream_t st, int Mq)
 {
-    const KnnScratch s = knn_layout(M, scratch);
+    const KnnScratch s = knn_layout(M, scratch, M);
     if (scratch_bytes < s.total) {
         set_error("knn scratch too small: %zu < %zu", scratch_bytes, s.total);
         return SLS_E_SCRATCH;
@@ -443,13 +492,9 @@ int launch_knn(int M, const float *xyz, float *out, void *scratch, size_t scratc
 
 // ---------------------------------------------------------------------------------------------------------------------
 // sls_nn_query: for every point of a SECOND cloud the nearest point of the indexed one — squared distance and the lowest
-// original index attaining it (include/sls_nn_math.h).  The queries get Hilbert codes in the target's cube (clamped to
-// its border cells outside), go through the same sorter and are searched 64 curve-consecutive ones per wave, exactly
-// as above with three differences: the box to start in comes from a binary search of the wave's first code among the
-// targets' sorted codes; the wave's bounding box is a reduction over its own queries; and the best candidate is ONE
-// packed key (bits(d2) << 32 | index), minimised.  A box whose gap EQUALS the bound is kept by every test (<=, and a
-// gap never exceeds the distance to a point inside the box: float subtraction, fma and max are monotone), so an equally
-// near target of lower index in another box is always met.
+// original index attaining it (include/sls_nn_math.h).  The queries are sorted along the target's curve (nn_front below)
+// and searched by nn_search above; the search is ONE packed key (bits(d2) << 32 | index), minimised, so the lowest index
+// among equally near targets wins.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void nn_gather_kernel(int Mq, const float *__restrict__ xyz,
                                                         const uint32_t *__restrict__ sorted_idx, float4 *__restrict__ qpts)
@@ -460,15 +505,22 @@ __global__ __launch_bounds__(256) void nn_gather_kernel(int Mq, const float *__r
     qpts[j] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __uint_as_float(i));
 }
 
-__device__ __forceinline__ void nn_scan32(const float4 *s_run, const float4 me, uint64_t &best)
-{
+struct BestKeySearch {
+    const float4 me;
+    uint64_t best;
+    __device__ __forceinline__ float bound() const { return sls_nn_key_dist2(best); }
+    // a copy of the run's first point: a minimum meets it twice and does not change, so no sentinel distance exists
+    __device__ __forceinline__ float4 pad(const float4 *__restrict__ pts, int r0) const { return pts[r0]; }
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
 #pragma unroll 8
-    for (int k = 0; k < kKnnSub; ++k) {
-        const float4 p = s_run[k];
-        const uint64_t key = sls_nn_key(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), __float_as_uint(p.w));
-        best = key < best ? key : best;
+        for (int k = 0; k < kKnnSub; ++k) {
+            const float4 p = s_run[k];
+            const uint64_t key = sls_nn_key(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), __float_as_uint(p.w));
+            best = key < best ? key : best;
+        }
     }
-}
+};
 
 __global__ __launch_bounds__(64) void nn_query_kernel(int Mt, int nboxes, const float4 *__restrict__ pts,
                                                       const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
@@ -476,142 +528,17 @@ __global__ __launch_bounds__(64) void nn_query_kernel(int Mt, int nboxes, const 
                                                       const float4 *__restrict__ qpts, const uint32_t *__restrict__ qkeys,
                                                       float *__restrict__ out_dist2, int32_t *__restrict__ out_index)
 {
-    constexpr int kSubs = kKnnBox / kKnnSub;
-    __shared__ float4 s_run[kKnnSub];                   // wave-private: the workgroup IS one wave
-    __shared__ uint32_t s_box[64];
-    __shared__ uint32_t s_sub[64 * kSubs];
-    const int lane = threadIdx.x;
-    const int q0 = blockIdx.x * 64, q = q0 + lane;      // (the grid has ceil(Mq / 64) waves: q0 < Mq)
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { Mt, nboxes, pts, boxes, subboxes };
+    const int q0 = blockIdx.x * 64, q = q0 + threadIdx.x;   // (the grid has ceil(Mq / 64) waves: q0 < Mq)
     const bool live = q < Mq;
     const float4 me = qpts[live ? q : Mq - 1];
-    const int nsub = (Mt + kKnnSub - 1) / kKnnSub;
-    uint64_t best = SLS_NN_KEY_NONE;
-
-    // the box to start in: the one holding the first target whose code is not below the wave's first code
-    int start_box;
-    {
-        const uint32_t code = qkeys[q0];
-        int lo = 0, hi = Mt;                            // lower bound in tkeys[0, Mt): at most 31 halvings
-        while (lo < hi) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (tkeys[mid] < code) lo = mid + 1; else hi = mid;
-        }
-        start_box = __builtin_amdgcn_readfirstlane(min(lo, Mt - 1) / kKnnBox);
-    }
-
-    // a. the runs of the starting box: a tight bound.  (A short last run is padded with copies of its first point,
-    //    which change no minimum.)
-    for (int t = 0; t < kSubs; ++t) {
-        const int sb = start_box * kSubs + t;
-        if (sb >= nsub) break;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < kKnnSub) {
-            const int k = sb * kKnnSub + lane;
-            s_run[lane] = pts[k < Mt ? k : sb * kKnnSub];
-        }
-        __syncthreads();
-        nn_scan32(s_run, me, best);
-    }
-
-    // bounding box of the wave's queries, and of its 8 groups of 8 consecutive ones (dead lanes: empty)
-    auto rl = [](float v, int k) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k)); };
-    float4 gmn = live ? me : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f);
-    float4 gmx = live ? me : make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
-#pragma unroll
-    for (int off = 1; off < 8; off <<= 1) {
-        gmn.x = fminf(gmn.x, __shfl_xor(gmn.x, off, 64)); gmn.y = fminf(gmn.y, __shfl_xor(gmn.y, off, 64));
-        gmn.z = fminf(gmn.z, __shfl_xor(gmn.z, off, 64));
-        gmx.x = fmaxf(gmx.x, __shfl_xor(gmx.x, off, 64)); gmx.y = fmaxf(gmx.y, __shfl_xor(gmx.y, off, 64));
-        gmx.z = fmaxf(gmx.z, __shfl_xor(gmx.z, off, 64));
-    }
-    float4 wmn = gmn, wmx = gmx;
-#pragma unroll
-    for (int off = 8; off < 64; off <<= 1) {
-        wmn.x = fminf(wmn.x, __shfl_xor(wmn.x, off, 64)); wmn.y = fminf(wmn.y, __shfl_xor(wmn.y, off, 64));
-        wmn.z = fminf(wmn.z, __shfl_xor(wmn.z, off, 64));
-        wmx.x = fmaxf(wmx.x, __shfl_xor(wmx.x, off, 64)); wmx.y = fmaxf(wmx.y, __shfl_xor(wmx.y, off, 64));
-        wmx.z = fmaxf(wmx.z, __shfl_xor(wmx.z, off, 64));
-    }
-
-    // b. the outward sweep over chunks of 64 boxes, as in knn_query_kernel (the bound is the lane's best distance)
-    const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;
-    for (int it = 0; it < nchunks; ++it) {
-        int chunk;
-        {
-            const int near = min(c0, nchunks - 1 - c0);
-            if (it <= 2 * near) chunk = c0 + ((it & 1) ? (it + 1) / 2 : -(it / 2));
-            else chunk = (c0 < nchunks - 1 - c0) ? it : nchunks - 1 - it;
-        }
-        float gB = live ? sls_nn_key_dist2(best) : 0.0f;
-        gB = fmaxf(gB, __shfl_xor(gB, 1, 64)); gB = fmaxf(gB, __shfl_xor(gB, 2, 64)); gB = fmaxf(gB, __shfl_xor(gB, 4, 64));
-        const float B2 = wave_max(gB);
-        auto reaches = [&](const float4 bmn, const float4 bmx) -> bool {
-            if (!(box_gap2(wmn, wmx, bmn, bmx) * 0.99999f <= B2)) return false;
-            bool r = false;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const float4 mn = make_float4(rl(gmn.x, 8 * g), rl(gmn.y, 8 * g), rl(gmn.z, 8 * g), 0.0f);
-                const float4 mx = make_float4(rl(gmx.x, 8 * g), rl(gmx.y, 8 * g), rl(gmx.z, 8 * g), 0.0f);
-                r = r || (box_gap2(mn, mx, bmn, bmx) * 0.99999f <= rl(gB, 8 * g));
-            }
-            return r;
-        };
-        const int b = chunk * 64 + lane;
-        bool c = false;
-        if (b < nboxes && b != start_box) c = reaches(boxes[2 * b], boxes[2 * b + 1]);
-        const uint64_t cm = __ballot(c);
-        const int nb = __builtin_popcountll(cm);
-        if (nb == 0) continue;
-        __builtin_amdgcn_wave_barrier();
-        if (c) s_box[__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u))] = (uint32_t)b;
-        __syncthreads();
-        int ns = 0;                                     // <= 8 * nb <= 512 = the size of s_sub
-        for (int g = 0; g < nb; g += 8) {
-            const int slot = g + (lane >> 3);
-            bool cs = false;
-            uint32_t sb = 0;
-            if (slot < nb) {
-                sb = s_box[slot] * kSubs + (uint32_t)(lane & 7);
-                if ((int)sb < nsub) cs = reaches(subboxes[2 * (size_t)sb], subboxes[2 * (size_t)sb + 1]);
-            }
-            const uint64_t sm = __ballot(cs);
-            if (cs) s_sub[ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u))] = sb;
-            ns += __builtin_popcountll(sm);
-        }
-        __syncthreads();
-        // c. the listed runs, 64 at a time: can one still improve (or tie) ANY query?  Then its 32 points go through LDS
-        for (int base = 0; base < ns; base += 64) {
-            const int nk = min(64, ns - base);
-            const uint32_t sbl = s_sub[base + min(lane, nk - 1)];
-            const float4 mnl = subboxes[2 * (size_t)sbl], mxl = subboxes[2 * (size_t)sbl + 1];
-            const float qb2 = live ? sls_nn_key_dist2(best) : -1.0f;
-            bool need = false;
-            for (int qi = 0; qi < 64; ++qi) {
-                const float4 qp = make_float4(rl(me.x, qi), rl(me.y, qi), rl(me.z, qi), 0.0f);
-                need = need || (box_gap2(qp, qp, mnl, mxl) * 0.99999f <= rl(qb2, qi));
-            }
-            uint64_t todo = __ballot(need && lane < nk);
-            auto fetch = [&](int k) -> float4 {         // lanes 0..31: the points of candidate k
-                const int r0 = __builtin_amdgcn_readlane((int)sbl, k) * kKnnSub, i = r0 + (lane & (kKnnSub - 1));
-                return pts[i < Mt ? i : r0];
-            };
-            float4 pre = make_float4(0, 0, 0, 0);
-            if (todo) pre = fetch(__builtin_ctzll(todo));
-            while (todo) {
-                todo &= todo - 1;
-                const float4 cur = pre;
-                if (todo) pre = fetch(__builtin_ctzll(todo));
-                __builtin_amdgcn_wave_barrier();
-                if (lane < kKnnSub) s_run[lane] = cur;
-                __syncthreads();
-                nn_scan32(s_run, me, best);
-            }
-        }
-    }
+    BestKeySearch s = { me, SLS_NN_KEY_NONE };
+    nn_search(ix, tkeys, qkeys[q0], live, me, s, lds);
     if (live) {
         const uint32_t i = __float_as_uint(me.w);
-        out_dist2[i] = sls_nn_key_dist2(best);
-        if (out_index) out_index[i] = (int32_t)sls_nn_key_index(best);
+        out_dist2[i] = sls_nn_key_dist2(s.best);
+        if (out_index) out_index[i] = (int32_t)sls_nn_key_index(s.best);
     }
 }
 
@@ -625,34 +552,41 @@ struct NnScratch {
 
 static NnScratch nn_layout(int Mt, int Mq, void *base)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     NnScratch s;
-    s.t = knn_layout(Mt, base);
-    const size_t sort_bytes = sort_scratch_bytes((uint64_t)(Mt > Mq ? Mt : Mq));
-    char *p = (char *)base;
-    size_t off = s.t.total - al(s.t.sort_bytes) + al(sort_bytes);
-    s.t.sort_bytes = sort_bytes;
-    s.qkeys = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
-    s.qkeys_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
-    s.qvals = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
-    s.qvals_tmp = (uint32_t *)(p + off); off += al(sizeof(uint32_t) * (size_t)Mq);
-    s.qpts = (float4 *)(p + off); off += al(sizeof(float4) * (size_t)Mq);
-    s.total = off < (size_t)SLS_NN_STATS_SCRATCH_BYTES ? (size_t)SLS_NN_STATS_SCRATCH_BYTES : off;
+    s.t = knn_layout(Mt, base, Mt > Mq ? Mt : Mq);
+    Arena a(base);
+    a.off = s.t.total;
+    s.qkeys = a.take<uint32_t>((size_t)Mq);
+    s.qkeys_tmp = a.take<uint32_t>((size_t)Mq);
+    s.qvals = a.take<uint32_t>((size_t)Mq);
+    s.qvals_tmp = a.take<uint32_t>((size_t)Mq);
+    s.qpts = a.take<float4>((size_t)Mq);
+    s.total = a.off < (size_t)SLS_NN_STATS_SCRATCH_BYTES ? (size_t)SLS_NN_STATS_SCRATCH_BYTES : a.off;
     return s;
 }
 
 size_t nn_scratch_bytes(int Mt, int Mq) { return (Mt > 0 && Mq >= 0) ? nn_layout(Mt, Mq, nullptr).total : 0; }
 
-int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
-                    void *scratch, hipStream_t st)
+// What both two-cloud launchers do before their query kernel: the target's index, then the queries' codes in the TARGET's
+// cube (knn_morton_kernel clamps to the border cells outside), the same sorter and the gather in curve order.  self_ok: a
+// cloud queried by itself is its own sorted query set, and the second code / sort / gather is skipped.
+struct NnFront {
+    NnScratch s;
+    const uint32_t *tkeys, *qkeys;      // the sorted codes of the targets and of the queries
+    const float4 *qpts;
+};
+
+static int nn_front(int Mt, const float *target_xyz, int Mq, const float *query_xyz, bool self_ok, void *scratch, hipStream_t st,
+                    NnFront *f)
 {
-    const NnScratch s = nn_layout(Mt, Mq, scratch);
+    const NnScratch &s = f->s = nn_layout(Mt, Mq, scratch);
     const int key_bits = knn_key_bits(Mt);
-    ScopedTimer tm(T_KNN, st);
     int which = 0, qwhich = 0;
     int rc = knn_build(Mt, target_xyz, s.t, key_bits, (uint32_t)Mq, st, &which);
     if (rc) return rc;
-    // the queries' codes in the TARGET's cube (knn_morton_kernel clamps to the border cells), the same sorter
+    f->tkeys = f->qkeys = which ? s.t.keys_tmp : s.t.keys;
+    f->qpts = s.t.pts;
+    if (self_ok && query_xyz == target_xyz && Mq == Mt) return SLS_OK;
     hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, s.t.bbox, s.qkeys, s.qvals,
                        key_bits);
     SLS_LAUNCH_CHECK("knn_morton_kernel");
@@ -662,46 +596,57 @@ int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_
     hipLaunchKernelGGL(nn_gather_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz,
                        qwhich ? s.qvals_tmp : s.qvals, s.qpts);
     SLS_LAUNCH_CHECK("nn_gather_kernel");
-    hipLaunchKernelGGL(nn_query_kernel, dim3((Mq + 63) / 64), dim3(64), 0, st, Mt, (Mt + kKnnBox - 1) / kKnnBox, s.t.pts,
-                       s.t.boxes, s.t.subboxes, which ? s.t.keys_tmp : s.t.keys, Mq, s.qpts,
-                       qwhich ? s.qkeys_tmp : s.qkeys, out_dist2, out_index);
+    f->qkeys = qwhich ? s.qkeys_tmp : s.qkeys;
+    f->qpts = s.qpts;
+    return SLS_OK;
+}
+
+int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
+                    void *scratch, hipStream_t st)
+{
+    ScopedTimer tm(T_KNN, st);
+    NnFront f;
+    const int rc = nn_front(Mt, target_xyz, Mq, query_xyz, false, scratch, st, &f);
+    if (rc) return rc;
+    hipLaunchKernelGGL(nn_query_kernel, dim3((Mq + 63) / 64), dim3(64), 0, st, Mt, (Mt + kKnnBox - 1) / kKnnBox, f.s.t.pts,
+                       f.s.t.boxes, f.s.t.subboxes, f.tkeys, Mq, f.qpts, f.qkeys, out_dist2, out_index);
     SLS_LAUNCH_CHECK("nn_query_kernel");
     return SLS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// sls_nn_query_k: the k nearest targets of every query (include/sls_outlier_math.h) — nn_query_kernel with the single
-// packed best replaced by a per-lane ascending list of K keys in registers (K = 4, 8, 16 or 32, the smallest >= k; every
-// index into it is a compile-time constant after unrolling) and the pruning bound by the lane's k-th best distance, +inf
-// until k targets are held.  The K - k slots in front are filled with the key 0, which nothing beats: the k real entries
-// then live in list[K - k .. K) and list[K - 1] is the k-th best whatever k is.  What keeps the search exact is kept:
-// every gap test is <= with the 0.99999 slack, and a candidate enters the list on a comparison of WHOLE keys.  Unlike a
-// minimum, a list counts what it meets: every target is presented exactly once (the sweep visits every box once, a short
-// last run is padded with SLS_NN_KEY_NONE, which never enters).  No cross-workgroup communication, no waiting, every loop
-// bounded by the box count.
-// Beyond k = 32 (sls_cloud_normals alone, up to SLS_NORMALS_NN_MAX = 64) the list is found in TWO passes of the same kernel:
-// the 32 nearest, whose last key L goes to a per-query buffer; then, with SECOND set, the k - 32 nearest among the targets
-// with key > L — a key names its target, so those are exactly the targets the first pass did not list — written behind the
-// first 32 of the row.  The second pass prunes by its own list alone (+inf until k - 32 such targets are held), which is
-// all exactness needs.  A 64-long register list was tried first: it compiled to 256 VGPRs + 40 AGPRs without scratch, 1 wave
-// per SIMD, and gave wrong lists on the device (3 % of the rows of a 1500-point cloud missed a neighbour); not shipped.
+// sls_nn_query_k: the k nearest targets of every query (include/sls_outlier_math.h).  The search is a per-lane ascending
+// list of K keys in registers (K = 4, 8, 16 or 32, the smallest >= k; every index into it is a compile-time constant after
+// unrolling) and its bound the lane's k-th best distance, +inf until k targets are held.  The K - k slots in front are
+// filled with the key 0, which nothing beats: the k real entries then live in list[K - k .. K) and list[K - 1] is the k-th
+// best whatever k is.  A candidate enters the list on a comparison of WHOLE keys.  Unlike a minimum, a list counts what it
+// meets, so it rests on the sweep presenting every target exactly once.
+// Beyond k = 32 (sls_cloud_normals alone, up to SLS_NORMALS_NN_MAX = 64) the list is found in TWO passes: the 32 nearest,
+// whose last key L goes to a per-query buffer; then, with SECOND set, the k - 32 nearest among the targets with key > L —
+// a key names its target, so exactly those the first pass did not list — written behind the first 32 of the row and
+// pruned by the second list alone.  (A 64-long register list gave wrong lists on the device: DESIGN.md, "Beyond k = 32".)
 // ---------------------------------------------------------------------------------------------------------------------
 template <int K, bool SECOND>
-__device__ __forceinline__ void nnk_scan32(const float4 *s_run, const float4 me, uint64_t (&list)[K], const uint64_t floor_key)
-{
-#pragma clang loop unroll_count(K <= 8 ? 4 : 1)
-    for (int j = 0; j < kKnnSub; ++j) {
-        const float4 p = s_run[j];
-        const uint64_t key = sls_nn_key(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), __float_as_uint(p.w));
-        if (key < list[K - 1] && (!SECOND || key > floor_key)) sls_knn_insert(list, K, key);
+struct ListSearch {
+    const float4 me;
+    const uint64_t floor_key;       // SECOND only: keys up to it belong to the first pass
+    uint64_t list[K];
+    __device__ __forceinline__ float bound() const { return sls_nn_key_dist2(list[K - 1]); }
+    // a point nothing is near to: d2 = +inf and index 0xFFFFFFFF make SLS_NN_KEY_NONE, which never enters
+    __device__ __forceinline__ float4 pad(const float4 *, int) const
+    {
+        return make_float4(1.0e30f, 1.0e30f, 1.0e30f, __uint_as_float(0xFFFFFFFFu));
     }
-}
-
-// a run's point for the LDS stage: beyond Mt a point nothing is near to, d2 = +inf and index 0xFFFFFFFF = SLS_NN_KEY_NONE
-__device__ __forceinline__ float4 nnk_point(const float4 *__restrict__ pts, int i, int Mt)
-{
-    return i < Mt ? pts[i] : make_float4(1.0e30f, 1.0e30f, 1.0e30f, __uint_as_float(0xFFFFFFFFu));
-}
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
+#pragma clang loop unroll_count(K <= 8 ? 4 : 1)
+        for (int j = 0; j < kKnnSub; ++j) {
+            const float4 p = s_run[j];
+            const uint64_t key = sls_nn_key(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), __float_as_uint(p.w));
+            if (key < list[K - 1] && (!SECOND || key > floor_key)) sls_knn_insert(list, K, key);
+        }
+    }
+};
 
 // stride: the floats (int32s) between two queries' rows of out_dist2 (out_index); floor_keys: SECOND only, by original index
 template <int K, bool SECOND>
@@ -713,138 +658,16 @@ __global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, cons
                                                         double *__restrict__ out_mean, uint64_t *__restrict__ out_last_key,
                                                         int stride, const uint64_t *__restrict__ floor_keys)
 {
-    constexpr int kSubs = kKnnBox / kKnnSub;
-    __shared__ float4 s_run[kKnnSub];                   // wave-private: the workgroup IS one wave
-    __shared__ uint32_t s_box[64];
-    __shared__ uint32_t s_sub[64 * kSubs];
-    const int lane = threadIdx.x;
-    const int q0 = blockIdx.x * 64, q = q0 + lane;      // (the grid has ceil(Mq / 64) waves: q0 < Mq)
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { Mt, nboxes, pts, boxes, subboxes };
+    const int q0 = blockIdx.x * 64, q = q0 + threadIdx.x;   // (the grid has ceil(Mq / 64) waves: q0 < Mq)
     const bool live = q < Mq;
     const float4 me = qpts[live ? q : Mq - 1];
-    const int nsub = (Mt + kKnnSub - 1) / kKnnSub;
     const int first = K - k;                            // (the launcher guarantees K / 2 < k <= K, or k <= K = 4)
-    uint64_t list[K];
+    ListSearch<K, SECOND> s = { me, SECOND ? floor_keys[__float_as_uint(me.w)] : 0ull, {} };
 #pragma unroll
-    for (int j = 0; j < K; ++j) list[j] = j < first ? 0ull : SLS_NN_KEY_NONE;
-    auto bound = [&]() -> float { return sls_nn_key_dist2(list[K - 1]); };
-    const uint64_t floor_key = SECOND ? floor_keys[__float_as_uint(me.w)] : 0ull;
-
-    int start_box;
-    {
-        const uint32_t code = qkeys[q0];
-        int lo = 0, hi = Mt;                            // lower bound in tkeys[0, Mt): at most 31 halvings
-        while (lo < hi) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (tkeys[mid] < code) lo = mid + 1; else hi = mid;
-        }
-        start_box = __builtin_amdgcn_readfirstlane(min(lo, Mt - 1) / kKnnBox);
-    }
-
-    // a. the runs of the starting box: a first bound
-    for (int t = 0; t < kSubs; ++t) {
-        const int sb = start_box * kSubs + t;
-        if (sb >= nsub) break;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < kKnnSub) s_run[lane] = nnk_point(pts, sb * kKnnSub + lane, Mt);
-        __syncthreads();
-        nnk_scan32<K, SECOND>(s_run, me, list, floor_key);
-    }
-
-    // bounding box of the wave's queries, and of its 8 groups of 8 consecutive ones (dead lanes: empty)
-    auto rl = [](float v, int i) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), i)); };
-    float4 gmn = live ? me : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f);
-    float4 gmx = live ? me : make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
-#pragma unroll
-    for (int off = 1; off < 8; off <<= 1) {
-        gmn.x = fminf(gmn.x, __shfl_xor(gmn.x, off, 64)); gmn.y = fminf(gmn.y, __shfl_xor(gmn.y, off, 64));
-        gmn.z = fminf(gmn.z, __shfl_xor(gmn.z, off, 64));
-        gmx.x = fmaxf(gmx.x, __shfl_xor(gmx.x, off, 64)); gmx.y = fmaxf(gmx.y, __shfl_xor(gmx.y, off, 64));
-        gmx.z = fmaxf(gmx.z, __shfl_xor(gmx.z, off, 64));
-    }
-    float4 wmn = gmn, wmx = gmx;
-#pragma unroll
-    for (int off = 8; off < 64; off <<= 1) {
-        wmn.x = fminf(wmn.x, __shfl_xor(wmn.x, off, 64)); wmn.y = fminf(wmn.y, __shfl_xor(wmn.y, off, 64));
-        wmn.z = fminf(wmn.z, __shfl_xor(wmn.z, off, 64));
-        wmx.x = fmaxf(wmx.x, __shfl_xor(wmx.x, off, 64)); wmx.y = fmaxf(wmx.y, __shfl_xor(wmx.y, off, 64));
-        wmx.z = fmaxf(wmx.z, __shfl_xor(wmx.z, off, 64));
-    }
-
-    // b. the outward sweep over chunks of 64 boxes, as in nn_query_kernel (the bound is the lane's k-th best distance)
-    const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;
-    for (int it = 0; it < nchunks; ++it) {
-        int chunk;
-        {
-            const int near = min(c0, nchunks - 1 - c0);
-            if (it <= 2 * near) chunk = c0 + ((it & 1) ? (it + 1) / 2 : -(it / 2));
-            else chunk = (c0 < nchunks - 1 - c0) ? it : nchunks - 1 - it;
-        }
-        float gB = live ? bound() : 0.0f;
-        gB = fmaxf(gB, __shfl_xor(gB, 1, 64)); gB = fmaxf(gB, __shfl_xor(gB, 2, 64)); gB = fmaxf(gB, __shfl_xor(gB, 4, 64));
-        const float B2 = wave_max(gB);
-        auto reaches = [&](const float4 bmn, const float4 bmx) -> bool {
-            if (!(box_gap2(wmn, wmx, bmn, bmx) * 0.99999f <= B2)) return false;
-            bool r = false;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const float4 mn = make_float4(rl(gmn.x, 8 * g), rl(gmn.y, 8 * g), rl(gmn.z, 8 * g), 0.0f);
-                const float4 mx = make_float4(rl(gmx.x, 8 * g), rl(gmx.y, 8 * g), rl(gmx.z, 8 * g), 0.0f);
-                r = r || (box_gap2(mn, mx, bmn, bmx) * 0.99999f <= rl(gB, 8 * g));
-            }
-            return r;
-        };
-        const int b = chunk * 64 + lane;
-        bool c = false;
-        if (b < nboxes && b != start_box) c = reaches(boxes[2 * b], boxes[2 * b + 1]);
-        const uint64_t cm = __ballot(c);
-        const int nb = __builtin_popcountll(cm);
-        if (nb == 0) continue;
-        __builtin_amdgcn_wave_barrier();
-        if (c) s_box[__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u))] = (uint32_t)b;
-        __syncthreads();
-        int ns = 0;                                     // <= 8 * nb <= 512 = the size of s_sub
-        for (int g = 0; g < nb; g += 8) {
-            const int slot = g + (lane >> 3);
-            bool cs = false;
-            uint32_t sb = 0;
-            if (slot < nb) {
-                sb = s_box[slot] * kSubs + (uint32_t)(lane & 7);
-                if ((int)sb < nsub) cs = reaches(subboxes[2 * (size_t)sb], subboxes[2 * (size_t)sb + 1]);
-            }
-            const uint64_t sm = __ballot(cs);
-            if (cs) s_sub[ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u))] = sb;
-            ns += __builtin_popcountll(sm);
-        }
-        __syncthreads();
-        // c. the listed runs, 64 at a time: can one still enter (or tie into) ANY query's list?  Then its 32 points go
-        //    through LDS
-        for (int base = 0; base < ns; base += 64) {
-            const int nk = min(64, ns - base);
-            const uint32_t sbl = s_sub[base + min(lane, nk - 1)];
-            const float4 mnl = subboxes[2 * (size_t)sbl], mxl = subboxes[2 * (size_t)sbl + 1];
-            const float qb2 = live ? bound() : -1.0f;
-            bool need = false;
-            for (int qi = 0; qi < 64; ++qi) {
-                const float4 qp = make_float4(rl(me.x, qi), rl(me.y, qi), rl(me.z, qi), 0.0f);
-                need = need || (box_gap2(qp, qp, mnl, mxl) * 0.99999f <= rl(qb2, qi));
-            }
-            uint64_t todo = __ballot(need && lane < nk);
-            auto fetch = [&](int i) -> float4 {         // lanes 0..31: the points of candidate i
-                return nnk_point(pts, __builtin_amdgcn_readlane((int)sbl, i) * kKnnSub + (lane & (kKnnSub - 1)), Mt);
-            };
-            float4 pre = make_float4(0, 0, 0, 0);
-            if (todo) pre = fetch(__builtin_ctzll(todo));
-            while (todo) {
-                todo &= todo - 1;
-                const float4 cur = pre;
-                if (todo) pre = fetch(__builtin_ctzll(todo));
-                __builtin_amdgcn_wave_barrier();
-                if (lane < kKnnSub) s_run[lane] = cur;
-                __syncthreads();
-                nnk_scan32<K, SECOND>(s_run, me, list, floor_key);
-            }
-        }
-    }
+    for (int j = 0; j < K; ++j) s.list[j] = j < first ? 0ull : SLS_NN_KEY_NONE;
+    nn_search(ix, tkeys, qkeys[q0], live, me, s, lds);
     if (live) {
         const size_t i = __float_as_uint(me.w);
         if (out_dist2 || out_index) {
@@ -852,18 +675,32 @@ __global__ __launch_bounds__(64) void nn_query_k_kernel(int Mt, int nboxes, cons
             for (int j = 0; j < K; ++j)
                 if (j >= first) {
                     const size_t o = i * (size_t)stride + (size_t)(j - first);
-                    if (out_dist2) out_dist2[o] = sls_nn_key_dist2(list[j]);
-                    if (out_index) out_index[o] = (int32_t)sls_nn_key_index(list[j]);      // (SLS_NN_KEY_NONE: -1)
+                    if (out_dist2) out_dist2[o] = sls_nn_key_dist2(s.list[j]);
+                    if (out_index) out_index[o] = (int32_t)sls_nn_key_index(s.list[j]);    // (SLS_NN_KEY_NONE: -1)
                 }
         }
-        if (out_mean) out_mean[i] = sls_knn_mean(list, K, first, min(k, Mt));
-        if (out_last_key) out_last_key[i] = list[K - 1];
+        if (out_mean) out_mean[i] = sls_knn_mean(s.list, K, first, min(k, Mt));
+        if (out_last_key) out_last_key[i] = s.list[K - 1];
     }
 }
 
-size_t nn_k_scratch_bytes(int Mt, int Mq, int k)
+size_t nn_k_scratch_bytes(int Mt, int Mq, int k) { return (k >= 1 && k <= SLS_NN_K_MAX) ? nn_scratch_bytes(Mt, Mq) : 0; }
+
+// one launch of the instantiation whose list length k needs
+template <bool SECOND>
+static void nnk_launch(int Mt, int Mq, const NnFront &f, int k, float *d2, int32_t *idx, double *mean, uint64_t *last_key,
+                       int stride, const uint64_t *floor_keys, hipStream_t st)
 {
-    return (k >= 1 && k <= SLS_NN_K_MAX) ? nn_scratch_bytes(Mt, Mq) : 0;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((Mq + 63) / 64), dim3(64), 0, st, Mt, (Mt + kKnnBox - 1) / kKnnBox, f.s.t.pts, f.s.t.boxes,
+                           f.s.t.subboxes, f.tkeys, Mq, f.qpts, f.qkeys, k, d2, idx, mean, last_key, stride, floor_keys);
+    };
+    switch (sls_knn_list_length(k)) {
+    case 4: go(nn_query_k_kernel<4, SECOND>); break;
+    case 8: go(nn_query_k_kernel<8, SECOND>); break;
+    case 16: go(nn_query_k_kernel<16, SECOND>); break;
+    default: go(nn_query_k_kernel<32, SECOND>); break;
+    }
 }
 
 int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, int k_max, float *out_dist2,
@@ -873,56 +710,19 @@ int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *quer
         set_error("launch_nn_query_k: k = %d outside [1, %d], or beyond %d with a mean or without the key buffer", k, k_max, SLS_NN_K_MAX);
         return SLS_E_ARG;
     }
-    const NnScratch s = nn_layout(Mt, Mq, scratch);
-    const int key_bits = knn_key_bits(Mt);
     ScopedTimer tm(T_KNN, st);
-    int which = 0, qwhich = 0;
-    int rc = knn_build(Mt, target_xyz, s.t, key_bits, (uint32_t)Mq, st, &which);
+    NnFront f;
+    const int rc = nn_front(Mt, target_xyz, Mq, query_xyz, true, scratch, st, &f);
     if (rc) return rc;
-    const uint32_t *tkeys = which ? s.t.keys_tmp : s.t.keys;
-    const float4 *qpts = s.t.pts;
-    const uint32_t *qkeys = tkeys;
-    // a cloud queried by itself is its own sorted query set; any other one goes through the target's cube and the sorter
-    if (!(query_xyz == target_xyz && Mq == Mt)) {
-        hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, s.t.bbox, s.qkeys, s.qvals,
-                           key_bits);
-        SLS_LAUNCH_CHECK("knn_morton_kernel");
-        rc = radix_sort_pairs_u32(s.qkeys, s.qvals, s.qkeys_tmp, s.qvals_tmp, s.t.bbox + 7, (uint32_t)Mq, key_bits, s.t.sort,
-                                  s.t.sort_bytes, &qwhich, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(nn_gather_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz,
-                           qwhich ? s.qvals_tmp : s.qvals, s.qpts);
-        SLS_LAUNCH_CHECK("nn_gather_kernel");
-        qpts = s.qpts;
-        qkeys = qwhich ? s.qkeys_tmp : s.qkeys;
-    }
-    const dim3 grid((Mq + 63) / 64);
-    const int nboxes = (Mt + kKnnBox - 1) / kKnnBox;
-#define SLS_NNK_LAUNCH(KK, SECOND, kk, d2, idx, mean, last, floor)                                                            \
-    hipLaunchKernelGGL((nn_query_k_kernel<KK, SECOND>), grid, dim3(64), 0, st, Mt, nboxes, s.t.pts, s.t.boxes, s.t.subboxes,  \
-                       tkeys, Mq, qpts, qkeys, kk, d2, idx, mean, last, k, floor)
     if (k <= SLS_NN_K_MAX) {
-        switch (sls_knn_list_length(k)) {
-        case 4: SLS_NNK_LAUNCH(4, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
-        case 8: SLS_NNK_LAUNCH(8, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
-        case 16: SLS_NNK_LAUNCH(16, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
-        default: SLS_NNK_LAUNCH(32, false, k, out_dist2, out_index, out_mean, out_last_key, nullptr); break;
-        }
+        nnk_launch<false>(Mt, Mq, f, k, out_dist2, out_index, out_mean, out_last_key, k, nullptr, st);
     } else {
         // two passes (see above): the 32 nearest and their last key, then the k - 32 nearest beyond that key
-        const int k2 = k - SLS_NN_K_MAX;
-        float *d2_b = out_dist2 ? out_dist2 + SLS_NN_K_MAX : nullptr;
-        int32_t *idx_b = out_index ? out_index + SLS_NN_K_MAX : nullptr;
-        SLS_NNK_LAUNCH(32, false, SLS_NN_K_MAX, out_dist2, out_index, nullptr, out_last_key, nullptr);
+        nnk_launch<false>(Mt, Mq, f, SLS_NN_K_MAX, out_dist2, out_index, nullptr, out_last_key, k, nullptr, st);
         SLS_LAUNCH_CHECK("nn_query_k_kernel");
-        switch (sls_knn_list_length(k2)) {
-        case 4: SLS_NNK_LAUNCH(4, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
-        case 8: SLS_NNK_LAUNCH(8, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
-        case 16: SLS_NNK_LAUNCH(16, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
-        default: SLS_NNK_LAUNCH(32, true, k2, d2_b, idx_b, nullptr, nullptr, (const uint64_t *)out_last_key); break;
-        }
+        nnk_launch<true>(Mt, Mq, f, k - SLS_NN_K_MAX, out_dist2 ? out_dist2 + SLS_NN_K_MAX : nullptr,
+                         out_index ? out_index + SLS_NN_K_MAX : nullptr, nullptr, nullptr, k, out_last_key, st);
     }
-#undef SLS_NNK_LAUNCH
     SLS_LAUNCH_CHECK("nn_query_k_kernel");
     return SLS_OK;
 }

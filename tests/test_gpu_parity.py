@@ -597,6 +597,10 @@ def test_knn_bitexact(device, oracle32):
         got = distCUDA2(torch.tensor(pts, device=device)).cpu().numpy()
         ref = oracle32.knn_dist2(pts)
         assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), f"M={M}"
+    # (M = 20 000 is two chunks of boxes) waves without a query leave early while the others sweep both chunks
+    for first in (1, 64, 10000):
+        part = distCUDA2(torch.tensor(pts, device=device), first=first).cpu().numpy()
+        assert part.shape == (first,) and np.array_equal(part.view(np.uint32), ref[:first].view(np.uint32)), first
     # duplicates and collinear points
     pts = np.repeat(np.array([[0, 0, 0], [1, 0, 0], [2, 0, 0], [5, 0, 0]], np.float32), 3, axis=0)
     got = distCUDA2(torch.tensor(pts, device=device)).cpu().numpy()
