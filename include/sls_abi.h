@@ -809,6 +809,40 @@ size_t sls_cloud_normals_scratch_bytes(int M, int k);
 int sls_cloud_normals(int M, const float *xyz, int k, float radius, const float *viewpoint3, float *out_normals,
                       int32_t *out_count, float *out_eigenvalues, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- the ground of a scan --------------------------------------------------------------------------------------------
+ * The reference's `preprocessing.enable_ground_segmentation` ("segment and assign up-facing normals to the ground",
+ * scene/preprocessing.py:85-118), which is not implemented there.  A region-wise ground-plane fit in the manner of
+ * Patchwork (Lim et al., RA-L 2021) — concentric zones, seeds from the lowest points of every bin, an iterated PCA plane
+ * fit, uprightness / elevation / flatness tests — RESTATED from the paper in include/sls_ground_math.h, with sectors cut in
+ * the diamond angle (no atan2): patchwork / patchwork++ are not dependencies and no parity with them is claimed; the
+ * defaults (sls_ground_defaults there) are a judgement.  One call, nothing read back inside it, no float atomics; the same
+ * input gives the same bits on every run, and the bits of the header compiled for the host.
+ *   xyz [M * 3] floats, sensor frame, z up.  Rows with a non-finite coordinate are legal: they have no bin.
+ *   prm: HOST memory, read before the call returns.
+ *   out_label [M] bytes: 1 ground, 0 not.  out_bin [M] int32: the point's bin, -1 for none.
+ *   out_planes [SLS_GROUND_BINS * 8] doubles: nx, ny, nz, d, mean_z, the eigenvalues ascending (zeros for a bin without a
+ *       fit); nz >= 0.  out_info [SLS_GROUND_BINS * 4] int32: n, seeds, candidates, state (SLS_GROUND_EMPTY ... _GROUND in
+ *       the header).  out_bin, out_planes, out_info may be null and are then skipped.
+ *   out_status (DEVICE, 8 words): [points with a bin, ground points, non-finite rows, GROUND bins, 0, 0, 0, 1].
+ *   scratch: sls_ground_scratch_bytes(M) bytes (0 for M < 1), 256-byte aligned, a multiple of 256, monotone in M.
+ * M == 0 succeeds and touches nothing but out_status.  Before anything is enqueued: SLS_E_ARG for M < 0, a null prm /
+ * out_status, for M > 0 a null xyz / out_label / scratch or misaligned scratch, a range, height or threshold that is not
+ * a finite number > 0, min_range >= max_range, num_iter outside [1, 8], num_lpr < 1, num_min_pts < 3; SLS_E_SCRATCH for
+ * too little scratch. */
+#define SLS_GROUND_BINS 504     /* (include/sls_ground_math.h defines the same) */
+#ifndef SLS_GROUND_PARAMS_DEFINED
+#define SLS_GROUND_PARAMS_DEFINED
+typedef struct SlsGroundParams {    /* (include/sls_ground_math.h defines the same) */
+    float sensor_height, min_range, max_range, th_seeds, th_dist, uprightness_thr, noise_margin, elevation_thr[4],
+        flatness_thr[4];
+    int32_t num_lpr, num_iter, num_min_pts;
+} SlsGroundParams;
+#endif
+size_t sls_ground_scratch_bytes(int M);
+int sls_ground_segment(int M, const float *xyz, const SlsGroundParams *prm, uint8_t *out_label, int32_t *out_bin,
+                       double *out_planes, int32_t *out_info, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                       void *stream);
+
 /* ---- voxel down-sampling and mesh sampling (what evaluate_recon does before its metric block) -----------------------
  * Open3D's voxel_down_sample for points only, restated (include/sls_cloud_math.h): every point gets the voxel
  * (ix, iy, iz), i_a = floor(((double)p_a - o_a) / voxel_size), o_a = (double)min_a - 0.5 * voxel_size, packed into the

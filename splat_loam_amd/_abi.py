@@ -59,6 +59,13 @@ class SlsAlignerResult(C.Structure):
                 ("inliers", C.c_int32), ("valid_query", C.c_int32), ("iterations", C.c_int32)]
 
 
+class SlsGroundParams(C.Structure):
+    _fields_ = [("sensor_height", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("th_seeds", C.c_float),
+                ("th_dist", C.c_float), ("uprightness_thr", C.c_float), ("noise_margin", C.c_float),
+                ("elevation_thr", C.c_float * 4), ("flatness_thr", C.c_float * 4), ("num_lpr", C.c_int32),
+                ("num_iter", C.c_int32), ("num_min_pts", C.c_int32)]
+
+
 class SlsMappingStatus(C.Structure):
     _fields_ = [("R", C.c_uint32), ("overflow", C.c_uint32), ("loss_sums", C.c_float * 4),
                 ("loss_reg", C.c_float), ("exchange_count", C.c_uint32)]
@@ -170,6 +177,8 @@ _PROTOS = {
     "sls_outlier_radius": (C.c_int, [C.c_int, _VP, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_cloud_normals_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_cloud_normals": (C.c_int, [C.c_int, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_ground_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_ground_segment": (C.c_int, [C.c_int, _VP, C.POINTER(SlsGroundParams), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_voxel_scratch_bytes": (C.c_size_t, [C.c_int]),
     "sls_voxel_downsample": (C.c_int, [C.c_int, _VP, C.c_double, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_mesh_sample_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -567,6 +567,37 @@ int sls_cloud_normals(int M, const float *xyz, int k, float radius, const float 
                                 (hipStream_t)stream);
 }
 
+size_t sls_ground_scratch_bytes(int M) { return ground_scratch_bytes(M); }
+
+int sls_ground_segment(int M, const float *xyz, const SlsGroundParams *prm, uint8_t *out_label, int32_t *out_bin,
+                       double *out_planes, int32_t *out_info, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                       void *stream)
+{
+    const auto positive = [](float v) { return v > 0.0f && v <= FLT_MAX; };
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE(prm && out_status, "null pointer (prm, out_status)");
+    SLS_REQUIRE(positive(prm->min_range) && positive(prm->max_range), "min_range, max_range: not finite numbers > 0");
+    SLS_REQUIRE(prm->min_range < prm->max_range, "min_range >= max_range");
+    SLS_REQUIRE(positive(prm->sensor_height), "sensor_height is not a finite number > 0");
+    SLS_REQUIRE(positive(prm->th_seeds) && positive(prm->th_dist) && positive(prm->uprightness_thr) && positive(prm->noise_margin),
+                "th_seeds, th_dist, uprightness_thr, noise_margin: not finite numbers > 0");
+    for (int c = 0; c < 4; ++c)
+        SLS_REQUIRE(positive(prm->elevation_thr[c]) && positive(prm->flatness_thr[c]),
+                    "elevation_thr, flatness_thr: not finite numbers > 0");
+    SLS_REQUIRE(prm->num_iter >= 1 && prm->num_iter <= 8, "num_iter outside [1, 8]");
+    SLS_REQUIRE(prm->num_lpr >= 1, "num_lpr < 1");
+    SLS_REQUIRE(prm->num_min_pts >= 3, "num_min_pts < 3");
+    if (M > 0) {
+        SLS_REQUIRE(xyz && out_label && scratch, "null pointer (xyz, out_label, scratch)");
+        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+        if (scratch_bytes < ground_scratch_bytes(M)) {
+            set_error("sls_ground_segment: scratch too small: %zu < %zu", scratch_bytes, ground_scratch_bytes(M));
+            return SLS_E_SCRATCH;
+        }
+    }
+    return launch_ground_segment(M, xyz, *prm, out_label, out_bin, out_planes, out_info, out_status, scratch, (hipStream_t)stream);
+}
+
 size_t sls_voxel_scratch_bytes(int M) { return voxel_scratch_bytes(M); }
 
 int sls_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,

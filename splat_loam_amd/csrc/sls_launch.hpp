@@ -201,6 +201,10 @@ int launch_outlier_radius(int M, const float *xyz, const float *normals, int nb_
 size_t cloud_normals_scratch_bytes(int M, int k);
 int launch_cloud_normals(int M, const float *xyz, int k, float radius, const float *viewpoint3, float *out_normals,
                          int32_t *out_count, float *out_eigenvalues, void *scratch, hipStream_t st);
+// ---- sls_ground.hip (the arguments are checked by the caller, sls_api.hip; M == 0: only the status is written) -----
+size_t ground_scratch_bytes(int M);
+int launch_ground_segment(int M, const float *xyz, const SlsGroundParams &prm, uint8_t *out_label, int32_t *out_bin,
+                          double *out_planes, int32_t *out_info, uint32_t *out_status, void *scratch, hipStream_t st);
 // ---- sls_cloud.hip (the arguments are checked by the caller, sls_api.hip) ------------------------------------------
 size_t voxel_scratch_bytes(int M);
 int launch_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,

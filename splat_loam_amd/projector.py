@@ -104,11 +104,19 @@ class DeviceProjector:
     range_image and valid are the "radial" ones.  Selecting the in-window points is a boolean selection whose size the
     host must learn before the next launch can be sized, so "pca" costs ONE host synchronisation per scan and gives up
     the "no host synchronisation" property above; everything else stays on the device.
+
+    ground=True is the reference's `preprocessing.enable_ground_segmentation` ("segment and assign up-facing normals to the
+    ground", not implemented there): after the normals image of either option is made, `evaluation.segment_ground(cloud,
+    sensor_height, **ground_params)` labels the WHOLE scan — every point gets a key, nothing is selected, so there is no
+    host synchronisation — and every pixel whose lut point is ground takes its bin's plane normal (unit, nz >= 0).  The
+    dict gains "ground", (H, W) bool.  lut, range_image and valid do not change.  The scan must be in the sensor frame,
+    z up.  A Patchwork-style restatement, not Patchwork itself: see `evaluation.segment_ground`.
     """
 
     def __init__(self, H: int, W: int, depth_min: float = 0.5, depth_max: float = 100.0,
                  full_azimuth_threshold_deg: float = 300.0, device="cuda:0", normals: str = "radial",
-                 normal_radius: float = 0.5, normal_max_nn: int = 50):
+                 normal_radius: float = 0.5, normal_max_nn: int = 50, ground: bool = False, sensor_height: float = 1.723,
+                 ground_params=None):
         import torch
         from . import _abi, evaluation
         if normals not in ("radial", "pca"):
@@ -116,6 +124,9 @@ class DeviceProjector:
         self.normals = normals
         if normals == "pca":                                    # checked before any work
             self.normal_radius, self.normal_max_nn, _ = evaluation._check_normals_args(normal_radius, normal_max_nn, (0.0, 0.0, 0.0))
+        self.ground = bool(ground)
+        if self.ground:                                         # likewise
+            self._ground_prm = evaluation._check_ground_args(sensor_height, dict(ground_params or {}))
         self.H, self.W = int(H), int(W)
         self.depth_min, self.depth_max = float(depth_min), float(depth_max)
         self.thr = float(full_azimuth_threshold_deg)
@@ -188,10 +199,27 @@ class DeviceProjector:
         image = per_point[lut.long().clamp_(min=0).view(-1)].view(self.H, self.W, 3)
         return torch.where(valid.unsqueeze(-1), image, torch.zeros_like(image))
 
+    def ground_image(self, cloud, lut, valid, normals_image):
+        """(normals_image with the bin's plane normal at every pixel whose lut point is ground, ground (H,W) bool) of
+        ground=True for a projected scan.  No host synchronisation."""
+        import torch
+        from . import evaluation
+        cloud = self._cloud(cloud)
+        label, bins, planes, _, _ = evaluation._ground_enqueue(cloud, self._ground_prm, False)
+        rows = lut.long().clamp_(min=0).view(-1)
+        ground = (label.view(torch.bool)[rows].view(self.H, self.W) & valid) if cloud.shape[0] else torch.zeros_like(valid)
+        if not cloud.shape[0]:
+            return normals_image, ground
+        plane = planes[:, :3].to(torch.float32)[bins.long().clamp_(min=0)[rows]].view(self.H, self.W, 3)
+        return torch.where(ground.unsqueeze(-1), plane, normals_image), ground
+
     def scan_to_images(self, cloud):
         intr = self.intrinsics(cloud)
         lut, rng, nrm, valid = self.project(cloud, intr)
         if self.normals == "pca":
             nrm = self.pca_normals_image(cloud, lut, valid)
-        return dict(K=intr[:9].view(3, 3), vfov=intr[9], hfov=intr[10], range_image=rng, normals_image=nrm,
-                    valid=valid, lut=lut)
+        out = dict(K=intr[:9].view(3, 3), vfov=intr[9], hfov=intr[10], range_image=rng, normals_image=nrm,
+                   valid=valid, lut=lut)
+        if self.ground:
+            out["normals_image"], out["ground"] = self.ground_image(cloud, lut, valid, nrm)
+        return out
