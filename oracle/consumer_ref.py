@@ -21,11 +21,11 @@ from __future__ import annotations
 import torch
 
 
-def pixel_rays64(K: torch.Tensor, H: int, W: int) -> torch.Tensor:
-    """(H, W, 3) float64 unit rays of the sensor frame, pixel (c, r) at (c - 0.5, r - 0.5)."""
-    Kinv = torch.linalg.inv(K.double())
-    xs = torch.arange(W, dtype=torch.float64) - 0.5
-    ys = torch.arange(H, dtype=torch.float64) - 0.5
+def pixel_rays64(K: torch.Tensor, H: int, W: int, dtype=torch.float64) -> torch.Tensor:
+    """(H, W, 3) unit rays of the sensor frame (float64 unless `dtype` says otherwise), pixel (c, r) at (c - 0.5, r - 0.5)."""
+    Kinv = torch.linalg.inv(K.to(dtype))
+    xs = torch.arange(W, dtype=dtype) - 0.5
+    ys = torch.arange(H, dtype=dtype) - 0.5
     gx, gy = xs[None, :].expand(H, W), ys[:, None].expand(H, W)
     az = Kinv[0, 0] * gx + Kinv[0, 1] * gy + Kinv[0, 2]
     el = Kinv[1, 0] * gx + Kinv[1, 1] * gy + Kinv[1, 2]
@@ -33,14 +33,19 @@ def pixel_rays64(K: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return torch.stack([torch.cos(az) * ce, torch.sin(az) * ce, torch.sin(el)], dim=-1)
 
 
-def pixel_loss64(allmap: torch.Tensor, K, gt_depth, valid, depth_ratio=0.0, lambda_normal=0.5, lambda_alpha=0.4):
+def pixel_loss64(allmap: torch.Tensor, K, gt_depth, valid, depth_ratio=0.0, lambda_normal=0.5, lambda_alpha=0.4,
+                 dtype=torch.float64, bce="clamped-log"):
     """allmap (7,H,W) float64 (requires_grad allowed) -> (total, geom_l1, normal_loss, alpha_loss) with the lambdas
     applied.  `valid` is the (H,W) bool mask `image_valid[0] == 1`, `gt_depth` (H,W).  The loss is invariant to
-    the sensor pose (both normals are rotated by the same matrix), so everything stays in the sensor frame."""
-    assert allmap.dtype == torch.float64
+    the sensor pose (both normals are rotated by the same matrix), so everything stays in the sensor frame.
+    `dtype`: the same text in another precision (float32: what float32 arithmetic itself costs on an image).
+    `bce`: "clamped-log" writes the alpha term as -clamp(log a), the value of torch's BCE at target 1; "torch" calls
+    F.binary_cross_entropy as slam/mapper.py:182-187 does — the same value, and torch's backward at the two ends of
+    [0, 1]: (a - 1) / max((1 - a) a, 1e-12), i.e. -1e12 at a == 0 and 0 at a == 1, where the clamped log has NaN and -1."""
+    assert allmap.dtype == dtype and bce in ("clamped-log", "torch")
     _, H, W = allmap.shape
-    K = torch.as_tensor(K).double().reshape(3, 3)
-    gt = torch.as_tensor(gt_depth).double().reshape(H, W)
+    K = torch.as_tensor(K).to(dtype).reshape(3, 3)
+    gt = torch.as_tensor(gt_depth).to(dtype).reshape(H, W)
     valid = torch.as_tensor(valid).reshape(H, W).bool()
     alpha = allmap[1]
     hit = alpha > 0.0
@@ -48,14 +53,17 @@ def pixel_loss64(allmap: torch.Tensor, K, gt_depth, valid, depth_ratio=0.0, lamb
     n_hat = torch.where(hit[None], allmap[2:5] / safe[None], allmap[2:5])
     d_exp = torch.where(hit, allmap[0] / safe, allmap[0])
     surf_depth = d_exp * (1.0 - depth_ratio) + allmap[5] * depth_ratio
-    pts = (surf_depth[..., None] * pixel_rays64(K, H, W)).permute(2, 0, 1)           # (3,H,W)
+    pts = (surf_depth[..., None] * pixel_rays64(K, H, W, dtype)).permute(2, 0, 1)           # (3,H,W)
     d_row = pts[:, 2:, 1:-1] - pts[:, :-2, 1:-1]
     d_col = pts[:, 1:-1, 2:] - pts[:, 1:-1, :-2]
-    n_surf = torch.zeros((3, H, W), dtype=torch.float64)
+    n_surf = torch.zeros((3, H, W), dtype=dtype)
     n_surf[:, 1:-1, 1:-1] = torch.nn.functional.normalize(torch.cross(d_row, d_col, dim=0), dim=0)
     n_surf = n_surf * alpha[None]
     geom = torch.abs(valid * (surf_depth - gt)).mean()
     normal = (1.0 - (n_hat[:, valid] * n_surf[:, valid]).sum(dim=0)).mean() * lambda_normal
     a = alpha[valid]
-    bce = -(torch.clamp(torch.log(a), min=-100.0)).mean() * lambda_alpha               # target 1: torch's BCE clamps the log
+    if bce == "torch":
+        bce = torch.nn.functional.binary_cross_entropy(a, torch.ones_like(a), reduction="mean") * lambda_alpha
+    else:
+        bce = -(torch.clamp(torch.log(a), min=-100.0)).mean() * lambda_alpha           # target 1: torch's BCE clamps the log
     return geom + normal + bce, geom, normal, bce

@@ -32,7 +32,7 @@ def _cameras(scene, G, device, first=0):
     return [Camera(sc["K"], depth, None, valid, poses[k], data_device=str(device)) for k in range(first, first + G)]
 
 
-def _engine(scene, device, flat=None, deterministic=False):
+def _engine(scene, device, flat=None, deterministic=False, depth_ratio=0.0):
     from splat_loam_amd.engine import MappingEngine
     from splat_loam_amd.mapping import MappingConfig
     from splat_loam_amd.scene import SurfelModel
@@ -43,7 +43,7 @@ def _engine(scene, device, flat=None, deterministic=False):
         N = flat.size // 10
         model = SurfelModel(flat[:3 * N].reshape(N, 3), flat[4 * N:6 * N].reshape(N, 2), flat[6 * N:].reshape(N, 4),
                             flat[3 * N:4 * N].reshape(N, 1), device=str(device))
-    eng = MappingEngine(model, MappingConfig(), lrs=LRS, betas=BETAS, eps=EPS)
+    eng = MappingEngine(model, MappingConfig(depth_ratio=depth_ratio), lrs=LRS, betas=BETAS, eps=EPS)
     if deterministic:
         eng.deterministic = True
     return eng, model
@@ -93,21 +93,23 @@ def _compare(got, ref, N, what):
         assert err <= 1e-5 * scale, f"{what}: {name} off by {err} (scale {scale})"
 
 
-@pytest.mark.parametrize("geo", [C5, RAGGED], ids=["config5", "ragged"])
-def test_batch_gradient_is_the_sum_of_singles(device, geo):
+# (depth_ratio 1: the batch's keyframes through the non-lean tile kernels and the launched loss stage, kernels B and C)
+@pytest.mark.parametrize("geo,depth_ratio", [(C5, 0.0), (RAGGED, 0.0), (C5, 1.0), (RAGGED, 1.0)],
+                         ids=["config5", "ragged", "config5-ratio1", "ragged-ratio1"])
+def test_batch_gradient_is_the_sum_of_singles(device, geo, depth_ratio):
     """Sum over the keyframes of the single-keyframe gradient (float64; the regulariser on keyframe 0 only) = the batch's
     gradient, and each keyframe's loss sums = its single step's."""
     N, H, W, G = geo["N"], geo["H"], geo["W"], geo["G"]
     scene = _scene(N, H, W)
     cams = _cameras(scene, G, device)
-    eng, _ = _engine(scene, device)
+    eng, _ = _engine(scene, device, depth_ratio=depth_ratio)
     total = np.zeros(10 * N, np.float64)
     singles = []
     for g, cam in enumerate(cams):
         grad, st = _single(eng, cam, with_regulariser=(g == 0))
         total += grad
         singles.append(st)
-    eng2, _ = _engine(scene, device)
+    eng2, _ = _engine(scene, device, depth_ratio=depth_ratio)
     got, bst, kst = _batch_grad(eng2, cams)
     _compare(got, total, N, f"G={G}")
     for g in range(G):
@@ -161,11 +163,20 @@ def _same(a, b):
 def test_g1_is_step_bit_for_bit(device):
     """Deterministic mode 1: a batch of one keyframe IS the single step — parameters, moments and loss sums after three
     iterations."""
+    _g1_is_step(device, 0.0)
+
+
+def test_g1_is_step_bit_for_bit_depth_ratio_1(device):
+    """The same at depth_ratio 1 (the median depth: kernels B and C launched, the non-lean tile kernels)."""
+    _g1_is_step(device, 1.0)
+
+
+def _g1_is_step(device, depth_ratio):
     N, H, W = C5["N"], C5["H"], C5["W"]
     scene = _scene(N, H, W)
     cam_a, cam_b = _cameras(scene, 1, device)[0], _cameras(scene, 1, device)[0]
-    ea, ma = _engine(scene, device, deterministic=True)
-    eb, mb = _engine(scene, device, deterministic=True)
+    ea, ma = _engine(scene, device, deterministic=True, depth_ratio=depth_ratio)
+    eb, mb = _engine(scene, device, deterministic=True, depth_ratio=depth_ratio)
     for s in range(3):
         sa = ea.step(cam_a)
         sb = eb.step_batch([cam_b])

@@ -720,13 +720,15 @@ def test_full_size_properties(device):
 
 
 def test_fused_consumer_matches_torch_render_and_loss(device):
-    """sls_consumer_fwd_bwd == mapping_loss(postprocess(allmap)) in value and in
-    dL/dallmap (the torch path is itself pinned to the reference by G2/G5)."""
+    """sls_consumer_fwd_bwd == the loss of render() + slam/mapper.py:158-187 in value and in dL/dallmap, on RENDERED
+    images, against the float64 reference (oracle/consumer_ref.py with torch's BCE; tests/test_consumer_math.py pins it
+    to mapping_loss(postprocess(allmap)), which G2/G5 pin to the reference project).  Per pixel, at the values where the
+    kernels branch and at a bar that follows float32's own cost: tests/test_consumer_parity.py."""
+    from oracle.consumer_ref import pixel_loss64
     from splat_loam_amd import synth
     from splat_loam_amd.fused import fused_pixel_loss
-    from splat_loam_amd.mapping import MappingConfig, mapping_loss
-    from splat_loam_amd.renderer import postprocess
-    from splat_loam_amd.scene import Camera, SurfelModel
+    from splat_loam_amd.mapping import MappingConfig
+    from splat_loam_amd.scene import Camera
     for (H, W, ratio, hfov) in ((32, 256, 0.0, 360.0), (40, 200, 0.3, 120.0)):
         sc, view, proj = scene_and_camera(6000, H, W, seed=8, hfov_deg=hfov, range_lo=2.0, range_hi=15.0)
         depth, valid = synth.make_targets(H, W, sc)
@@ -735,16 +737,14 @@ def test_fused_consumer_matches_torch_render_and_loss(device):
         view, proj = synth.camera_matrices(sc["K"], synth.keyframe_poses(2)[1])
         st, _ = hip_forward(device, sc, view, proj, H, W)
         cfg = MappingConfig(depth_ratio=ratio, opt_scaling_max_penalty=0.0)
-        model = SurfelModel.from_activated(sc["means"], sc["scales"], sc["rots"], sc["opac"], device=str(device))
-        am1 = st.allmap.clone().double().requires_grad_(True)       # float64 torch reference
-        cam64 = Camera(sc["K"], depth, None, valid, synth.keyframe_poses(2)[1], data_device=str(device))
-        l_ref = mapping_loss(postprocess(cam64, am1.float(), ratio), cam64, model, cfg)
+        am1 = st.allmap.cpu().double().requires_grad_(True)         # float64 from the image on: no .float() on the way
+        l_ref = pixel_loss64(am1, sc["K"], depth[0], valid[0] == 1, ratio, cfg.opt_lambda_normal, cfg.opt_lambda_alpha, bce="torch")[0]
         l_ref.backward()
         am2 = st.allmap.clone().requires_grad_(True)
         l_hip = fused_pixel_loss(am2, cam, cfg)
         (3.0 * l_hip).backward()
-        assert abs(float(l_hip) - float(l_ref)) <= 2e-5 * abs(float(l_ref))
-        g_ref, g_hip = am1.grad.float().cpu().numpy(), am2.grad.cpu().numpy() / 3.0
+        assert abs(float(l_hip.detach()) - float(l_ref.detach())) <= 2e-5 * abs(float(l_ref.detach()))
+        g_ref, g_hip = am1.grad.numpy(), am2.grad.cpu().numpy() / 3.0
         for c in range(7):
             scale = max(np.abs(g_ref[c]).max(), 1e-30)
             assert np.abs(g_hip[c] - g_ref[c]).max() <= 2e-4 * scale + 1e-12, (H, W, c)
@@ -783,6 +783,17 @@ def test_mapping_engine_matches_unfused_step(device):
     sync inside) == optimize_step (torch activations + torch render/loss + torch
     Adam): same loss, same gradients, same parameter trajectory; the instance
     buffers overflow once on purpose and the iteration is repeated."""
+    _mapping_engine_matches_unfused_step(device, 0.0)
+
+
+def test_mapping_engine_matches_unfused_step_depth_ratio_1(device):
+    """The same at depth_ratio 1 — the median depth, as meshing renders it: the torch path render(cam, model, 1.0) +
+    mapping_loss is the reference; the engine leaves its lean / fused path (kernels B and C launched, the tile backward
+    carrying the median's gradient)."""
+    _mapping_engine_matches_unfused_step(device, 1.0)
+
+
+def _mapping_engine_matches_unfused_step(device, depth_ratio):
     from splat_loam_amd import synth
     from splat_loam_amd.engine import MappingEngine
     from splat_loam_amd.mapping import MappingConfig, mapping_loss
@@ -793,7 +804,7 @@ def test_mapping_engine_matches_unfused_step(device):
     depth, valid = synth.make_targets(H, W, sc)
     valid = valid.copy(); valid[0, :2, :9] = 0
     cam = Camera(sc["K"], depth, None, valid, synth.keyframe_poses(2)[1], data_device=str(device))
-    cfg = MappingConfig()
+    cfg = MappingConfig(depth_ratio=depth_ratio)
     a = SurfelModel.from_activated(sc["means"], sc["scales"], sc["rots"] * 1.7, sc["opac"], device=str(device))
     b = SurfelModel.from_activated(sc["means"], sc["scales"], sc["rots"] * 1.7, sc["opac"], device=str(device))
     a.training_setup(fused=False)
