@@ -843,6 +843,60 @@ int sls_ground_segment(int M, const float *xyz, const SlsGroundParams *prm, uint
                        double *out_planes, int32_t *out_info, uint32_t *out_status, void *scratch, size_t scratch_bytes,
                        void *stream);
 
+/* ---- registration of two clouds: ICP ---------------------------------------------------------------------------------
+ * Gauss-Newton point-to-plane (SLS_ICP_PLANE) or point-to-point (SLS_ICP_POINT) ICP of a source cloud onto a target cloud,
+ * on the EXACT nearest neighbours of sls_nn_query with a hard distance gate and no robust weight; the rule — transform,
+ * association, the 29 sums and their order, the damped Cholesky solve, the Cayley update, the convergence test — is
+ * include/sls_icp_math.h.  It is NOT a global registration: the initial pose must bring the clouds within the gate.  Not
+ * Open3D's registration_icp, which is not a dependency; no parity with it is claimed.  One call, nothing read back inside
+ * it, no float atomics: the target's index is built once, every pass moves the source by the device-resident pose, sorts
+ * it along the target's curve, searches, linearises (a thread per point, fixed-order float64 sums) and solves.  The same
+ * input gives the same bits on every run, and the bits of the header compiled for the host.
+ *   source_xyz [Ms * 3], target_xyz [Mt * 3], target_normals [Mt * 3] floats (DEVICE); the normals may be null for
+ *       SLS_ICP_POINT, which ignores them.
+ *   prm (HOST, read before the call returns): method; max_distance: the gate, a finite number > 0; iterations in
+ *       [0, 1000]: up to that many updates, then ONE evaluation pass at the final pose (0: one linearisation at the initial
+ *       pose); damping: finite, >= 0; eps_rot, eps_trans: finite, >= 0; min_inliers >= 0.  The defaults
+ *       (sls_icp_defaults in the header) are a judgement.
+ *   init_pose12 (HOST, read before the call returns): 12 finite doubles, the row-major 3 x 4 target_T_source.
+ *   out_status (DEVICE, SLS_ICP_STATUS_WORDS 64-bit words): [updates applied, inliers, Ms, Mt, flags (SLS_ICP_FLAG_*), the
+ *       bits of the double sum of r^2, the bits of the 12 pose doubles (words 6 .. 17), 2 (the evaluation pass has run), 0].
+ *       Inliers and the sum belong to the final pose.  After an update that converged, or a pass that kept the pose (too
+ *       few inliers, a system that is not positive definite), the remaining passes change nothing: iterations = 50 on
+ *       an input that ends after k updates gives the bits of iterations = k.
+ *   out_system (optional, 32 doubles): the 29 sums of the last linearisation (21 upper entries of J^T J row-major, J^T r,
+ *       sum r^2, inliers), then three zeros.
+ *   out_index [Ms] int32, out_dist2 [Ms] floats (optional): the last association, as sls_nn_query writes it.
+ *   scratch: sls_cloud_icp_scratch_bytes(Ms, Mt) bytes (0 for Ms < 0 or Mt < 1), 256-byte aligned, a multiple of 256,
+ *       monotone in both, never below sls_nn_scratch_bytes(Mt, Ms).
+ * Ms == 0 succeeds: the pose is the initial pose, flags = SLS_ICP_FLAG_FEW, only out_status (and out_system) written.
+ * Before anything is enqueued: SLS_E_ARG for a negative size, Mt < 1, a null source_xyz (Ms > 0) / target_xyz / prm /
+ * init_pose12 / out_status / scratch, normals missing for the plane method, an unknown method, a max_distance that is not
+ * a finite number > 0, a damping / eps_rot / eps_trans that is NaN, negative or infinite, a negative min_inliers,
+ * iterations outside [0, 1000], a pose entry that is not finite, misaligned scratch; SLS_E_SCRATCH for too little scratch.
+ * Coordinates and normals must be finite (not checked; every access stays inside the buffers). */
+#define SLS_ICP_PLANE 0
+#define SLS_ICP_POINT 1
+#define SLS_ICP_STATUS_WORDS 20
+#define SLS_ICP_MAX_ITERATIONS 1000
+#ifndef SLS_ICP_FLAG_CONVERGED
+#define SLS_ICP_FLAG_CONVERGED 1    /* (include/sls_icp_math.h defines the same) */
+#define SLS_ICP_FLAG_FEW 2
+#define SLS_ICP_FLAG_NOT_PD 4
+#endif
+#ifndef SLS_ICP_PARAMS_DEFINED
+#define SLS_ICP_PARAMS_DEFINED
+typedef struct SlsIcpParams {       /* (include/sls_icp_math.h defines the same) */
+    int32_t method, iterations, min_inliers;
+    float max_distance;
+    double damping, eps_rot, eps_trans;
+} SlsIcpParams;
+#endif
+size_t sls_cloud_icp_scratch_bytes(int Ms, int Mt);
+int sls_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_xyz, const float *target_normals,
+                  const SlsIcpParams *prm, const double *init_pose12, uint64_t *out_status, double *out_system,
+                  int32_t *out_index, float *out_dist2, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- voxel down-sampling and mesh sampling (what evaluate_recon does before its metric block) -----------------------
  * Open3D's voxel_down_sample for points only, restated (include/sls_cloud_math.h): every point gets the voxel
  * (ix, iy, iz), i_a = floor(((double)p_a - o_a) / voxel_size), o_a = (double)min_a - 0.5 * voxel_size, packed into the

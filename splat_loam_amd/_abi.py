@@ -66,6 +66,11 @@ class SlsGroundParams(C.Structure):
                 ("num_iter", C.c_int32), ("num_min_pts", C.c_int32)]
 
 
+class SlsIcpParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("iterations", C.c_int32), ("min_inliers", C.c_int32), ("max_distance", C.c_float),
+                ("damping", C.c_double), ("eps_rot", C.c_double), ("eps_trans", C.c_double)]
+
+
 class SlsMappingStatus(C.Structure):
     _fields_ = [("R", C.c_uint32), ("overflow", C.c_uint32), ("loss_sums", C.c_float * 4),
                 ("loss_reg", C.c_float), ("exchange_count", C.c_uint32)]
@@ -179,6 +184,9 @@ _PROTOS = {
     "sls_cloud_normals": (C.c_int, [C.c_int, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_ground_scratch_bytes": (C.c_size_t, [C.c_int]),
     "sls_ground_segment": (C.c_int, [C.c_int, _VP, C.POINTER(SlsGroundParams), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_cloud_icp_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_cloud_icp": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, C.POINTER(SlsIcpParams), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+                                _VP]),
     "sls_voxel_scratch_bytes": (C.c_size_t, [C.c_int]),
     "sls_voxel_downsample": (C.c_int, [C.c_int, _VP, C.c_double, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_mesh_sample_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -598,6 +598,33 @@ int sls_ground_segment(int M, const float *xyz, const SlsGroundParams *prm, uint
     return launch_ground_segment(M, xyz, *prm, out_label, out_bin, out_planes, out_info, out_status, scratch, (hipStream_t)stream);
 }
 
+size_t sls_cloud_icp_scratch_bytes(int Ms, int Mt) { return cloud_icp_scratch_bytes(Ms, Mt); }
+
+int sls_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_xyz, const float *target_normals,
+                  const SlsIcpParams *prm, const double *init_pose12, uint64_t *out_status, double *out_system,
+                  int32_t *out_index, float *out_dist2, void *scratch, size_t scratch_bytes, void *stream)
+{
+    const auto non_negative = [](double v) { return v >= 0.0 && v <= DBL_MAX; };
+    SLS_REQUIRE(Ms >= 0, "negative Ms");
+    SLS_REQUIRE(Mt >= 1, "Mt < 1: the target cloud is empty");
+    SLS_REQUIRE(prm && init_pose12 && out_status && target_xyz && scratch && (source_xyz || Ms == 0), "null pointer");
+    SLS_REQUIRE(prm->method == SLS_ICP_PLANE || prm->method == SLS_ICP_POINT, "unknown method");
+    SLS_REQUIRE(prm->method == SLS_ICP_POINT || target_normals, "the plane method needs target_normals");
+    SLS_REQUIRE(prm->max_distance > 0.0f && prm->max_distance <= FLT_MAX, "max_distance is not a finite number > 0");
+    SLS_REQUIRE(non_negative(prm->damping) && non_negative(prm->eps_rot) && non_negative(prm->eps_trans),
+                "damping, eps_rot, eps_trans: not finite numbers >= 0");
+    SLS_REQUIRE(prm->iterations >= 0 && prm->iterations <= SLS_ICP_MAX_ITERATIONS, "iterations outside [0, 1000]");
+    SLS_REQUIRE(prm->min_inliers >= 0, "negative min_inliers");
+    for (int k = 0; k < 12; ++k) SLS_REQUIRE(fabs(init_pose12[k]) <= DBL_MAX, "init_pose12 holds a value that is not finite");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < cloud_icp_scratch_bytes(Ms, Mt)) {
+        set_error("sls_cloud_icp: scratch too small: %zu < %zu", scratch_bytes, cloud_icp_scratch_bytes(Ms, Mt));
+        return SLS_E_SCRATCH;
+    }
+    return launch_cloud_icp(Ms, source_xyz, Mt, target_xyz, target_normals, *prm, init_pose12, out_status, out_system, out_index,
+                            out_dist2, scratch, (hipStream_t)stream);
+}
+
 size_t sls_voxel_scratch_bytes(int M) { return voxel_scratch_bytes(M); }
 
 int sls_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_xyz, int32_t *out_count, uint32_t *out_status,

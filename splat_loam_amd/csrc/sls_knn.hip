@@ -66,49 +66,13 @@ __global__ __launch_bounds__(256) void knn_bbox_kernel(int M, const float *__res
     else if (threadIdx.x < 6) atomicMax(&bbox[threadIdx.x], s_box[threadIdx.x]);
 }
 
-__device__ __forceinline__ uint32_t spread10(uint32_t v)
-{   // 10 bits -> every third bit
-    v &= 0x3FFu;
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
 __global__ __launch_bounds__(256) void knn_morton_kernel(int M, const float *__restrict__ xyz,
                                                          const uint32_t *__restrict__ bbox,
                                                          uint32_t *__restrict__ keys, uint32_t *__restrict__ vals, int key_bits)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= M) return;
-    const float mnx = ord2f(bbox[0]), mny = ord2f(bbox[1]), mnz = ord2f(bbox[2]);
-    const float ext = fmaxf(fmaxf(ord2f(bbox[3]) - mnx, ord2f(bbox[4]) - mny), fmaxf(ord2f(bbox[5]) - mnz, 1e-30f));
-    const float s = 1024.0f / ext;
-    const uint32_t qx = (uint32_t)fminf(fmaxf((xyz[3 * i] - mnx) * s, 0.0f), 1023.0f);
-    const uint32_t qy = (uint32_t)fminf(fmaxf((xyz[3 * i + 1] - mny) * s, 0.0f), 1023.0f);
-    const uint32_t qz = (uint32_t)fminf(fmaxf((xyz[3 * i + 2] - mnz) * s, 0.0f), 1023.0f);
-    // Hilbert index of the cell (Skilling's axes-to-transpose form, 10 bits per axis): unlike the Morton
-    // order it has no jumps, so runs of consecutive points (the boxes below) stay compact in space.
-    uint32_t X[3] = { qx, qy, qz };
-#pragma unroll
-    for (uint32_t Q = 512u; Q > 1u; Q >>= 1) {
-        const uint32_t P = Q - 1u;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (X[a] & Q) X[0] ^= P;
-            else { const uint32_t t = (X[0] ^ X[a]) & P; X[0] ^= t; X[a] ^= t; }
-        }
-    }
-    X[1] ^= X[0]; X[2] ^= X[1];
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t Q = 512u; Q > 1u; Q >>= 1)
-        if (X[2] & Q) t ^= Q - 1u;
-    X[0] ^= t; X[1] ^= t; X[2] ^= t;
-    // small clouds are sorted on the top 21 bits only (two 11-bit radix passes instead of three 10-bit ones;
-    // points of one 2^-7 cell stay in input order): measured faster up to ~200 k points, slower beyond
-    keys[i] = ((spread10(X[0]) << 2) | (spread10(X[1]) << 1) | spread10(X[2])) >> (30 - key_bits);
+    keys[i] = curve_code(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], bbox, key_bits);
     vals[i] = (uint32_t)i;
 }
 
@@ -576,28 +540,51 @@ struct NnFront {
     const float4 *qpts;
 };
 
-static int nn_front(int Mt, const float *target_xyz, int Mq, const float *query_xyz, bool self_ok, void *scratch, hipStream_t st,
-                    NnFront *f)
+// the target half: its index, built once.  Mq: the item count of the queries' sort that follows (bbox[7])
+static int nn_front_target(int Mt, const float *target_xyz, int Mq, void *scratch, hipStream_t st, NnFront *f)
 {
     const NnScratch &s = f->s = nn_layout(Mt, Mq, scratch);
-    const int key_bits = knn_key_bits(Mt);
-    int which = 0, qwhich = 0;
-    int rc = knn_build(Mt, target_xyz, s.t, key_bits, (uint32_t)Mq, st, &which);
+    int which = 0;
+    const int rc = knn_build(Mt, target_xyz, s.t, knn_key_bits(Mt), (uint32_t)Mq, st, &which);
     if (rc) return rc;
     f->tkeys = f->qkeys = which ? s.t.keys_tmp : s.t.keys;
     f->qpts = s.t.pts;
-    if (self_ok && query_xyz == target_xyz && Mq == Mt) return SLS_OK;
-    hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, s.t.bbox, s.qkeys, s.qvals,
-                       key_bits);
-    SLS_LAUNCH_CHECK("knn_morton_kernel");
-    rc = radix_sort_pairs_u32(s.qkeys, s.qvals, s.qkeys_tmp, s.qvals_tmp, s.t.bbox + 7, (uint32_t)Mq, key_bits, s.t.sort,
-                              s.t.sort_bytes, &qwhich, st);
+    return SLS_OK;
+}
+
+// the query half behind codes that are already in s.qkeys / s.qvals: the sort and the gather in curve order
+static int nn_front_sorted_queries(int Mt, int Mq, const float *query_xyz, hipStream_t st, NnFront *f)
+{
+    const NnScratch &s = f->s;
+    int qwhich = 0;
+    const int rc = radix_sort_pairs_u32(s.qkeys, s.qvals, s.qkeys_tmp, s.qvals_tmp, s.t.bbox + 7, (uint32_t)Mq, knn_key_bits(Mt),
+                                        s.t.sort, s.t.sort_bytes, &qwhich, st);
     if (rc) return rc;
     hipLaunchKernelGGL(nn_gather_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz,
                        qwhich ? s.qvals_tmp : s.qvals, s.qpts);
     SLS_LAUNCH_CHECK("nn_gather_kernel");
     f->qkeys = qwhich ? s.qkeys_tmp : s.qkeys;
     f->qpts = s.qpts;
+    return SLS_OK;
+}
+
+static int nn_front(int Mt, const float *target_xyz, int Mq, const float *query_xyz, bool self_ok, void *scratch, hipStream_t st,
+                    NnFront *f)
+{
+    int rc = nn_front_target(Mt, target_xyz, Mq, scratch, st, f);
+    if (rc) return rc;
+    if (self_ok && query_xyz == target_xyz && Mq == Mt) return SLS_OK;
+    hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, f->s.t.bbox, f->s.qkeys,
+                       f->s.qvals, knn_key_bits(Mt));
+    SLS_LAUNCH_CHECK("knn_morton_kernel");
+    return nn_front_sorted_queries(Mt, Mq, query_xyz, st, f);
+}
+
+static int nn_query_launch(int Mt, int Mq, const NnFront &f, float *out_dist2, int32_t *out_index, hipStream_t st)
+{
+    hipLaunchKernelGGL(nn_query_kernel, dim3((Mq + 63) / 64), dim3(64), 0, st, Mt, (Mt + kKnnBox - 1) / kKnnBox, f.s.t.pts,
+                       f.s.t.boxes, f.s.t.subboxes, f.tkeys, Mq, f.qpts, f.qkeys, out_dist2, out_index);
+    SLS_LAUNCH_CHECK("nn_query_kernel");
     return SLS_OK;
 }
 
@@ -608,10 +595,30 @@ int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_
     NnFront f;
     const int rc = nn_front(Mt, target_xyz, Mq, query_xyz, false, scratch, st, &f);
     if (rc) return rc;
-    hipLaunchKernelGGL(nn_query_kernel, dim3((Mq + 63) / 64), dim3(64), 0, st, Mt, (Mt + kKnnBox - 1) / kKnnBox, f.s.t.pts,
-                       f.s.t.boxes, f.s.t.subboxes, f.tkeys, Mq, f.qpts, f.qkeys, out_dist2, out_index);
-    SLS_LAUNCH_CHECK("nn_query_kernel");
+    return nn_query_launch(Mt, Mq, f, out_dist2, out_index, st);
+}
+
+// One target index queried many times (sls_icp.hip).  nn_index_target builds it and names where the caller's own kernel
+// writes the queries' codes (curve_code in the target's cube) and the identity; nn_index_query then sorts them, gathers
+// the queries from query_xyz and runs nn_query_kernel, as launch_nn_query does behind its code kernel.
+int nn_index_target(int Mt, const float *target_xyz, int Mq, void *scratch, hipStream_t st, NnIndexRef *ref)
+{
+    NnFront f;
+    const int rc = nn_front_target(Mt, target_xyz, Mq, scratch, st, &f);
+    if (rc) return rc;
+    ref->bbox = f.s.t.bbox; ref->tkeys = f.tkeys; ref->qkeys = f.s.qkeys; ref->qvals = f.s.qvals; ref->key_bits = knn_key_bits(Mt);
     return SLS_OK;
+}
+
+int nn_index_query(int Mt, int Mq, const float *query_xyz, const NnIndexRef &ref, float *out_dist2, int32_t *out_index, void *scratch,
+                   hipStream_t st)
+{
+    NnFront f;
+    f.s = nn_layout(Mt, Mq, scratch);
+    f.tkeys = ref.tkeys;
+    const int rc = nn_front_sorted_queries(Mt, Mq, query_xyz, st, &f);
+    if (rc) return rc;
+    return nn_query_launch(Mt, Mq, f, out_dist2, out_index, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -191,6 +191,23 @@ int launch_nn_stats(int M, const float *dist2, float truncation, float threshold
 size_t nn_k_scratch_bytes(int Mt, int Mq, int k);
 int launch_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, int k_max, float *out_dist2,
                       int32_t *out_index, double *out_mean, uint64_t *out_last_key, void *scratch, hipStream_t st);
+// One target index queried many times (sls_icp.hip): nn_index_target builds it once, scratch laid out as for
+// launch_nn_query(Mt, .., Mq, ..); the caller's own kernel then writes, per round, the Mq queries' curve codes
+// (curve_code(.., bbox, key_bits), sls_geom.hpp) to qkeys and the identity to qvals, and nn_index_query sorts them,
+// gathers the queries from query_xyz and searches.  Mq >= 1.
+struct NnIndexRef {
+    const uint32_t *bbox, *tkeys;
+    uint32_t *qkeys, *qvals;
+    int key_bits;
+};
+int nn_index_target(int Mt, const float *target_xyz, int Mq, void *scratch, hipStream_t st, NnIndexRef *ref);
+int nn_index_query(int Mt, int Mq, const float *query_xyz, const NnIndexRef &ref, float *out_dist2, int32_t *out_index, void *scratch,
+                   hipStream_t st);
+// ---- sls_icp.hip (the arguments are checked by the caller, sls_api.hip; init_pose12: host memory) ------------------
+size_t cloud_icp_scratch_bytes(int Ms, int Mt);
+int launch_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_xyz, const float *target_normals,
+                     const SlsIcpParams &prm, const double *init_pose12, uint64_t *out_status, double *out_system,
+                     int32_t *out_index, float *out_dist2, void *scratch, hipStream_t st);
 // ---- sls_outlier.hip (the arguments are checked by the caller, sls_api.hip) ----------------------------------------
 size_t outlier_scratch_bytes(int M, int k);
 int launch_outlier_statistical(int M, const float *xyz, const float *normals, int k, double std_ratio, float *out_xyz,

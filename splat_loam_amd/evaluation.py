@@ -377,6 +377,134 @@ def remove_radius_outlier(points: torch.Tensor, nb_points: int, radius: float, n
     return res
 
 
+ICP_METHODS = {"plane": 0, "point": 1}                # SLS_ICP_PLANE, SLS_ICP_POINT (include/sls_abi.h)
+ICP_STATUS_WORDS = 20                                   # SLS_ICP_STATUS_WORDS
+ICP_MAX_ITERATIONS = 1000                               # SLS_ICP_MAX_ITERATIONS
+ICP_FLAG_CONVERGED, ICP_FLAG_FEW, ICP_FLAG_NOT_PD = 1, 2, 4
+# a judgement, as in include/sls_icp_math.h (sls_icp_defaults), where the reasons are given
+ICP_DEFAULTS = dict(damping=1e-9, eps_rot=1e-7, eps_trans=1e-7, min_inliers=6)
+
+
+def _check_icp_args(max_distance, iterations, method, init, params) -> tuple[_abi.SlsIcpParams, list]:
+    """The parameters of register_icp as the C struct and the initial pose as 12 floats, checked as sls_cloud_icp checks
+    them (before any work)."""
+    unknown = sorted(set(params) - set(ICP_DEFAULTS))
+    if unknown:
+        raise ValueError(f"unknown ICP parameter {unknown[0]!r}; the parameters are {sorted(ICP_DEFAULTS)}")
+    if method not in ICP_METHODS:
+        raise ValueError(f"method must be one of {sorted(ICP_METHODS)}")
+    p = dict(ICP_DEFAULTS, **params)
+    prm = _abi.SlsIcpParams()
+    prm.method = ICP_METHODS[method]
+    prm.iterations = _check_k(iterations, "iterations", 0, ICP_MAX_ITERATIONS)
+    prm.min_inliers = _check_k(p["min_inliers"], "min_inliers", 0, 2**31 - 1)
+    try:
+        gate = ctypes.c_float(float(max_distance)).value                    # what the C struct will hold
+    except (TypeError, ValueError):
+        raise ValueError("max_distance must be a number") from None
+    if not 0.0 < gate < math.inf:
+        raise ValueError("max_distance must be finite and > 0 as a float32")
+    prm.max_distance = gate
+    for name in ("damping", "eps_rot", "eps_trans"):
+        try:
+            v = float(p[name])
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number") from None
+        if not 0.0 <= v < math.inf:
+            raise ValueError(f"{name} must be a finite number >= 0")
+        setattr(prm, name, v)
+    if init is None:
+        pose = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]
+    else:
+        t = (init.detach() if isinstance(init, torch.Tensor) else torch.as_tensor(init, dtype=torch.float64)).to("cpu", torch.float64)
+        if tuple(t.shape) == (4, 4):
+            t = t[:3]
+        if t.numel() != 12 or tuple(t.shape) not in ((3, 4), (12,)):
+            raise ValueError("init must be a 4x4 or 3x4 matrix, or 12 numbers (row-major 3x4 target_T_source)")
+        pose = [float(v) for v in t.reshape(-1).tolist()]
+        if not all(math.isfinite(v) for v in pose):
+            raise ValueError("init must be finite")
+    return prm, pose
+
+
+def _icp_enqueue(lib, source, target, normals, prm: _abi.SlsIcpParams, pose12, details: bool, st):
+    """sls_cloud_icp without a host read: (status (20,) int64, system (32,) float64 | None, index (Ms,) int32 | None,
+    dist2 (Ms,) float32 | None)."""
+    Ms, Mt = int(source.shape[0]), int(target.shape[0])
+    dev = target.device
+    status = torch.empty((ICP_STATUS_WORDS,), dtype=torch.int64, device=dev)
+    system = torch.empty((32,), dtype=torch.float64, device=dev) if details else None
+    index = torch.empty((Ms,), dtype=torch.int32, device=dev) if details else None
+    dist2 = torch.empty((Ms,), dtype=torch.float32, device=dev) if details else None
+    _, aligned, nbytes = _scratch_bytes(lib.sls_cloud_icp_scratch_bytes(Ms, Mt), dev)
+    init = (ctypes.c_double * 12)(*pose12)                                  # host memory, read before the call returns
+    _abi.check(lib.sls_cloud_icp(Ms, source.data_ptr() if Ms else None, Mt, target.data_ptr(),
+                                 normals.data_ptr() if normals is not None else None, ctypes.byref(prm), ctypes.addressof(init),
+                                 status.data_ptr(), system.data_ptr() if details else None,
+                                 index.data_ptr() if (details and Ms) else None, dist2.data_ptr() if (details and Ms) else None,
+                                 aligned, nbytes, st), "sls_cloud_icp")
+    return status, system, index, dist2
+
+
+def _icp_result(words) -> dict:
+    """The status words of sls_cloud_icp as register_icp returns them."""
+    bits = lambda v: struct.unpack("<d", struct.pack("<q", v))[0]
+    inliers, Ms, flags, sum_r2 = int(words[1]), int(words[2]), int(words[4]), bits(words[5])
+    pose = torch.eye(4, dtype=torch.float64)
+    pose[:3] = torch.tensor([bits(w) for w in words[6:18]], dtype=torch.float64).view(3, 4)
+    return {"target_T_source": pose, "fitness": inliers / Ms if Ms else 0.0,
+            "inlier_rmse": math.sqrt(sum_r2 / inliers) if inliers else 0.0, "inliers": inliers, "sum_r2": sum_r2,
+            "updates": int(words[0]), "converged": bool(flags & ICP_FLAG_CONVERGED), "too_few_inliers": bool(flags & ICP_FLAG_FEW),
+            "not_positive_definite": bool(flags & ICP_FLAG_NOT_PD), "flags": flags}
+
+
+def register_icp(source: torch.Tensor, target: torch.Tensor, target_normals=None, init=None, max_distance: float = 1.0,
+                 iterations: int = 30, method: str = "plane", return_details: bool = False, **params):
+    """Register `source` (Ms,3) onto `target` (Mt,3): Gauss-Newton ICP on the EXACT nearest neighbours of `nearest`, with
+    a hard distance gate (a pair counts iff d2 <= max_distance * max_distance, one float32 product) and NO robust weight
+    (include/sls_icp_math.h; pinned against a NumPy restatement, tests/icp_ref.py).  `method="plane"` minimises
+    n . (R p + t - q) over the target's normals, `"point"` the distances themselves.  It is NOT a global registration:
+    `init` (4x4, 3x4 or 12 numbers, default the identity) must bring the clouds within the gate.  No multi-scale, no
+    robust kernel; not Open3D's `registration_icp`, which is not a dependency, and no parity with it is claimed.
+
+    `iterations` (0 ... 1000) updates at most, then one evaluation pass at the final pose; the updates end early once a
+    step is below `eps_rot` / `eps_trans` (converged), or when fewer than `min_inliers` pairs pass the gate or the damped
+    system is not positive definite (the pose is then kept).  `params`: damping, eps_rot, eps_trans, min_inliers; the
+    defaults (ICP_DEFAULTS) are a judgement.
+
+    Returns a dict: `target_T_source` (4x4 float64, CPU), `fitness` = inliers / Ms, `inlier_rmse` = sqrt(sum r^2 /
+    inliers) of the final pose (r: the plane distance, or the point distance), `inliers`, `sum_r2`, `updates`,
+    `converged`, `too_few_inliers`, `not_positive_definite`, `flags`.  With `return_details=True` also `system` (32,)
+    float64 — the 29 sums of the last linearisation — and the last association, `index` (Ms,) int32 and `dist2` (Ms,)
+    float32, all on the device.  ONE native call (sls_cloud_icp) and ONE host read, of the status words; with
+    `method="plane"` and no `target_normals` it first calls `estimate_normals(target)` — a second native call, still no
+    further host read.  Fixed-order float64 sums, no float atomics: the same input gives the same bits on every run.
+    Device float32 (M,3) only; coordinates and normals must be finite (not checked)."""
+    source, target = _cloud(source, "source"), _cloud(target, "target")
+    if source.device != target.device:
+        raise ValueError("source and target must live on the same device")
+    if target.shape[0] == 0:
+        raise ValueError("the target cloud is empty")
+    prm, pose12 = _check_icp_args(max_distance, iterations, method, init, params)
+    normals = _normals(target_normals, target) if method == "plane" else None
+    if method == "plane" and normals is None:
+        normals = estimate_normals(target)
+    lib = _abi.lib()
+    with torch.cuda.device(target.device):
+        st = torch.cuda.current_stream(target.device).cuda_stream
+        status, system, index, dist2 = _icp_enqueue(lib, source, target, normals, prm, pose12, return_details, st)
+        res = _icp_result(status.cpu().tolist())                            # the one host read
+    if return_details:
+        res.update(system=system, index=index, dist2=dist2)
+    return res
+
+
+def transform_points(points: torch.Tensor, pose: torch.Tensor) -> torch.Tensor:
+    """(M,3) float32: R p + t for a 4x4 (or 3x4) pose, computed in float64 on the points' device and rounded once."""
+    pose = torch.as_tensor(pose, dtype=torch.float64).to(points.device)
+    return (points.double() @ pose[:3, :3].T + pose[:3, 3]).float()
+
+
 def crop_union_mask(reference: torch.Tensor, estimate: torch.Tensor, threshold_dist: float = 1.2) -> torch.Tensor:
     """bool (Mref,): the reference points with an estimate point nearer than `threshold_dist` — `crop_union`
     (eval_utils.py:202-250) after its mesh sampling; `estimate` is the merged cloud of all methods.  The comparison is
@@ -553,9 +681,29 @@ def sample_mesh(vertices: torch.Tensor, faces: torch.Tensor, n: int, seed: int =
     return (out, face) if return_faces else out
 
 
+ALIGN_MAX_POINTS = 200_000
+
+
+def _align_vertices(reference: torch.Tensor, vertices: torch.Tensor, align) -> dict:
+    """evaluate_recon's `align`: register_icp of a bounded subset of the vertices onto the reference cloud."""
+    if not isinstance(align, dict) or "max_distance" not in align:
+        raise ValueError("align must be a dict with at least max_distance (the arguments of register_icp)")
+    args = dict(align)
+    max_points = _check_k(args.pop("max_points", ALIGN_MAX_POINTS), "max_points", 1, 2**31 - 1)
+    draw_seed = int(args.pop("seed", 0))
+    if "return_details" in args:
+        raise ValueError("align takes no return_details")
+    source = vertices
+    if vertices.shape[0] > max_points:
+        g = torch.Generator(device=vertices.device)
+        g.manual_seed(draw_seed)
+        source = vertices[torch.randint(0, int(vertices.shape[0]), (max_points,), generator=g, device=vertices.device)]
+    return register_icp(source, reference, **args)
+
+
 def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, down_sample_res: float = 0.02,
                    threshold: float = 0.2, truncation_acc: float = 0.5, truncation_com: float = 0.5,
-                   crop_to_reference: bool = False, mesh_sample_point: int = 10_000_000, seed: int = 0) -> dict:
+                   crop_to_reference: bool = False, mesh_sample_point: int = 10_000_000, seed: int = 0, align=None) -> dict:
     """The reference's `evaluate_recon` (utils/eval_utils.py:67-154) for a reference cloud and an estimated mesh already
     on the device, with its dictionary keys and units: sample `mesh_sample_point` points from the mesh, voxel-down-sample
     both clouds at `down_sample_res` (skipped where that is <= 0, as in the reference), then the metric block of
@@ -566,13 +714,25 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
     discards what it returns (eval_utils.py:109; Open3D's crop does not work in place), so the numbers it publishes
     are those of the UNCROPPED mesh.  True does what it intended: only the faces whose vertices all lie inside the
     reference cloud's bounding box, padded by `down_sample_res` along z, are sampled (the box is computed on the device).
-    The sampling is seeded (`seed`), where the reference's is not: a rerun gives the same numbers."""
+    The sampling is seeded (`seed`), where the reference's is not: a rerun gives the same numbers.
+
+    `align` (default None: nothing of what follows happens, no extra call, no extra host read): a dict of `register_icp`
+    arguments — `max_distance` is required; `iterations`, `method`, `init`, `target_normals` (of the reference cloud) and
+    its `params` are optional — plus `max_points` (default 200 000) and `seed`.  The mesh's VERTICES are then registered
+    onto the reference cloud before anything is sampled: on at most `max_points` of them, a seeded device draw with
+    replacement where there are more; every vertex is moved by the pose found, and the metrics are those of the moved
+    mesh.  The result gets one more key, "Alignment": what `register_icp` returns.  One more host read (its status
+    words), and with the plane method and no normals the `estimate_normals` call on the reference cloud."""
     reference = _cloud(reference_points, "reference_points")
     vertices, faces = _mesh(vertices, faces)
     if reference.device != vertices.device:
         raise ValueError("the reference cloud and the mesh must live on the same device")
     if reference.shape[0] == 0:
         raise ValueError("the reference cloud is empty")
+    alignment = None
+    if align is not None:
+        alignment = _align_vertices(reference, vertices, align)
+        vertices = transform_points(vertices, alignment["target_T_source"])
     n = int(mesh_sample_point)
     if n < 1:
         raise ValueError("mesh_sample_point must be at least 1")
@@ -600,10 +760,13 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
             reference = reference[:_voxel_status(w[8:12], "evaluate_recon: the reference cloud")]
     m = cloud_metrics(reference, estimate, threshold=threshold, truncation_acc=truncation_acc,
                       truncation_com=truncation_com)                        # host read 2 of 2
-    return {
+    out = {
         "MAE_accuracy (cm)": m["accuracy_m"] * 100, "MAE_completeness (cm)": m["completeness_m"] * 100,
         "Chamfer_L1 (cm)": m["chamfer_l1_m"] * 100, "Precision [Accuracy] (%)": m["precision"] * 100.0,
         "Recall [Completeness] (%)": m["recall"] * 100.0, "F-score (%)": m["fscore"] * 100.0,
         "Inlier_threshold (m)": float(threshold), "Outlier_truncation_acc (m)": float(truncation_acc),
         "Outlier_truncation_com (m)": float(truncation_com),
     }
+    if alignment is not None:
+        out["Alignment"] = alignment
+    return out

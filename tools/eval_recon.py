@@ -4,11 +4,16 @@ mesh, on the device (splat_loam_amd.evaluation.evaluate_recon), one JSON line wi
 
     python tools/eval_recon.py REFERENCE.ply MESH.ply [--down-sample-res 0.02] [--threshold 0.2] [--truncation-acc 0.5]
                                [--truncation-com 0.5] [--mesh-sample-point 10000000] [--seed 0] [--crop-to-reference]
+                               [--align D [--align-iterations 30] [--align-method plane|point]]
 
 REFERENCE.ply: binary little-endian PLY with `x y z` as float or double.  MESH.ply: binary little-endian PLY with a
 `vertex` element and one `face` element of triangles (`list uchar int vertex_indices`: what Open3D writes for a Poisson
 mesh).  The defaults are the reference's.  --crop-to-reference samples only the faces inside the reference cloud's
-bounding box (z padded by the voxel size): what the reference intended but does not do, so it is off by default."""
+bounding box (z padded by the voxel size): what the reference intended but does not do, so it is off by default.
+--align D first registers the mesh's vertices onto the reference cloud (evaluation.register_icp: ICP on exact nearest
+neighbours, pairs farther apart than D metres ignored; no global registration — the mesh must already lie within D of the
+cloud) and evaluates the moved mesh; the line then holds "Alignment": the pose in KITTI order (12 numbers, row-major 3x4
+reference_T_mesh), fitness, inlier_rmse, updates and the flags.  Without it nothing changes."""
 import argparse
 import json
 import os
@@ -33,15 +38,26 @@ def main():
     ap.add_argument("--mesh-sample-point", type=int, default=10_000_000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--crop-to-reference", action="store_true")
+    ap.add_argument("--align", type=float, default=None, metavar="D", help="register the mesh to the reference first, gate D metres")
+    ap.add_argument("--align-iterations", type=int, default=30)
+    ap.add_argument("--align-method", choices=("plane", "point"), default="plane")
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args()
+    align = None
+    if a.align is not None:
+        align = dict(max_distance=a.align, iterations=a.align_iterations, method=a.align_method, seed=a.seed)
+        evaluation._check_icp_args(a.align, a.align_iterations, a.align_method, None, {})     # before the files are read
     dev = torch.device(a.device)
     reference = torch.from_numpy(ply_io.load_point_cloud(a.reference_ply)[0]).to(dev)
     vertices, faces = ply_io.load_mesh(a.mesh_ply)
-    print(json.dumps(evaluation.evaluate_recon(
+    res = evaluation.evaluate_recon(
         reference, torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev), down_sample_res=a.down_sample_res,
         threshold=a.threshold, truncation_acc=a.truncation_acc, truncation_com=a.truncation_com,
-        crop_to_reference=a.crop_to_reference, mesh_sample_point=a.mesh_sample_point, seed=a.seed)))
+        crop_to_reference=a.crop_to_reference, mesh_sample_point=a.mesh_sample_point, seed=a.seed, align=align)
+    if align is not None:
+        al = res["Alignment"]
+        al["target_T_source"] = al["target_T_source"][:3].reshape(-1).tolist()
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
