@@ -990,6 +990,49 @@ int sls_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const
                           double voxel_size, const double *origin3, const uint32_t *prefix, uint32_t T, float *triangles_out,
                           void *stream);
 
+/* ---- screened Poisson reconstruction over the block volume ----------------------------------------------------------
+ * include/sls_poisson_math.h states every rule and every order of summation; DESIGN.md section 2, "Poisson volume".  The
+ * grid is the TSDF volume's: blocks (B x 3 int32, DEVICE) in ascending key order, voxel l of block k at slot 512 k + l.
+ * It IS a least-squares fit of the gradient of an indicator to the splatted normal field on a uniform band, screened by
+ * the sample density, solved by Jacobi-preconditioned conjugate gradients.  It is NOT Kazhdan's adaptive octree, uses
+ * trilinear splats (not B-splines), has no Dirichlet envelope and is not compared against Open3D, which is not a
+ * dependency.  Every result equals the header run on the host bit for bit; no floating-point atomics.
+ *
+ * splat: the M DEVICE points (xyz, normals: M x 3 floats each) into out_field (B x 512 x 4 floats: Vx, Vy, Vz, W).
+ *   out_status (DEVICE, 4 words): [points with a non-finite value, points out of index range, points with at least one
+ *   dropped corner (a point whose cell lies in no block is dropped whole and counted here), 1].
+ *   scratch: sls_poisson_splat_scratch_bytes(M, B) bytes (0 for M < 1 or sizes beyond the limits).  M == 0 succeeds,
+ *   writes [0, 0, 0, 1] to out_status when that is non-null and touches nothing else; B == 0 counts and writes no field.
+ * solve: (L + alpha diag(W)) x = b from x = 0, at most `iterations` passes, ended when <r,r> <= tol^2 <b,b>; out_chi
+ *   (B x 512 floats) = x - iso, iso the W-weighted mean of x.  out_status (DEVICE, SLS_POISSON_STATUS_WORDS 64-bit
+ *   words): [passes run, flags (SLS_POISSON_FLAG_*), B, the bits of the doubles <r,r>, <b,b>, iso, sum W, 0].  Nothing
+ *   is read back and nothing synchronises inside the call; once ended the remaining passes change nothing.
+ *   scratch: sls_poisson_solve_scratch_bytes(B).  B == 0 succeeds: [0, CONVERGED | EMPTY, 0, ...].
+ * density: W after `sweeps` averaging sweeps over the present neighbours, as out_density (B x 512 floats).
+ *   scratch: sls_poisson_density_scratch_bytes(B).  B == 0 succeeds and writes nothing.
+ * Before anything is enqueued: SLS_E_ARG for a null pointer, M or B negative or above SLS_TSDF_MAX_POINTS /
+ * SLS_TSDF_MAX_BLOCKS, a voxel_size that is not finite and > 0, an origin that is not finite, alpha not finite and > 0,
+ * tol NaN, negative or infinite, iterations outside [0, SLS_POISSON_MAX_ITERATIONS], sweeps outside
+ * [0, SLS_POISSON_MAX_SWEEPS], misaligned scratch; SLS_E_SCRATCH for too little scratch. */
+#define SLS_POISSON_MAX_ITERATIONS 1000
+#define SLS_POISSON_MAX_SWEEPS 64
+#ifndef SLS_POISSON_FLAG_CONVERGED
+#define SLS_POISSON_FLAG_CONVERGED 1    /* (include/sls_poisson_math.h defines the same, and refuses to compile after other values) */
+#define SLS_POISSON_FLAG_NOT_PD 2
+#define SLS_POISSON_FLAG_EMPTY 4
+#define SLS_POISSON_STATUS_WORDS 8
+#endif
+size_t sls_poisson_splat_scratch_bytes(int M, int B);
+int sls_poisson_splat(int M, const float *xyz, const float *normals, int B, const int32_t *blocks, double voxel_size,
+                      const double *origin3, float *out_field, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                      void *stream);
+size_t sls_poisson_solve_scratch_bytes(int B);
+int sls_poisson_solve(int B, const int32_t *blocks, const float *field, double alpha, int iterations, double tol,
+                      float *out_chi, uint64_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+size_t sls_poisson_density_scratch_bytes(int B);
+int sls_poisson_density(int B, const int32_t *blocks, const float *field, int sweeps, float *out_density, void *scratch,
+                        size_t scratch_bytes, void *stream);
+
 /* ---- cleaning an extracted mesh: weld, clusters, selection, vertex normals ------------------------------------------
  * include/sls_mesh_math.h states every rule; DESIGN.md section 2, "Mesh cleaning".  Every pointer is a DEVICE pointer;
  * every scratch is 256-byte aligned and its size comes from the matching _scratch_bytes (0 for a size below 1 or above

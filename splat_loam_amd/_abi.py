@@ -197,6 +197,12 @@ _PROTOS = {
                                      C.c_float, C.c_float, C.c_float, _VP]),
     "sls_tsdf_extract_count": (C.c_int, [C.c_int, _VP, _VP, _VP, C.c_float, _VP, _VP, _VP, _VP]),
     "sls_tsdf_extract_emit": (C.c_int, [C.c_int, _VP, _VP, _VP, C.c_float, C.c_double, _VP, _VP, C.c_uint32, _VP, _VP]),
+    "sls_poisson_splat_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_poisson_splat": (C.c_int, [C.c_int, _VP, _VP, C.c_int, _VP, C.c_double, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_poisson_solve_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_poisson_solve": (C.c_int, [C.c_int, _VP, _VP, C.c_double, C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_poisson_density_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_poisson_density": (C.c_int, [C.c_int, _VP, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP]),
     "sls_mesh_weld_scratch_bytes": (C.c_size_t, [C.c_int]),
     "sls_mesh_weld": (C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_mesh_clusters_scratch_bytes": (C.c_size_t, [C.c_int]),

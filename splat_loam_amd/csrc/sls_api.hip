@@ -738,6 +738,68 @@ int sls_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const
                                     (hipStream_t)stream);
 }
 
+size_t sls_poisson_splat_scratch_bytes(int M, int B) { return poisson_splat_scratch_bytes(M, B); }
+size_t sls_poisson_solve_scratch_bytes(int B) { return poisson_solve_scratch_bytes(B); }
+size_t sls_poisson_density_scratch_bytes(int B) { return poisson_density_scratch_bytes(B); }
+
+int sls_poisson_splat(int M, const float *xyz, const float *normals, int B, const int32_t *blocks, double voxel_size,
+                      const double *origin3, float *out_field, uint32_t *out_status, void *scratch, size_t scratch_bytes,
+                      void *stream)
+{
+    SLS_REQUIRE(M >= 0 && M <= SLS_TSDF_MAX_POINTS, "M negative or above SLS_TSDF_MAX_POINTS");
+    SLS_REQUIRE(B >= 0 && B <= SLS_TSDF_MAX_BLOCKS, "B negative or above SLS_TSDF_MAX_BLOCKS");
+    SLS_REQUIRE(voxel_size > 0.0 && voxel_size <= DBL_MAX, "voxel_size is not a finite number > 0");
+    SLS_REQUIRE(tsdf_origin_ok(origin3), "origin3 is null or not finite");
+    if (M == 0) {
+        if (out_status) {
+            SLS_HIP_CHECK(hipMemsetAsync(out_status, 0, 3 * sizeof(uint32_t), (hipStream_t)stream));
+            SLS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(out_status + 3), 1, 1, (hipStream_t)stream));
+        }
+        return SLS_OK;
+    }
+    SLS_REQUIRE(xyz && normals && out_status && scratch && (B == 0 || (blocks && out_field)), "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < poisson_splat_scratch_bytes(M, B)) {
+        set_error("sls_poisson_splat: scratch too small: %zu < %zu", scratch_bytes, poisson_splat_scratch_bytes(M, B));
+        return SLS_E_SCRATCH;
+    }
+    return launch_poisson_splat(M, xyz, normals, B, blocks, voxel_size, origin3, out_field, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_poisson_solve(int B, const int32_t *blocks, const float *field, double alpha, int iterations, double tol,
+                      float *out_chi, uint64_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(B >= 0 && B <= SLS_TSDF_MAX_BLOCKS, "B negative or above SLS_TSDF_MAX_BLOCKS");
+    SLS_REQUIRE(alpha > 0.0 && alpha <= DBL_MAX, "alpha is not a finite number > 0");
+    SLS_REQUIRE(tol >= 0.0 && tol <= DBL_MAX, "tol is not a finite number >= 0");
+    SLS_REQUIRE(iterations >= 0 && iterations <= SLS_POISSON_MAX_ITERATIONS, "iterations outside [0, 1000]");
+    SLS_REQUIRE(out_status, "null pointer (out_status)");
+    if (B > 0) {
+        SLS_REQUIRE(blocks && field && out_chi && scratch, "null pointer");
+        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+        if (scratch_bytes < poisson_solve_scratch_bytes(B)) {
+            set_error("sls_poisson_solve: scratch too small: %zu < %zu", scratch_bytes, poisson_solve_scratch_bytes(B));
+            return SLS_E_SCRATCH;
+        }
+    }
+    return launch_poisson_solve(B, blocks, field, alpha, iterations, tol, out_chi, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_poisson_density(int B, const int32_t *blocks, const float *field, int sweeps, float *out_density, void *scratch,
+                        size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(B >= 0 && B <= SLS_TSDF_MAX_BLOCKS, "B negative or above SLS_TSDF_MAX_BLOCKS");
+    SLS_REQUIRE(sweeps >= 0 && sweeps <= SLS_POISSON_MAX_SWEEPS, "sweeps outside [0, 64]");
+    if (B == 0) return SLS_OK;
+    SLS_REQUIRE(blocks && field && out_density && scratch, "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < poisson_density_scratch_bytes(B)) {
+        set_error("sls_poisson_density: scratch too small: %zu < %zu", scratch_bytes, poisson_density_scratch_bytes(B));
+        return SLS_E_SCRATCH;
+    }
+    return launch_poisson_density(B, blocks, field, sweeps, out_density, scratch, (hipStream_t)stream);
+}
+
 size_t sls_mesh_weld_scratch_bytes(int n_rows) { return mesh_weld_scratch_bytes(n_rows); }
 size_t sls_mesh_clusters_scratch_bytes(int T) { return mesh_clusters_scratch_bytes(T); }
 size_t sls_mesh_filter_scratch_bytes(int V, int T) { return mesh_filter_scratch_bytes(V, T); }

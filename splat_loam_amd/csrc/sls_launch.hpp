@@ -241,6 +241,15 @@ int launch_tsdf_extract_count(int B, const int32_t *blocks, const float *tsdf, c
 int launch_tsdf_extract_emit(int B, const int32_t *blocks, const float *tsdf, const float *weight, float min_weight,
                              double voxel_size, const double *origin, const uint32_t *prefix, uint32_t T, float *triangles,
                              hipStream_t st);
+// ---- sls_poisson.hip (the arguments are checked by the caller, sls_api.hip; origin: host memory) -------------------
+size_t poisson_splat_scratch_bytes(int M, int B);
+int launch_poisson_splat(int M, const float *xyz, const float *normals, int B, const int32_t *blocks, double voxel_size,
+                         const double *origin, float *out_field, uint32_t *out_status, void *scratch, hipStream_t st);
+size_t poisson_solve_scratch_bytes(int B);
+int launch_poisson_solve(int B, const int32_t *blocks, const float *field, double alpha, int iterations, double tol, float *out_chi,
+                         uint64_t *out_status, void *scratch, hipStream_t st);
+size_t poisson_density_scratch_bytes(int B);
+int launch_poisson_density(int B, const int32_t *blocks, const float *field, int sweeps, float *out_density, void *scratch, hipStream_t st);
 // ---- sls_mesh.hip (the arguments are checked by the caller, sls_api.hip) -------------------------------------------
 size_t mesh_weld_scratch_bytes(int64_t n_rows);
 int launch_mesh_weld(int n_rows, const float *soup, float *out_vertices, int32_t *out_index, uint32_t *out_status, void *scratch,

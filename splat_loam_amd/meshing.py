@@ -353,3 +353,90 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
             det["outlier"] = outlier
         return mesh + (det,)
     return mesh
+
+
+@torch.no_grad()
+def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, screening: float = 4.0, iterations: int = 300,
+                 tol: float = 1e-4, min_density=None, min_density_quantile=None, density_sweeps: int = 2, kf_interval: int = -1,
+                 kf_samples: int = 5000, min_opacity: float = 0.5, max_depth_dist: float = 0.1, use_median_depth: bool = False,
+                 seed=None, device="cuda", details: bool = False, image_height=None, image_width=None, keep_clusters=None,
+                 min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
+                 regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
+                 smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False, fill_holes: int = None,
+                 fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0):
+    """The reference's `mesh_poisson` (scene/postprocessing.py) to its end, on the device: `sample_surface` (its options
+    unchanged: `kf_interval`, `kf_samples`, `min_opacity`, `max_depth_dist`, `use_median_depth`, `seed`, `outlier_nb`, ...),
+    then `poisson.reconstruct` on the merged oriented cloud — blocks `margin` around the samples, the splat, the screened
+    solve, marching tetrahedra — the density trim, and the clean-up options of `mesh_tsdf`, passed on to
+    `mesh_ops.clean_mesh` unchanged (`normals=True` returns `(vertices, faces, normals)`).
+
+    What it IS NOT: Open3D's octree solver.  It is a uniform band of `voxel_size` voxels with trilinear splats (see
+    `poisson.py`); `voxel_size` takes the place of the reference's octree `depth`.  `min_density=t` trims by an absolute
+    smoothed density; `min_density_quantile=q` takes t as the q-quantile of the smoothed density over the voxels with
+    W > 0 (torch on the device, over an even stride of them beyond 4 M: plumbing, one more host read).  That is NOT the reference's `poisson_min_density`, which is
+    a quantile of the vertex densities of Open3D's octree: no parity is claimed.  `margin`, `screening`, `iterations`, `tol`
+    and `density_sweeps` are judgements (`poisson.py` says why).
+
+    Host reads: those of `sample_surface`, one for the blocks, one for the solve, one for the triangles.  `details=True` adds
+    dict(blocks, triangles, samples, solve, min_density, stage_ms, volume: the PoissonVolume) and synchronises between the
+    stages to time them."""
+    import time
+
+    from . import poisson, tsdf
+    _check_outlier(outlier_nb, outlier_std)
+    if min_density is not None and min_density_quantile is not None:
+        raise ValueError("give min_density or min_density_quantile, not both")
+    if min_density_quantile is not None and not (0.0 <= float(min_density_quantile) <= 1.0):
+        raise ValueError("min_density_quantile must lie in [0, 1]")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("mesh_poisson runs on a ROCm device; there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    voxel_size = float(voxel_size)
+    margin = poisson.DEFAULT_MARGIN_VOXELS * voxel_size if margin is None else float(margin)
+    stage_ms, t0 = {}, time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        if details:
+            torch.cuda.synchronize(dev)
+            stage_ms[name], t0 = (time.perf_counter() - t0) * 1e3, time.perf_counter()
+    points, cloud_normals, det = sample_surface(graph_dir_or_yaml, kf_interval=kf_interval, kf_samples=kf_samples, min_opacity=min_opacity,
+                                                max_depth_dist=max_depth_dist, use_median_depth=use_median_depth, seed=seed, device=dev,
+                                                details=True, image_height=image_height, image_width=image_width,
+                                                outlier_nb=outlier_nb, outlier_std=outlier_std)
+    lap("sample")
+    outlier = det.get("outlier")
+    volume = poisson.PoissonVolume(tsdf.allocate_blocks(points, voxel_size, margin), voxel_size)
+    lap("allocate")
+    volume.splat(points, cloud_normals)
+    lap("splat")
+    solved = volume.solve(screening=screening, iterations=iterations, tol=tol)
+    lap("solve")
+    threshold = None if min_density is None else float(min_density)
+    if min_density_quantile is not None:
+        dens = volume.density(density_sweeps)
+        seen = dens[volume.field[..., 3] > 0]
+        threshold = float(torch.quantile(seen[:: max(1, seen.numel() // (1 << 22))], float(min_density_quantile))) if seen.numel() else 0.0
+    vertices, faces = volume.extract(min_density=threshold, density_sweeps=density_sweeps)
+    lap("extract")
+    mesh, clean = (vertices, faces), None
+    if keep_clusters is not None or normals or simplify is not None or smooth is not None or fill_holes is not None:
+        from . import mesh_ops
+        *mesh, clean = mesh_ops.clean_mesh(vertices, faces, weld=True, keep_clusters=keep_clusters, min_triangles=min_triangles,
+                                           normals=normals, details=True, simplify=simplify, contraction=contraction,
+                                           regularisation=regularisation, smooth=smooth, smooth_method=smooth_method,
+                                           smooth_weights=smooth_weights, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
+                                           fix_boundary=fix_boundary, fill_holes=fill_holes, fill_max_size=fill_max_size)
+        mesh = tuple(mesh)
+        lap("clean")
+    if details:
+        out = {"blocks": int(volume.blocks.shape[0]), "triangles": int(faces.shape[0]), "samples": int(points.shape[0]), "solve": solved,
+               "min_density": threshold, "frame_ids": det["frame_ids"], "stage_ms": stage_ms, "volume": volume}
+        if clean is not None:
+            out["clean"] = clean
+        if outlier is not None:
+            out["outlier"] = outlier
+        return mesh + (out,)
+    return mesh

@@ -155,26 +155,34 @@ class TsdfVolume:
         `weight >= min_weight`.  `weld=True` merges bit-equal vertices (`torch.unique`; the surface is watertight by
         construction, so shared vertices are bit-equal).  One host read (T).  `details=True` adds dict(counts: the
         triangles per block, a device tensor)."""
-        lib = _abi.lib()
-        dev = self.blocks.device
-        B = int(self.blocks.shape[0])
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            counts = torch.empty((max(B, 1),), dtype=torch.int32, device=dev)
-            prefix = torch.empty((max(B, 1),), dtype=torch.int32, device=dev)
-            status = torch.empty((4,), dtype=torch.int32, device=dev)
-            _abi.check(lib.sls_tsdf_extract_count(B, self.blocks.data_ptr(), self.tsdf.data_ptr(), self.weight.data_ptr(),
-                                                  float(min_weight), counts.data_ptr(), prefix.data_ptr(), status.data_ptr(), st),
-                       "sls_tsdf_extract_count")
-            T = int(status.cpu().numpy().view(np.uint32)[0])            # the one host read
-            tri = torch.empty((T, 3, 3), dtype=torch.float32, device=dev)
-            _abi.check(lib.sls_tsdf_extract_emit(B, self.blocks.data_ptr(), self.tsdf.data_ptr(), self.weight.data_ptr(),
-                                                 float(min_weight), self.voxel_size, self.origin.ctypes.data, prefix.data_ptr(), T,
-                                                 tri.data_ptr(), st), "sls_tsdf_extract_emit")
-        vertices = tri.view(-1, 3)
-        faces = torch.arange(3 * T, dtype=torch.int32, device=dev).view(T, 3)
-        if weld:
-            vertices, faces = weld_soup(vertices)
-        if details:
-            return vertices, faces, {"counts": counts[:B]}
-        return vertices, faces
+        return extract_surface(self.blocks, self.tsdf, self.weight, self.voxel_size, self.origin, min_weight, weld, details)
+
+
+@torch.no_grad()
+def extract_surface(blocks: torch.Tensor, values: torch.Tensor, weight: torch.Tensor, voxel_size: float, origin, min_weight: float = 1.0,
+                    weld: bool = False, details: bool = False):
+    """Marching tetrahedra over any `(B,512)` float32 value / weight arrays on the blocks (sls_tsdf_extract_count / _emit): what
+    `TsdfVolume.extract` returns for its tsdf and `poisson.PoissonVolume.extract` for its chi.  `origin`: three float64 on
+    the host."""
+    lib = _abi.lib()
+    dev = blocks.device
+    B = int(blocks.shape[0])
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        counts = torch.empty((max(B, 1),), dtype=torch.int32, device=dev)
+        prefix = torch.empty((max(B, 1),), dtype=torch.int32, device=dev)
+        status = torch.empty((4,), dtype=torch.int32, device=dev)
+        _abi.check(lib.sls_tsdf_extract_count(B, blocks.data_ptr(), values.data_ptr(), weight.data_ptr(), float(min_weight),
+                                              counts.data_ptr(), prefix.data_ptr(), status.data_ptr(), st), "sls_tsdf_extract_count")
+        T = int(status.cpu().numpy().view(np.uint32)[0])            # the one host read
+        tri = torch.empty((T, 3, 3), dtype=torch.float32, device=dev)
+        _abi.check(lib.sls_tsdf_extract_emit(B, blocks.data_ptr(), values.data_ptr(), weight.data_ptr(), float(min_weight),
+                                             float(voxel_size), origin.ctypes.data, prefix.data_ptr(), T, tri.data_ptr(), st),
+                   "sls_tsdf_extract_emit")
+    vertices = tri.view(-1, 3)
+    faces = torch.arange(3 * T, dtype=torch.int32, device=dev).view(T, 3)
+    if weld:
+        vertices, faces = weld_soup(vertices)
+    if details:
+        return vertices, faces, {"counts": counts[:B]}
+    return vertices, faces
