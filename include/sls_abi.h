@@ -731,6 +731,35 @@ int sls_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz
 int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
                  void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- exact point-to-mesh distance, error colours ---------------------------------------------------------------------
+ * For every query point the nearest TRIANGLE of a mesh (include/sls_meshdist_math.h): with d2(q, f) the header's squared
+ * distance of q to face f, float32,
+ *   out_dist2[q] = min over f of d2(q, f),
+ *   out_face[q] = the LOWEST face index attaining that minimum (optional: may be null),
+ *   out_closest[q] (Mq x 3, optional) = the header's closest point of that face, recomputed once from (q, face),
+ * in the caller's query order: the values of the header, bit for bit, for (query, returned face).  Unsigned: no inside or
+ * outside.  The search is the box sweep of sls_nn_query over an index of triangles whose boxes bound all three vertices;
+ * it prunes with a relative slack of 1e-5 on squared gaps, so the float64 distance to the returned face exceeds the true
+ * minimum by no more than the header's own rounding error.  All pointers DEVICE; vertices (V x 3)
+ * row-major floats, faces (F x 3) int32, query_xyz (Mq x 3).  Queries must be finite: this is not checked, but every
+ * access stays inside the buffers.
+ *   out_status (4 words): [F, faces with a vertex index outside [0, V), faces with a non-finite vertex, 1].  Such faces
+ *       are never dereferenced out of range; when either count is non-zero the other outputs are unspecified.
+ *   scratch: sls_mesh_distance_scratch_bytes(V, F, Mq) bytes (0 for V < 1, F < 1 or Mq < 0), 256-byte aligned; a multiple
+ *       of 256, monotone, and never below SLS_NN_STATS_SCRATCH_BYTES, so sls_nn_stats can follow on the same scratch.
+ * Mq == 0 succeeds and writes only the status (query_xyz and out_dist2 may be null then).  Before anything is enqueued:
+ * SLS_E_ARG for V < 1, F < 1, Mq < 0, a null pointer other than the two optional ones, scratch that is not 256-byte
+ * aligned; SLS_E_SCRATCH for too little scratch.
+ *
+ * sls_error_colors: out_rgb[i] (M x 3 bytes) = the header's error colour of dist2[i] at `truncation` — green at 0, yellow
+ * at half the truncation, red at or beyond it, blue for a NaN.  SLS_E_ARG for M < 0, a null pointer (M > 0), a
+ * truncation that is not finite and > 0.  M == 0 succeeds and writes nothing. */
+size_t sls_mesh_distance_scratch_bytes(int V, int F, int Mq);
+int sls_mesh_distance(int V, const float *vertices, int F, const int32_t *faces, int Mq, const float *query_xyz,
+                      float *out_dist2, int32_t *out_face, float *out_closest, uint32_t *out_status, void *scratch,
+                      size_t scratch_bytes, void *stream);
+int sls_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, void *stream);
+
 /* ---- the k nearest neighbours, outlier removal ---------------------------------------------------------------------
  * sls_nn_query with k answers per query (include/sls_outlier_math.h): query q's list is the min(k, Mt) smallest keys
  * (bits(d2) << 32 | original target index) over ALL targets, ascending — nearer first, then the lower index; a target

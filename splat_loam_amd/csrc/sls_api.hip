@@ -478,6 +478,32 @@ int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, i
     return launch_nn_stats(M, dist2, truncation, threshold, include_truncated, out_stats, scratch, (hipStream_t)stream);
 }
 
+size_t sls_mesh_distance_scratch_bytes(int V, int F, int Mq) { return mesh_distance_scratch_bytes(V, F, Mq); }
+
+int sls_mesh_distance(int V, const float *vertices, int F, const int32_t *faces, int Mq, const float *query_xyz, float *out_dist2,
+                      int32_t *out_face, float *out_closest, uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(V >= 1, "V < 1: the mesh has no vertex");
+    SLS_REQUIRE(F >= 1, "F < 1: the mesh has no face");
+    SLS_REQUIRE(Mq >= 0, "negative Mq");
+    SLS_REQUIRE(vertices && faces && out_status && scratch && ((query_xyz && out_dist2) || Mq == 0), "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < mesh_distance_scratch_bytes(V, F, Mq)) {
+        set_error("sls_mesh_distance: scratch too small: %zu < %zu", scratch_bytes, mesh_distance_scratch_bytes(V, F, Mq));
+        return SLS_E_SCRATCH;
+    }
+    return launch_mesh_distance(V, vertices, F, faces, Mq, query_xyz, out_dist2, out_face, out_closest, out_status, scratch,
+                                (hipStream_t)stream);
+}
+
+int sls_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE((dist2 && out_rgb) || M == 0, "null pointer");
+    SLS_REQUIRE(truncation > 0.0f && truncation <= 3.4028234e38f, "truncation must be finite and > 0");
+    return launch_error_colors(M, dist2, truncation, out_rgb, (hipStream_t)stream);
+}
+
 size_t sls_nn_k_scratch_bytes(int Mt, int Mq, int k) { return nn_k_scratch_bytes(Mt, Mq, k); }
 
 int sls_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,

@@ -8,13 +8,15 @@
 //   3. points gathered in curve order (float4: xyz + original index) and
 //      axis-aligned boxes over runs of 256 consecutive points;
 //   4. one wave per 64 consecutive points, one lane per point: the own box first for a tight bound, then the sweep
-//      (knn_sweep below) over the other boxes; the two-cloud searches (sls_nn_query, sls_nn_query_k) run it too.
+//      (knn_sweep below) over the other boxes; the two-cloud searches (sls_nn_query, sls_nn_query_k) run it too, and so
+//      does the point-to-mesh distance (sls_mesh_distance), whose index holds triangles.
 // Squared distances use the fixed expression fma(dz,dz,fma(dy,dy,dx*dx)), so
 // the result is reproducible bit for bit by a CPU brute force.
 #include <float.h>
 
 #include "sls_geom.hpp"
 #include "../../include/sls_nn_math.h"
+#include "../../include/sls_meshdist_math.h"
 #include "../../include/sls_outlier_math.h"
 
 namespace sls {
@@ -90,20 +92,11 @@ __device__ __forceinline__ void box_merge(float4 &mn, float4 &mx, int off)
              make_float4(__shfl_xor(mx.x, off, 64), __shfl_xor(mx.y, off, 64), __shfl_xor(mx.z, off, 64), 0.0f));
 }
 
-__global__ __launch_bounds__(256) void knn_gather_boxes_kernel(int M, const float *__restrict__ xyz,
-                                                               const uint32_t *__restrict__ sorted_idx,
-                                                               float4 *__restrict__ pts, float4 *__restrict__ boxes,
-                                                               float4 *__restrict__ subboxes)
+// One block per box of kKnnBox == blockDim.x items, (mn, mx) the thread's item's box (none: min > max): the boxes of the
+// block's 8 runs and of the block itself
+__device__ __forceinline__ void store_boxes(float4 mn, float4 mx, float4 *__restrict__ boxes, float4 *__restrict__ subboxes)
 {
-    // one block per box of kKnnBox == blockDim.x points
     __shared__ float4 s_mn[4], s_mx[4];
-    const int j = blockIdx.x * kKnnBox + threadIdx.x;
-    float4 mn = make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f), mx = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
-    if (j < M) {
-        const uint32_t i = sorted_idx[j];
-        mn = mx = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
-        pts[j] = make_float4(mn.x, mn.y, mn.z, __uint_as_float(i));
-    }
 #pragma unroll
     for (int off = 16; off > 0; off >>= 1) box_merge(mn, mx, off);
     if ((threadIdx.x & (kKnnSub - 1)) == 0) {   // tight boxes over runs of 32 points (empty run: min > max)
@@ -121,8 +114,23 @@ __global__ __launch_bounds__(256) void knn_gather_boxes_kernel(int M, const floa
     }
 }
 
+__global__ __launch_bounds__(256) void knn_gather_boxes_kernel(int M, const float *__restrict__ xyz,
+                                                               const uint32_t *__restrict__ sorted_idx,
+                                                               float4 *__restrict__ pts, float4 *__restrict__ boxes,
+                                                               float4 *__restrict__ subboxes)
+{
+    const int j = blockIdx.x * kKnnBox + threadIdx.x;
+    float4 mn = make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f), mx = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
+    if (j < M) {
+        const uint32_t i = sorted_idx[j];
+        mn = mx = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
+        pts[j] = make_float4(mn.x, mn.y, mn.z, __uint_as_float(i));
+    }
+    store_boxes(mn, mx, boxes, subboxes);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
-// The sweep: the ONE exact spatial search of all three query kernels.  One WAVE per 64 curve-consecutive queries (lane =
+// The sweep: the ONE exact spatial search of all four query kernels.  One WAVE per 64 curve-consecutive queries (lane =
 // query), the workgroup IS the wave: no workgroup waits on another, every loop is bounded by the box count.  A kernel sets
 // up its queries and a SEARCH (what a lane keeps of the targets it is shown), scans one box for a first bound (its own, or
 // the one a binary search names) and calls knn_sweep for the others:
@@ -143,17 +151,28 @@ __global__ __launch_bounds__(256) void knn_gather_boxes_kernel(int M, const floa
 //   * sweep_chunk permutes the chunks and a run is listed once: no target is shown twice, which a search that COUNTS what
 //     it meets (the list) needs, and one shown for another lane's sake lies beyond this lane's bound;
 //   * each pad() changes nothing, for the reason given there.
+// (TriBestSearch's d2 is a longer float32 computation than a point's: it may fall below the true distance by 2e-7 of the
+// scale, so there the argument holds up to that — the returned face is a nearest one within the header's own error, and
+// exact duplicates, equal to the bit, still resolve to the lower index wherever the 1e-5 slack covers that error.)
 // ---------------------------------------------------------------------------------------------------------------------
-struct KnnIndex {           // a cloud in curve order (knn_build)
+// The sweep knows an index by its boxes alone; what an ITEM is (a point: float4, xyz + original index; a triangle: TriItem
+// below) matters to the stage, which copies items, and to the search, which reads them.
+template <class ItemT>
+struct SweepIndex {         // M items in curve order, boxes over runs of 256, sub-boxes over runs of 32
+    typedef ItemT Item;
     int M, nboxes;
-    const float4 *__restrict__ pts, *__restrict__ boxes, *__restrict__ subboxes;
+    const Item *__restrict__ pts;
+    const float4 *__restrict__ boxes, *__restrict__ subboxes;
     __device__ __forceinline__ int nsub() const { return (M + kKnnSub - 1) / kKnnSub; }
 };
+typedef SweepIndex<float4> KnnIndex;       // a cloud in curve order (knn_build)
 
-struct SweepLds {           // wave-private: 2 816 bytes
-    float4 run[kKnnSub];
+template <class Item>
+struct SweepLdsOf {         // wave-private: 2 816 bytes for points, 3 840 for triangles
+    Item run[kKnnSub];
     uint32_t box[64], sub[64 * kKnnSubs];
 };
+typedef SweepLdsOf<float4> SweepLds;
 
 __device__ __forceinline__ float rl(float v, int k)
 {
@@ -196,28 +215,30 @@ __device__ __forceinline__ int wave_compact(bool keep, uint32_t v, uint32_t *dst
     return __builtin_popcountll(m);
 }
 
-// point `lane & 31` of run sb for the LDS stage; LOW: loaded by lanes 0..31 alone, the ones that stage it
-template <bool LOW, class Search>
-__device__ __forceinline__ float4 run_point(const KnnIndex &ix, int sb, const Search &s)
+// item `lane & 31` of run sb for the LDS stage; LOW: loaded by lanes 0..31 alone, the ones that stage it
+template <bool LOW, class Index, class Search>
+__device__ __forceinline__ typename Index::Item run_point(const Index &ix, int sb, const Search &s)
 {
     const int r0 = sb * kKnnSub, i = r0 + ((int)threadIdx.x & (kKnnSub - 1));
-    if (LOW && threadIdx.x >= kKnnSub) return make_float4(0, 0, 0, 0);
+    if (LOW && threadIdx.x >= kKnnSub) return typename Index::Item{};
     return i < ix.M ? ix.pts[i] : s.pad(ix.pts, r0);
 }
 
-// a run's 32 points -> LDS, for every lane to scan
-__device__ __forceinline__ void stage(SweepLds &lds, const float4 p)
+// a run's 32 items -> LDS, for every lane to scan
+template <class Item>
+__device__ __forceinline__ void stage(SweepLdsOf<Item> &lds, const Item &p)
 {
     __builtin_amdgcn_wave_barrier();
     if (threadIdx.x < kKnnSub) lds.run[threadIdx.x] = p;
     __syncthreads();
 }
 
-template <class Search>
-__device__ __forceinline__ void knn_sweep(const KnnIndex &ix, const int start_box, const bool live, const float4 me,
+template <class Index, class Search>
+__device__ __forceinline__ void knn_sweep(const Index &ix, const int start_box, const bool live, const float4 me,
                                           const float4 wmn, const float4 wmx, const float4 gmn, const float4 gmx, Search &s,
-                                          SweepLds &lds)
+                                          SweepLdsOf<typename Index::Item> &lds)
 {
+    typedef typename Index::Item Item;
     const int lane = threadIdx.x, nboxes = ix.nboxes, nsub = ix.nsub();   // start_box: scanned by the caller, skipped here
     const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;
     for (int it = 0; it < nchunks; ++it) {
@@ -271,11 +292,11 @@ __device__ __forceinline__ void knn_sweep(const KnnIndex &ix, const int start_bo
                 need = need || within(box_gap2(qp, qp, mnl, mxl), rl(qb2, qi));
             }
             uint64_t todo = __ballot(need && lane < nk);
-            float4 pre = make_float4(0, 0, 0, 0);
+            Item pre = Item{};
             if (todo) pre = run_point<false>(ix, __builtin_amdgcn_readlane((int)sbl, __builtin_ctzll(todo)), s);
             while (todo) {
                 todo &= todo - 1;
-                const float4 cur = pre;
+                const Item cur = pre;
                 if (todo) pre = run_point<false>(ix, __builtin_amdgcn_readlane((int)sbl, __builtin_ctzll(todo)), s);
                 stage(lds, cur);
                 s.scan(lds.run);
@@ -287,9 +308,9 @@ __device__ __forceinline__ void knn_sweep(const KnnIndex &ix, const int start_bo
 // The body of both nn_* kernels behind their set-up, the queries being ANOTHER cloud's: the start box is the one holding
 // the first target whose code is not below the wave's first code; its runs give a first bound; the wave's box is a
 // reduction over its own queries.
-template <class Search>
-__device__ __forceinline__ void nn_search(const KnnIndex &ix, const uint32_t *__restrict__ tkeys, const uint32_t code,
-                                          const bool live, const float4 me, Search &s, SweepLds &lds)
+template <class Index, class Search>
+__device__ __forceinline__ void nn_search(const Index &ix, const uint32_t *__restrict__ tkeys, const uint32_t code,
+                                          const bool live, const float4 me, Search &s, SweepLdsOf<typename Index::Item> &lds)
 {
     int lo = 0, hi = ix.M;                              // lower bound in tkeys[0, M): at most 31 halvings
     while (lo < hi) {
@@ -813,6 +834,243 @@ int launch_nn_stats(int M, const float *dist2, float truncation, float threshold
     hipLaunchKernelGGL(nn_stats_final_kernel, dim3(1), dim3(256), 0, st, M, nblocks, partials,
                        (unsigned long long *)out_stats);
     SLS_LAUNCH_CHECK("nn_stats_final_kernel");
+    return SLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sls_mesh_distance: for every query point the nearest TRIANGLE of a mesh — the squared distance of
+// include/sls_meshdist_math.h and the lowest face index attaining it.  The fourth user of the sweep: an index whose items
+// are triangles (three float4: the vertices, the face index in a.w) in the curve order of their CENTROIDS, and whose boxes
+// and sub-boxes bound ALL THREE vertices of their 256 / 32 triangles — the sweep prunes by "a gap never exceeds the
+// distance to anything in the box", which a box over centroids would break.  A few huge triangles among many small ones
+// make their runs' boxes loose: more runs are scanned, nothing is missed.  The codes live in the cube of the valid faces'
+// vertices, so the queries' codes (knn_morton_kernel, nn_front_sorted_queries: unchanged) live there too.
+// A face with a vertex index outside [0, V) or a non-finite vertex is counted in the status words and indexed as three
+// points at the origin: nothing is read out of range, and the caller discards the outputs.
+// ---------------------------------------------------------------------------------------------------------------------
+struct TriItem { float4 a, b, c; };
+typedef SweepIndex<TriItem> TriIndex;
+
+// the face's vertices; false for an index outside [0, V) (*bad_index) or a non-finite coordinate
+__device__ __forceinline__ bool tri_load(int V, const float *__restrict__ vertices, const int32_t *__restrict__ faces, size_t f,
+                                         float4 &a, float4 &b, float4 &c, bool *bad_index)
+{
+    const int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+    a = b = c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    *bad_index = i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V;
+    if (*bad_index) return false;
+    const float4 ta = make_float4(vertices[3 * (size_t)i0], vertices[3 * (size_t)i0 + 1], vertices[3 * (size_t)i0 + 2], 0.0f);
+    const float4 tb = make_float4(vertices[3 * (size_t)i1], vertices[3 * (size_t)i1 + 1], vertices[3 * (size_t)i1 + 2], 0.0f);
+    const float4 tc = make_float4(vertices[3 * (size_t)i2], vertices[3 * (size_t)i2 + 1], vertices[3 * (size_t)i2 + 2], 0.0f);
+    auto finite = [](const float4 v) { return fabsf(v.x) <= FLT_MAX && fabsf(v.y) <= FLT_MAX && fabsf(v.z) <= FLT_MAX; };
+    if (!(finite(ta) && finite(tb) && finite(tc))) return false;
+    a = ta; b = tb; c = tc;
+    return true;
+}
+
+__global__ void tri_init_kernel(uint32_t *bbox, uint32_t *status, uint32_t F, uint32_t Mq)
+{
+    if (threadIdx.x < 3) bbox[threadIdx.x] = 0xFFFFFFFFu;
+    else if (threadIdx.x < 6) bbox[threadIdx.x] = 0u;
+    else if (threadIdx.x == 6) bbox[6] = F;
+    else if (threadIdx.x == 7) bbox[7] = Mq;
+    else if (threadIdx.x < 12) status[threadIdx.x - 8] = threadIdx.x == 8 ? F : (threadIdx.x == 11 ? 1u : 0u);
+}
+
+// the cube of the valid faces' vertices and the counts of the others (integer atomics: any order gives the same words)
+__global__ __launch_bounds__(256) void tri_bbox_kernel(int V, const float *__restrict__ vertices, int F,
+                                                       const int32_t *__restrict__ faces, uint32_t *bbox, uint32_t *status)
+{
+    float mn[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, mx[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+    uint32_t n_index = 0, n_nonfinite = 0;
+    for (int f = blockIdx.x * 256 + threadIdx.x; f < F; f += gridDim.x * 256) {
+        float4 a, b, c;
+        bool bad_index;
+        if (!tri_load(V, vertices, faces, (size_t)f, a, b, c, &bad_index)) {
+            if (bad_index) ++n_index; else ++n_nonfinite;
+            continue;
+        }
+        mn[0] = fminf(mn[0], fminf(a.x, fminf(b.x, c.x))); mx[0] = fmaxf(mx[0], fmaxf(a.x, fmaxf(b.x, c.x)));
+        mn[1] = fminf(mn[1], fminf(a.y, fminf(b.y, c.y))); mx[1] = fmaxf(mx[1], fmaxf(a.y, fmaxf(b.y, c.y)));
+        mn[2] = fminf(mn[2], fminf(a.z, fminf(b.z, c.z))); mx[2] = fmaxf(mx[2], fmaxf(a.z, fmaxf(b.z, c.z)));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            mn[k] = fminf(mn[k], __shfl_xor(mn[k], off, 64));
+            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], off, 64));
+        }
+        n_index += __shfl_xor(n_index, off, 64);
+        n_nonfinite += __shfl_xor(n_nonfinite, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (mn[k] <= mx[k]) { atomicMin(&bbox[k], f2ord(mn[k])); atomicMax(&bbox[3 + k], f2ord(mx[k])); }
+        }
+        if (n_index) atomicAdd(&status[1], n_index);
+        if (n_nonfinite) atomicAdd(&status[2], n_nonfinite);
+    }
+}
+
+__global__ __launch_bounds__(256) void tri_code_kernel(int V, const float *__restrict__ vertices, int F,
+                                                       const int32_t *__restrict__ faces, const uint32_t *__restrict__ bbox,
+                                                       uint32_t *__restrict__ keys, uint32_t *__restrict__ vals, int key_bits)
+{
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    float4 a, b, c;
+    bool bad_index;
+    tri_load(V, vertices, faces, (size_t)f, a, b, c, &bad_index);
+    const float third = 1.0f / 3.0f;
+    keys[f] = curve_code(((a.x + b.x) + c.x) * third, ((a.y + b.y) + c.y) * third, ((a.z + b.z) + c.z) * third, bbox, key_bits);
+    vals[f] = (uint32_t)f;
+}
+
+__global__ __launch_bounds__(256) void tri_gather_boxes_kernel(int V, const float *__restrict__ vertices, int F,
+                                                               const int32_t *__restrict__ faces,
+                                                               const uint32_t *__restrict__ sorted_idx,
+                                                               TriItem *__restrict__ items, float4 *__restrict__ boxes,
+                                                               float4 *__restrict__ subboxes)
+{
+    const int j = blockIdx.x * kKnnBox + threadIdx.x;
+    float4 mn = make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.0f), mx = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, 0.0f);
+    if (j < F) {
+        const uint32_t f = sorted_idx[j];
+        TriItem t;
+        bool bad_index;
+        tri_load(V, vertices, faces, (size_t)f, t.a, t.b, t.c, &bad_index);
+        mn = make_float4(fminf(t.a.x, fminf(t.b.x, t.c.x)), fminf(t.a.y, fminf(t.b.y, t.c.y)), fminf(t.a.z, fminf(t.b.z, t.c.z)), 0.0f);
+        mx = make_float4(fmaxf(t.a.x, fmaxf(t.b.x, t.c.x)), fmaxf(t.a.y, fmaxf(t.b.y, t.c.y)), fmaxf(t.a.z, fmaxf(t.b.z, t.c.z)), 0.0f);
+        t.a.w = __uint_as_float(f);
+        items[j] = t;
+    }
+    store_boxes(mn, mx, boxes, subboxes);
+}
+
+struct TriBestSearch {
+    const float4 me;
+    uint64_t best;
+    __device__ __forceinline__ float bound() const { return sls_nn_key_dist2(best); }
+    // a copy of the run's first triangle, as BestKeySearch pads: a sentinel at 1e30 would give inf - inf inside the arithmetic
+    __device__ __forceinline__ TriItem pad(const TriItem *__restrict__ items, int r0) const { return items[r0]; }
+    __device__ __forceinline__ void scan(const TriItem *s_run)
+    {
+#pragma unroll 2
+        for (int k = 0; k < kKnnSub; ++k) {
+            const float4 a = s_run[k].a, b = s_run[k].b, c = s_run[k].c;
+            const float d2 = sls_meshdist_triangle(me.x, me.y, me.z, a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, nullptr);
+            const uint64_t key = sls_nn_key(d2, __float_as_uint(a.w));
+            best = key < best ? key : best;
+        }
+    }
+};
+
+__global__ __launch_bounds__(64) void tri_query_kernel(int F, int nboxes, const TriItem *__restrict__ items,
+                                                       const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                       const uint32_t *__restrict__ tkeys, int Mq,
+                                                       const float4 *__restrict__ qpts, const uint32_t *__restrict__ qkeys, int V,
+                                                       const float *__restrict__ vertices, const int32_t *__restrict__ faces,
+                                                       float *__restrict__ out_dist2, int32_t *__restrict__ out_face,
+                                                       float *__restrict__ out_closest)
+{
+    __shared__ SweepLdsOf<TriItem> lds;
+    const TriIndex ix = { F, nboxes, items, boxes, subboxes };
+    const int q0 = blockIdx.x * 64, q = q0 + threadIdx.x;   // (the grid has ceil(Mq / 64) waves: q0 < Mq)
+    const bool live = q < Mq;
+    const float4 me = qpts[live ? q : Mq - 1];
+    TriBestSearch s = { me, SLS_NN_KEY_NONE };
+    nn_search(ix, tkeys, qkeys[q0], live, me, s, lds);
+    if (live) {
+        const size_t i = __float_as_uint(me.w);
+        const uint32_t face = sls_nn_key_index(s.best);
+        out_dist2[i] = sls_nn_key_dist2(s.best);
+        if (out_face) out_face[i] = (int32_t)face;
+        if (out_closest) {
+            // the winner's closest point, recomputed once from (q, face); a query that met only NaN holds no face
+            float cp[3] = { me.x, me.y, me.z };
+            float4 a, b, c;
+            bool bad_index;
+            if (face < (uint32_t)F && tri_load(V, vertices, faces, (size_t)face, a, b, c, &bad_index))
+                sls_meshdist_triangle(me.x, me.y, me.z, a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, cp);
+            out_closest[3 * i] = cp[0];
+            out_closest[3 * i + 1] = cp[1];
+            out_closest[3 * i + 2] = cp[2];
+        }
+    }
+}
+
+// scratch: sls_nn_query's for (F, Mq) — codes, sorter, boxes, the queries' buffers; its float4 per target stays unused —
+// then the triangles
+static NnScratch mesh_distance_layout(int F, int Mq, void *base, TriItem **items)
+{
+    NnScratch s = nn_layout(F, Mq, base);
+    Arena a(base);
+    a.off = (s.total + 255) & ~(size_t)255;
+    *items = a.take<TriItem>((size_t)F);
+    s.total = a.off;
+    return s;
+}
+
+size_t mesh_distance_scratch_bytes(int V, int F, int Mq)
+{
+    TriItem *items;
+    return (V >= 1 && F >= 1 && Mq >= 0) ? mesh_distance_layout(F, Mq, nullptr, &items).total : 0;
+}
+
+int launch_mesh_distance(int V, const float *vertices, int F, const int32_t *faces, int Mq, const float *query_xyz,
+                         float *out_dist2, int32_t *out_face, float *out_closest, uint32_t *out_status, void *scratch,
+                         hipStream_t st)
+{
+    ScopedTimer tm(T_KNN, st);
+    NnFront f;
+    TriItem *items;
+    const NnScratch &s = f.s = mesh_distance_layout(F, Mq, scratch, &items);
+    const int nb = (F + 255) / 256, key_bits = knn_key_bits(F), nboxes = (F + kKnnBox - 1) / kKnnBox;
+    hipLaunchKernelGGL(tri_init_kernel, dim3(1), dim3(64), 0, st, s.t.bbox, out_status, (uint32_t)F, (uint32_t)Mq);
+    SLS_LAUNCH_CHECK("tri_init_kernel");
+    hipLaunchKernelGGL(tri_bbox_kernel, dim3(nb < 256 ? nb : 256), dim3(256), 0, st, V, vertices, F, faces, s.t.bbox, out_status);
+    SLS_LAUNCH_CHECK("tri_bbox_kernel");
+    if (Mq == 0) return SLS_OK;                         // the status alone
+    hipLaunchKernelGGL(tri_code_kernel, dim3(nb), dim3(256), 0, st, V, vertices, F, faces, s.t.bbox, s.t.keys, s.t.vals, key_bits);
+    SLS_LAUNCH_CHECK("tri_code_kernel");
+    int which = 0;
+    int rc = radix_sort_pairs_u32(s.t.keys, s.t.vals, s.t.keys_tmp, s.t.vals_tmp, s.t.bbox + 6, (uint32_t)F, key_bits, s.t.sort,
+                                  s.t.sort_bytes, &which, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tri_gather_boxes_kernel, dim3(nboxes), dim3(kKnnBox), 0, st, V, vertices, F, faces,
+                       which ? s.t.vals_tmp : s.t.vals, items, s.t.boxes, s.t.subboxes);
+    SLS_LAUNCH_CHECK("tri_gather_boxes_kernel");
+    f.tkeys = which ? s.t.keys_tmp : s.t.keys;
+    hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, s.t.bbox, s.qkeys, s.qvals,
+                       key_bits);
+    SLS_LAUNCH_CHECK("knn_morton_kernel");
+    rc = nn_front_sorted_queries(F, Mq, query_xyz, st, &f);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tri_query_kernel, dim3((Mq + 63) / 64), dim3(64), 0, st, F, nboxes, items, s.t.boxes, s.t.subboxes, f.tkeys,
+                       Mq, f.qpts, f.qkeys, V, vertices, faces, out_dist2, out_face, out_closest);
+    SLS_LAUNCH_CHECK("tri_query_kernel");
+    return SLS_OK;
+}
+
+__global__ __launch_bounds__(256) void error_colors_kernel(int M, const float *__restrict__ dist2, float truncation,
+                                                           uint8_t *__restrict__ out_rgb)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)M) return;
+    uint8_t rgb[3];
+    sls_error_color(dist2[i], truncation, rgb);
+    out_rgb[3 * i] = rgb[0];
+    out_rgb[3 * i + 1] = rgb[1];
+    out_rgb[3 * i + 2] = rgb[2];
+}
+
+int launch_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, hipStream_t st)
+{
+    if (M == 0) return SLS_OK;
+    hipLaunchKernelGGL(error_colors_kernel, dim3((M + 255) / 256), dim3(256), 0, st, M, dist2, truncation, out_rgb);
+    SLS_LAUNCH_CHECK("error_colors_kernel");
     return SLS_OK;
 }
 

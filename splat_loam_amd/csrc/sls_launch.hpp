@@ -203,6 +203,13 @@ struct NnIndexRef {
 int nn_index_target(int Mt, const float *target_xyz, int Mq, void *scratch, hipStream_t st, NnIndexRef *ref);
 int nn_index_query(int Mt, int Mq, const float *query_xyz, const NnIndexRef &ref, float *out_dist2, int32_t *out_index, void *scratch,
                    hipStream_t st);
+// the nearest triangle of a mesh (sls_knn.hip: the same sweep over an index of triangles) and the error colours; the
+// arguments are checked by the caller, sls_api.hip.  Mq == 0: only the status is written
+size_t mesh_distance_scratch_bytes(int V, int F, int Mq);
+int launch_mesh_distance(int V, const float *vertices, int F, const int32_t *faces, int Mq, const float *query_xyz,
+                         float *out_dist2, int32_t *out_face, float *out_closest, uint32_t *out_status, void *scratch,
+                         hipStream_t st);
+int launch_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, hipStream_t st);
 // ---- sls_icp.hip (the arguments are checked by the caller, sls_api.hip; init_pose12: host memory) ------------------
 size_t cloud_icp_scratch_bytes(int Ms, int Mt);
 int launch_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_xyz, const float *target_normals,

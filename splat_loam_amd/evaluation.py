@@ -13,8 +13,16 @@ Open3D is not a dependency: voxel_down_sample and sample_points_uniformly are re
 (include/sls_cloud_math.h) with the two things Open3D leaves open — the order of the voxels, the random stream — defined
 here, and pinned against NumPy restatements (tests/cloud_ref.py), not against Open3D itself.
 
+`point_to_mesh` is the exact distance of points to a triangle mesh (sls_mesh_distance: the same box sweep over an index
+of triangles, include/sls_meshdist_math.h) — unsigned, no BVH, not compared against Open3D's RaycastingScene.  With it
+`evaluate_recon(completeness="exact")` measures every reference point against the mesh itself, not against samples
+of it, and `error_map=True` returns where the mesh is wrong: the error map the reference's `evaluate_recon` announces
+and raises NotImplementedError for (eval_utils.py:93-94, 131-133) — per-vertex distances to the reference cloud and
+per-reference-point distances to the mesh, coloured by `error_colors` (sls_error_colors: green, yellow at half the
+truncation, red at or beyond it).  The defaults of both are off and change nothing.
+
 Not done here: reading files (splat_loam_amd/ply_io.py: load_point_cloud, load_mesh; tools/eval_recon.py puts the two
-together) and the reference's error map, which it does not implement either.
+together).
 """
 from __future__ import annotations
 
@@ -543,6 +551,11 @@ def cloud_metrics(reference: torch.Tensor, estimate: torch.Tensor, threshold: fl
         _abi.check(lib.sls_nn_stats(Mr, d_com.data_ptr(), float(truncation_com), float(threshold), 1,
                                     words.data_ptr() + 32, aligned, nbytes, st), "sls_nn_stats")
         w = words.cpu().tolist()                                  # the one host read
+    return _metrics(w, threshold, truncation_acc, truncation_com)
+
+
+def _metrics(w, threshold, truncation_acc, truncation_com) -> dict:
+    """cloud_metrics' dict from the eight words of its two sls_nn_stats calls."""
     bits = lambda v: struct.unpack("<d", struct.pack("<q", v))[0]
     n_acc, below_acc, sum_acc = w[0], w[1], bits(w[2])
     n_com, below_com, sum_com = w[4], w[5], bits(w[6])
@@ -681,6 +694,135 @@ def sample_mesh(vertices: torch.Tensor, faces: torch.Tensor, n: int, seed: int =
     return (out, face) if return_faces else out
 
 
+def _mesh_distance_enqueue(lib, points, vertices, faces, want_face: bool, want_closest: bool, st):
+    """sls_mesh_distance without a host read: (dist2 (M,), face (M,) | None, closest (M,3) | None, status (4,) int32,
+    scratch) — the scratch serves a following sls_nn_stats."""
+    dev = vertices.device
+    V, F, M = int(vertices.shape[0]), int(faces.shape[0]), int(points.shape[0])
+    if V < 1 or F < 1:
+        raise ValueError("the mesh needs at least one vertex and one face")
+    dist2 = torch.empty((M,), dtype=torch.float32, device=dev)
+    face = torch.empty((M,), dtype=torch.int32, device=dev) if want_face else None
+    closest = torch.empty((M, 3), dtype=torch.float32, device=dev) if want_closest else None
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    scratch = _scratch_bytes(lib.sls_mesh_distance_scratch_bytes(V, F, M), dev)
+    _abi.check(lib.sls_mesh_distance(V, vertices.data_ptr(), F, faces.data_ptr(), M, points.data_ptr() if M else None,
+                                     dist2.data_ptr() if M else None, face.data_ptr() if (want_face and M) else None,
+                                     closest.data_ptr() if (want_closest and M) else None, status.data_ptr(), scratch[1],
+                                     scratch[2], st), "sls_mesh_distance")
+    return dist2, face, closest, status, scratch
+
+
+def _mesh_distance_status(words, what: str) -> None:
+    _, n_index, n_nonfinite = (int(w) & 0xFFFFFFFF for w in words[:3])
+    if n_index:
+        raise ValueError(f"{what}: {n_index} faces have a vertex index outside the vertices")
+    if n_nonfinite:
+        raise ValueError(f"{what}: {n_nonfinite} faces have a vertex with a non-finite coordinate")
+
+
+def point_to_mesh(points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, return_face: bool = True,
+                  return_closest: bool = False):
+    """The exact, UNSIGNED distance of every row of `points` (M,3) to the triangle mesh (`vertices` (V,3), `faces` (F,3)
+    integers): `dist2` (M,) float32, the squared distance to the nearest face as include/sls_meshdist_math.h defines it
+    (the minimum over points that lie on the triangle: its three edge segments and the plane's foot point where that
+    falls inside; a zero-area face is its segment or its point); with `return_face` (the default) also `face` (M,)
+    int32, the lowest face index among those of equal dist2 bits; with `return_closest` also `closest` (M,3) float32,
+    the nearest point of that face.  Returned as `dist2`, `(dist2, face)`, `(dist2, closest)` or `(dist2, face, closest)`.
+
+    dist2 and closest are the bits of the header compiled for the host for (point, returned face); the float64
+    distance to the returned face exceeds the true minimum over all faces by no more than 1e-5 of the scale (the
+    largest distance from the point to that face's vertices; measured: DESIGN.md section 7).  Outside a convex mesh a
+    point nearest to a shared edge or vertex has several faces at the same true distance: which of them is named is
+    decided by float32 bits, then by the lower index.  One native call (sls_mesh_distance), one host read (the status
+    words), no float atomics: the same input gives the same bits on every run.
+
+    It is not a signed distance (that needs pseudo-normals at edges and vertices) and there is no BVH: the faces are
+    indexed in the curve order of their centroids, in runs of 32 whose boxes bound all three vertices, so a few huge
+    triangles among many small ones make their runs' boxes loose — that costs time, never exactness.  Device tensors
+    only; the points must be finite (not checked; every access stays inside the buffers).
+    ValueError: a face with a vertex index outside the vertices or with a non-finite vertex; an empty mesh."""
+    points = _cloud(points, "points")
+    vertices, faces = _mesh(vertices, faces)
+    if points.device != vertices.device:
+        raise ValueError("the points and the mesh must live on the same device")
+    lib = _abi.lib()
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        dist2, face, closest, status, _ = _mesh_distance_enqueue(lib, points, vertices, faces, bool(return_face),
+                                                                 bool(return_closest), st)
+        _mesh_distance_status(status.cpu().tolist(), "point_to_mesh")          # the one host read
+    res = (dist2,) + ((face,) if return_face else ()) + ((closest,) if return_closest else ())
+    return res[0] if len(res) == 1 else res
+
+
+def _check_truncation(truncation) -> float:
+    try:
+        t = ctypes.c_float(float(truncation)).value                             # what the native call will see
+    except (TypeError, ValueError):
+        raise ValueError("truncation must be a number") from None
+    if not 0.0 < t < math.inf:
+        raise ValueError("truncation must be finite and > 0 as a float32")
+    return t
+
+
+def error_colors(dist2: torch.Tensor, truncation: float) -> torch.Tensor:
+    """(M,3) uint8 RGB of squared distances (M,) at `truncation` metres (include/sls_meshdist_math.h): with
+    t = sqrt(dist2) / truncation in float32 and L = 255 for t >= 1, else int(t * 256): (2 L, 255, 0) up to L = 127, then
+    (255, 2 (255 - L), 0) — green is good, yellow is at half the truncation, red at or beyond it; a NaN gives blue
+    (0, 0, 255).  One native call (sls_error_colors), no host read."""
+    if not isinstance(dist2, torch.Tensor) or not dist2.is_cuda:
+        raise RuntimeError("dist2 must be a ROCm device tensor (libsls_hip.so); there is no CPU fallback")
+    if dist2.dim() != 1:
+        raise ValueError("dist2 must be (M,)")
+    t = _check_truncation(truncation)
+    dist2 = dist2.detach().float().contiguous()
+    M = int(dist2.shape[0])
+    lib = _abi.lib()
+    with torch.cuda.device(dist2.device):
+        st = torch.cuda.current_stream(dist2.device).cuda_stream
+        rgb = torch.empty((M, 3), dtype=torch.uint8, device=dist2.device)
+        _abi.check(lib.sls_error_colors(M, dist2.data_ptr() if M else None, t, rgb.data_ptr() if M else None, st),
+                   "sls_error_colors")
+    return rgb
+
+
+def _recon_metrics(reference, estimate, vertices, faces, exact: bool, error_map: bool, threshold, truncation_acc,
+                   truncation_com):
+    """evaluate_recon's metric block where the completeness is exact or the error map is wanted: cloud_metrics' calls with
+    sls_mesh_distance (reference points against the mesh, then the unchanged sls_nn_stats) and, for the map, one more
+    sls_nn_query (the mesh's vertices against the reference cloud) and two sls_error_colors.  One host read: the eight
+    metric words and the four status words of sls_mesh_distance together.  (metrics, error map | None)"""
+    Mr, Me = int(reference.shape[0]), int(estimate.shape[0])
+    lib = _abi.lib()
+    dev = reference.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        scratch = _scratch(lib, max(Mr, Me), max(Mr, Me), dev)
+        _, aligned, nbytes = scratch
+        words = torch.empty((8,), dtype=torch.int64, device=dev)
+        d_acc, _ = _query(lib, reference, estimate, False, scratch, st)
+        _abi.check(lib.sls_nn_stats(Me, d_acc.data_ptr(), float(truncation_acc), float(threshold), 0, words.data_ptr(),
+                                    aligned, nbytes, st), "sls_nn_stats")
+        d_mesh, _, _, status, (_, m_aligned, m_nbytes) = _mesh_distance_enqueue(lib, reference, vertices, faces, False, False, st)
+        if exact:
+            _abi.check(lib.sls_nn_stats(Mr, d_mesh.data_ptr(), float(truncation_com), float(threshold), 1,
+                                        words.data_ptr() + 32, m_aligned, m_nbytes, st), "sls_nn_stats")
+        else:
+            d_com, _ = _query(lib, estimate, reference, False, scratch, st)
+            _abi.check(lib.sls_nn_stats(Mr, d_com.data_ptr(), float(truncation_com), float(threshold), 1,
+                                        words.data_ptr() + 32, aligned, nbytes, st), "sls_nn_stats")
+        emap = None
+        if error_map:
+            d_vert, _ = nearest(reference, vertices, return_index=False)
+            emap = {"vertices": vertices, "vertex_dist2": d_vert, "vertex_colors": error_colors(d_vert, truncation_acc),
+                    "points": reference, "point_dist2": d_mesh, "point_colors": error_colors(d_mesh, truncation_com)}
+        w = torch.cat([words, status.to(torch.int64)]).cpu().tolist()          # the one host read
+    _mesh_distance_status(w[8:12], "evaluate_recon")
+    return _metrics(w[:8], threshold, truncation_acc, truncation_com), emap
+
+
 ALIGN_MAX_POINTS = 200_000
 
 
@@ -703,7 +845,8 @@ def _align_vertices(reference: torch.Tensor, vertices: torch.Tensor, align) -> d
 
 def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, down_sample_res: float = 0.02,
                    threshold: float = 0.2, truncation_acc: float = 0.5, truncation_com: float = 0.5,
-                   crop_to_reference: bool = False, mesh_sample_point: int = 10_000_000, seed: int = 0, align=None) -> dict:
+                   crop_to_reference: bool = False, mesh_sample_point: int = 10_000_000, seed: int = 0, align=None,
+                   completeness: str = "sampled", error_map: bool = False) -> dict:
     """The reference's `evaluate_recon` (utils/eval_utils.py:67-154) for a reference cloud and an estimated mesh already
     on the device, with its dictionary keys and units: sample `mesh_sample_point` points from the mesh, voxel-down-sample
     both clouds at `down_sample_res` (skipped where that is <= 0, as in the reference), then the metric block of
@@ -722,7 +865,27 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
     onto the reference cloud before anything is sampled: on at most `max_points` of them, a seeded device draw with
     replacement where there are more; every vertex is moved by the pose found, and the metrics are those of the moved
     mesh.  The result gets one more key, "Alignment": what `register_icp` returns.  One more host read (its status
-    words), and with the plane method and no normals the `estimate_normals` call on the reference cloud."""
+    words), and with the plane method and no normals the `estimate_normals` call on the reference cloud.
+
+    `completeness` (default "sampled": nothing of what follows happens, the same calls, the same two host reads, the
+    same bits): "exact" measures every reference point, after its voxel down-sampling, against the MESH ITSELF
+    (`point_to_mesh`: sls_mesh_distance, then the unchanged sls_nn_stats) instead of against its nearest sample.  The
+    sampled value depends on `seed` and on `mesh_sample_point` and is biased upwards by the sample spacing; the exact value
+    depends on neither.  (A sample lies ON the surface, so with `down_sample_res <= 0` no exact distance exceeds its
+    sampled one; voxel-averaged samples leave a curved surface a little, and there that holds for the means.)  The
+    accuracy side stays sampled: it is points of the surface against a cloud.  With `crop_to_reference` the distance is
+    to the faces the sampler keeps, selected with torch on the device: one more host synchronisation (the boolean
+    index), none otherwise.  Still two host reads: the status words of sls_mesh_distance ride with the metric words.
+
+    `error_map=True` adds the key "ErrorMap", a dict of device tensors: `vertices` (V,3) (moved, with `align`; all of
+    them, also with `crop_to_reference`), `vertex_dist2` (V,) their squared distances to the evaluated reference cloud
+    (`nearest`), `vertex_colors` (V,3) uint8 = `error_colors(vertex_dist2, truncation_acc)`; `points` (the evaluated
+    reference points), `point_dist2` their EXACT squared distances to the mesh, whatever `completeness` is, and
+    `point_colors` = `error_colors(point_dist2, truncation_com)`.  No further host read."""
+    if completeness not in ("sampled", "exact"):
+        raise ValueError('completeness must be "sampled" or "exact"')
+    if not isinstance(error_map, bool):
+        raise ValueError("error_map must be True or False")
     reference = _cloud(reference_points, "reference_points")
     vertices, faces = _mesh(vertices, faces)
     if reference.device != vertices.device:
@@ -758,8 +921,19 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
         if down:
             estimate = estimate[:_voxel_status(w[4:8], "evaluate_recon: the sampled mesh")]
             reference = reference[:_voxel_status(w[8:12], "evaluate_recon: the reference cloud")]
-    m = cloud_metrics(reference, estimate, threshold=threshold, truncation_acc=truncation_acc,
-                      truncation_com=truncation_com)                        # host read 2 of 2
+    emap = None
+    if completeness == "sampled" and not error_map:
+        m = cloud_metrics(reference, estimate, threshold=threshold, truncation_acc=truncation_acc,
+                          truncation_com=truncation_com)                    # host read 2 of 2
+    else:
+        if reference.shape[0] == 0 or estimate.shape[0] == 0:
+            raise ValueError("both clouds need at least one point")
+        kept = faces
+        if box is not None:                                                 # the faces the sampler keeps (closed box)
+            inside = ((vertices >= box[:3]) & (vertices <= box[3:])).all(1)
+            kept = faces[inside[faces.long()].all(1)].contiguous()          # (a host synchronisation: the boolean index)
+        m, emap = _recon_metrics(reference, estimate, vertices, kept, completeness == "exact", error_map, threshold,
+                                 truncation_acc, truncation_com)            # host read 2 of 2
     out = {
         "MAE_accuracy (cm)": m["accuracy_m"] * 100, "MAE_completeness (cm)": m["completeness_m"] * 100,
         "Chamfer_L1 (cm)": m["chamfer_l1_m"] * 100, "Precision [Accuracy] (%)": m["precision"] * 100.0,
@@ -769,4 +943,6 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
     }
     if alignment is not None:
         out["Alignment"] = alignment
+    if emap is not None:
+        out["ErrorMap"] = emap
     return out

@@ -16,6 +16,7 @@ import numpy as np
 PROPS = ["x", "y", "z", "opacity", "scale_0", "scale_1", "rot_0", "rot_1", "rot_2", "rot_3",
          "f_dc_0", "f_dc_1", "f_dc_2"]
 CLOUD_PROPS = ["x", "y", "z", "nx", "ny", "nz"]
+COLOR_PROPS = ["red", "green", "blue"]
 
 
 def save_ply(path, xyz, opacity_raw, scaling_raw, rotation_raw) -> None:
@@ -33,9 +34,23 @@ def save_ply(path, xyz, opacity_raw, scaling_raw, rotation_raw) -> None:
         f.write(data.tobytes())
 
 
-def save_point_cloud(path, points, normals) -> None:
+def _colored(rows, names, colors):
+    """(vertex bytes, header lines) of float32 columns followed by `uchar red green blue` (e.g. `evaluation.error_colors`)"""
+    colors = np.asarray(colors.detach().cpu().numpy() if hasattr(colors, "detach") else colors)
+    if colors.dtype != np.uint8 or colors.shape != (len(rows), 3):
+        raise ValueError("colors must be uint8 of shape (rows, 3)")
+    rec = np.empty(len(rows), np.dtype([(p, "<f4") for p in names] + [(c, "u1") for c in COLOR_PROPS]))
+    for k, p in enumerate(names):
+        rec[p] = rows[:, k]
+    for k, c in enumerate(COLOR_PROPS):
+        rec[c] = colors[:, k]
+    return rec.tobytes(), "".join(f"property float {p}\n" for p in names) + "".join(f"property uchar {c}\n" for c in COLOR_PROPS)
+
+
+def save_point_cloud(path, points, normals, colors=None) -> None:
     """An oriented point cloud (`meshing.sample_surface`) as binary little-endian PLY: one `vertex` element with float32
-    `x y z nx ny nz`, the property names Open3D's `read_point_cloud` looks up — the input of Poisson reconstruction."""
+    `x y z nx ny nz`, the property names Open3D's `read_point_cloud` looks up — the input of Poisson reconstruction.
+    `colors` (N,3) uint8: the element gains `uchar red green blue`; without them the bytes are the same as ever."""
     def host(a):
         return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
     points, normals = host(points).reshape(-1, 3), host(normals).reshape(-1, 3)
@@ -44,19 +59,25 @@ def save_point_cloud(path, points, normals) -> None:
     n = points.shape[0]
     data = np.concatenate([points, normals], axis=1).astype("<f4")
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % n
-    header += "".join(f"property float {p}\n" for p in CLOUD_PROPS) + "end_header\n"
+    if colors is None:
+        body, props = data.tobytes(), "".join(f"property float {p}\n" for p in CLOUD_PROPS)
+    else:
+        body, props = _colored(data, CLOUD_PROPS, colors)
+    header += props + "end_header\n"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
-        f.write(data.tobytes())
+        f.write(body)
 
 
-def save_mesh(path, vertices, faces, normals=None) -> None:
+def save_mesh(path, vertices, faces, normals=None, colors=None) -> None:
     """A triangle mesh (`tsdf.TsdfVolume.extract`, `meshing.mesh_tsdf`) as binary little-endian PLY: a `vertex` element
     with float32 `x y z`, then a `face` element with `list uchar int vertex_indices` — what `load_mesh` reads back bit for
     bit, and the layout Open3D and MeshLab write for a plain triangle mesh.  `normals` (V,3), e.g. of
     `mesh_ops.vertex_normals`: the vertex element gains float32 `nx ny nz` (`load_point_cloud` returns them; `load_mesh`
-    skips them); without them the bytes are the same as ever."""
+    skips them); without them the bytes are the same as ever.  `colors` (V,3) uint8, e.g. of `evaluation.error_colors`:
+    the vertex element gains `uchar red green blue` behind the floats (what MeshLab and Open3D show as vertex colours);
+    without them, again, the same bytes."""
     def host(a, dt):
         return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=dt)
     vertices, faces = host(vertices, np.float32).reshape(-1, 3), host(faces, np.int64).reshape(-1, 3)
@@ -71,12 +92,16 @@ def save_mesh(path, vertices, faces, normals=None) -> None:
     rec = np.empty(len(faces), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
     rec["n"], rec["i"] = 3, faces
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(vertices)
-    header += "".join(f"property float {p}\n" for p in props)
+    if colors is None:
+        body, lines = vertices.astype("<f4").tobytes(), "".join(f"property float {p}\n" for p in props)
+    else:
+        body, lines = _colored(vertices, list(props), colors)
+    header += lines
     header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(faces)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
-        f.write(vertices.astype("<f4").tobytes())
+        f.write(body)
         f.write(rec.tobytes())
 
 
@@ -133,11 +158,18 @@ def load_ply(path) -> dict:
                 scaling=np.stack([col(s) for s in scale_names], 1), rotation=np.stack([col(s) for s in rot_names], 1))
 
 
-def load_point_cloud(path):
+def _colors(rec, names):
+    """(N,3) uint8 of `red green blue` where the vertex element has all three as uchar, else None"""
+    if all(c in names and rec.dtype[c] == np.uint8 for c in COLOR_PROPS):
+        return np.stack([np.asarray(rec[c]) for c in COLOR_PROPS], 1)
+    return None
+
+
+def load_point_cloud(path, return_colors: bool = False):
     """`(points (N,3) float32, normals (N,3) float32 | None)` of a binary little-endian PLY point cloud: `x y z` as float
     or double (scan exports often store doubles; they are rounded to float32 once), `nx ny nz` where the file has all
     three.  Reads what `save_point_cloud` writes; other vertex properties and the elements behind the vertices (faces)
-    are ignored."""
+    are ignored.  `return_colors=True`: a third item, `uchar red green blue` as (N,3) uint8, or None without them."""
     rec, names = _read_vertices(path)
     for p in ("x", "y", "z"):
         if p not in names:
@@ -147,7 +179,7 @@ def load_point_cloud(path):
     col = lambda name: np.asarray(rec[name], dtype=np.float32)
     points = np.stack([col("x"), col("y"), col("z")], 1)
     normals = np.stack([col("nx"), col("ny"), col("nz")], 1) if all(p in names for p in ("nx", "ny", "nz")) else None
-    return points, normals
+    return (points, normals, _colors(rec, names)) if return_colors else (points, normals)
 
 
 def _xyz(path, rec, names):
@@ -159,15 +191,16 @@ def _xyz(path, rec, names):
     return np.stack([np.asarray(rec[p], dtype=np.float32) for p in ("x", "y", "z")], 1)
 
 
-def load_mesh(path):
+def load_mesh(path, return_colors: bool = False):
     """`(vertices (V,3) float32, faces (F,3) int32)` of a binary little-endian PLY triangle mesh, as Open3D writes one
     (a Poisson reconstruction): a `vertex` element with `x y z` as float or double (other vertex properties are
     skipped), then one `face` element whose only property is `list uchar int|uint vertex_indices` (or `vertex_index`).
     Every face must be a triangle; an ASCII or big-endian file, a face with another vertex count or a face element with
     further properties is refused with a ValueError.  Indices are not range-checked here (sls_mesh_sample counts the
-    faces that point outside the vertices); a uint index above 2^31 - 1 is refused."""
+    faces that point outside the vertices); a uint index above 2^31 - 1 is refused.  `return_colors=True`: a third item,
+    the vertices' `uchar red green blue` as (V,3) uint8, or None without them."""
     blob, offset, elements = _parse_header(path)
-    vertices = faces = None
+    vertices = faces = colors = None
     for name, count, props in elements:
         lists = [tok for _, kind, tok in props if kind is None]
         if name == "face":
@@ -192,10 +225,12 @@ def load_mesh(path):
             raise ValueError(f"{path}: element {name} with list properties comes before the faces")
         rec_t = np.dtype([(p, k) for p, k, _ in props])
         if name == "vertex":
-            vertices = _xyz(path, np.frombuffer(blob, dtype=rec_t, count=count, offset=offset), [p for p, _, _ in props])
+            vrec = np.frombuffer(blob, dtype=rec_t, count=count, offset=offset)
+            vertices = _xyz(path, vrec, [p for p, _, _ in props])
+            colors = _colors(vrec, [p for p, _, _ in props])
         offset += count * rec_t.itemsize
     if vertices is None:
         raise ValueError(f"{path}: no vertex element in front of the faces")
     if faces is None:
         raise ValueError(f"{path}: no face element")
-    return vertices, faces
+    return (vertices, faces, colors) if return_colors else (vertices, faces)

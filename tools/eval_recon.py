@@ -5,6 +5,7 @@ mesh, on the device (splat_loam_amd.evaluation.evaluate_recon), one JSON line wi
     python tools/eval_recon.py REFERENCE.ply MESH.ply [--down-sample-res 0.02] [--threshold 0.2] [--truncation-acc 0.5]
                                [--truncation-com 0.5] [--mesh-sample-point 10000000] [--seed 0] [--crop-to-reference]
                                [--align D [--align-iterations 30] [--align-method plane|point]]
+                               [--exact-completeness] [--error-map PREFIX]
 
 REFERENCE.ply: binary little-endian PLY with `x y z` as float or double.  MESH.ply: binary little-endian PLY with a
 `vertex` element and one `face` element of triangles (`list uchar int vertex_indices`: what Open3D writes for a Poisson
@@ -13,7 +14,12 @@ bounding box (z padded by the voxel size): what the reference intended but does 
 --align D first registers the mesh's vertices onto the reference cloud (evaluation.register_icp: ICP on exact nearest
 neighbours, pairs farther apart than D metres ignored; no global registration — the mesh must already lie within D of the
 cloud) and evaluates the moved mesh; the line then holds "Alignment": the pose in KITTI order (12 numbers, row-major 3x4
-reference_T_mesh), fitness, inlier_rmse, updates and the flags.  Without it nothing changes."""
+reference_T_mesh), fitness, inlier_rmse, updates and the flags.  Without it nothing changes.
+--exact-completeness measures every reference point against the mesh itself (evaluation.point_to_mesh), not against its
+nearest sample: the completeness then depends neither on --seed nor on --mesh-sample-point.  --error-map PREFIX writes
+PREFIX_accuracy.ply, the mesh with its vertices coloured by their distance to the reference cloud (red at
+--truncation-acc), and PREFIX_completeness.ply, the evaluated reference points coloured by their exact distance to the mesh
+(red at --truncation-com); green is good, yellow is half the truncation.  Without either nothing changes."""
 import argparse
 import json
 import os
@@ -41,6 +47,8 @@ def main():
     ap.add_argument("--align", type=float, default=None, metavar="D", help="register the mesh to the reference first, gate D metres")
     ap.add_argument("--align-iterations", type=int, default=30)
     ap.add_argument("--align-method", choices=("plane", "point"), default="plane")
+    ap.add_argument("--exact-completeness", action="store_true")
+    ap.add_argument("--error-map", default=None, metavar="PREFIX")
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args()
     align = None
@@ -53,7 +61,12 @@ def main():
     res = evaluation.evaluate_recon(
         reference, torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev), down_sample_res=a.down_sample_res,
         threshold=a.threshold, truncation_acc=a.truncation_acc, truncation_com=a.truncation_com,
-        crop_to_reference=a.crop_to_reference, mesh_sample_point=a.mesh_sample_point, seed=a.seed, align=align)
+        crop_to_reference=a.crop_to_reference, mesh_sample_point=a.mesh_sample_point, seed=a.seed, align=align,
+        completeness="exact" if a.exact_completeness else "sampled", error_map=a.error_map is not None)
+    if a.error_map is not None:
+        em = res.pop("ErrorMap")
+        ply_io.save_mesh(a.error_map + "_accuracy.ply", em["vertices"], faces, colors=em["vertex_colors"])
+        ply_io.save_point_cloud(a.error_map + "_completeness.ply", em["points"], torch.zeros_like(em["points"]), em["point_colors"])
     if align is not None:
         al = res["Alignment"]
         al["target_T_source"] = al["target_T_source"][:3].reshape(-1).tolist()
