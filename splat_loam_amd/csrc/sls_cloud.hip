@@ -9,7 +9,7 @@
 //   voxel_keys                  key = ix | iy << 21 | iz << 42 and the identity permutation; a non-finite point, or one
 //                               with an index >= 2^21, gets key 0 (and is counted): nothing a key holds is an address
 //   the stable LSD sort         63 key bits = six passes of 11-bit digits over (u64 key, u32 index) pairs
-//                               (sls_sort.hip: radix_sort_pairs_u64) — stable, so a voxel's points stay in input order
+//                               (sls_radix.hip: radix_sort_pairs_u64) — stable, so a voxel's points stay in input order
 //   voxel_heads / _scan / _segments   head flags of the sorted keys, their scan in chunks of 1024 positions:
 //                               seg_start[v] = first sorted position of voxel v, seg_start[n_voxels] = M, the status words
 //   voxel_sum                   a lane per voxel adds its points in sorted (= input) order; a voxel of more than 64

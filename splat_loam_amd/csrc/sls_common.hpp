@@ -160,7 +160,7 @@ inline DevCam make_devcam(const SlsCamera &c)
 // 0.01 pixels of slack.  ONE word: column lo (9 bits) | n + 1 (10 bits, 0: nothing) | row lo (6 bits) | hi + 1 (7 bits)
 // — images up to 4096 x 128 (block_box_fits).  Written per surfel by the preprocess; the emission puts it into the
 // upper half of every instance word, the tile sort's scatter turns it into the mask of the blocks of the instance's
-// tile that the surfel can reach (sls_sort.hip: block_mask_of).
+// tile that the surfel can reach (block_mask_of, below).
 __host__ __device__ inline bool block_box_fits(int W, int H) { return W <= 4096 && H <= 128; }
 __device__ __forceinline__ uint32_t make_block_box(float cx, float cy, float ex, float ey, int NC)
 {
@@ -173,6 +173,61 @@ __device__ __forceinline__ uint32_t make_block_box(float cx, float cy, float ex,
     const int r1 = (int)fminf(floorf((cy + ey + 0.01f) * 0.5f), 63.0f);
     if (n < 0 || r1 < r0) return 0u;
     return (uint32_t)c0 | ((uint32_t)(n + 1) << 9) | ((uint32_t)r0 << 19) | ((uint32_t)(r1 + 1) << 25);
+}
+
+// The tile sort's list with block masks (launch_bin_sort, the mapping iteration): per instance, in list order, the
+// pair (surfel, mask of the sixteen 8x2 pixel blocks of its tile that the surfel's support box can reach) INSTEAD of
+// the bare surfel index.  An instance is then a 64-bit word: the packed (tile, surfel) word below, the surfel's block
+// box (make_block_box, one word per surfel from the preprocess, fetched by the emission with the
+// gather it makes anyway) above; the pass sorts on the same digit, and the scatter — tile and box in registers —
+// stores the pair with the ONE scattered store it would spend on the value.  The forward tile kernel reads the masks
+// instead of the records to decide what to stage (render_fwd_dense_kernel).  (Measured on the way: masks computed in
+// the emission from the records' support boxes — a gather from the 40 MB record array — +12...17 us there at 500 k
+// surfels and +4.7 us in the scatter that carried them; computed in the scatter from a per-surfel gather but stored
+// as a second, 2-byte array: +8.1 us in the scatter at 500 k — a scattered store instruction costs what it costs,
+// whatever its width; the gather alone, with the pair store: +6.3 us at 500 k, +3.2 us at 50 k — a round trip in a
+// chain of latencies.)
+struct BlockMaskArgs { uint2 *out; int GX; float invGX; int NC; };
+// bit 2*by + bx of the mask of an instance of `tile`; box = the surfel's block box
+__device__ __forceinline__ uint32_t block_mask_of(const BlockMaskArgs &a, uint32_t tile, uint32_t box)
+{
+    const int ty = (int)(((float)tile + 0.5f) * a.invGX), tx = (int)tile - ty * a.GX;
+    const int bc_lo = (int)(box & 511u), bc_n = (int)((box >> 9) & 1023u) - 1;       // columns [bc_lo, bc_lo + bc_n] mod NC
+    const int br_lo = (int)((box >> 19) & 63u), br_hi = (int)(box >> 25) - 1;        // rows [br_lo, br_hi]
+    const int r0 = max(br_lo - ty * (kTileH / 2), 0), r1 = min(br_hi - ty * (kTileH / 2), kTileH / 2 - 1);
+    const uint32_t ym = r0 <= r1 ? (((4u << (2 * r1)) - 1u) & ~((1u << (2 * r0)) - 1u)) : 0u;
+    int d0 = 2 * tx - bc_lo;
+    d0 += d0 < 0 ? a.NC : 0;
+    const int d1 = d0 + 1 >= a.NC ? d0 + 1 - a.NC : d0 + 1;
+    const uint32_t xm = (d0 <= bc_n ? 0x5555u : 0u) | (d1 <= bc_n ? 0xAAAAu : 0u);
+    return ym & xm;
+}
+
+// ---- shared by the radix sorter (sls_radix.hip) and the binning (sls_sort.hip) ----
+constexpr int kSortMaxBins = 2048;   // 11-bit digits at most
+
+// the item count of a device-sized launch: read on the device, clipped to the buffers' capacity
+__device__ __forceinline__ uint32_t load_count(const uint32_t *count_ptr, uint32_t cap)
+{
+    const uint32_t c = *count_ptr;
+    return c < cap ? c : cap;
+}
+
+// Stable ranking inside a round of 64 items: BITS ballots leave the set of valid lanes that hold my digit;
+// rank = how many of them sit below me, count = all of them.  Call it from wave-uniform control flow;
+// lt_mask = (1 << lane) - 1.
+template <int BITS>
+__device__ __forceinline__ void wave_digit_rank(bool valid, uint32_t digit, uint64_t lt_mask, uint32_t &rank, uint32_t &count)
+{
+    uint64_t peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < BITS; ++b) {
+        const bool bit = (digit >> b) & 1u;
+        const uint64_t bal = __ballot(bit);
+        peers &= bit ? bal : ~bal;
+    }
+    rank = (uint32_t)__popcll(peers & lt_mask);
+    count = (uint32_t)__popcll(peers);
 }
 
 // Ballot / all over the wave straight from the condition's lane mask.  HIP's __ballot() goes through an integer

@@ -139,7 +139,7 @@ __device__ __forceinline__ uint64_t pair_key(const uint32_t *__restrict__ sa, co
     return ((uint64_t)sa[p] << 32) | (uint64_t)sb[p];
 }
 
-// Orders the n directed pairs (a2[0][i], b2[0][i]) by (a, b) with two stable sorts of `bits` key bits each — by b with a as
+// Orders the n directed pairs (a2[0][i], b2[0][i]) by (a, b) with two stable sorts (sls_radix.hip) of `bits` key bits each — by b with a as
 // the value, then by a with b as the value: the order of a << bits | b at 8 bytes per item and pass instead of 12.
 // a2[1] / b2[1] are the ping-pong copies; a2[*cur] / b2[*cur] hold the result.
 inline int sort_pairs_ab(uint32_t *const a2[2], uint32_t *const b2[2], const uint32_t *count_ptr, uint32_t n, int bits, void *sort,

@@ -5,7 +5,7 @@
 //   ground_keys     a thread per point: key = bin << 32 | ordered z (bin SLS_GROUND_BINS: no bin), value = the row; the
 //                   label of a point without a bin is written 0 here, its bin -1; non-finite rows are counted with one
 //                   integer atomic per wave
-//   the stable LSD sort   41 key bits = four passes of 11-bit digits (sls_sort.hip: radix_sort_pairs_u64) — stable, so
+//   the stable LSD sort   41 key bits = four passes of 11-bit digits (sls_radix.hip: radix_sort_pairs_u64) — stable, so
 //                   equal z inside a bin stay in row order
 //   ground_gather   the sorted rows as float4 (x, y, z, row as bits): the fit reads contiguous 16-byte rows, several times
 //                   each, instead of 12-byte gathers through the permutation (sls_normals.hip: what those cost there)

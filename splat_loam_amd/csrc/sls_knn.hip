@@ -4,7 +4,7 @@
 //
 // Exact 3-NN, built for LiDAR-like (very non-uniform) clouds:
 //   1. bounding cube, 30-bit Hilbert-curve index per point;
-//   2. wave64 LSD radix sort of (code, index) — the sorter of sls_sort.hip;
+//   2. wave64 LSD radix sort of (code, index) — the sorter of sls_radix.hip;
 //   3. points gathered in curve order (float4: xyz + original index) and
 //      axis-aligned boxes over runs of 256 consecutive points;
 //   4. one wave per 64 consecutive points, one lane per point: the own box first for a tight bound, then the sweep

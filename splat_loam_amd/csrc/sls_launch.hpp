@@ -13,6 +13,49 @@ struct ConsumerArgs;    // sls_consumer_dev.hpp
 // for "this image has a launch order", for the hand-over buffer and for the callers' block_order buffers alike
 inline bool launch_order_possible(int T) { return T % 32 == 0 && kTileW == 16 && kTileH == 16; }
 
+// ---- sls_radix.hip: the radix sorter -------------------------------------------------------------------------------
+size_t sort_scratch_bytes(uint64_t cap);
+// of which the count table + digit totals; behind them the list of (surfel, block mask) pairs and the 64-bit instances
+// it is sorted from
+size_t sort_core_bytes(uint64_t cap);
+uint2 *sort_bmask_buffer(void *scratch, uint64_t cap);
+uint64_t *sort_wide_buffer(void *scratch, uint64_t cap);
+int sort_passes(int nbits);     // passes of the sorter over nbits key bits
+int radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uint32_t *vals_tmp,
+                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
+                         int *result_in_tmp, hipStream_t st);
+// the same sorter on 64-bit keys (sls_cloud.hip: the 63-bit voxel keys)
+int radix_sort_pairs_u64(uint64_t *keys, uint32_t *vals, uint64_t *keys_tmp, uint32_t *vals_tmp,
+                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
+                         int *result_in_tmp, hipStream_t st);
+// ... with what the depth order and the tile sort (sls_sort.hip) ask of it:
+struct RadixOptions {
+    uint2 *ranges_out; int nranges;     // single-pass sorts only: [start, end) of every key value < nranges ((0,0): absent)
+    bool drop_sorted_keys;              // the last pass writes the permuted values only
+    int base_shift;                     // the digits start at this bit; vals == null: the value is the key's low base_shift bits
+    BlockMaskArgs bm;                   // 64-bit keys, single pass: (value, block mask) pairs to bm.out instead of the values
+};
+constexpr RadixOptions kNoRadixOptions = { nullptr, 0, false, 0, { nullptr, 1, 1.0f, 1 } };     // = radix_sort_pairs_*
+int radix_sort_options_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uint32_t *vals_tmp,
+                           const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
+                           int *result_in_tmp, hipStream_t st, const RadixOptions &opt);
+int radix_sort_options_u64(uint64_t *keys, uint32_t *vals, uint64_t *keys_tmp, uint32_t *vals_tmp,
+                           const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
+                           int *result_in_tmp, hipStream_t st, const RadixOptions &opt);
+// One pass of `bits`-bit digits (8 .. 11) over the EMISSION's chunks, which counted their digits themselves (cnt: 2^bits
+// rows of nchunks words): row scan + scatter, no histogram launch.  chunk c = items [chunk_start[c], chunk_start[c + 1]);
+// the values go to vals_out (or the pairs to bm.out), the sorted keys are not written.
+struct EmitChunkSort {
+    const uint32_t *vals; uint32_t *vals_out;       // vals null: the value is (key & packed_val_mask)
+    const uint32_t *chunk_start; uint32_t cap; int shift, bits;
+    uint32_t *cnt, *totals; int nchunks;
+    uint2 *ranges_out; int nranges; uint32_t packed_val_mask; BlockMaskArgs bm;
+};
+int tile_sort_emit_chunks_u32(const uint32_t *keys, const EmitChunkSort &a, hipStream_t st);
+int tile_sort_emit_chunks_u64(const uint64_t *keys, const EmitChunkSort &a, hipStream_t st);
+// its row scan alone (the direct binning): every row of a table of rows x nchunks words scanned exclusively in place
+int sort_rowscan_rows(uint32_t *cnt, int rows, int nchunks, uint32_t *totals, uint32_t cap, hipStream_t st);
+
 // ---- sls_sort.hip: depth order, binning ----------------------------------------------------------------------------
 // What the depth-order stage hands to the binning that follows it
 struct ScanHandoff {
@@ -42,15 +85,7 @@ struct DirectBin {
 };
 constexpr int kDirectGroup = 16;
 
-size_t sort_scratch_bytes(uint64_t cap);
 size_t order_scratch_bytes(int N);
-int radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uint32_t *vals_tmp,
-                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
-                         int *result_in_tmp, hipStream_t st);
-// the same sorter on 64-bit keys (sls_cloud.hip: the 63-bit voxel keys)
-int radix_sort_pairs_u64(uint64_t *keys, uint32_t *vals, uint64_t *keys_tmp, uint32_t *vals_tmp,
-                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
-                         int *result_in_tmp, hipStream_t st);
 // where preprocess writes the depth sort's input (keys, identity permutation, N on the device) and the repair its pairs
 void depth_order_key_buffers(int N, void *scratch, uint32_t *order, uint32_t **keys, uint32_t **vals0, uint32_t **n_dev);
 uint64_t *resort_comp_buffer(int N, void *scratch);

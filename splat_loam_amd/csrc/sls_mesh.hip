@@ -6,7 +6,7 @@
 //
 // sls_mesh_weld, launches ordered by the stream alone:
 //   mesh_word_keys x 3 + the stable LSD sort x 3   (u32 key, u32 row) pairs over the sign-flipped words z, then y, then
-//                               x (sls_sort.hip: radix_sort_pairs_u32, 32 bits each): rows in ascending (x, y, z)
+//                               x (sls_radix.hip: radix_sort_pairs_u32, 32 bits each): rows in ascending (x, y, z)
 //   weld_heads / _scan / _write head flags of the sorted rows (a row that differs from its predecessor), their scan in
 //                               chunks of 2048 positions, the unique rows, the rank of every row and the status words
 //

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SLS_FWD_WAVE
 // compaction 780, round end 280 shader clocks, against 825 per step) and the tile's list is the TILE's: of the 64
 // entries of a round only 25-50 % can reach this block's 16 pixels at all.  Here the list is read twice: a SCAN tests
 // 256 entries per round — four coalesced 8-byte loads per lane: the (surfel, block mask) pairs the tile sort's
-// scatter stored in list order (sls_sort.hip: block_mask_of, from the surfels' block boxes) — and queues the
+// scatter stored in list order (sls_common.hpp: block_mask_of, from the surfels' block boxes) — and queues the
 // survivors; a ROUND stages, culls and blends 64 queued survivors.  Rounds per block 5.3 -> 3.3 at BASELINE config 3,
 // 14.6 -> 5.0 at 170 k surfels / 64 x 1024, 6.2 -> 2.9 at 50 k.  The first 64 entries go straight into round 0, so
 // that the first records are requested as early as before.  Everything a pixel

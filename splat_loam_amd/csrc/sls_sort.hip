@@ -14,20 +14,8 @@
 //      together an instance is ONE packed word.  The pass's digit bases are the tile ranges.
 // LSD radix principle (least-significant part first, stable passes after); the
 // result is bit-identical to a stable 64-bit sort and costs ~24 B of HBM traffic
-// per instance instead of ~190 B.
-//
-// Radix sort building block (wave64-native, no vendor library):
-//   * 8..11-bit digits (sort_plan); the unit of work is ONE WAVE owning kSortWaveItems =
-//     1024 consecutive items (16 rounds of 64): no workgroup barrier inside a pass, each
-//     wave keeps its 2^BITS running bucket cursors in a private LDS slice; a workgroup is
-//     SortBlock<BITS>::kWaves waves (8 up to 10-bit digits, 4 for 11) so that the count
-//     table is written and read back in runs of that many chunks per digit;
-//   * stable ranking inside a round by BITS ballots (the set of lanes holding my
-//     digit), rank = popcount(peers below me);
-//   * per pass: histogram -> per-digit row scan over chunks -> scatter;
-//   * the item count is read from DEVICE memory (count_ptr), grids are sized for
-//     a host-side capacity, so a whole iteration can be enqueued without a
-//     device->host sync (sls_mapping_step).
+// per instance instead of ~190 B.  The radix sorter itself is sls_radix.hip; what lives here is the depth order
+// (its repair included), the direct binning, the emission and the launchers that choose between them.
 #include <cstdlib>
 #include "sls_common.hpp"
 #include "sls_resort.hpp"
@@ -35,56 +23,7 @@
 
 namespace sls {
 
-// (build-time knobs for A/B runs; measured on the bench scene, A/B inside one box, iteration time with
-//  rounds x waves per block = 16x16: 0.2652 ms, 16x8: 0.2613 (scatter 18.6 -> 15.8 us: twice the workgroups for
-//  the 1260 wave chunks of the tile sort), 16x4: 0.266 (the stray-word table access), 24x8: 0.2618, 32x8: 0.264,
-//  8x16: 0.268 and 8x8: 0.269 (row scan +4 us), 4x16: 0.280)
-#ifndef SLS_SORT_ROUNDS
-#define SLS_SORT_ROUNDS 16
-#endif
-#ifndef SLS_SORT_WAVES
-#define SLS_SORT_WAVES 8
-#endif
-constexpr int kSortRounds = SLS_SORT_ROUNDS;
-constexpr int kSortWaveItems = kWave * kSortRounds;  // 1024 items per wave
-constexpr int kSortMaxBins = 2048;   // 11-bit digits at most
 constexpr int kDepthKeyBits = 29;    // compressed depth key, see depth_order_key()
-
-__device__ __forceinline__ uint32_t load_count(const uint32_t *count_ptr, uint32_t cap)
-{
-    const uint32_t c = *count_ptr;
-    return c < cap ? c : cap;
-}
-
-__device__ __forceinline__ void resort_verify(int nwin, const uint64_t *__restrict__ edges, uint32_t *__restrict__ flag);
-
-// The tile sort's list with block masks (launch_bin_sort, the mapping iteration): per instance, in list order, the
-// pair (surfel, mask of the sixteen 8x2 pixel blocks of its tile that the surfel's support box can reach) INSTEAD of
-// the bare surfel index.  An instance is then a 64-bit word: the packed (tile, surfel) word below, the surfel's block
-// box (sls_common.hpp: make_block_box, one word per surfel from the preprocess, fetched by the emission with the
-// gather it makes anyway) above; the pass sorts on the same digit, and the scatter — tile and box in registers —
-// stores the pair with the ONE scattered store it would spend on the value.  The forward tile kernel reads the masks
-// instead of the records to decide what to stage (render_fwd_dense_kernel).  (Measured on the way: masks computed in
-// the emission from the records' support boxes — a gather from the 40 MB record array — +12...17 us there at 500 k
-// surfels and +4.7 us in the scatter that carried them; computed in the scatter from a per-surfel gather but stored
-// as a second, 2-byte array: +8.1 us in the scatter at 500 k — a scattered store instruction costs what it costs,
-// whatever its width; the gather alone, with the pair store: +6.3 us at 500 k, +3.2 us at 50 k — a round trip in a
-// chain of latencies.)
-struct BlockMaskArgs { uint2 *out; int GX; float invGX; int NC; };
-// bit 2*by + bx of the mask of an instance of `tile`; box = the surfel's block box
-__device__ __forceinline__ uint32_t block_mask_of(const BlockMaskArgs &a, uint32_t tile, uint32_t box)
-{
-    const int ty = (int)(((float)tile + 0.5f) * a.invGX), tx = (int)tile - ty * a.GX;
-    const int bc_lo = (int)(box & 511u), bc_n = (int)((box >> 9) & 1023u) - 1;       // columns [bc_lo, bc_lo + bc_n] mod NC
-    const int br_lo = (int)((box >> 19) & 63u), br_hi = (int)(box >> 25) - 1;        // rows [br_lo, br_hi]
-    const int r0 = max(br_lo - ty * (kTileH / 2), 0), r1 = min(br_hi - ty * (kTileH / 2), kTileH / 2 - 1);
-    const uint32_t ym = r0 <= r1 ? (((4u << (2 * r1)) - 1u) & ~((1u << (2 * r0)) - 1u)) : 0u;
-    int d0 = 2 * tx - bc_lo;
-    d0 += d0 < 0 ? a.NC : 0;
-    const int d1 = d0 + 1 >= a.NC ? d0 + 1 - a.NC : d0 + 1;
-    const uint32_t xm = (d0 <= bc_n ? 0x5555u : 0u) | (d1 <= bc_n ? 0xAAAAu : 0u);
-    return ym & xm;
-}
 
 // ---------------------------------------------------------------------------
 // Direct binning (round 4): the tile instances are never materialised unsorted.
@@ -96,7 +35,7 @@ __device__ __forceinline__ uint32_t block_mask_of(const BlockMaskArgs &a, uint32
 //      after a from-scratch sort — gathers, per position, the surfel's emission record {rectangle, block box}, writes it
 //      to an array indexed by POSITION (the third kernel reads it coalesced) and counts its chunk's tiles in LDS:
 //      one column of the table;
-//   2. sort_rowscan_kernel: exclusive scan of every tile's row + the tile totals;
+//   2. the sorter's row scan (sls_radix.hip: sort_rowscan_rows): exclusive scan of every tile's row + the tile totals;
 //   3. bin_direct_kernel, one workgroup per chunk: digit bases (= tile ranges, R), per-wave counts -> cursors, then every
 //      wave deals its instances out 64 at a time (owner by binary search in the wave's scan, tile from the rectangle),
 //      ranks them with the BITS ballots of the radix scatter and stores (surfel[, block mask]) at the final position.
@@ -203,484 +142,6 @@ __device__ __forceinline__ void diff_finish(int GX, int bins, uint32_t *s_hist, 
         }
         s_hist[d] += (uint32_t)(carry + v);
     }
-}
-
-// ---------------------------------------------------------------------------
-// step 1 of a pass: per-wave-chunk digit histogram -> cnt[digit][chunk]
-// ---------------------------------------------------------------------------
-// A block is WAVES chunks: the count table cnt[digit][chunk] is written (and read back by the scatter)
-// in runs of WAVES consecutive chunks per digit — 32 contiguous bytes with 8 waves — instead of one
-// stray word per (digit, wave).  The LDS rows are padded by one word so that the transposed access
-// (lanes = consecutive waves of one digit) spreads over the banks.
-template <int BITS> struct SortBlock { static constexpr int kWaves = BITS <= 9 ? SLS_SORT_WAVES : (BITS == 10 ? (SLS_SORT_WAVES < 8 ? SLS_SORT_WAVES : 8) : 4); };
-
-template <typename KeyT, int BITS>
-__global__ __launch_bounds__(64 * SortBlock<BITS>::kWaves) void sort_hist_kernel(
-    const KeyT *__restrict__ keys, const uint32_t *__restrict__ count_ptr, uint32_t cap, int shift,
-    uint32_t *__restrict__ cnt, int nchunks_cap)
-{
-    constexpr int BINS = 1 << BITS, WAVES = SortBlock<BITS>::kWaves, STR = BINS + 1;
-    __shared__ uint32_t s_hist[WAVES * STR];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int chunk0 = blockIdx.x * WAVES, chunk = chunk0 + wave;
-    const uint32_t R = load_count(count_ptr, cap);
-    const int nchunks = (int)((R + kSortWaveItems - 1) / kSortWaveItems);
-    if (chunk0 >= nchunks) return;             // whole block beyond the data
-#pragma unroll
-    for (int k = 0; k < BINS / 64; ++k) s_hist[wave * STR + lane + 64 * k] = 0;
-    __builtin_amdgcn_wave_barrier();
-    if (chunk < nchunks) {
-        const uint32_t base = (uint32_t)chunk * kSortWaveItems + lane;
-        KeyT k[kSortRounds];
-#pragma unroll
-        for (int r = 0; r < kSortRounds; ++r) k[r] = keys[min(base + (uint32_t)r * 64, R - 1u)];   // (chunk < nchunks: R >= 1)
-#pragma unroll
-        for (int r = 0; r < kSortRounds; ++r) {
-            const uint32_t idx = base + (uint32_t)r * 64;
-            if (idx < R) atomicAdd(&s_hist[wave * STR + ((uint32_t)(k[r] >> shift) & (uint32_t)(BINS - 1))], 1u);
-        }
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < BINS * WAVES; idx += 64 * WAVES) {
-        const int d = idx / WAVES, w = idx % WAVES;
-        if (chunk0 + w < nchunks_cap) cnt[(size_t)d * nchunks_cap + chunk0 + w] = s_hist[w * STR + d];
-    }
-}
-
-// step 2: block d scans row d of cnt[][] exclusively in place, writes the row total.
-// Thread t owns P = ceil(nchunks / 256) CONSECUTIVE entries: one pass to sum them, one wave scan + one barrier for
-// the 256 partial sums, one pass to write the running prefix (a loop over 256-entry slabs with two barriers each
-// cost 2 us more on the 1260-chunk rows of the tile sort: the kernel is nothing but its chain of latencies).
-// nchunks_fixed > 0: the rows have that many entries (chunks of the emission, see emit_tiles_kernel)
-__global__ __launch_bounds__(256) void sort_rowscan_kernel(uint32_t *__restrict__ cnt,
-                                                           const uint32_t *__restrict__ count_ptr, uint32_t cap,
-                                                           int nchunks_cap, uint32_t *__restrict__ totals,
-                                                           int nchunks_fixed)
-{
-    __shared__ uint32_t s_wave[4];
-    const uint32_t R = nchunks_fixed > 0 ? 0u : load_count(count_ptr, cap);
-    const int nchunks = nchunks_fixed > 0 ? nchunks_fixed : (int)((R + kSortWaveItems - 1) / kSortWaveItems);
-    uint32_t *row = cnt + (size_t)blockIdx.x * nchunks_cap;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int P = (nchunks + 255) / 256, i0 = (int)threadIdx.x * P, i1 = min(i0 + P, nchunks);
-    constexpr int kKeep = 8;                 // entries kept in registers between the two passes (P <= 8 up to 2 M items)
-    uint32_t keep[kKeep];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int j = 0; j < kKeep; ++j) { keep[j] = (i0 + j < i1) ? row[i0 + j] : 0u; sum += keep[j]; }
-    for (int i = i0 + kKeep; i < i1; ++i) sum += row[i];
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum;
-    for (int w = 0; w < wave; ++w) run += s_wave[w];
-#pragma unroll
-    for (int j = 0; j < kKeep; ++j) {
-        if (i0 + j < i1) row[i0 + j] = run;
-        run += keep[j];
-    }
-    for (int i = i0 + kKeep; i < i1; ++i) { const uint32_t v = row[i]; row[i] = run; run += v; }
-    if (threadIdx.x == 255) totals[blockIdx.x] = run;
-}
-
-// step 3: stable scatter
-template <typename KeyT, int BITS>
-__global__ __launch_bounds__(64 * SortBlock<BITS>::kWaves) void sort_scatter_kernel(const KeyT *__restrict__ keys_in,
-                                                           const uint32_t *__restrict__ vals_in,
-                                                           KeyT *__restrict__ keys_out,
-                                                           uint32_t *__restrict__ vals_out,
-                                                           const uint32_t *__restrict__ count_ptr, uint32_t cap,
-                                                           int shift, const uint32_t *__restrict__ cnt,
-                                                           const uint32_t *__restrict__ totals, int nchunks_cap,
-                                                           uint2 *__restrict__ ranges_out, int nranges,
-                                                           uint32_t packed_val_mask, BlockMaskArgs bm)
-{
-    constexpr int BINS = 1 << BITS, PER = BINS / 256;   // digit totals handled per thread (of the first 256)
-    constexpr int WAVES = SortBlock<BITS>::kWaves, STR = BINS + 1;
-    __shared__ uint32_t s_cursor[WAVES * STR];
-    __shared__ uint32_t s_digit_base[BINS];
-    __shared__ uint32_t s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int chunk0 = blockIdx.x * WAVES, chunk = chunk0 + wave;
-    // Everything the block needs from memory is requested up front — its items, its rows of the count
-    // table, the digit totals, the item count — so the waits below overlap into ONE round trip (with one
-    // wave per SIMD nothing else would hide them).  Loads are guarded by the buffers' capacity, validity
-    // (idx < R) is applied afterwards.
-    const uint32_t base = (uint32_t)chunk * kSortWaveItems + lane;
-    KeyT k[kSortRounds];
-    uint32_t v[kSortRounds];
-    // (clamped addresses instead of predicated loads: a conditional load per round compiles into a branch
-    //  and a full wait per round — sixteen serialised round trips)
-#pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) k[r] = keys_in[min(base + (uint32_t)r * 64, cap - 1u)];
-    if (vals_in) {
-#pragma unroll
-        for (int r = 0; r < kSortRounds; ++r) v[r] = vals_in[min(base + (uint32_t)r * 64, cap - 1u)];
-    } else {   // packed mode: the value is the low part of the key
-#pragma unroll
-        for (int r = 0; r < kSortRounds; ++r) v[r] = (uint32_t)k[r] & packed_val_mask;
-    }
-    constexpr int CPT = BINS / 64;             // count-table entries per thread: BINS * WAVES / (64 * WAVES)
-    uint32_t my_cnt[CPT];
-#pragma unroll
-    for (int q = 0; q < CPT; ++q) {
-        const int idx = threadIdx.x + q * 64 * WAVES, d = idx / WAVES, w = idx % WAVES;
-        my_cnt[q] = (chunk0 + w < nchunks_cap) ? cnt[(size_t)d * nchunks_cap + chunk0 + w] : 0u;
-    }
-    const bool scanner = threadIdx.x < 256;
-    uint32_t tot[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) tot[q] = scanner ? totals[threadIdx.x * PER + q] : 0u;
-    const uint32_t R = load_count(count_ptr, cap);
-    const int nchunks = (int)((R + kSortWaveItems - 1) / kSortWaveItems);
-    if (chunk0 >= nchunks) return;   // whole block beyond the data
-    {   // exclusive scan of the BINS digit totals (PER consecutive ones per thread, first 256 threads)
-        uint32_t loc[PER];
-        uint32_t v = 0;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) { loc[k] = v; v += tot[k]; }
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (scanner && lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        if (scanner) {
-            uint32_t wave_prefix = 0;
-            for (int w = 0; w < wave; ++w) wave_prefix += s_wave[w];
-#pragma unroll
-            for (int k = 0; k < PER; ++k) s_digit_base[threadIdx.x * PER + k] = wave_prefix + incl - v + loc[k];
-            // single-pass sort by tile id: the digit bases ARE the tile ranges (A5)
-            if (ranges_out && blockIdx.x == 0) {
-#pragma unroll
-                for (int k = 0; k < PER; ++k) {
-                    const int d = threadIdx.x * PER + k;
-                    const uint32_t b0 = wave_prefix + incl - v + loc[k], c = tot[k];
-                    if (d < nranges) ranges_out[d] = c ? make_uint2(b0, b0 + c) : make_uint2(0u, 0u);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // cursors of the block's WAVES chunks: runs of WAVES consecutive counts per digit (see sort_hist_kernel)
-#pragma unroll
-    for (int q = 0; q < CPT; ++q) {
-        const int idx = threadIdx.x + q * 64 * WAVES, d = idx / WAVES, w = idx % WAVES;
-        s_cursor[w * STR + d] = s_digit_base[d] + my_cnt[q];
-    }
-    __syncthreads();
-    if (chunk >= nchunks) return;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) {
-        const uint32_t idx = base + (uint32_t)r * 64;
-        const bool valid = idx < R;
-        const uint32_t digit = (uint32_t)(k[r] >> shift) & (uint32_t)(BINS - 1);
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < BITS; ++b) {
-            const bool bit = (digit >> b) & 1u;
-            const uint64_t bal = __ballot(bit);
-            peers &= bit ? bal : ~bal;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & lt_mask);
-        const uint32_t count = (uint32_t)__popcll(peers);
-        uint32_t pos = 0;
-        if (valid) pos = s_cursor[wave * STR + digit] + rank;
-        __builtin_amdgcn_wave_barrier();
-        if (valid) {
-            if (keys_out) keys_out[pos] = k[r];     // (a caller that only wants the permutation passes null in the last pass)
-            if (sizeof(KeyT) == 8 && bm.out) bm.out[pos] = make_uint2(v[r], block_mask_of(bm, digit, (uint32_t)((uint64_t)k[r] >> 32)));
-            else vals_out[pos] = v[r];
-            if (rank == count - 1) s_cursor[wave * STR + digit] = pos + 1;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// step 3 when the chunks are the EMISSION's (emit_tiles_kernel counted the digits of the instances each of its
-// workgroups wrote: no histogram launch): chunk c = instances [chunk_start[c], chunk_start[c + 1]), a few hundred
-// to a few thousand; one wave per chunk, 16 rounds of 64 in registers at a time.  Same positions as the pass over
-// fixed 1024-item chunks: a stable partition does not care where the chunk boundaries are.
-template <typename KeyT, int BITS>
-__global__ __launch_bounds__(64 * SortBlock<BITS>::kWaves) void sort_scatter_chunks_kernel(
-    const KeyT *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, KeyT *__restrict__ keys_out,
-    uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ chunk_start, uint32_t cap, int shift,
-    const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ totals, int nchunks,
-    uint2 *__restrict__ ranges_out, int nranges, uint32_t packed_val_mask, BlockMaskArgs bm)
-{
-    constexpr int BINS = 1 << BITS, PER = BINS / 256;
-    constexpr int WAVES = SortBlock<BITS>::kWaves, STR = BINS + 1;
-    __shared__ uint32_t s_cursor[WAVES * STR];
-    __shared__ uint32_t s_digit_base[BINS];
-    __shared__ uint32_t s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int chunk0 = blockIdx.x * WAVES, chunk = chunk0 + wave;
-    // (the chunk's bounds, its rows of the count table and the digit totals travel together; the items follow)
-    const uint32_t cs = min(chunk_start[min(chunk, nchunks)], cap), ce = min(chunk_start[min(chunk + 1, nchunks)], cap);
-    KeyT k[kSortRounds];
-    uint32_t v[kSortRounds];
-#pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) k[r] = keys_in[min(cs + (uint32_t)(r * 64 + lane), cap - 1u)];
-    if (vals_in) {
-#pragma unroll
-        for (int r = 0; r < kSortRounds; ++r) v[r] = vals_in[min(cs + (uint32_t)(r * 64 + lane), cap - 1u)];
-    }
-    constexpr int CPT = BINS / 64;
-    uint32_t my_cnt[CPT];
-#pragma unroll
-    for (int q = 0; q < CPT; ++q) {
-        const int idx = threadIdx.x + q * 64 * WAVES, d = idx / WAVES, w = idx % WAVES;
-        my_cnt[q] = (chunk0 + w < nchunks) ? cnt[(size_t)d * nchunks + chunk0 + w] : 0u;
-    }
-    const bool scanner = threadIdx.x < 256;
-    uint32_t tot[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) tot[q] = scanner ? totals[threadIdx.x * PER + q] : 0u;
-    {   // exclusive scan of the BINS digit totals (PER consecutive ones per thread, first 256 threads)
-        uint32_t loc[PER];
-        uint32_t sum = 0;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) { loc[q] = sum; sum += tot[q]; }
-        uint32_t incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (scanner && lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        if (scanner) {
-            uint32_t wave_prefix = 0;
-            for (int w = 0; w < wave; ++w) wave_prefix += s_wave[w];
-#pragma unroll
-            for (int q = 0; q < PER; ++q) s_digit_base[threadIdx.x * PER + q] = wave_prefix + incl - sum + loc[q];
-            if (ranges_out && blockIdx.x == 0) {      // the digit bases ARE the tile ranges (A5)
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    const int d = threadIdx.x * PER + q;
-                    const uint32_t b0 = wave_prefix + incl - sum + loc[q], c = tot[q];
-                    if (d < nranges) ranges_out[d] = c ? make_uint2(b0, b0 + c) : make_uint2(0u, 0u);
-                }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < CPT; ++q) {
-        const int idx = threadIdx.x + q * 64 * WAVES, d = idx / WAVES, w = idx % WAVES;
-        s_cursor[w * STR + d] = s_digit_base[d] + my_cnt[q];
-    }
-    __syncthreads();
-    if (chunk >= nchunks) return;
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    for (uint32_t b0 = cs; b0 < ce; b0 += (uint32_t)kSortWaveItems) {
-        if (b0 != cs) {     // (a chunk of more than 1024 instances: the next 16 rounds)
-#pragma unroll
-            for (int r = 0; r < kSortRounds; ++r) k[r] = keys_in[min(b0 + (uint32_t)(r * 64 + lane), cap - 1u)];
-            if (vals_in) {
-#pragma unroll
-                for (int r = 0; r < kSortRounds; ++r) v[r] = vals_in[min(b0 + (uint32_t)(r * 64 + lane), cap - 1u)];
-            }
-        }
-        if (!vals_in) {     // packed mode: the value is the low part of the key
-#pragma unroll
-            for (int r = 0; r < kSortRounds; ++r) v[r] = (uint32_t)k[r] & packed_val_mask;
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 0; r < kSortRounds; ++r) {
-            const uint32_t idx = b0 + (uint32_t)(r * 64 + lane);
-            if (b0 + (uint32_t)(r * 64) >= ce) break;       // (wave-uniform)
-            const bool valid = idx < ce;
-            const uint32_t digit = (uint32_t)(k[r] >> shift) & (uint32_t)(BINS - 1);
-            uint64_t peers = __ballot(valid);
-#pragma unroll
-            for (int b = 0; b < BITS; ++b) {
-                const bool bit = (digit >> b) & 1u;
-                const uint64_t bal = __ballot(bit);
-                peers &= bit ? bal : ~bal;
-            }
-            const uint32_t rank = (uint32_t)__popcll(peers & lt_mask);
-            const uint32_t count = (uint32_t)__popcll(peers);
-            uint32_t pos = 0;
-            if (valid) pos = s_cursor[wave * STR + digit] + rank;
-            __builtin_amdgcn_wave_barrier();
-            if (valid) {
-                if (keys_out) keys_out[pos] = k[r];
-                if (sizeof(KeyT) == 8 && bm.out) bm.out[pos] = make_uint2(v[r], block_mask_of(bm, digit, (uint32_t)((uint64_t)k[r] >> 32)));
-                else vals_out[pos] = v[r];
-                if (rank == count - 1) s_cursor[wave * STR + digit] = pos + 1;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-}
-
-// rows of the emission's count table + scatter over its chunks (the histogram was the emission's)
-template <typename KeyT, int BITS>
-static int tile_sort_emit_chunks(const KeyT *kin, const uint32_t *vin, KeyT *kout, uint32_t *vout,
-                                 const uint32_t *chunk_start, uint32_t cap, int shift, uint32_t *cnt, uint32_t *totals,
-                                 int nchunks, uint2 *ranges_out, int nranges, uint32_t packed_val_mask, hipStream_t st,
-                                 const BlockMaskArgs &bm)
-{
-    {
-        ScopedTimer tm(T_SORT_ROWSCAN, st);
-        hipLaunchKernelGGL(sort_rowscan_kernel, dim3(1 << BITS), dim3(256), 0, st, cnt, (const uint32_t *)nullptr, cap, nchunks,
-                           totals, nchunks);
-    }
-    SLS_LAUNCH_CHECK("sort_rowscan_kernel");
-    {
-        ScopedTimer tm(T_SORT_SCATTER, st);
-        const int nblocks = (nchunks + SortBlock<BITS>::kWaves - 1) / SortBlock<BITS>::kWaves;
-        hipLaunchKernelGGL((sort_scatter_chunks_kernel<KeyT, BITS>), dim3(nblocks), dim3(64 * SortBlock<BITS>::kWaves), 0, st,
-                           kin, vin, kout, vout, chunk_start, cap, shift, (const uint32_t *)cnt, (const uint32_t *)totals,
-                           nchunks, ranges_out, nranges, packed_val_mask, bm);
-    }
-    SLS_LAUNCH_CHECK("sort_scatter_chunks_kernel");
-    return SLS_OK;
-}
-
-// ---------------------------------------------------------------------------
-static size_t sort_core_bytes(uint64_t cap)
-{
-    const uint64_t nchunks = (cap + kSortWaveItems - 1) / kSortWaveItems;
-    return (size_t)(kSortMaxBins * (nchunks ? nchunks : 1) + kSortMaxBins) * sizeof(uint32_t);
-}
-// (count table + digit totals, and behind them the list of (surfel, block mask) pairs and the 64-bit instances it
-//  is sorted from: sort_bmask_buffer, sort_wide_buffer)
-size_t sort_scratch_bytes(uint64_t cap)
-{
-    return sort_core_bytes(cap) + 2 * sizeof(uint64_t) * (size_t)cap + 64;
-}
-uint2 *sort_bmask_buffer(void *scratch, uint64_t cap)
-{
-    return (uint2 *)((char *)scratch + ((sort_core_bytes(cap) + 15) & ~(size_t)15));
-}
-uint64_t *sort_wide_buffer(void *scratch, uint64_t cap)
-{
-    return (uint64_t *)(sort_bmask_buffer(scratch, cap) + cap);
-}
-
-// digit width: as few passes as 11-bit digits allow, then the narrowest digit that still fits
-static void sort_plan(int nbits, int &npasses, int &bits)
-{
-    npasses = (nbits + 10) / 11;
-    bits = (nbits + npasses - 1) / npasses;
-    if (bits < 8) bits = 8;
-}
-int sort_passes(int nbits)
-{
-    int np, b;
-    sort_plan(nbits, np, b);
-    return np;
-}
-
-template <typename KeyT, int BITS>
-static int radix_pass(const KeyT *kin, const uint32_t *vin, KeyT *kout, uint32_t *vout, const uint32_t *count_ptr,
-                      uint32_t cap, int shift, uint32_t *cnt, uint32_t *totals, int nchunks, int /*unused*/,
-                      uint2 *ranges_out, int nranges, uint32_t packed_val_mask, hipStream_t st,
-                      const BlockMaskArgs &bm)
-{
-    const int nblocks = (nchunks + SortBlock<BITS>::kWaves - 1) / SortBlock<BITS>::kWaves;
-    {
-        ScopedTimer tm(T_SORT_HIST, st);
-        hipLaunchKernelGGL((sort_hist_kernel<KeyT, BITS>), dim3(nblocks), dim3(64 * SortBlock<BITS>::kWaves), 0, st, kin,
-                           count_ptr, cap, shift, cnt, nchunks);
-    }
-    SLS_LAUNCH_CHECK("sort_hist_kernel");
-    {
-        ScopedTimer tm(T_SORT_ROWSCAN, st);
-        hipLaunchKernelGGL(sort_rowscan_kernel, dim3(1 << BITS), dim3(256), 0, st, cnt, count_ptr, cap, nchunks, totals, 0);
-    }
-    SLS_LAUNCH_CHECK("sort_rowscan_kernel");
-    {
-        ScopedTimer tm(T_SORT_SCATTER, st);
-        hipLaunchKernelGGL((sort_scatter_kernel<KeyT, BITS>), dim3(nblocks), dim3(64 * SortBlock<BITS>::kWaves), 0, st, kin, vin, kout, vout,
-                           count_ptr, cap, shift, (const uint32_t *)cnt, (const uint32_t *)totals, nchunks, ranges_out,
-                           nranges, packed_val_mask, bm);
-    }
-    SLS_LAUNCH_CHECK("sort_scatter_kernel");
-    return SLS_OK;
-}
-
-// Stable LSD radix sort of (key, u32 value) pairs on the low `nbits` key bits.
-// Item count = min(*count_ptr, cap), read on the device.  Ping-pongs between
-// (keys, vals) and (keys_tmp, vals_tmp); *result_in_tmp says where the sorted
-// data ended up.  ranges_out (single-pass sorts only): [start, end) of every key
-// value < nranges in the sorted output ((0,0) for absent values).  drop_sorted_keys: the
-// last pass writes the permuted values only.
-// (Counting the next pass's digits inside the scatter / the producer with global
-// atomics was measured and is slower than the histogram kernel: +35 us per pass.)
-template <typename KeyT>
-static int radix_sort_pairs_t(KeyT *keys, uint32_t *vals, KeyT *keys_tmp, uint32_t *vals_tmp,
-                              const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch,
-                              size_t scratch_bytes, int *result_in_tmp, hipStream_t st,
-                              uint2 *ranges_out = nullptr, int nranges = 0, bool drop_sorted_keys = false,
-                              int base_shift = 0, BlockMaskArgs bm = BlockMaskArgs{ nullptr, 1, 1.0f, 1 })
-{
-    *result_in_tmp = 0;
-    if (cap == 0 || nbits <= 0) return SLS_OK;
-    if (scratch_bytes < sort_scratch_bytes(cap)) {
-        set_error("sort scratch too small: %zu < %zu", scratch_bytes, sort_scratch_bytes(cap));
-        return SLS_E_SCRATCH;
-    }
-    const int nchunks = (int)(((uint64_t)cap + kSortWaveItems - 1) / kSortWaveItems);
-    uint32_t *cnt = (uint32_t *)scratch;
-    int npasses, bits;
-    sort_plan(nbits, npasses, bits);
-    if (ranges_out && npasses != 1) {
-        set_error("internal: ranges need a single-pass sort");
-        return SLS_E_ARG;
-    }
-    uint32_t *totals = cnt + ((size_t)1 << bits) * nchunks;
-    KeyT *kb[2] = { keys, keys_tmp };
-    uint32_t *vb[2] = { vals, vals_tmp };
-    for (int p = 0; p < npasses; ++p) {
-        const int shift = base_shift + bits * p;
-        const int src = p & 1, dst = src ^ 1;
-        // packed single-pass sort (vals == null): the value travels in the key's low base_shift bits
-        const uint32_t packed_val_mask = (vals == nullptr && base_shift > 0) ? ((1u << base_shift) - 1u) : 0u;
-        int rc;
-        KeyT *kout = (drop_sorted_keys && p + 1 == npasses) ? nullptr : kb[dst];
-#define SLS_PASS(B) radix_pass<KeyT, B>(kb[src], vb[src], kout, vb[dst], count_ptr, cap, shift, cnt, totals, nchunks, \
-                                        0, ranges_out, nranges, packed_val_mask, st,                           \
-                                        (npasses == 1 ? bm : BlockMaskArgs{ nullptr, 1, 1.0f, 1 }))
-        switch (bits) {
-        case 8: rc = SLS_PASS(8); break;
-        case 9: rc = SLS_PASS(9); break;
-        case 10: rc = SLS_PASS(10); break;
-        default: rc = SLS_PASS(11); break;
-        }
-#undef SLS_PASS
-        if (rc) return rc;
-    }
-    *result_in_tmp = npasses & 1;
-    return SLS_OK;
-}
-
-int radix_sort_pairs_u32(uint32_t *keys, uint32_t *vals, uint32_t *keys_tmp, uint32_t *vals_tmp,
-                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
-                         int *result_in_tmp, hipStream_t st)
-{
-    return radix_sort_pairs_t<uint32_t>(keys, vals, keys_tmp, vals_tmp, count_ptr, cap, nbits, scratch,
-                                        scratch_bytes, result_in_tmp, st);
-}
-
-int radix_sort_pairs_u64(uint64_t *keys, uint32_t *vals, uint64_t *keys_tmp, uint32_t *vals_tmp,
-                         const uint32_t *count_ptr, uint32_t cap, int nbits, void *scratch, size_t scratch_bytes,
-                         int *result_in_tmp, hipStream_t st)
-{
-    return radix_sort_pairs_t<uint64_t>(keys, vals, keys_tmp, vals_tmp, count_ptr, cap, nbits, scratch,
-                                        scratch_bytes, result_in_tmp, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -875,6 +336,13 @@ __global__ __launch_bounds__(kResortThreads) void resort_merge_kernel(int N, con
     }
 }
 
+// step C, run by block 0 of the scan's first kernel
+__device__ __forceinline__ void resort_verify(int nwin, const uint64_t *__restrict__ edges, uint32_t *__restrict__ flag)
+{
+    for (int b = threadIdx.x; b + 1 < nwin; b += 256)
+        if (edges[2 * b + 1] >= edges[2 * (b + 1)]) atomicOr(flag, kResortFailed);
+}
+
 // step 1 of the direct binning after a from-scratch depth sort (and in the staged API): chunks of 1024 positions
 __global__ __launch_bounds__(kDirectChunk) void gather_count_kernel(int N, int GX, const uint32_t *__restrict__ order,
                                                                     const uint2 *__restrict__ erec_box,
@@ -909,13 +377,6 @@ __global__ __launch_bounds__(kDirectChunk) void gather_count_kernel(int N, int G
     }
 }
 
-// step C, run by block 0 of the scan's first kernel
-__device__ __forceinline__ void resort_verify(int nwin, const uint64_t *__restrict__ edges, uint32_t *__restrict__ flag)
-{
-    for (int b = threadIdx.x; b + 1 < nwin; b += 256)
-        if (edges[2 * b + 1] >= edges[2 * (b + 1)]) atomicOr(flag, kResortFailed);
-}
-
 // inclusive max-scan over the 64 lanes of a wave (DPP: shifts inside the rows of 16, then the two row broadcasts)
 __device__ __forceinline__ uint32_t wave_max_scan(uint32_t v)
 {
@@ -930,18 +391,18 @@ __device__ __forceinline__ uint32_t wave_max_scan(uint32_t v)
     return v;
 }
 
-// step 3 of the direct binning.  A chunk of 1024 depth positions is served by SPLIT workgroups of 1024 / SPLIT threads:
-// the chunks at the front of the depth order hold the near surfels — ten and more tiles each, 10-15 k instances per
-// chunk against 1.5 k at the far end — and a launch lasts as long as its heaviest workgroup.  Workgroup `sub` of a chunk
-// first counts the rectangles of the sub-chunks in front of it (LDS counts only: a tenth of what emitting them costs)
-// to know where its own instances start.
-// A workgroup one of whose waves holds kHeavyWave instances or more (near surfels: rectangles of a hundred tiles and more,
-// all at the front of the depth order — 14 k instances in ONE wave at the bench window's last keyframes, 222 rounds where
-// the launch's median wave has two: profiles/r05a_bin_tail.txt) leaves the wave-by-wave rounds: see "heavy" below.
+// step 3 of the direct binning.  A chunk of 1024 depth positions is served by ONE workgroup of 1024 threads, a thread per
+// position: digit bases from the tile totals, the chunk's column of the count table and the waves' own counts make the
+// per-wave cursors; then every wave deals its instances out 64 at a time and ranks them as the radix scatter does.
+// The chunks at the front of the depth order hold the near surfels — ten and more tiles each, 10-15 k instances per
+// chunk against 1.5 k at the far end.  A workgroup one of whose waves holds kHeavyWave instances or more (rectangles of a
+// hundred tiles and more — 14 k instances in ONE wave at the bench window's last keyframes, 222 rounds where the launch's
+// median wave has two: profiles/r05a_bin_tail.txt) leaves the wave-by-wave rounds, and the first kHeavyChunks chunks
+// have helper workgroups for that case: see "heavy" below.
 constexpr uint32_t kHeavyWave = 1536;
 constexpr int kHeavyParts = 4, kHeavyChunks = 16;
-template <int BITS, bool PAIRS, int SPLIT>
-__global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N, int GX, DirectBin db,
+template <int BITS, bool PAIRS>
+__global__ __launch_bounds__(kDirectChunk) void bin_direct_kernel(int N, int GX, DirectBin db,
                                                                   const uint32_t *__restrict__ order,
                                                                   const uint2 *__restrict__ erec_box,
                                                                   const int4 *__restrict__ rect,
@@ -954,48 +415,39 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
                                                                   uint32_t *__restrict__ fail_flag,
                                                                   uint32_t *__restrict__ status_mirror)
 {
-    constexpr int BINS = 1 << BITS, TPB = kDirectChunk / SPLIT, WAVES = TPB / 64;
+    constexpr int BINS = 1 << BITS, TPB = kDirectChunk, WAVES = TPB / 64;
     constexpr int PER = BINS > TPB ? BINS / TPB : 1;          // tiles per thread in the per-tile steps
     static_assert(BINS <= kDirectMaxBins && TPB % 64 == 0 && (BINS % TPB == 0 || BINS < TPB), "tiles dealt evenly to the threads");
     __shared__ uint32_t s_cur[WAVES * BINS];     // per wave and tile: first the instance counts, then the running cursors
-    __shared__ uint32_t s_pre[BINS];             // per tile: instances of the chunk's sub-chunks in front of this one
+    __shared__ uint32_t s_pre[BINS];             // heavy workgroups: per tile, its first slot for this chunk
     __shared__ uint4 s_lane[WAVES][64];          // per wave and lane: {rectangle, block box, surfel, first instance of the lane}
     __shared__ uint32_t s_mark[WAVES][64];       // per wave: which lane's instances start at each slot of the current round
     __shared__ uint32_t s_part[WAVES];
     __shared__ uint32_t s_ws[WAVES];             // the waves' instance counts (which workgroup is "heavy")
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    // Workgroups in front of the grid's chunks (SPLIT = 1): HELPERS of the first kHeavyChunks chunks — where the near
+    // Workgroups in front of the grid's chunks: HELPERS of the first kHeavyChunks chunks — where the near
     // surfels sit — kHeavyParts - 1 each.  A helper looks at its chunk; if that is not heavy (almost always) it leaves at
     // once, else it takes one quarter of the chunk's tiles (pass `part` below) while the chunk's own workgroup takes
     // quarter 0: a heavy chunk's 70 k scattered 8-byte stores are what ONE compute unit's address pipeline takes 35 us for
     // (measured with the stores compiled out), its instances' arithmetic as much again — four compute units share both.
-    const int nhelp = SPLIT == 1 ? min(kHeavyChunks, db.nchunks) * (kHeavyParts - 1) : 0;
+    const int nhelp = min(kHeavyChunks, db.nchunks) * (kHeavyParts - 1);
     const bool helper = (int)blockIdx.x < nhelp;
-    const int chunk = helper ? (int)blockIdx.x / (kHeavyParts - 1) : ((int)blockIdx.x - nhelp) / SPLIT;
-    const int sub = helper ? 0 : ((int)blockIdx.x - nhelp) % SPLIT;
+    const int chunk = helper ? (int)blockIdx.x / (kHeavyParts - 1) : (int)blockIdx.x - nhelp;
     const int part = helper ? 1 + (int)blockIdx.x % (kHeavyParts - 1) : 0;
-    const bool lead = !helper && chunk == 0 && sub == 0;      // the launch's first chunk: ranges, R, the void bits, the status mirror
+    const bool lead = !helper && chunk == 0;      // the launch's first chunk: ranges, R, the void bits, the status mirror
     if (resort_windows > 0 && lead) {
         for (int b = tid; b + 1 < resort_windows; b += TPB)
             if (resort_edges[2 * b + 1] >= resort_edges[2 * (b + 1)]) atomicOr(fail_flag, kResortFailed);
     }
-    // everything the workgroup needs from memory is requested up front: its positions' records (and the rectangles of
-    // the sub-chunks in front), its column of the count table, the tile totals
-    const int pos0 = db.pos0 + chunk * kDirectChunk;
-    const int pos = pos0 + sub * TPB + tid;
+    // everything the workgroup needs from memory is requested up front: its positions' records, its column of the
+    // count table, the tile totals
+    const int pos = db.pos0 + chunk * kDirectChunk + tid;
     const bool real = pos >= 0 && pos < N;
     uint2 er = make_uint2(0u, 0u);
     uint32_t g = 0u;
     if (real) {
         g = order[pos];
         er = db.serec ? db.serec[pos] : load_emit_record(erec_box, rect, sbox, g);
-    }
-    uint32_t front[SPLIT > 1 ? SPLIT - 1 : 1];
-#pragma unroll
-    for (int m = 0; m < SPLIT - 1; ++m) {
-        const int p2 = pos0 + m * TPB + tid;
-        front[m] = 0u;
-        if (m < sub && p2 >= 0 && p2 < N) front[m] = db.serec ? db.serec[p2].x : load_emit_record(erec_box, rect, sbox, order[p2]).x;
     }
     uint32_t tot[PER], ccol[PER];
 #pragma unroll
@@ -1042,7 +494,6 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
         }
     }
     for (int i = tid; i < WAVES * BINS; i += TPB) s_cur[i] = 0u;
-    for (int i = tid; i < BINS; i += TPB) s_pre[i] = 0u;
     const uint32_t t = ((er.x >> 9) & 1023u) * (er.x >> 25);
     uint32_t incl = t;
 #pragma unroll
@@ -1056,15 +507,11 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
     if (lane == 63) s_ws[w] = S;
     __syncthreads();
     bool heavy = false;                          // (workgroup-uniform)
-    if (SPLIT == 1) {
 #pragma unroll
-        for (int k = 0; k < WAVES; ++k) heavy = heavy || s_ws[k] >= kHeavyWave;
-    }
+    for (int k = 0; k < WAVES; ++k) heavy = heavy || s_ws[k] >= kHeavyWave;
     if (helper && !heavy) return;                // (workgroup-uniform: nothing to help with)
     // per-wave counts (the order inside a wave does not matter for counting: every lane walks its own rectangle)
     if (!heavy) count_rect_tiles_wave(er.x, GX, s_cur + w * BINS);
-#pragma unroll
-    for (int m = 0; m < SPLIT - 1; ++m) count_rect_tiles_wave(front[m], GX, s_pre);
     // digit bases: exclusive scan of the tile totals (PER consecutive ones per thread)
     uint32_t loc[PER], dsum = 0;
 #pragma unroll
@@ -1098,7 +545,7 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
             uint32_t c[WAVES];
 #pragma unroll
             for (int k = 0; k < WAVES; ++k) c[k] = s_cur[k * BINS + d];
-            uint32_t run = dbase + ccol[q] + s_pre[d];
+            uint32_t run = dbase + ccol[q];
 #pragma unroll
             for (int k = 0; k < WAVES; ++k) { s_cur[k * BINS + d] = run; run += c[k]; }
         }
@@ -1129,7 +576,7 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
     // the last lane whose first instance is <= q — every lane marks the slot its instances start at, a max-scan over the
     // round's 64 slots (carried on from the previous round) names the owner: one LDS round trip and six DPP steps.
     const uint64_t lt_mask = (1ull << lane) - 1ull;
-    if (SPLIT == 1 && heavy) {
+    if (heavy) {
         // ---- heavy workgroup: every INSTANCE of the chunk goes to a thread, whatever surfel it belongs to.
         // An instance's place is   first slot of its tile for this chunk + set bits of the tile's membership mask below
         // its depth position,   the mask M[wave][tile] = one bit per lane of the wave whose rectangle holds the tile.  1024
@@ -1289,15 +736,8 @@ __global__ __launch_bounds__(kDirectChunk / SPLIT) void bin_direct_kernel(int N,
         int tx = (int)(o.x & 511u) + (int)kx;
         if (tx >= GX) tx -= GX;
         const uint32_t tile = valid ? (uint32_t)(((int)((o.x >> 19) & 63u) + (int)ky) * GX + tx) : 0u;
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < BITS; ++b) {
-            const bool bit = (tile >> b) & 1u;
-            const uint64_t bal = __ballot(bit);
-            peers &= bit ? bal : ~bal;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & lt_mask);
-        const uint32_t count = (uint32_t)__popcll(peers);
+        uint32_t rank, count;
+        wave_digit_rank<BITS>(valid, tile, lt_mask, rank, count);
         uint32_t p = 0;
         if (valid) p = cur[tile] + rank;
         __builtin_amdgcn_wave_barrier();
@@ -1620,8 +1060,9 @@ int launch_depth_order_scan(const DepthOrderScan &a, hipStream_t st, ScanHandoff
         resort_edges = edges;
     } else {
         int which = 0;
-        int rc = radix_sort_pairs_t<uint32_t>(keys, v0, s.keys_tmp, v1, s.n_dev, (uint32_t)N, kDepthKeyBits, s.sort_scratch,
-                                              sort_scratch_bytes((uint64_t)N), &which, st, nullptr, 0, true);   // only the order is used
+        const RadixOptions opt = { nullptr, 0, true, 0, kNoRadixOptions.bm };      // only the order is used
+        int rc = radix_sort_options_u32(keys, v0, s.keys_tmp, v1, s.n_dev, (uint32_t)N, kDepthKeyBits, s.sort_scratch,
+                                        sort_scratch_bytes((uint64_t)N), &which, st, opt);
         if (rc) return rc;
         if ((which != 0) != s.odd) {
             set_error("internal: depth order ended in the wrong buffer");
@@ -1716,28 +1157,26 @@ int launch_bin_sort(const DevCam &cam, const BinSortLaunch &a, hipStream_t st, i
     int which = 0;
     int rc;
     if (emit_hist) {
-        const uint32_t *vin = packed ? nullptr : vals;
-        const int shift = packed ? idx_bits : 0;
-        const uint32_t pmask = packed ? ((1u << idx_bits) - 1u) : 0u;
-#define SLS_CASE(K_, B) case B: rc = tile_sort_emit_chunks<K_, B>(wide ? (const K_ *)wide : (const K_ *)tkeys, vin, (K_ *)nullptr, vals_tmp, chunk_start, \
-                                                              cap, shift, cnt, totals, nemit, (uint2 *)ranges, T, pmask, st, bm); break;
-        if (wide) {
-            switch (tile_bits < 8 ? 8 : tile_bits) { SLS_CASE(uint64_t, 8) SLS_CASE(uint64_t, 9) SLS_CASE(uint64_t, 10) default: SLS_CASE(uint64_t, 11) }
-        } else {
-            switch (tile_bits < 8 ? 8 : tile_bits) { SLS_CASE(uint32_t, 8) SLS_CASE(uint32_t, 9) SLS_CASE(uint32_t, 10) default: SLS_CASE(uint32_t, 11) }
-        }
-#undef SLS_CASE
+        EmitChunkSort e{};
+        e.vals = packed ? nullptr : vals; e.vals_out = vals_tmp; e.chunk_start = chunk_start; e.cap = cap;
+        e.shift = packed ? idx_bits : 0; e.bits = tile_bits < 8 ? 8 : tile_bits;
+        e.cnt = cnt; e.totals = totals; e.nchunks = nemit; e.ranges_out = (uint2 *)ranges; e.nranges = T;
+        e.packed_val_mask = packed ? ((1u << idx_bits) - 1u) : 0u; e.bm = bm;
+        rc = wide ? tile_sort_emit_chunks_u64(wide, e, st) : tile_sort_emit_chunks_u32(tkeys, e, st);
         which = 1;
     } else if (wide) {
-        rc = radix_sort_pairs_t<uint64_t>(wide, nullptr, nullptr, vals_tmp, a.count_ptr, cap, tile_bits, scratch,
-                                          a.scratch_bytes, &which, st, (uint2 *)ranges, T, true, idx_bits, bm);
+        const RadixOptions opt = { (uint2 *)ranges, T, true, idx_bits, bm };
+        rc = radix_sort_options_u64(wide, nullptr, nullptr, vals_tmp, a.count_ptr, cap, tile_bits, scratch, a.scratch_bytes,
+                                    &which, st, opt);
     } else if (packed) {
-        rc = radix_sort_pairs_t<uint32_t>(tkeys, nullptr, tkeys_tmp, vals_tmp, a.count_ptr, cap, tile_bits, scratch,
-                                          a.scratch_bytes, &which, st, (uint2 *)ranges, T, true, idx_bits);
+        const RadixOptions opt = { (uint2 *)ranges, T, true, idx_bits, kNoRadixOptions.bm };
+        rc = radix_sort_options_u32(tkeys, nullptr, tkeys_tmp, vals_tmp, a.count_ptr, cap, tile_bits, scratch, a.scratch_bytes,
+                                    &which, st, opt);
     } else {
-        rc = radix_sort_pairs_t<uint32_t>(tkeys, vals, tkeys_tmp, vals_tmp, a.count_ptr, cap, tile_bits, scratch,
-                                          a.scratch_bytes, &which, st, fused_ranges ? (uint2 *)ranges : nullptr, T,
-                                          fused_ranges);   // nobody reads the sorted tile ids then
+        // (with the ranges from the pass nobody reads the sorted tile ids)
+        const RadixOptions opt = { fused_ranges ? (uint2 *)ranges : nullptr, T, fused_ranges, 0, kNoRadixOptions.bm };
+        rc = radix_sort_options_u32(tkeys, vals, tkeys_tmp, vals_tmp, a.count_ptr, cap, tile_bits, scratch, a.scratch_bytes,
+                                    &which, st, opt);
     }
     if (rc) return rc;
     *sorted_in_tmp = which;
@@ -1814,10 +1253,7 @@ int launch_bin_direct(const DevCam &cam, const BinDirectLaunch &a, hipStream_t s
         SLS_LAUNCH_CHECK("gather_count_kernel");
     }
     if (!db.coarse) {       // (with the coarse table bin_direct sums what lies in front of a chunk itself)
-        ScopedTimer tm(T_SORT_ROWSCAN, st);
-        hipLaunchKernelGGL(sort_rowscan_kernel, dim3(db.bins), dim3(256), 0, st, db.cnt, (const uint32_t *)nullptr, cap,
-                           db.nchunks, db.totals, db.nchunks);
-        SLS_LAUNCH_CHECK("sort_rowscan_kernel");
+        if (int rc = sort_rowscan_rows(db.cnt, db.bins, db.nchunks, db.totals, cap, st)) return rc;
     }
     // (surfel, block mask) pairs under the rule of launch_bin_sort: long lists (or always / never)
     const bool long_lists = a.bmask_mode == 1 || (a.bmask_mode == 0 && (uint64_t)cap >= 1500ull * (uint64_t)T);
@@ -1830,10 +1266,10 @@ int launch_bin_direct(const DevCam &cam, const BinDirectLaunch &a, hipStream_t s
     {
         ScopedTimer tm(T_BIN_DIRECT, st);
         // (every chunk split over 2 / 4 workgroups was measured in round 4 — 24.0 / 26.6 against 24.8 us, profiles/r04f_bin_trace.txt:
-        //  the launch is its chain of phases, not its heaviest chunk — the template keeps the parameter, nothing launches it;
+        //  the launch is its chain of phases, not its heaviest chunk — and the kernel no longer has the variant;
         //  what IS split, since round 6, are the heavy chunks at the front of the depth order: the helper workgroups)
         const int nhelp = (db.nchunks < kHeavyChunks ? db.nchunks : kHeavyChunks) * (kHeavyParts - 1);
-#define SLS_DIRECT(B_, P_) hipLaunchKernelGGL((bin_direct_kernel<B_, P_, 1>), dim3(nhelp + db.nchunks), dim3(kDirectChunk), 0, st, N, cam.GX, db, \
+#define SLS_DIRECT(B_, P_) hipLaunchKernelGGL((bin_direct_kernel<B_, P_>), dim3(nhelp + db.nchunks), dim3(kDirectChunk), 0, st, N, cam.GX, db, \
                                a.order, (const uint2 *)a.erec_box, (const int4 *)a.rect, a.sbox, cap, a.vals_out, bm, (uint2 *)a.ranges, T, \
                                a.total_out, a.overflow, a.resort_windows, a.resort_edges, a.overflow, a.status_mirror)
         if (db.bins == 256) { if (bm.out) SLS_DIRECT(8, true); else SLS_DIRECT(8, false); }

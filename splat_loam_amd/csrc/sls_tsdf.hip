@@ -7,7 +7,7 @@
 // sls_tsdf_blocks, launches ordered by the stream alone:
 //   tsdf_init / tsdf_keys       27 candidate keys per point (0 where the point names nothing), the identity permutation,
 //                               the counts of non-finite and out-of-range points (integer atomics: order-free)
-//   the stable LSD sort         63 key bits over (u64 key, u32 index) pairs (sls_sort.hip: radix_sort_pairs_u64)
+//   the stable LSD sort         63 key bits over (u64 key, u32 index) pairs (sls_radix.hip: radix_sort_pairs_u64)
 //   tsdf_heads / _scan / _write head flags of the sorted keys (a non-zero key that differs from its predecessor), their
 //                               scan in chunks of 2048 positions, the block coordinates and the status words
 //

@@ -27,12 +27,12 @@ LONG_ROW = 64                   # SLS_SMOOTH_LONG, SLS_FILL_LONG: rows / loops a
 
 # (file, the text the file must hold, the size tests that stop covering their path when it changes)
 SOURCES = (
-    ("splat_loam_amd/csrc/sls_sort.hip", "#define SLS_SORT_ROUNDS 16", "weld, voxel, tsdf: every P threshold of the sorter"),
-    ("splat_loam_amd/csrc/sls_sort.hip", "constexpr int kSortWaveItems = kWave * kSortRounds;", "weld, voxel, tsdf"),
+    ("splat_loam_amd/csrc/sls_radix.hip", "#define SLS_SORT_ROUNDS 16", "weld, voxel, tsdf: every P threshold of the sorter"),
+    ("splat_loam_amd/csrc/sls_radix.hip", "constexpr int kSortWaveItems = kWave * kSortRounds;", "weld, voxel, tsdf"),
     ("splat_loam_amd/csrc/sls_common.hpp", "constexpr int kWave = 64;", "weld, voxel, tsdf"),
-    ("splat_loam_amd/csrc/sls_sort.hip", "__global__ __launch_bounds__(256) void sort_rowscan_kernel(", "weld, voxel, tsdf"),
-    ("splat_loam_amd/csrc/sls_sort.hip", "const int P = (nchunks + 255) / 256,", "weld, voxel, tsdf"),
-    ("splat_loam_amd/csrc/sls_sort.hip", "constexpr int kKeep = 8;", "test_weld_rowscan_and_head_scan[2098177], test_tsdf_blocks_sort_tail"),
+    ("splat_loam_amd/csrc/sls_radix.hip", "__global__ __launch_bounds__(256) void sort_rowscan_kernel(", "weld, voxel, tsdf"),
+    ("splat_loam_amd/csrc/sls_radix.hip", "const int P = (nchunks + 255) / 256,", "weld, voxel, tsdf"),
+    ("splat_loam_amd/csrc/sls_radix.hip", "constexpr int kKeep = 8;", "test_weld_rowscan_and_head_scan[2098177], test_tsdf_blocks_sort_tail"),
     ("splat_loam_amd/csrc/sls_cloud.hip", "constexpr int kCloudThreads = 256;", "test_voxel_*"),
     ("splat_loam_amd/csrc/sls_cloud.hip", "using CloudChunks = Chunks<kCloudThreads, 4>;", "test_voxel_*, test_mesh_sample_*"),
     ("splat_loam_amd/csrc/sls_outlier.hip", "constexpr int kOutThreads = 256;", "test_statistical_*, test_radius_*"),

@@ -1,5 +1,6 @@
-"""The block-box arithmetic behind the forward tile kernel's dense rounds (sls_common.hpp: make_block_box,
-sls_sort.hip: block_mask_of), restated in NumPy and checked against the test it has to be a superset of: the tile
+"""The block-box arithmetic behind the forward tile kernel's dense rounds (sls_common.hpp: make_block_box and
+block_mask_of, which the scatter of sls_radix.hip and the direct binning of sls_sort.hip call), restated in NumPy and
+checked against the test it has to be a superset of: the tile
 kernels' cull_pass on a whole 8x2 pixel block (sls_tile.hpp).  CPU only — the device code itself is exercised end to end
 by the engine-vs-checker tests with block_masks forced on (tests/test_timed_path.py)."""
 import numpy as np

@@ -129,6 +129,41 @@ def test_tile_cull_thresholds_parity(device, oracle32, kmin):
     _compare_backward(oracle32, st, t, ost, sc, f"tile_cull_min{kmin}")
 
 
+def _emission_counts_its_chunks(N, T, R):
+    """launch_bin_sort's rule (sls_sort.hip, emit_hist) for a single-pass tile sort: the emission's workgroups of 256
+    positions are the pass's chunks while their count table is small and fits the sorter's (sort_core_bytes)"""
+    bins, nemit = max(256, 1 << (T - 1).bit_length()), (N + 255) // 256
+    core = (2048 * max((R + 1023) // 1024, 1) + 2048) * 4
+    return bins * nemit <= 400000 and (bins * nemit + bins + nemit + 1) * 4 <= core
+
+
+SCATTER_CASES = [
+    # name, W, hfov, scene, the emission's chunks?  (D10 on: the direct binning is out, emission + one radix pass)
+    ("emission_chunks", 1024, 360.0, {}, True),                 # 256 bins x 79 chunks: sort_scatter_chunks_kernel
+    ("fixed_chunks", 512, 60.0, dict(range_lo=8.0, scale_lo=0.005, scale_hi=0.02), False),   # five surfels in six are
+]                                                               # out of view: the table outgrows the sorter's, sort_scatter_kernel
+
+
+@pytest.mark.parametrize("list_pairs", [2, 1], ids=["u32-packed", "u64-pairs"])
+@pytest.mark.parametrize("name,W,hfov,kw,chunks", SCATTER_CASES, ids=[c[0] for c in SCATTER_CASES])
+def test_tile_sort_scatter_variants_parity(device, oracle32, name, W, hfov, kw, chunks, list_pairs):
+    """Both scatter kernels of the radix sorter (sls_radix.hip) in the tile sort's single pass with ranges, each with
+    packed 32-bit instances (plain list) and with 64-bit instances stored as (surfel, block mask) pairs: sorted lists,
+    ranges and image against the checker.  Which kernel ran follows from N, the tile count and R by the launcher's rule."""
+    from splat_loam_amd import _abi
+    N, H = 20000, 64
+    sc, view, proj = scene_and_camera(N, H, W, seed=31, hfov_deg=hfov, **kw)
+    st, t = hip_forward(device, sc, view, proj, H, W, tile_cull_min=2, list_pairs=list_pairs)
+    tw, th = _abi.tile_size()
+    print(f"\n[{name}] R={st.R}")
+    assert st.R > 0 and _emission_counts_its_chunks(N, (H // th) * (W // tw), st.R) == chunks
+    assert st.vals_stride == (2 if list_pairs == 1 else 1)
+    cam = oracle32.camera(H, W, view, proj, tile=(tw, th), tile_cull=2)
+    ost = oracle32.forward(cam, sc["means"], sc["scales"], sc["rots"], sc["opac"])
+    _compare_forward(oracle32, st, ost, cam, f"{name}-{list_pairs}")
+    _compare_backward(oracle32, st, t, ost, sc, f"{name}-{list_pairs}")
+
+
 @pytest.mark.parametrize("offset", [(-0.5, -0.5), (0.25, -0.125)])
 def test_pixel_centre_offset_parity(device, oracle32, offset):
     """D1 as a parameter (SlsCamera.pix_offset): pixel (c, r) at image coordinate (c + ox, r + oy).  The reference's
