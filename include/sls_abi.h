@@ -807,6 +807,49 @@ int sls_outlier_radius(int M, const float *xyz, const float *normals, int nb_poi
                        float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, size_t scratch_bytes,
                        void *stream);
 
+/* ---- clusters of a cloud ---------------------------------------------------------------------------------------------
+ * sls_cloud_dbscan: DBSCAN over exact radius neighbours, with the border rule of Open3D's cluster_dbscan as restated in
+ * include/sls_cluster_math.h (Open3D is not a dependency; no parity is claimed).  With r2 = eps * eps (a float32 product)
+ * and d2 the expression of sls_nn_query, t is a neighbour of q iff d2 <= r2 — itself and exact copies included; a point
+ * is CORE iff at least min_points points are its neighbours; the clusters are the connected components of the cores,
+ * numbered in ascending order of their lowest core index; a non-core point with a core neighbour takes the lowest
+ * cluster number among its core neighbours' clusters and joins nothing; any other point is noise.  One call, nothing read
+ * back inside it; integers and one float32 comparison: the same input gives the same bytes on every run, those of the
+ * header's all-pairs routine, on any finite input.  The cost grows with the pairs within eps: eps is meant to be a few
+ * point spacings.  Coordinates must be finite (not checked; every access stays inside the buffers).
+ *   out_labels [M] int32: the cluster number, -1 for noise.  out_counts [room for M] int32: entries 0 .. C-1, the points
+ *       of each cluster, cores and borders; the entries from C on are not written.
+ *   out_status (DEVICE, SLS_CLUSTER_STATUS_WORDS words): [C, cores, borders, noise, the largest count, M, 0, 1].
+ *   scratch: sls_cloud_dbscan_scratch_bytes(M) bytes (0 for M < 1), 256-byte aligned, a multiple of 256, monotone in M.
+ * M == 0 succeeds and writes only out_status.  Before anything is enqueued: SLS_E_ARG for M < 0, an eps that is not a
+ * finite number > 0 or whose square is not finite, min_points < 1, a null out_status, for M > 0 a null xyz / out_labels /
+ * out_counts / scratch or misaligned scratch; SLS_E_SCRATCH for too little scratch.
+ *
+ * sls_cloud_select: the rule of sls_mesh_filter over the clusters of a cloud.  C = cluster_status[0] is read on the
+ * device; n_min = max(max(min_cluster_points, 0), the min(keep, C)-th largest count), the second term 0 for keep <= 0; a
+ * point is kept iff its label is >= 0 and counts[label] >= n_min (ties at the K-th place all stay).  An ordered
+ * compaction, as in the outlier filters:
+ *   normals (optional, M x 3): rows that travel with their points into out_normals.
+ *   out_xyz, out_normals (M x 3 floats), out_index (M int32: the original row): room for M rows each, the kept rows in
+ *       ascending original index, the rows from `kept` on not written.  Each may be null and is then skipped
+ *       (out_normals must be null when normals is).
+ *   out_status (DEVICE, SLS_CLUSTER_SELECT_STATUS_WORDS words): [kept, n_min, M, 1].
+ *   scratch: sls_cloud_select_scratch_bytes(M) bytes (0 for M < 1), 256-byte aligned.
+ * M == 0 succeeds and writes only out_status.  Before anything is enqueued: SLS_E_ARG for M < 0, a null out_status, for
+ * M > 0 a null xyz / labels / counts / cluster_status / scratch, out_normals without normals, misaligned scratch;
+ * SLS_E_SCRATCH for too little scratch. */
+#ifndef SLS_CLUSTER_STATUS_WORDS
+#define SLS_CLUSTER_STATUS_WORDS 8      /* (include/sls_cluster_math.h defines the same) */
+#define SLS_CLUSTER_SELECT_STATUS_WORDS 4
+#endif
+size_t sls_cloud_dbscan_scratch_bytes(int M);
+int sls_cloud_dbscan(int M, const float *xyz, float eps, int min_points, int32_t *out_labels, int32_t *out_counts,
+                     uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+size_t sls_cloud_select_scratch_bytes(int M);
+int sls_cloud_select(int M, const float *xyz, const float *normals, const int32_t *labels, const int32_t *counts,
+                     const uint32_t *cluster_status, int keep, int min_cluster_points, float *out_xyz, float *out_normals,
+                     int32_t *out_index, uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- normals of a cloud by PCA --------------------------------------------------------------------------------------
  * Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn = k)) followed by
  * orient_normals_towards_camera_location(viewpoint), restated in include/sls_normals_math.h (Open3D is not a dependency).

@@ -183,6 +183,10 @@ _PROTOS = {
     "sls_outlier_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_outlier_statistical": (C.c_int, [C.c_int, _VP, _VP, C.c_int, C.c_double, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_outlier_radius": (C.c_int, [C.c_int, _VP, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_cloud_dbscan_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_cloud_dbscan": (C.c_int, [C.c_int, _VP, C.c_float, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_cloud_select_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "sls_cloud_select": (C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_cloud_normals_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sls_cloud_normals": (C.c_int, [C.c_int, _VP, C.c_int, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_ground_scratch_bytes": (C.c_size_t, [C.c_int]),

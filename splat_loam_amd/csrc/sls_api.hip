@@ -10,6 +10,7 @@
 #include "sls_consumer_dev.hpp"
 #include "sls_launch.hpp"
 #include "../../include/sls_smooth_math.h"
+#include "../../include/sls_cluster_math.h"
 
 namespace sls {
 
@@ -572,6 +573,47 @@ int sls_outlier_radius(int M, const float *xyz, const float *normals, int nb_poi
     if (rc || done) return rc;
     return launch_outlier_radius(M, xyz, normals, nb_points, radius, out_xyz, out_normals, out_index, out_status, scratch,
                                  (hipStream_t)stream);
+}
+
+size_t sls_cloud_dbscan_scratch_bytes(int M) { return cloud_dbscan_scratch_bytes(M); }
+size_t sls_cloud_select_scratch_bytes(int M) { return cloud_select_scratch_bytes(M); }
+
+int sls_cloud_dbscan(int M, const float *xyz, float eps, int min_points, int32_t *out_labels, int32_t *out_counts,
+                     uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE(eps > 0.0f && eps <= FLT_MAX, "eps is not a finite number > 0");
+    SLS_REQUIRE(sls_cluster_eps_ok(eps), "eps * eps is not finite");
+    SLS_REQUIRE(min_points >= 1, "min_points < 1");
+    SLS_REQUIRE(out_status, "null pointer");
+    if (M > 0) {
+        SLS_REQUIRE(xyz && out_labels && out_counts && scratch, "null pointer");
+        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+        if (scratch_bytes < cloud_dbscan_scratch_bytes(M)) {
+            set_error("sls_cloud_dbscan: scratch too small: %zu < %zu", scratch_bytes, cloud_dbscan_scratch_bytes(M));
+            return SLS_E_SCRATCH;
+        }
+    }
+    return launch_cloud_dbscan(M, xyz, eps, min_points, out_labels, out_counts, out_status, scratch, (hipStream_t)stream);
+}
+
+int sls_cloud_select(int M, const float *xyz, const float *normals, const int32_t *labels, const int32_t *counts,
+                     const uint32_t *cluster_status, int keep, int min_cluster_points, float *out_xyz, float *out_normals,
+                     int32_t *out_index, uint32_t *out_status, void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE(out_status, "null pointer");
+    if (M > 0) {
+        SLS_REQUIRE(xyz && labels && counts && cluster_status && scratch, "null pointer");
+        SLS_REQUIRE(!(out_normals && !normals), "out_normals without normals");
+        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+        if (scratch_bytes < cloud_select_scratch_bytes(M)) {
+            set_error("sls_cloud_select: scratch too small: %zu < %zu", scratch_bytes, cloud_select_scratch_bytes(M));
+            return SLS_E_SCRATCH;
+        }
+    }
+    return launch_cloud_select(M, xyz, normals, labels, counts, cluster_status, keep, min_cluster_points, out_xyz, out_normals,
+                               out_index, out_status, scratch, (hipStream_t)stream);
 }
 
 size_t sls_cloud_normals_scratch_bytes(int M, int k) { return cloud_normals_scratch_bytes(M, k); }

@@ -9,7 +9,8 @@
 //      axis-aligned boxes over runs of 256 consecutive points;
 //   4. one wave per 64 consecutive points, one lane per point: the own box first for a tight bound, then the sweep
 //      (knn_sweep below) over the other boxes; the two-cloud searches (sls_nn_query, sls_nn_query_k) run it too, and so
-//      does the point-to-mesh distance (sls_mesh_distance), whose index holds triangles.
+//      does the point-to-mesh distance (sls_mesh_distance), whose index holds triangles, and so do the three radius
+//      searches of sls_cloud_dbscan (count, unite, border: at the end of this file).
 // Squared distances use the fixed expression fma(dz,dz,fma(dy,dy,dx*dx)), so
 // the result is reproducible bit for bit by a CPU brute force.
 #include <float.h>
@@ -18,6 +19,8 @@
 #include "../../include/sls_nn_math.h"
 #include "../../include/sls_meshdist_math.h"
 #include "../../include/sls_outlier_math.h"
+#include "../../include/sls_cluster_math.h"
+#include "sls_unionfind.hpp"
 
 namespace sls {
 
@@ -1071,6 +1074,192 @@ int launch_error_colors(int M, const float *dist2, float truncation, uint8_t *ou
     if (M == 0) return SLS_OK;
     hipLaunchKernelGGL(error_colors_kernel, dim3((M + 255) / 256), dim3(256), 0, st, M, dist2, truncation, out_rgb);
     SLS_LAUNCH_CHECK("error_colors_kernel");
+    return SLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// sls_cloud_dbscan's three searches (include/sls_cluster_math.h; the stages between them live in sls_cluster.hip).  All
+// three are the cloud's SELF-query at the constant radius r2 — the own box first, then the sweep, as knn_query_kernel
+// does, but a point is its own neighbour: no lane leaves itself out.
+//   count   CountSearch: the neighbours within r2, the bound r2 until the lane's count reaches min_points and after that
+//           a value nothing passes, so a wave whose lanes are all core lists nothing more.  A count rests on the sweep
+//           showing every target once; a saturated lane may be shown more for another lane's sake, which only raises a
+//           count that is read as `>= min_points`.
+//   unite   UniteSearch, core lanes alone: uf_unite(own index, target's index) for the core targets of LOWER index within
+//           r2 — each pair joined once.  parent is indexed by ORIGINAL index, so a root is its component's lowest core.
+//   border  BorderSearch, non-core lanes alone: the lowest root among the core targets within r2.
+// The core flag rides in the staged item: cluster_mark_kernel, between count and unite, sets the top bit of pts[].w (an
+// original index is below 2^31).  The pad of a short last run is a far point: d2 = +inf passes no radius.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kClusterCoreBit = 0x80000000u;
+
+__device__ __forceinline__ float4 cluster_pad() { return make_float4(1.0e30f, 1.0e30f, 1.0e30f, 0.0f); }
+
+struct CountSearch {
+    const float4 me;
+    const float r2;
+    const int min_points;
+    int count;
+    __device__ __forceinline__ float bound() const { return sls_cluster_count_bound(count, min_points, r2); }
+    __device__ __forceinline__ float4 pad(const float4 *, int) const { return cluster_pad(); }
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
+#pragma unroll 8
+        for (int k = 0; k < kKnnSub; ++k) {
+            const float4 p = s_run[k];
+            count += sls_cluster_near(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), r2);
+        }
+    }
+};
+
+struct UniteSearch {
+    const float4 me;
+    const float r2;
+    const bool active;              // a core lane: the others are shown the runs and do nothing
+    const uint32_t mine;            // the lane's original index
+    uint32_t *parent;
+    __device__ __forceinline__ float bound() const { return r2; }
+    __device__ __forceinline__ float4 pad(const float4 *, int) const { return cluster_pad(); }
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
+        for (int k = 0; k < kKnnSub; ++k) {
+            const float4 p = s_run[k];
+            const uint32_t w = __float_as_uint(p.w);        // a core target of lower index: w - bit < mine
+            if (active && sls_cluster_near(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), r2) && w >= kClusterCoreBit &&
+                (w ^ kClusterCoreBit) < mine)
+                uf_unite(parent, mine, w ^ kClusterCoreBit);
+        }
+    }
+};
+
+struct BorderSearch {
+    const float4 me;
+    const float r2;
+    const bool active;
+    const uint32_t *__restrict__ root;
+    uint32_t best;
+    __device__ __forceinline__ float bound() const { return r2; }
+    __device__ __forceinline__ float4 pad(const float4 *, int) const { return cluster_pad(); }
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
+        for (int k = 0; k < kKnnSub; ++k) {
+            const float4 p = s_run[k];
+            const uint32_t w = __float_as_uint(p.w);
+            if (active && sls_cluster_near(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), r2) && w >= kClusterCoreBit)
+                best = min(best, root[w ^ kClusterCoreBit]);
+        }
+    }
+};
+
+// the body of the three kernels behind their set-up: the wave's own box in full, then the sweep over the others
+template <class Search>
+__device__ __forceinline__ void self_search(const KnnIndex &ix, const bool live, const float4 me, Search &s, SweepLds &lds)
+{
+    const int own_box = (blockIdx.x * 64) / kKnnBox, own_sub0 = (blockIdx.x * 64) / kKnnSub, nsub = ix.nsub();
+    for (int t = 0; t < kKnnSubs; ++t) {
+        const int sb = own_box * kKnnSubs + ((t + (own_sub0 % kKnnSubs)) % kKnnSubs);
+        if (sb >= nsub) continue;
+        stage(lds, run_point<true>(ix, sb, s));
+        s.scan(lds.run);
+    }
+    float4 wmn = ix.subboxes[2 * (size_t)own_sub0], wmx = ix.subboxes[2 * (size_t)own_sub0 + 1];
+    if (own_sub0 + 1 < nsub) box_join(wmn, wmx, ix.subboxes[2 * (size_t)own_sub0 + 2], ix.subboxes[2 * (size_t)own_sub0 + 3]);
+    float4 gmn, gmx;
+    group_boxes(live, me, gmn, gmx);
+    knn_sweep(ix, own_box, live, me, wmn, wmx, gmn, gmx, s, lds);
+}
+
+// core[i] = 1 / 0 and parent[i] = i, both by original index
+__global__ __launch_bounds__(64) void cluster_count_kernel(int M, int nboxes, const float4 *__restrict__ pts,
+                                                           const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                           float r2, int min_points, uint32_t *__restrict__ core,
+                                                           uint32_t *__restrict__ parent)
+{
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { M, nboxes, pts, boxes, subboxes };
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    const bool live = q < M;
+    const float4 me = pts[live ? q : M - 1];
+    CountSearch s = { me, r2, min_points, 0 };
+    self_search(ix, live, me, s, lds);
+    if (live) {
+        const uint32_t i = __float_as_uint(me.w);
+        core[i] = (uint32_t)sls_cluster_core(s.count, min_points);
+        parent[i] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void cluster_mark_kernel(int M, float4 *__restrict__ pts, const uint32_t *__restrict__ core)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const uint32_t i = __float_as_uint(pts[j].w);
+    if (core[i]) pts[j].w = __uint_as_float(i | kClusterCoreBit);
+}
+
+__global__ __launch_bounds__(64) void cluster_unite_kernel(int M, int nboxes, const float4 *__restrict__ pts,
+                                                           const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                           float r2, uint32_t *parent)
+{
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { M, nboxes, pts, boxes, subboxes };
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    const float4 me = pts[q < M ? q : M - 1];
+    const bool live = q < M && __float_as_uint(me.w) >= kClusterCoreBit;
+    if (!__ballot(live)) return;                        // a wave without a core point joins nothing
+    UniteSearch s = { me, r2, live, __float_as_uint(me.w) & ~kClusterCoreBit, parent };
+    self_search(ix, live, me, s, lds);
+}
+
+// root[i] of the non-core points: the lowest root among their core neighbours, SLS_CLUSTER_NONE without one (the cores'
+// entries, written by the flatten pass before this launch, are only read)
+__global__ __launch_bounds__(64) void cluster_border_kernel(int M, int nboxes, const float4 *__restrict__ pts,
+                                                            const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                            float r2, uint32_t *root)
+{
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { M, nboxes, pts, boxes, subboxes };
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    const float4 me = pts[q < M ? q : M - 1];
+    const bool live = q < M && __float_as_uint(me.w) < kClusterCoreBit;
+    if (!__ballot(live)) return;                        // a wave of core points has no border to find
+    BorderSearch s = { me, r2, live, root, SLS_CLUSTER_NONE };
+    self_search(ix, live, me, s, lds);
+    if (live) root[__float_as_uint(me.w)] = s.best;
+}
+
+// The cloud's index in `scratch` (knn_scratch_bytes(M), 256-byte aligned), the count and the mark; then, after the
+// caller's own stages, the other two searches over the same index.  core, parent, root: [M] words by original index.
+int cluster_index_count(int M, const float *xyz, float r2, int min_points, uint32_t *core, uint32_t *parent, void *scratch,
+                        hipStream_t st)
+{
+    const KnnScratch s = knn_layout(M, scratch, M);
+    int which = 0;
+    const int rc = knn_build(M, xyz, s, knn_key_bits(M), 0u, st, &which);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cluster_count_kernel, dim3((M + 63) / 64), dim3(64), 0, st, M, (M + kKnnBox - 1) / kKnnBox,
+                       (const float4 *)s.pts, (const float4 *)s.boxes, (const float4 *)s.subboxes, r2, min_points, core, parent);
+    SLS_LAUNCH_CHECK("cluster_count_kernel");
+    hipLaunchKernelGGL(cluster_mark_kernel, dim3((M + 255) / 256), dim3(256), 0, st, M, s.pts, (const uint32_t *)core);
+    SLS_LAUNCH_CHECK("cluster_mark_kernel");
+    return SLS_OK;
+}
+
+int cluster_unite(int M, float r2, uint32_t *parent, void *scratch, hipStream_t st)
+{
+    const KnnScratch s = knn_layout(M, scratch, M);
+    hipLaunchKernelGGL(cluster_unite_kernel, dim3((M + 63) / 64), dim3(64), 0, st, M, (M + kKnnBox - 1) / kKnnBox,
+                       (const float4 *)s.pts, (const float4 *)s.boxes, (const float4 *)s.subboxes, r2, parent);
+    SLS_LAUNCH_CHECK("cluster_unite_kernel");
+    return SLS_OK;
+}
+
+int cluster_border(int M, float r2, uint32_t *root, void *scratch, hipStream_t st)
+{
+    const KnnScratch s = knn_layout(M, scratch, M);
+    hipLaunchKernelGGL(cluster_border_kernel, dim3((M + 63) / 64), dim3(64), 0, st, M, (M + kKnnBox - 1) / kKnnBox,
+                       (const float4 *)s.pts, (const float4 *)s.boxes, (const float4 *)s.subboxes, r2, root);
+    SLS_LAUNCH_CHECK("cluster_border_kernel");
     return SLS_OK;
 }
 

@@ -256,6 +256,14 @@ int launch_outlier_statistical(int M, const float *xyz, const float *normals, in
                                float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st);
 int launch_outlier_radius(int M, const float *xyz, const float *normals, int nb_points, float radius, float *out_xyz,
                           float *out_normals, int32_t *out_index, uint64_t *out_status, void *scratch, hipStream_t st);
+// ---- sls_cluster.hip (the arguments are checked by the caller, sls_api.hip; M == 0: only the status is written) ----
+size_t cloud_dbscan_scratch_bytes(int M);
+int launch_cloud_dbscan(int M, const float *xyz, float eps, int min_points, int32_t *out_labels, int32_t *out_counts,
+                        uint32_t *out_status, void *scratch, hipStream_t st);
+size_t cloud_select_scratch_bytes(int M);
+int launch_cloud_select(int M, const float *xyz, const float *normals, const int32_t *labels, const int32_t *counts,
+                        const uint32_t *cluster_status, int keep, int min_cluster_points, float *out_xyz, float *out_normals,
+                        int32_t *out_index, uint32_t *out_status, void *scratch, hipStream_t st);
 // ---- sls_normals.hip (the arguments are checked by the caller, sls_api.hip; viewpoint3: host memory) ---------------
 size_t cloud_normals_scratch_bytes(int M, int k);
 int launch_cloud_normals(int M, const float *xyz, int k, float radius, const float *viewpoint3, float *out_normals,

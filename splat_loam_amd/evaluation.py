@@ -385,6 +385,121 @@ def remove_radius_outlier(points: torch.Tensor, nb_points: int, radius: float, n
     return res
 
 
+CLUSTER_STATUS_WORDS = 8        # SLS_CLUSTER_STATUS_WORDS, and behind them the SLS_CLUSTER_SELECT_STATUS_WORDS = 4 of the selection
+INT32_MAX = 2 ** 31 - 1
+
+
+def _check_cluster_args(eps, min_points) -> tuple[float, int]:
+    """(eps, min_points) as sls_cloud_dbscan accepts them — before any launch."""
+    eps = float(eps)
+    f32 = struct.unpack("<f", struct.pack("<f", eps))[0] if math.isfinite(eps) and abs(eps) <= 3.4028234663852886e38 else math.inf
+    if not (eps > 0.0 and math.isfinite(f32) and f32 > 0.0 and f32 * f32 <= 3.4028234663852886e38):
+        raise ValueError("eps must be a finite number > 0 whose square is a finite float32")
+    if isinstance(min_points, bool) or int(min_points) != min_points or not 1 <= int(min_points) <= INT32_MAX:
+        raise ValueError("min_points must be an integer >= 1")
+    return f32, int(min_points)
+
+
+def _check_select_args(keep, min_cluster_points) -> tuple[int, int]:
+    for name, v in (("keep", keep), ("min_cluster_points", min_cluster_points)):
+        if isinstance(v, bool) or int(v) != v or not -INT32_MAX <= int(v) <= INT32_MAX:
+            raise ValueError(f"{name} must be an integer")
+    return int(keep), int(min_cluster_points)
+
+
+def _dbscan_enqueue(lib, points, eps: float, min_points: int, status: torch.Tensor, st):
+    """sls_cloud_dbscan without a host read: (labels (M,) int32, counts (M,) int32: the first C entries); status: 8 int32."""
+    M = int(points.shape[0])
+    dev = points.device
+    labels = torch.empty((M,), dtype=torch.int32, device=dev)
+    counts = torch.empty((M,), dtype=torch.int32, device=dev)
+    _, aligned, nbytes = _scratch_bytes(lib.sls_cloud_dbscan_scratch_bytes(M), dev)
+    _abi.check(lib.sls_cloud_dbscan(M, points.data_ptr() if M else None, eps, min_points, labels.data_ptr() if M else None,
+                                    counts.data_ptr() if M else None, status.data_ptr(), aligned if M else None, nbytes, st),
+               "sls_cloud_dbscan")
+    return labels, counts
+
+
+def _cluster_details(words) -> dict:
+    return {"clusters": int(words[0]), "core": int(words[1]), "border": int(words[2]), "noise": int(words[3]),
+            "largest": int(words[4])}
+
+
+def cluster_dbscan(points: torch.Tensor, eps: float, min_points: int = 10, return_counts: bool = False, details: bool = False):
+    """DBSCAN over exact radius neighbours (include/sls_cluster_math.h), with the border rule of Open3D's `cluster_dbscan`
+    as restated there — Open3D is not a dependency and no parity is claimed; the rule is pinned against a NumPy
+    restatement (tests/cluster_ref.py) and the header's all-pairs routine.  t is a neighbour of q iff
+    d2 <= eps * eps (one float32 product, d2 the exact float32 expression of `nearest`), itself and exact copies
+    included; a point is core iff at least `min_points` points are its neighbours; the clusters are the connected
+    components of the cores, numbered in ascending order of their lowest core index; a non-core point with a core
+    neighbour takes the lowest cluster number among its core neighbours' clusters and connects nothing; the rest is
+    noise, -1.  Integers and one comparison: the same cloud gives the same bytes on every run.
+
+    The cost grows with the number of pairs within eps — eps is meant to be a few point spacings; many spacings on
+    millions of points is quadratic, as it is anywhere.  min_points = 10 is a judgement.
+
+    Returns labels (M,) int32; with `return_counts=True` then counts (C,) int32, the points of every cluster; with
+    `details=True` then a dict: clusters, core, border, noise, largest.  One native call (sls_cloud_dbscan), one host
+    read (the status words).  Coordinates must be finite, as for `nearest`."""
+    points = _cloud(points, "points")
+    eps, min_points = _check_cluster_args(eps, min_points)
+    lib = _abi.lib()
+    dev = points.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        status = torch.empty((CLUSTER_STATUS_WORDS,), dtype=torch.int32, device=dev)
+        labels, counts = _dbscan_enqueue(lib, points, eps, min_points, status, st)
+        words = status.cpu().tolist()                                       # the one host read
+    res = [labels]
+    if return_counts:
+        res.append(counts[:int(words[0])])
+    if details:
+        res.append(_cluster_details(words))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def keep_clusters(points: torch.Tensor, eps: float, min_points: int = 10, keep: int = 1, min_cluster_points: int = 0, normals=None,
+                  return_index: bool = False, details: bool = False):
+    """The large pieces of a cloud: `cluster_dbscan(eps, min_points)`, then the rule of `mesh_ops`' cluster filter over
+    its clusters — n_min = max(max(min_cluster_points, 0), the min(keep, C)-th largest count), the second term 0 for
+    keep <= 0; a point stays iff it has a cluster and that cluster holds at least n_min points (clusters that tie at the
+    keep-th place all stay; noise always goes).  Two native calls back to back (sls_cloud_dbscan, sls_cloud_select), ONE
+    host read in total.  keep = 1 is a judgement.
+
+    Returns as `remove_statistical_outlier`: the kept rows in their original order, (kept,3) float32; then the kept rows
+    of `normals` where given, with `return_index=True` their original row numbers (kept,) int32, with `details=True` a
+    dict: kept, removed, n_min and the words of `cluster_dbscan`."""
+    points = _cloud(points, "points")
+    eps, min_points = _check_cluster_args(eps, min_points)
+    keep, min_cluster_points = _check_select_args(keep, min_cluster_points)
+    normals = _normals(normals, points)
+    lib = _abi.lib()
+    dev = points.device
+    M = int(points.shape[0])
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        status = torch.empty((CLUSTER_STATUS_WORDS + 4,), dtype=torch.int32, device=dev)
+        labels, counts = _dbscan_enqueue(lib, points, eps, min_points, status, st)
+        out = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        out_n = torch.empty((M, 3), dtype=torch.float32, device=dev) if normals is not None else None
+        index = torch.empty((M,), dtype=torch.int32, device=dev) if return_index else None
+        _, aligned, nbytes = _scratch_bytes(lib.sls_cloud_select_scratch_bytes(M), dev)
+        ptr = lambda t: t.data_ptr() if (t is not None and M) else None
+        _abi.check(lib.sls_cloud_select(M, ptr(points), ptr(normals), ptr(labels), ptr(counts), status.data_ptr() if M else None, keep,
+                                        min_cluster_points, ptr(out), ptr(out_n), ptr(index), status[CLUSTER_STATUS_WORDS:].data_ptr(),
+                                        aligned if M else None, nbytes, st), "sls_cloud_select")
+        words = status.cpu().tolist()                                       # the one host read
+    kept = int(words[CLUSTER_STATUS_WORDS])
+    res = [out[:kept]]
+    if normals is not None:
+        res.append(out_n[:kept])
+    if return_index:
+        res.append(index[:kept])
+    if details:
+        res.append({"kept": kept, "removed": M - kept, "n_min": int(words[CLUSTER_STATUS_WORDS + 1]), **_cluster_details(words)})
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 ICP_METHODS = {"plane": 0, "point": 1}                # SLS_ICP_PLANE, SLS_ICP_POINT (include/sls_abi.h)
 ICP_STATUS_WORDS = 20                                   # SLS_ICP_STATUS_WORDS
 ICP_MAX_ITERATIONS = 1000                               # SLS_ICP_MAX_ITERATIONS

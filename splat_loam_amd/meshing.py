@@ -187,10 +187,19 @@ def _check_outlier(outlier_nb, outlier_std):
     return evaluation._check_stat_args(outlier_nb, outlier_std)
 
 
+def _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_size):
+    """None, or (eps, min_points, keep, min_cluster_points) checked as evaluation.keep_clusters checks them — before any work."""
+    if cluster_eps is None:
+        return None
+    from . import evaluation
+    return evaluation._check_cluster_args(cluster_eps, cluster_min_points) + evaluation._check_select_args(cluster_keep, cluster_min_size)
+
+
 @torch.no_grad()
 def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int = 5000, min_opacity: float = 0.5,
                    max_depth_dist: float = 0.1, use_median_depth: bool = False, seed=None, device="cuda",
-                   details: bool = False, image_height=None, image_width=None, outlier_nb=None, outlier_std: float = 2.0):
+                   details: bool = False, image_height=None, image_width=None, outlier_nb=None, outlier_std: float = 2.0,
+                   cluster_eps=None, cluster_min_points: int = 10, cluster_keep: int = 1, cluster_min_size: int = 0):
     """`mesh_poisson`'s steps 1-4 (postprocessing.py:122-190) over a results directory (`graph.yaml`, `models/*.ply`,
     optionally `cfg.yaml` for the image size): returns (points (M,3), normals (M,3)), float32 device tensors in keyframe
     order, `kf_samples` rows per keyframe that has a valid pixel (the reference raises on one that has none; here it
@@ -203,9 +212,17 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
     reference's `remove_statistical_outlier(nb_neighbors=20, std_ratio=2.0)` (postprocessing.py:192) meant to do, at its
     place in the sequence — the reference discards that call's result.  One more host read; the rows keep their order
     and `details` gains `outlier` (the filter's statistics and `index`, the surviving rows of the unfiltered cloud).
-    The default None leaves the cloud as it always was, to the bit."""
+    The default None leaves the cloud as it always was, to the bit.
+
+    `cluster_eps=e` then keeps the large pieces of the cloud, after the outlier stage:
+    `evaluation.keep_clusters(e, cluster_min_points, cluster_keep, cluster_min_size)` — DBSCAN over exact radius
+    neighbours, the `cluster_keep` largest clusters and those of at least `cluster_min_size` points kept — which removes
+    what the outlier filters cannot, a floater whose points have each other for neighbours.  One more host read; `details`
+    gains `cluster` (its statistics and `index`, the surviving rows of the cloud that entered the stage).  Default None: off,
+    and the cloud is what it was, to the bit."""
     from . import traj_io
     outlier = _check_outlier(outlier_nb, outlier_std)
+    cluster = _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_size)
     path = Path(graph_dir_or_yaml)
     graph_file = path / "graph.yaml" if path.is_dir() else path
     graph_dir = graph_file.parent
@@ -250,11 +267,19 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
         points, normals, index, outlier_det = evaluation.remove_statistical_outlier(points, outlier[0], outlier[1], normals=normals,
                                                                                     return_index=True, details=True)
         outlier_det["index"] = index
+    cluster_det = None
+    if cluster is not None:
+        from . import evaluation
+        points, normals, index, cluster_det = evaluation.keep_clusters(points, cluster[0], cluster[1], cluster[2], cluster[3],
+                                                                       normals=normals, return_index=True, details=True)
+        cluster_det["index"] = index
     if details:
         det = {"frame_ids": [fid for _, fid in used], "n_valid": words[:, 0].astype(np.int64), "pixels": pixels,
                "kept": kept.copy(), "seed": used_seed}
         if outlier_det is not None:
             det["outlier"] = outlier_det
+        if cluster_det is not None:
+            det["cluster"] = cluster_det
         return points, normals, det
     return points, normals
 
@@ -266,7 +291,8 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
               min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
               regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
               smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False, fill_holes: int = None,
-              fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0):
+              fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0,
+              cluster_eps=None, cluster_min_points: int = 10, cluster_keep: int = 1, cluster_min_size: int = 0):
     """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
     frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
 
@@ -288,6 +314,8 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     `outlier_nb=k` (with `outlier_std`) goes to `sample_surface`: the samples that name the TSDF blocks are the filtered
     ones, so a block that only stray samples at a depth discontinuity would have named is never allocated;
     `details["outlier"]` holds the filter's statistics.  Default None: off.
+    `cluster_eps=e` (with `cluster_min_points`, `cluster_keep`, `cluster_min_size`) goes there too: the samples of a floater
+    that the outlier filter passes name no block either; `details["cluster"]` holds the statistics.  Default None: off.
 
     Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
     its cloud: blocks of 8^3 voxels of edge `voxel_size`, truncation `trunc` (default 4 voxel_size).  Pass 2 renders every
@@ -299,6 +327,7 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
 
     from . import traj_io, tsdf
     _check_outlier(outlier_nb, outlier_std)
+    _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_size)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("mesh_tsdf runs on a ROCm device; there is no CPU fallback")
@@ -316,9 +345,10 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
     points, _, det = sample_surface(graph_dir_or_yaml, kf_interval=kf_interval, kf_samples=kf_samples, min_opacity=min_opacity,
                                     max_depth_dist=max_depth_dist, use_median_depth=use_median_depth, seed=seed, device=dev,
                                     details=True, image_height=image_height, image_width=image_width, outlier_nb=outlier_nb,
-                                    outlier_std=outlier_std)
+                                    outlier_std=outlier_std, cluster_eps=cluster_eps, cluster_min_points=cluster_min_points,
+                                    cluster_keep=cluster_keep, cluster_min_size=cluster_min_size)
     lap("sample")
-    outlier = det.get("outlier")
+    outlier, cluster = det.get("outlier"), det.get("cluster")
     volume = tsdf.TsdfVolume(tsdf.allocate_blocks(points, voxel_size, trunc), voxel_size, trunc)
     lap("allocate")
     path = Path(graph_dir_or_yaml)
@@ -351,6 +381,8 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_i
             det["clean"] = clean
         if outlier is not None:
             det["outlier"] = outlier
+        if cluster is not None:
+            det["cluster"] = cluster
         return mesh + (det,)
     return mesh
 
@@ -363,9 +395,10 @@ def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, 
                  min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
                  regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
                  smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False, fill_holes: int = None,
-                 fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0):
+                 fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0,
+                 cluster_eps=None, cluster_min_points: int = 10, cluster_keep: int = 1, cluster_min_size: int = 0):
     """The reference's `mesh_poisson` (scene/postprocessing.py) to its end, on the device: `sample_surface` (its options
-    unchanged: `kf_interval`, `kf_samples`, `min_opacity`, `max_depth_dist`, `use_median_depth`, `seed`, `outlier_nb`, ...),
+    unchanged: `kf_interval`, `kf_samples`, `min_opacity`, `max_depth_dist`, `use_median_depth`, `seed`, `outlier_nb`, `cluster_eps`, ...),
     then `poisson.reconstruct` on the merged oriented cloud — blocks `margin` around the samples, the splat, the screened
     solve, marching tetrahedra — the density trim, and the clean-up options of `mesh_tsdf`, passed on to
     `mesh_ops.clean_mesh` unchanged (`normals=True` returns `(vertices, faces, normals)`).
@@ -384,6 +417,7 @@ def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, 
 
     from . import poisson, tsdf
     _check_outlier(outlier_nb, outlier_std)
+    _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_size)
     if min_density is not None and min_density_quantile is not None:
         raise ValueError("give min_density or min_density_quantile, not both")
     if min_density_quantile is not None and not (0.0 <= float(min_density_quantile) <= 1.0):
@@ -405,9 +439,11 @@ def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, 
     points, cloud_normals, det = sample_surface(graph_dir_or_yaml, kf_interval=kf_interval, kf_samples=kf_samples, min_opacity=min_opacity,
                                                 max_depth_dist=max_depth_dist, use_median_depth=use_median_depth, seed=seed, device=dev,
                                                 details=True, image_height=image_height, image_width=image_width,
-                                                outlier_nb=outlier_nb, outlier_std=outlier_std)
+                                                outlier_nb=outlier_nb, outlier_std=outlier_std, cluster_eps=cluster_eps,
+                                                cluster_min_points=cluster_min_points, cluster_keep=cluster_keep,
+                                                cluster_min_size=cluster_min_size)
     lap("sample")
-    outlier = det.get("outlier")
+    outlier, cluster = det.get("outlier"), det.get("cluster")
     volume = poisson.PoissonVolume(tsdf.allocate_blocks(points, voxel_size, margin), voxel_size)
     lap("allocate")
     volume.splat(points, cloud_normals)
@@ -438,5 +474,7 @@ def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, 
             out["clean"] = clean
         if outlier is not None:
             out["outlier"] = outlier
+        if cluster is not None:
+            out["cluster"] = cluster
         return mesh + (out,)
     return mesh

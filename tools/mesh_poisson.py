@@ -6,7 +6,7 @@ reconstruction on the device (splat_loam_amd.meshing.mesh_poisson; DESIGN.md sec
     python tools/mesh_poisson.py RESULTS_DIR OUT.ply --voxel 0.1 [--margin M] [--screening A] [--iterations N] [--tol T]
                                  [--min-density D | --min-density-quantile Q] [--density-sweeps S]
                                  [--kf-interval N] [--kf-samples K] [--min-opacity A] [--max-depth-dist D]
-                                 [--use-median-depth] [--outlier-nb 20 [--outlier-std 2.0]] [--weld]
+                                 [--use-median-depth] [--outlier-nb 20 [--outlier-std 2.0]] [--cluster-eps E [--cluster-min-points 10]] [--weld]
                                  [--keep-clusters K] [--min-triangles N] [--normals]
                                  [--simplify RES [--contraction quadric] [--regularisation L]]
                                  [--smooth N [--smooth-method laplacian] [--smooth-weights uniform] [--fix-boundary]]
@@ -62,6 +62,8 @@ def main():
     ap.add_argument("--fill-max-size", type=float, default=None, help="... whose bounding box has at most this diagonal (with --fill-holes)")
     ap.add_argument("--outlier-nb", type=int, default=None, help="statistical outlier removal of the surface samples: neighbours (1..32)")
     ap.add_argument("--outlier-std", type=float, default=2.0, help="... and the threshold in standard deviations (with --outlier-nb)")
+    ap.add_argument("--cluster-eps", type=float, default=None, help="keep the largest DBSCAN cluster of the surface samples: the radius, a few sample spacings")
+    ap.add_argument("--cluster-min-points", type=int, default=10, help="... and the neighbours, itself included, that make a sample core (with --cluster-eps)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -76,7 +78,8 @@ def main():
                                       normals=a.normals, simplify=a.simplify, contraction=a.contraction, regularisation=a.regularisation,
                                       smooth=a.smooth, smooth_method=a.smooth_method, smooth_weights=a.smooth_weights,
                                       fix_boundary=a.fix_boundary, fill_holes=a.fill_holes, fill_max_size=a.fill_max_size,
-                                      outlier_nb=a.outlier_nb, outlier_std=a.outlier_std)
+                                      outlier_nb=a.outlier_nb, outlier_std=a.outlier_std, cluster_eps=a.cluster_eps,
+                                      cluster_min_points=a.cluster_min_points)
     vertices, faces, normals = mesh[0], mesh[1], (mesh[2] if a.normals else None)
     if a.weld and "clean" not in det:
         vertices, faces = tsdf.weld_soup(vertices)
@@ -86,6 +89,8 @@ def main():
             "stage_ms": {k: round(v, 3) for k, v in det["stage_ms"].items()}, "out": a.out_ply}
     if "outlier" in det:
         line["outlier"] = dict({k: v for k, v in det["outlier"].items() if k != "index"}, nb_neighbors=a.outlier_nb, std_ratio=a.outlier_std)
+    if "cluster" in det:
+        line["cluster"] = dict({k: v for k, v in det["cluster"].items() if k != "index"}, eps=a.cluster_eps, min_points=a.cluster_min_points)
     if "clean" in det:
         line["clean"] = {k: det["clean"][k] for k in ("welded_vertices", "clusters", "degenerate", "boundary_edges", "nonmanifold_edges",
                                                       "n_min")}

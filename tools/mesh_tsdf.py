@@ -9,7 +9,7 @@ rendered depth of every keyframe fused into a sparse TSDF volume, the zero surfa
                               [--simplify RES [--contraction quadric] [--regularisation L]]
                               [--smooth N [--smooth-method laplacian] [--smooth-weights uniform] [--fix-boundary]]
                               [--fill-holes 64 [--fill-max-size M]]
-                              [--outlier-nb 20 [--outlier-std 2.0]]
+                              [--outlier-nb 20 [--outlier-std 2.0]] [--cluster-eps E [--cluster-min-points 10]]
                               [--seed S] [--image-height H --image-width W]
 
 OUT.ply is a binary little-endian triangle mesh (`ply_io.save_mesh`), what `tools/eval_recon.py` takes as the estimate.
@@ -62,6 +62,8 @@ def main():
     ap.add_argument("--fill-max-size", type=float, default=None, help="... whose bounding box has at most this diagonal (with --fill-holes)")
     ap.add_argument("--outlier-nb", type=int, default=None, help="statistical outlier removal of the surface samples: neighbours (1..32)")
     ap.add_argument("--outlier-std", type=float, default=2.0, help="... and the threshold in standard deviations (with --outlier-nb)")
+    ap.add_argument("--cluster-eps", type=float, default=None, help="keep the largest DBSCAN cluster of the surface samples: the radius, a few sample spacings")
+    ap.add_argument("--cluster-min-points", type=int, default=10, help="... and the neighbours, itself included, that make a sample core (with --cluster-eps)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -74,7 +76,8 @@ def main():
                                    normals=a.normals, simplify=a.simplify, contraction=a.contraction, regularisation=a.regularisation,
                                    smooth=a.smooth, smooth_method=a.smooth_method, smooth_weights=a.smooth_weights,
                                    fix_boundary=a.fix_boundary, fill_holes=a.fill_holes, fill_max_size=a.fill_max_size,
-                                   outlier_nb=a.outlier_nb, outlier_std=a.outlier_std)
+                                   outlier_nb=a.outlier_nb, outlier_std=a.outlier_std, cluster_eps=a.cluster_eps,
+                                   cluster_min_points=a.cluster_min_points)
     vertices, faces, normals = mesh[0], mesh[1], (mesh[2] if a.normals else None)
     if a.weld and "clean" not in det:
         vertices, faces = tsdf.weld_soup(vertices)
@@ -84,6 +87,8 @@ def main():
             "stage_ms": {k: round(v, 3) for k, v in det["stage_ms"].items()}, "out": a.out_ply}
     if "outlier" in det:
         line["outlier"] = dict({k: v for k, v in det["outlier"].items() if k != "index"}, nb_neighbors=a.outlier_nb, std_ratio=a.outlier_std)
+    if "cluster" in det:
+        line["cluster"] = dict({k: v for k, v in det["cluster"].items() if k != "index"}, eps=a.cluster_eps, min_points=a.cluster_min_points)
     if "clean" in det:
         line["clean"] = {k: det["clean"][k] for k in ("welded_vertices", "clusters", "degenerate", "boundary_edges", "nonmanifold_edges",
                                                       "n_min")}

@@ -4,10 +4,11 @@ reconstruction takes — the reference's `run.py mesh` up to the Poisson solve (
 
     python tools/sample_surface.py RESULTS_DIR OUT.ply [--kf-interval N] [--kf-samples K] [--min-opacity A]
                                    [--max-depth-dist D] [--use-median-depth] [--seed S] [--image-height H --image-width W]
-                                   [--outlier-nb 20 [--outlier-std 2.0]]
+                                   [--outlier-nb 20 [--outlier-std 2.0]] [--cluster-eps E [--cluster-min-points 10]]
 
 --outlier-nb K filters the merged cloud with `evaluation.remove_statistical_outlier(K, --outlier-std)`: the call the
-reference makes at this place (postprocessing.py:192) and whose result it discards.  OUT.ply holds float32 `x y z nx ny nz`; elsewhere: `o3d.io.read_point_cloud(OUT.ply)` and
+reference makes at this place (postprocessing.py:192) and whose result it discards.  --cluster-eps E then keeps the
+largest DBSCAN cluster of the cloud (`evaluation.keep_clusters(E, --cluster-min-points)`: E a few sample spacings).  OUT.ply holds float32 `x y z nx ny nz`; elsewhere: `o3d.io.read_point_cloud(OUT.ply)` and
 `o3d.geometry.TriangleMesh.create_from_point_cloud_poisson(pcd, depth=...)` (INTEGRATION.md).
 
     python tools/sample_surface.py --probe [--probe-out FILE.json]
@@ -138,6 +139,8 @@ def main():
     ap.add_argument("--use-median-depth", action="store_true")
     ap.add_argument("--outlier-nb", type=int, default=None, help="statistical outlier removal of the merged cloud: neighbours (1..32)")
     ap.add_argument("--outlier-std", type=float, default=2.0, help="... and the threshold in standard deviations (with --outlier-nb)")
+    ap.add_argument("--cluster-eps", type=float, default=None, help="keep the largest DBSCAN cluster of the cloud: the radius, a few sample spacings")
+    ap.add_argument("--cluster-min-points", type=int, default=10, help="... and the neighbours, itself included, that make a point core (with --cluster-eps)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--image-height", type=int, default=None)
     ap.add_argument("--image-width", type=int, default=None)
@@ -154,12 +157,13 @@ def main():
                                            min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist,
                                            use_median_depth=a.use_median_depth, seed=a.seed, device=a.device, details=True,
                                            image_height=a.image_height, image_width=a.image_width, outlier_nb=a.outlier_nb,
-                                           outlier_std=a.outlier_std)
+                                           outlier_std=a.outlier_std, cluster_eps=a.cluster_eps, cluster_min_points=a.cluster_min_points)
     ply_io.save_point_cloud(a.out_ply, pts, nrm)
     empty = [f for f, kept in zip(det["frame_ids"], det["kept"]) if not kept]
     print(f"{pts.shape[0]} oriented points from {int(det['kept'].sum())} of {len(det['frame_ids'])} keyframes "
           f"(seed {det['seed']}) -> {a.out_ply}" + (f"; no valid pixel in frames {empty}" if empty else "") +
-          (f"; {det['outlier']['removed']} outliers removed (threshold {det['outlier']['threshold']:.4f} m)" if "outlier" in det else ""))
+          (f"; {det['outlier']['removed']} outliers removed (threshold {det['outlier']['threshold']:.4f} m)" if "outlier" in det else "") +
+          (f"; {det['cluster']['removed']} points outside the largest of {det['cluster']['clusters']} clusters removed" if "cluster" in det else ""))
 
 
 if __name__ == "__main__":
