@@ -65,6 +65,7 @@ SLS_HD float sls_cluster_count_bound(int32_t count, int32_t min_points, float r2
     return sls_cluster_core(count, min_points) ? -1.0f : r2;
 }
 
+/* (the twins of this rule for the clusters of a mesh: sls_mesh_keep_rank / sls_mesh_n_min, include/sls_mesh_math.h) */
 /* k of the k-th-largest term: min(keep, C), 0 when there is no such term */
 SLS_HD uint32_t sls_cluster_keep_rank(int32_t keep, uint32_t C)
 {

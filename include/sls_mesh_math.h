@@ -82,6 +82,7 @@ SLS_HD uint64_t sls_mesh_edge_key(const int32_t f[3], int e, int bits)
     return ((uint64_t)lo << bits) | (uint64_t)hi;
 }
 
+/* (the twins of this rule for the clusters of a cloud: sls_cluster_n_min / sls_cluster_keep_rank, include/sls_cluster_math.h) */
 /* n_min from the two arguments and the k-th largest cluster count (0 where there is no such term) */
 SLS_HD uint32_t sls_mesh_n_min(int32_t min_triangles, uint32_t kth)
 {

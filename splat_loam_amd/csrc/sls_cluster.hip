@@ -14,8 +14,11 @@
 //      which is the lowest core index; cluster_label: labels, counts and the three tallies by integer atomics — sums of
 //      integers, the same words on every run; cluster_status: the largest count and the status words.
 // Every loop is bounded by the box count or is the lock-free retry of uf_unite; nothing waits on another workgroup.
+// Steps 3 and 5 number the components as sls_mesh.hip numbers its clusters of triangles, and sls_cloud_select keeps the
+// largest as sls_mesh_filter does: uf_root and uf_kth_largest (sls_unionfind.hpp) serve both.  The compaction's rows are
+// written by Chunks::write_rows (sls_scan.hpp), as sls_outlier.hip's.
 #include "sls_launch.hpp"
-#include "sls_scan.hpp"
+#include "sls_unionfind.hpp"
 #include "../../include/sls_cluster_math.h"
 
 namespace sls {
@@ -49,9 +52,7 @@ __global__ __launch_bounds__(kCluThreads) void cluster_flatten_kernel(uint32_t M
         if (i < M) {
             uint32_t x = SLS_CLUSTER_NONE;
             if (core[i]) {
-                x = parent[i];
-                uint32_t p = parent[x];
-                while (p != x) { x = p; p = parent[x]; }
+                x = uf_root(parent, parent[i]);
                 nroots += x == i ? 1u : 0u;
             }
             root[i] = x;
@@ -204,29 +205,13 @@ int launch_cloud_dbscan(int M, const float *xyz, float eps, int min_points, int3
 // ---------------------------------------------------------------------------------------------------------------------
 // selection and compaction
 // ---------------------------------------------------------------------------------------------------------------------
-// One workgroup: the k-th largest of the C counts = the largest value v with #{c : counts[c] >= v} >= k, by bisection
-// over v in [1, M] (every count is at least 1, so v = 1 qualifies whenever k <= C) — as mesh_nmin_kernel does
+// One workgroup: n_min from the k-th largest of the C counts (uf_kth_largest)
 __global__ __launch_bounds__(kCluThreads) void cluster_nmin_kernel(uint32_t M, const uint32_t *__restrict__ cluster_status,
                                                                    const int32_t *__restrict__ counts, int keep,
                                                                    int min_cluster_points, uint32_t *__restrict__ hdr)
 {
-    __shared__ uint32_t s_wave[kCluThreads / 64];
     const uint32_t C = min(cluster_status[0], M);
-    const uint32_t k = sls_cluster_keep_rank(keep, C);
-    uint32_t lo = 0u;
-    if (k > 0u) {
-        uint32_t hi = M;
-        lo = 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo + 1u) / 2u;
-            uint32_t mine = 0u;
-            for (uint32_t c = threadIdx.x; c < C; c += kCluThreads) mine += (uint32_t)counts[c] >= mid ? 1u : 0u;
-            uint32_t total;
-            block_scan<uint32_t, kCluThreads>(mine, s_wave, &total);
-            if (total >= k) lo = mid; else hi = mid - 1u;
-            __syncthreads();                        // (s_wave is written again in the next round)
-        }
-    }
+    const uint32_t lo = uf_kth_largest<CluChunks>(M, C, sls_cluster_keep_rank(keep, C), counts);
     if (threadIdx.x == 0) hdr[CH_NMIN] = sls_cluster_n_min(min_cluster_points, lo);
 }
 
@@ -268,21 +253,8 @@ __global__ __launch_bounds__(kCluThreads) void cluster_keep_write_kernel(uint32_
                                                                          float *__restrict__ out_normals, int32_t *__restrict__ out_index)
 {
     const uint32_t C = min(cluster_status[0], M);
-    const uint32_t i0 = CluChunks::first();
-    const uint32_t mask = cluster_kept_mask(M, C, hdr[CH_NMIN], labels, counts, i0);
-    uint32_t id = CluChunks::rank((uint32_t)__popc(mask), blk);
-#pragma unroll
-    for (int j = 0; j < CluChunks::kPer; ++j)
-        if ((mask >> j) & 1u) {                     // (id <= i < M: the outputs hold M rows)
-            const size_t i = i0 + (uint32_t)j, o = id;
-            if (out_xyz) { out_xyz[3 * o] = xyz[3 * i]; out_xyz[3 * o + 1] = xyz[3 * i + 1]; out_xyz[3 * o + 2] = xyz[3 * i + 2]; }
-            if (out_normals) {
-                out_normals[3 * o] = normals[3 * i]; out_normals[3 * o + 1] = normals[3 * i + 1];
-                out_normals[3 * o + 2] = normals[3 * i + 2];
-            }
-            if (out_index) out_index[o] = (int32_t)i;
-            ++id;
-        }
+    CluChunks::write_rows(cluster_kept_mask(M, C, hdr[CH_NMIN], labels, counts, CluChunks::first()), blk, xyz, normals, out_xyz,
+                          out_normals, out_index);
 }
 
 struct SelectScratch {

@@ -21,6 +21,7 @@
 //                               compare-and-swap, and parents only decrease.  Edge statistics from the runs of equal keys.
 //   mesh_flatten / _rootscan / _rank / _label   every triangle's root (plain loads: nothing writes parent any more), the
 //                               roots ranked in ascending order by a chunked scan, labels, counts by integer atomics
+//                               (sls_cluster.hip numbers the clusters of a cloud so: uf_root and uf_kth_largest serve both)
 //
 // sls_mesh_filter:  mesh_nmin (one workgroup: the k-th largest count by bisection over the value), mesh_mark (kept
 //                   triangles flag their vertices), mesh_vcount, mesh_filter_scan, mesh_vwrite, mesh_fwrite: two ordered
@@ -228,8 +229,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_flatten_kernel(uint32_t T, 
         if (t < T) {
             uint32_t x = parent[t];
             if (x != kMeshNone) {
-                uint32_t p = parent[x];
-                while (p != x) { x = p; p = parent[x]; }
+                x = uf_root(parent, x);
                 nroots += x == t ? 1u : 0u;
             }
             root[t] = x;
@@ -353,29 +353,13 @@ int launch_mesh_clusters(int T, const int32_t *faces, int V, int32_t *out_labels
 // ---------------------------------------------------------------------------------------------------------------------
 // selection and compaction
 // ---------------------------------------------------------------------------------------------------------------------
-// One workgroup: the k-th largest of the C counts = the largest value v with #{c : counts[c] >= v} >= k, by bisection
-// over v in [1, T] (every count is at least 1, so v = 1 qualifies whenever k <= C)
+// One workgroup: n_min from the k-th largest of the C counts (uf_kth_largest)
 __global__ __launch_bounds__(kMeshThreads) void mesh_nmin_kernel(uint32_t T, const uint32_t *__restrict__ cluster_status,
                                                                  const int32_t *__restrict__ counts, int keep_clusters, int min_triangles,
                                                                  uint32_t *__restrict__ hdr)
 {
-    __shared__ uint32_t s_wave[kMeshThreads / 64];
     const uint32_t C = min(cluster_status[0], T);
-    const uint32_t k = sls_mesh_keep_rank(keep_clusters, C);
-    uint32_t lo = 0u;
-    if (k > 0u) {
-        uint32_t hi = T;
-        lo = 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo + 1u) / 2u;
-            uint32_t mine = 0u;
-            for (uint32_t c = threadIdx.x; c < C; c += kMeshThreads) mine += (uint32_t)counts[c] >= mid ? 1u : 0u;
-            uint32_t total;
-            block_scan<uint32_t, kMeshThreads>(mine, s_wave, &total);
-            if (total >= k) lo = mid; else hi = mid - 1u;
-            __syncthreads();                        // (s_wave is written again in the next round)
-        }
-    }
+    const uint32_t lo = uf_kth_largest<MeshChunks>(T, C, sls_mesh_keep_rank(keep_clusters, C), counts);
     if (threadIdx.x == 0) hdr[MH_NMIN] = sls_mesh_n_min(min_triangles, lo);
 }
 

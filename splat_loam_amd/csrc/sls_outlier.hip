@@ -9,7 +9,7 @@
 //      workgroup then adds the partials the same way; no float atomics) — first the zero count and the sum, then the
 //      squared deviations — and the threshold, all on the device;
 //   3. an ordered compaction through Chunks (sls_scan.hpp): the keep flags are recomputed from the 8 bytes where they are
-//      needed, kept rows come out in ascending original index, normals travel with their points.
+//      needed; write_rows, shared with sls_cluster.hip: kept rows in ascending original index, normals with their points.
 #include "sls_launch.hpp"
 #include "sls_scan.hpp"
 #include "../../include/sls_outlier_math.h"
@@ -140,21 +140,8 @@ __global__ __launch_bounds__(kOutThreads) void outlier_write_kernel(uint32_t M, 
                                                                     const float *__restrict__ normals, float *__restrict__ out_xyz,
                                                                     float *__restrict__ out_normals, int32_t *__restrict__ out_index)
 {
-    const uint32_t i0 = OutChunks::first();
-    const uint32_t mask = outlier_keep_mask<RADIUS>(M, vals, hdr, radius, i0);
-    uint32_t id = OutChunks::rank((uint32_t)__popc(mask), blk);
-#pragma unroll
-    for (int j = 0; j < OutChunks::kPer; ++j)
-        if ((mask >> j) & 1u) {                     // (id <= i < M: the outputs hold M rows)
-            const size_t i = i0 + (uint32_t)j, o = id;
-            if (out_xyz) { out_xyz[3 * o] = xyz[3 * i]; out_xyz[3 * o + 1] = xyz[3 * i + 1]; out_xyz[3 * o + 2] = xyz[3 * i + 2]; }
-            if (out_normals) {
-                out_normals[3 * o] = normals[3 * i]; out_normals[3 * o + 1] = normals[3 * i + 1];
-                out_normals[3 * o + 2] = normals[3 * i + 2];
-            }
-            if (out_index) out_index[o] = (int32_t)i;
-            ++id;
-        }
+    OutChunks::write_rows(outlier_keep_mask<RADIUS>(M, vals, hdr, radius, OutChunks::first()), blk, xyz, normals, out_xyz,
+                          out_normals, out_index);
 }
 
 struct OutlierScratch {

@@ -1,10 +1,11 @@
-// sls_scan.hpp — what the device geometry ops (sls_cloud, sls_tsdf, sls_mesh, sls_simplify, sls_smooth, sls_fill) share
-// of their scans.  block_scan / scan_in_place: workgroup-wide exclusive scans, wave scans of 64 lanes, then the wave sums
-// through LDS.  Chunks<THREADS, PER>: the chunked layer on top — an array is cut into chunks of THREADS * PER positions,
+// sls_scan.hpp — what the device geometry ops (sls_cloud, sls_tsdf, sls_mesh, sls_simplify, sls_smooth, sls_fill, sls_outlier,
+// sls_cluster) share of their scans.  block_scan / scan_in_place: workgroup-wide exclusive scans, wave scans of 64 lanes, then
+// the wave sums through LDS.  Chunks<THREADS, PER>: the chunked layer on top — an array is cut into chunks of THREADS * PER positions,
 // a workgroup per chunk, thread t owning PER consecutive positions — with the three launches of an ordered compaction:
 //   total      every workgroup's sum of its threads' values (popc of a head or flag mask, or any integer sum) -> blk[chunk]
 //   scan_totals  one workgroup: blk <- its exclusive scan, the caller's epilogue stores the grand total
 //   rank       the values recomputed: blk[chunk] + the scan inside the workgroup = this thread's rank in the whole array
+// and write_rows, the third launch's body where the compacted thing is a cloud: rows of xyz, normals and the row index.
 // Integer types only (the order of the additions then does not matter).
 #pragma once
 #include "sls_common.hpp"
@@ -54,7 +55,7 @@ __device__ __forceinline__ T scan_in_place(const T *in, T *out, int n, T *s_wave
 // The chunk geometry and the per-chunk steps.  total / scan_totals / rank own their LDS wave array: one of them per kernel.
 template <int THREADS, int PER>
 struct Chunks {
-    static constexpr int kPer = PER, kChunk = THREADS * PER;
+    static constexpr int kThreads = THREADS, kPer = PER, kChunk = THREADS * PER;
 
     static int count(size_t n) { return (int)((n + kChunk - 1) / kChunk); }     // host: the chunks (= workgroups) of n positions
     static __device__ __forceinline__ uint32_t first() { return blockIdx.x * (uint32_t)kChunk + threadIdx.x * (uint32_t)PER; }
@@ -127,6 +128,28 @@ struct Chunks {
         __shared__ T s_wave[THREADS / 64];
         T sum;
         return blk[blockIdx.x] + block_scan<T, THREADS>(v, s_wave, &sum);
+    }
+
+    // The kept rows of a cloud in their order (mask: the keep flags of this thread's positions first() .. + PER - 1, blk: the
+    // scanned chunk totals): row i goes to row rank(i) of out_xyz, out_normals and out_index, each written where it is given
+    static __device__ __forceinline__ void write_rows(uint32_t mask, const uint32_t *__restrict__ blk, const float *__restrict__ xyz,
+                                                      const float *__restrict__ normals, float *__restrict__ out_xyz,
+                                                      float *__restrict__ out_normals, int32_t *__restrict__ out_index)
+    {
+        const uint32_t i0 = first();
+        uint32_t id = rank((uint32_t)__popc(mask), blk);
+#pragma unroll
+        for (int j = 0; j < PER; ++j)
+            if ((mask >> j) & 1u) {                 // (id <= i < the rows of the cloud: the outputs hold as many)
+                const size_t i = i0 + (uint32_t)j, o = id;
+                if (out_xyz) { out_xyz[3 * o] = xyz[3 * i]; out_xyz[3 * o + 1] = xyz[3 * i + 1]; out_xyz[3 * o + 2] = xyz[3 * i + 2]; }
+                if (out_normals) {
+                    out_normals[3 * o] = normals[3 * i]; out_normals[3 * o + 1] = normals[3 * i + 1];
+                    out_normals[3 * o + 2] = normals[3 * i + 2];
+                }
+                if (out_index) out_index[o] = (int32_t)i;
+                ++id;
+            }
     }
 };
 

@@ -46,10 +46,10 @@ def _cloud(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def _scratch(lib, Mt: int, Mq: int, device) -> tuple[torch.Tensor, int, int]:
-    nbytes = int(lib.sls_nn_scratch_bytes(Mt, Mq))
-    buf = torch.empty((nbytes + 256,), dtype=torch.uint8, device=device)
-    return buf, (buf.data_ptr() + 255) & ~255, nbytes
+def _scratch(nbytes: int, device) -> tuple[torch.Tensor, int, int]:
+    """A scratch buffer for a native call: (the tensor that owns it, its 256-byte aligned address, nbytes)."""
+    buf = torch.empty((int(nbytes) + 256,), dtype=torch.uint8, device=device)
+    return buf, (buf.data_ptr() + 255) & ~255, int(nbytes)
 
 
 def _query(lib, target, query, want_index, scratch, st):
@@ -75,7 +75,7 @@ def nearest(target: torch.Tensor, query: torch.Tensor, return_index: bool = True
     lib = _abi.lib()
     with torch.cuda.device(target.device):
         st = torch.cuda.current_stream(target.device).cuda_stream
-        scratch = _scratch(lib, int(target.shape[0]), int(query.shape[0]), target.device)
+        scratch = _scratch(lib.sls_nn_scratch_bytes(int(target.shape[0]), int(query.shape[0])), target.device)
         return _query(lib, target, query, return_index, scratch, st)
 
 
@@ -110,7 +110,7 @@ def nearest_k(target: torch.Tensor, query: torch.Tensor, k: int, return_index: b
         dist2 = torch.empty((Mq, k), dtype=torch.float32, device=dev)
         index = torch.empty((Mq, k), dtype=torch.int32, device=dev) if return_index else None
         if Mq:
-            _, aligned, nbytes = _scratch_bytes(lib.sls_nn_k_scratch_bytes(Mt, Mq, k), dev)
+            _, aligned, nbytes = _scratch(lib.sls_nn_k_scratch_bytes(Mt, Mq, k), dev)
             _abi.check(lib.sls_nn_query_k(Mt, target.data_ptr(), Mq, query.data_ptr(), k, dist2.data_ptr(),
                                           index.data_ptr() if return_index else None, None, aligned, nbytes, st), "sls_nn_query_k")
     return dist2, index
@@ -164,7 +164,7 @@ def _estimate_normals(points, radius, max_nn, viewpoint, details: bool, lists: b
         eig = torch.empty((M, 3), dtype=torch.float32, device=dev) if details else None
         rows = (torch.empty((M, k), dtype=torch.float32, device=dev), torch.empty((M, k), dtype=torch.int32, device=dev)) if lists else ()
         if M:
-            buf, aligned, nbytes = _scratch_bytes(lib.sls_cloud_normals_scratch_bytes(M, k), dev)
+            buf, aligned, nbytes = _scratch(lib.sls_cloud_normals_scratch_bytes(M, k), dev)
             view3 = (ctypes.c_float * 3)(*view)                   # host memory, read before the call returns
             _abi.check(lib.sls_cloud_normals(M, points.data_ptr(), k, radius, ctypes.addressof(view3), normals.data_ptr(),
                                              count.data_ptr() if details else None, eig.data_ptr() if details else None,
@@ -236,7 +236,7 @@ def _ground_enqueue(points: torch.Tensor, prm: _abi.SlsGroundParams, details: bo
         planes = torch.zeros((GROUND_BINS, 8), dtype=torch.float64, device=dev)
         info = torch.zeros((GROUND_BINS, 4), dtype=torch.int32, device=dev) if details else None
         status = torch.empty((8,), dtype=torch.int32, device=dev)
-        _, aligned, nbytes = _scratch_bytes(lib.sls_ground_scratch_bytes(M), dev)
+        _, aligned, nbytes = _scratch(lib.sls_ground_scratch_bytes(M), dev)
         _abi.check(lib.sls_ground_segment(M, points.data_ptr() if M else None, ctypes.byref(prm), label.data_ptr() if M else None,
                                           bins.data_ptr() if M else None, planes.data_ptr(),
                                           info.data_ptr() if details else None, status.data_ptr(), aligned if M else None,
@@ -301,25 +301,26 @@ def _outlier_enqueue(lib, call, name: str, points, normals, k: int, args: tuple,
     out_n = torch.empty((M, 3), dtype=torch.float32, device=dev) if normals is not None else None
     index = torch.empty((M,), dtype=torch.int32, device=dev)
     status = torch.empty((8,), dtype=torch.int64, device=dev)
-    _, aligned, nbytes = _scratch_bytes(lib.sls_outlier_scratch_bytes(M, k), dev)
+    _, aligned, nbytes = _scratch(lib.sls_outlier_scratch_bytes(M, k), dev)
     _abi.check(call(M, points.data_ptr() if M else None, normals.data_ptr() if (normals is not None and M) else None, *args,
                     out.data_ptr() if M else None, out_n.data_ptr() if (out_n is not None and M) else None,
                     index.data_ptr() if M else None, status.data_ptr(), aligned if M else None, nbytes, st), name)
     return out, out_n, index, status
 
 
+def _kept_result(kept: int, out, out_n, index, details):
+    """What the filters of a cloud return: the first `kept` rows of out, then — each where it is not None — of out_n and of
+    index, then details; the rows alone without any of these."""
+    res = [out[:kept]] + [t[:kept] for t in (out_n, index) if t is not None] + ([details] if details is not None else [])
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def _outlier_result(out, out_n, index, words, has_normals: bool, return_index: bool, details: bool):
     bits = lambda v: struct.unpack("<d", struct.pack("<q", v))[0]
     kept = int(words[0])
-    res = [out[:kept]]
-    if has_normals:
-        res.append(out_n[:kept])
-    if return_index:
-        res.append(index[:kept])
-    if details:
-        res.append({"kept": kept, "removed": int(words[5]) - kept, "zero_mean": int(words[1]), "cloud_mean": bits(words[2]),
-                    "std": bits(words[3]), "threshold": bits(words[4])})
-    return res[0] if len(res) == 1 else tuple(res)
+    det = {"kept": kept, "removed": int(words[5]) - kept, "zero_mean": int(words[1]), "cloud_mean": bits(words[2]),
+           "std": bits(words[3]), "threshold": bits(words[4])} if details else None
+    return _kept_result(kept, out, out_n if has_normals else None, index if return_index else None, det)
 
 
 def _check_stat_args(nb_neighbors, std_ratio) -> tuple[int, float]:
@@ -413,7 +414,7 @@ def _dbscan_enqueue(lib, points, eps: float, min_points: int, status: torch.Tens
     dev = points.device
     labels = torch.empty((M,), dtype=torch.int32, device=dev)
     counts = torch.empty((M,), dtype=torch.int32, device=dev)
-    _, aligned, nbytes = _scratch_bytes(lib.sls_cloud_dbscan_scratch_bytes(M), dev)
+    _, aligned, nbytes = _scratch(lib.sls_cloud_dbscan_scratch_bytes(M), dev)
     _abi.check(lib.sls_cloud_dbscan(M, points.data_ptr() if M else None, eps, min_points, labels.data_ptr() if M else None,
                                     counts.data_ptr() if M else None, status.data_ptr(), aligned if M else None, nbytes, st),
                "sls_cloud_dbscan")
@@ -483,21 +484,15 @@ def keep_clusters(points: torch.Tensor, eps: float, min_points: int = 10, keep: 
         out = torch.empty((M, 3), dtype=torch.float32, device=dev)
         out_n = torch.empty((M, 3), dtype=torch.float32, device=dev) if normals is not None else None
         index = torch.empty((M,), dtype=torch.int32, device=dev) if return_index else None
-        _, aligned, nbytes = _scratch_bytes(lib.sls_cloud_select_scratch_bytes(M), dev)
+        _, aligned, nbytes = _scratch(lib.sls_cloud_select_scratch_bytes(M), dev)
         ptr = lambda t: t.data_ptr() if (t is not None and M) else None
         _abi.check(lib.sls_cloud_select(M, ptr(points), ptr(normals), ptr(labels), ptr(counts), status.data_ptr() if M else None, keep,
                                         min_cluster_points, ptr(out), ptr(out_n), ptr(index), status[CLUSTER_STATUS_WORDS:].data_ptr(),
                                         aligned if M else None, nbytes, st), "sls_cloud_select")
         words = status.cpu().tolist()                                       # the one host read
     kept = int(words[CLUSTER_STATUS_WORDS])
-    res = [out[:kept]]
-    if normals is not None:
-        res.append(out_n[:kept])
-    if return_index:
-        res.append(index[:kept])
-    if details:
-        res.append({"kept": kept, "removed": M - kept, "n_min": int(words[CLUSTER_STATUS_WORDS + 1]), **_cluster_details(words)})
-    return res[0] if len(res) == 1 else tuple(res)
+    det = {"kept": kept, "removed": M - kept, "n_min": int(words[CLUSTER_STATUS_WORDS + 1]), **_cluster_details(words)} if details else None
+    return _kept_result(kept, out, out_n, index, det)
 
 
 ICP_METHODS = {"plane": 0, "point": 1}                # SLS_ICP_PLANE, SLS_ICP_POINT (include/sls_abi.h)
@@ -559,7 +554,7 @@ def _icp_enqueue(lib, source, target, normals, prm: _abi.SlsIcpParams, pose12, d
     system = torch.empty((32,), dtype=torch.float64, device=dev) if details else None
     index = torch.empty((Ms,), dtype=torch.int32, device=dev) if details else None
     dist2 = torch.empty((Ms,), dtype=torch.float32, device=dev) if details else None
-    _, aligned, nbytes = _scratch_bytes(lib.sls_cloud_icp_scratch_bytes(Ms, Mt), dev)
+    _, aligned, nbytes = _scratch(lib.sls_cloud_icp_scratch_bytes(Ms, Mt), dev)
     init = (ctypes.c_double * 12)(*pose12)                                  # host memory, read before the call returns
     _abi.check(lib.sls_cloud_icp(Ms, source.data_ptr() if Ms else None, Mt, target.data_ptr(),
                                  normals.data_ptr() if normals is not None else None, ctypes.byref(prm), ctypes.addressof(init),
@@ -656,7 +651,7 @@ def cloud_metrics(reference: torch.Tensor, estimate: torch.Tensor, threshold: fl
     dev = reference.device
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
-        scratch = _scratch(lib, max(Mr, Me), max(Mr, Me), dev)
+        scratch = _scratch(lib.sls_nn_scratch_bytes(max(Mr, Me), max(Mr, Me)), dev)
         _, aligned, nbytes = scratch
         words = torch.empty((8,), dtype=torch.int64, device=dev)
         d_acc, _ = _query(lib, reference, estimate, False, scratch, st)
@@ -688,11 +683,6 @@ def _metrics(w, threshold, truncation_acc, truncation_com) -> dict:
     }
 
 
-def _scratch_bytes(nbytes: int, device) -> tuple[torch.Tensor, int, int]:
-    buf = torch.empty((int(nbytes) + 256,), dtype=torch.uint8, device=device)
-    return buf, (buf.data_ptr() + 255) & ~255, int(nbytes)
-
-
 def _voxel_enqueue(lib, points: torch.Tensor, voxel_size: float, want_counts: bool, st):
     """sls_voxel_downsample without a host read: (rows (M,3), counts (M,) | None, status (4,) int32)."""
     M = int(points.shape[0])
@@ -700,7 +690,7 @@ def _voxel_enqueue(lib, points: torch.Tensor, voxel_size: float, want_counts: bo
     out = torch.empty((M, 3), dtype=torch.float32, device=dev)
     counts = torch.empty((M,), dtype=torch.int32, device=dev) if want_counts else None
     status = torch.empty((4,), dtype=torch.int32, device=dev)
-    scratch, aligned, nbytes = _scratch_bytes(lib.sls_voxel_scratch_bytes(M), dev)
+    scratch, aligned, nbytes = _scratch(lib.sls_voxel_scratch_bytes(M), dev)
     _abi.check(lib.sls_voxel_downsample(M, points.data_ptr() if M else None, float(voxel_size), out.data_ptr() if M else None,
                                         counts.data_ptr() if (want_counts and M) else None, status.data_ptr(),
                                         aligned if M else None, nbytes, st), "sls_voxel_downsample")
@@ -763,7 +753,7 @@ def _mesh_enqueue(lib, vertices, faces, n: int, seed: int, crop_box, want_faces:
     out = torch.empty((n, 3), dtype=torch.float32, device=dev)
     face = torch.empty((n,), dtype=torch.int32, device=dev) if want_faces else None
     status = torch.empty((4,), dtype=torch.int32, device=dev)
-    scratch, aligned, nbytes = _scratch_bytes(lib.sls_mesh_sample_scratch_bytes(V, F, n), dev)
+    scratch, aligned, nbytes = _scratch(lib.sls_mesh_sample_scratch_bytes(V, F, n), dev)
     _abi.check(lib.sls_mesh_sample(V, vertices.data_ptr() if V else None, F, faces.data_ptr() if F else None,
                                    crop_box.data_ptr() if crop_box is not None else None, n, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                    out.data_ptr() if n else None, face.data_ptr() if (want_faces and n) else None,
@@ -820,7 +810,7 @@ def _mesh_distance_enqueue(lib, points, vertices, faces, want_face: bool, want_c
     face = torch.empty((M,), dtype=torch.int32, device=dev) if want_face else None
     closest = torch.empty((M, 3), dtype=torch.float32, device=dev) if want_closest else None
     status = torch.empty((4,), dtype=torch.int32, device=dev)
-    scratch = _scratch_bytes(lib.sls_mesh_distance_scratch_bytes(V, F, M), dev)
+    scratch = _scratch(lib.sls_mesh_distance_scratch_bytes(V, F, M), dev)
     _abi.check(lib.sls_mesh_distance(V, vertices.data_ptr(), F, faces.data_ptr(), M, points.data_ptr() if M else None,
                                      dist2.data_ptr() if M else None, face.data_ptr() if (want_face and M) else None,
                                      closest.data_ptr() if (want_closest and M) else None, status.data_ptr(), scratch[1],
@@ -914,7 +904,7 @@ def _recon_metrics(reference, estimate, vertices, faces, exact: bool, error_map:
     dev = reference.device
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
-        scratch = _scratch(lib, max(Mr, Me), max(Mr, Me), dev)
+        scratch = _scratch(lib.sls_nn_scratch_bytes(max(Mr, Me), max(Mr, Me)), dev)
         _, aligned, nbytes = scratch
         words = torch.empty((8,), dtype=torch.int64, device=dev)
         d_acc, _ = _query(lib, reference, estimate, False, scratch, st)

@@ -15,7 +15,7 @@ import outlier_ref
 SORT_WAVE_ITEMS = 1024          # items per wave (= per chunk of the count table) of the radix sort: 64 lanes x 16 rounds
 ROWSCAN_THREADS = 256           # sort_rowscan_kernel: thread t owns P = ceil(nchunks / 256) consecutive entries of a row
 ROWSCAN_KEEP = 8                # ... of which it keeps 8 in registers; the tail loop runs from P = 9 on
-CLOUD_THREADS, CLOUD_CHUNK = 256, 1024      # Chunks<256, 4>: voxel down-sampling, mesh sampling, the outlier filters
+CLOUD_THREADS, CLOUD_CHUNK = 256, 1024      # Chunks<256, 4>: voxel down-sampling, mesh sampling, the outlier filters, the clusters
 MESH_THREADS, MESH_CHUNK = 512, 2048        # Chunks<512, 4>: weld, clusters, filter, simplify, adjacency, fill, TSDF blocks
 KNN_BOX = 256                   # target points per box of the box search
 SWEEP_BOXES = 64                # boxes per chunk of the outward sweep (a box per lane)
@@ -38,6 +38,8 @@ SOURCES = (
     ("splat_loam_amd/csrc/sls_outlier.hip", "constexpr int kOutThreads = 256;", "test_statistical_*, test_radius_*"),
     ("splat_loam_amd/csrc/sls_outlier.hip", "using OutChunks = Chunks<kOutThreads, 4>;", "test_statistical_*, test_radius_*"),
     ("splat_loam_amd/csrc/sls_outlier.hip", "constexpr int kOutMaxBlocks = 1024;", "test_statistical_*"),
+    ("splat_loam_amd/csrc/sls_cluster.hip", "constexpr int kCluThreads = 256;", "test_cluster_scans_above_256_chunks"),
+    ("splat_loam_amd/csrc/sls_cluster.hip", "using CluChunks = Chunks<kCluThreads, 4>;", "test_cluster_scans_above_256_chunks"),
     ("splat_loam_amd/csrc/sls_mesh.hip", "constexpr int kMeshThreads = 512;", "test_weld_*, test_tetrahedra_*"),
     ("splat_loam_amd/csrc/sls_mesh.hip", "using MeshChunks = Chunks<kMeshThreads, 4>;", "test_weld_*, test_tetrahedra_*"),
     ("splat_loam_amd/csrc/sls_simplify.hip", "constexpr int kSimpThreads = 512;", "test_simplify_*"),

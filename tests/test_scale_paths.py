@@ -469,3 +469,33 @@ def test_simplify_scans_above_512_chunks(device, contraction):
     assert np.array_equal(bits(got_v[:nv]), bits(want_v))
     assert (got_v[nv:] == 7.0).all() and (got_f[nt:] == -7).all()   # rows beyond V' / T' are untouched
     clock.report(f"simplify, strip of {n}, contraction {contraction}")
+
+
+# ---- 8. the cloud's component numbering and row compaction above 256 chunks --------------------------------------------
+def test_cluster_scans_above_256_chunks(device):
+    """90000 groups of three points, group g at a = (16 (g % 300), 16 (g // 300), 0): a, a + (1, 0, 0), a + (8, 0, 0).  At
+    eps = 1.5 and min_points = 2 the first two are each other's neighbours and core, the third has nobody: labels g, g, -1
+    in closed form.  M = 270000 is 264 chunks of 1024, so cluster_rootscan_kernel and cluster_keep_scan_kernel add 264 chunk
+    totals with 256 threads, and cluster_rank / cluster_keep_write rank past the first 256 chunks.  Integers below 2^13:
+    every distance is exact."""
+    G = 90000
+    M = 3 * G
+    assert M > S.CLOUD_THREADS * S.CLOUD_CHUNK and S.chunks(M, S.CLOUD_CHUNK) == 264
+    assert S.scan_p(M, S.CLOUD_THREADS, S.CLOUD_CHUNK) == 2         # cluster_rootscan_kernel, cluster_keep_scan_kernel: P >= 2
+    clock = Clock(device)
+    g = np.arange(G)
+    a = np.stack([16 * (g % 300), 16 * (g // 300), 0 * g], 1)
+    points = (a[:, None, :] + np.array([[0, 0, 0], [1, 0, 0], [8, 0, 0]])[None]).reshape(M, 3).astype(np.float32)
+    assert points.max() < 2 ** 13
+    want_labels = np.stack([g, g, -np.ones_like(g)], 1).reshape(M).astype(np.int32)
+    want_index = np.flatnonzero(np.arange(M) % 3 != 2).astype(np.int32)
+    want_details = {"clusters": G, "core": 2 * G, "border": 0, "noise": G, "largest": 2}
+    p = _dev(points, device)
+    labels, counts, det = clock.dev(lambda: evaluation.cluster_dbscan(p, 1.5, 2, return_counts=True, details=True))
+    assert labels.dtype == torch.int32 and counts.dtype == torch.int32 and counts.shape == (G,)
+    assert np.array_equal(labels.cpu().numpy(), want_labels) and bool((counts == 2).all()) and det == want_details
+    out, index, kdet = clock.dev(lambda: evaluation.keep_clusters(p, 1.5, 2, keep=0, min_cluster_points=2, return_index=True, details=True))
+    assert kdet == {"kept": 2 * G, "removed": G, "n_min": 2, **want_details}
+    assert index.dtype == torch.int32 and np.array_equal(index.cpu().numpy(), want_index)
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), points[want_index].view(np.uint32))
+    clock.report(f"cluster_dbscan + keep_clusters, M={M}")
