@@ -195,7 +195,13 @@ def _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_si
     return evaluation._check_cluster_args(cluster_eps, cluster_min_points) + evaluation._check_select_args(cluster_keep, cluster_min_size)
 
 
-@torch.no_grad()
+def _resolve_device(caller: str, device) -> torch.device:
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{caller} runs on a ROCm device; there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
 def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int = 5000, min_opacity: float = 0.5,
                    max_depth_dist: float = 0.1, use_median_depth: bool = False, seed=None, device="cuda",
                    details: bool = False, image_height=None, image_width=None, outlier_nb=None, outlier_std: float = 2.0,
@@ -220,6 +226,21 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
     what the outlier filters cannot, a floater whose points have each other for neighbours.  One more host read; `details`
     gains `cluster` (its statistics and `index`, the surviving rows of the cloud that entered the stage).  Default None: off,
     and the cloud is what it was, to the bit."""
+    points, normals, det, _ = _sample_surface(graph_dir_or_yaml, device, details, kf_interval=kf_interval, kf_samples=kf_samples,
+                                              min_opacity=min_opacity, max_depth_dist=max_depth_dist, use_median_depth=use_median_depth,
+                                              seed=seed, image_height=image_height, image_width=image_width, outlier_nb=outlier_nb,
+                                              outlier_std=outlier_std, cluster_eps=cluster_eps, cluster_min_points=cluster_min_points,
+                                              cluster_keep=cluster_keep, cluster_min_size=cluster_min_size)
+    return (points, normals, det) if details else (points, normals)
+
+
+@torch.no_grad()
+def _sample_surface(graph_dir_or_yaml, device, details, *, kf_interval, kf_samples, min_opacity, max_depth_dist, use_median_depth, seed,
+                    image_height, image_width, outlier_nb, outlier_std, cluster_eps, cluster_min_points, cluster_keep, cluster_min_size):
+    """The work of `sample_surface`, whose options these are: (points, normals, its `details` dict or None, context).  The
+    context is what the pass read and derived, for a second pass over the same keyframes (`mesh_tsdf`): dict(graph_dir, graph:
+    the parsed graph.yaml, size: (H, W), used: [(model index, frame id)], poses: their model_T_frame, kept: which of them
+    contributed rows)."""
     from . import traj_io
     outlier = _check_outlier(outlier_nb, outlier_std)
     cluster = _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_size)
@@ -228,11 +249,7 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
     graph_dir = graph_file.parent
     graph = traj_io.read_graph(graph_file)
     H, W = _image_size(graph_dir, image_height, image_width)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("sample_surface runs on a ROCm device; there is no CPU fallback")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _resolve_device("sample_surface", device)
     used_seed = int(torch.initial_seed() if seed is None else seed)
     k = int(kf_samples)
     if k < 1:
@@ -273,135 +290,126 @@ def sample_surface(graph_dir_or_yaml, *, kf_interval: int = -1, kf_samples: int 
         points, normals, index, cluster_det = evaluation.keep_clusters(points, cluster[0], cluster[1], cluster[2], cluster[3],
                                                                        normals=normals, return_index=True, details=True)
         cluster_det["index"] = index
+    det = None
     if details:
         det = {"frame_ids": [fid for _, fid in used], "n_valid": words[:, 0].astype(np.int64), "pixels": pixels,
                "kept": kept.copy(), "seed": used_seed}
-        if outlier_det is not None:
-            det["outlier"] = outlier_det
-        if cluster_det is not None:
-            det["cluster"] = cluster_det
-        return points, normals, det
-    return points, normals
+        _add_stages(det, None, outlier_det, cluster_det)
+    return points, normals, det, {"graph_dir": graph_dir, "graph": graph, "size": (H, W), "used": used, "poses": poses, "kept": kept}
 
 
-@torch.no_grad()
-def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, kf_interval: int = -1, kf_samples: int = 5000,
-              min_opacity: float = 0.5, max_depth_dist: float = 0.1, use_median_depth: bool = False, min_weight: float = 1.0,
-              seed=None, device="cuda", details: bool = False, image_height=None, image_width=None, keep_clusters=None,
-              min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
-              regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
-              smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False, fill_holes: int = None,
-              fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0,
-              cluster_eps=None, cluster_min_points: int = 10, cluster_keep: int = 1, cluster_min_size: int = 0):
-    """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
-    frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
+# What `mesh_tsdf` and `mesh_poisson` take as **options, by the function an option goes to.  That function's signature is
+# the one place that gives the option its default, and its docstring the one that describes it.
+_SAMPLE_OPTIONS = ("kf_interval", "kf_samples", "min_opacity", "max_depth_dist", "use_median_depth", "seed", "image_height", "image_width",
+                   "outlier_nb", "outlier_std", "cluster_eps", "cluster_min_points", "cluster_keep", "cluster_min_size")   # sample_surface
+_CLEAN_OPTIONS = ("keep_clusters", "min_triangles", "normals", "simplify", "contraction", "regularisation", "smooth", "smooth_method",
+                  "smooth_weights", "smooth_lambda", "smooth_mu", "fix_boundary", "fill_holes", "fill_max_size")         # mesh_ops.clean_mesh
 
-    `keep_clusters=K` (or `normals=True`) cleans the soup with `mesh_ops.clean_mesh`: bit-equal vertices welded, only the
-    K largest edge-connected clusters and those of at least `min_triangles` triangles kept (the floaters a fused LiDAR
-    volume leaves at depth discontinuities go), and with `normals=True` the return value is `(vertices, faces, normals)`
-    with area-weighted vertex normals.  One more host read; `details` gains `clean` (the statistics of `clean_mesh`) and
-    `stage_ms` a "clean" lap.  `simplify=h` (metres; a multiple of `voxel_size` is the natural choice) also runs the clean
-    stage and, after the selection, `mesh_ops.simplify_vertex_clustering(h, contraction, regularisation)`: the vertices of
-    every voxel of edge h become one, at their mean ("average") or at the minimum of the voxel's error quadric ("quadric");
-    `details["clean"]["simplify"]` holds its counts.  `smooth=n` also runs the clean stage and, before the normals, n sweeps
-    of `mesh_ops.smooth(n, smooth_method, smooth_weights, smooth_lambda, smooth_mu, fix_boundary)` over the edge graph
-    (Taubin by default: the terraces and the per-voxel jitter of a nearest-pixel fusion go, the faces stay);
-    `details["clean"]["smooth"]` holds its counts.  `fill_holes=n` also runs the clean stage and, after the selection,
-    `mesh_ops.fill_holes(max_edges=n, max_size=fill_max_size)`: the closed boundary loops of at most n edges — what a voxel
-    no keyframe observed leaves — get a fan over their centroid; `details["clean"]["fill"]` holds its counts.  With the defaults nothing of this runs and the soup is returned as it
-    always was.
 
-    `outlier_nb=k` (with `outlier_std`) goes to `sample_surface`: the samples that name the TSDF blocks are the filtered
-    ones, so a block that only stray samples at a depth discontinuity would have named is never allocated;
-    `details["outlier"]` holds the filter's statistics.  Default None: off.
-    `cluster_eps=e` (with `cluster_min_points`, `cluster_keep`, `cluster_min_size`) goes there too: the samples of a floater
-    that the outlier filter passes name no block either; `details["cluster"]` holds the statistics.  Default None: off.
+def _route_options(caller: str, options: dict):
+    """A front end's **options as (the keyword arguments of `_sample_surface`: `sample_surface`'s defaults under what the
+    caller gave, the keyword arguments the caller gave for `clean_mesh`) — checked before any work: a name in neither tuple
+    is a TypeError, then the outlier and the cluster arguments as `sample_surface` checks them."""
+    for name in options:
+        if name not in _SAMPLE_OPTIONS and name not in _CLEAN_OPTIONS:
+            raise TypeError(f"{caller}() got an unexpected keyword argument '{name}'")
+    defaults = sample_surface.__kwdefaults__                    # (of its keyword-only parameters, as its signature states them)
+    sample = {k: options.get(k, defaults[k]) for k in _SAMPLE_OPTIONS}
+    _check_outlier(sample["outlier_nb"], sample["outlier_std"])
+    _check_cluster(sample["cluster_eps"], sample["cluster_min_points"], sample["cluster_keep"], sample["cluster_min_size"])
+    return sample, {k: v for k, v in options.items() if k in _CLEAN_OPTIONS}
 
-    Pass 1 is `sample_surface` (same `kf_interval`, `kf_samples`, thresholds and seed) and `tsdf.allocate_blocks` around
-    its cloud: blocks of 8^3 voxels of edge `voxel_size`, truncation `trunc` (default 4 voxel_size).  Pass 2 renders every
-    keyframe that contributed samples again (the full allmap) and fuses it (`TsdfVolume.integrate`, nearest pixel, weight
-    1 per observation); then the zero surface of the voxels seen at least `min_weight` times is extracted.  Host reads:
-    those of `sample_surface`, one for the number of blocks, one for the number of triangles.  `details=True` adds
-    dict(blocks, volume_bytes, triangles, samples, frame_ids, stage_ms, volume: the TsdfVolume) and synchronises between the stages to time them."""
+
+def _lap_timer(dev, on: bool):
+    """(stage_ms, lap): with `on`, `lap(name)` synchronises and puts the milliseconds since the last lap under `name`."""
     import time
-
-    from . import traj_io, tsdf
-    _check_outlier(outlier_nb, outlier_std)
-    _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_size)
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("mesh_tsdf runs on a ROCm device; there is no CPU fallback")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    voxel_size = float(voxel_size)
-    trunc = 4.0 * voxel_size if trunc is None else float(trunc)
     stage_ms, t0 = {}, time.perf_counter()
 
     def lap(name):
         nonlocal t0
-        if details:
+        if on:
             torch.cuda.synchronize(dev)
             stage_ms[name], t0 = (time.perf_counter() - t0) * 1e3, time.perf_counter()
-    points, _, det = sample_surface(graph_dir_or_yaml, kf_interval=kf_interval, kf_samples=kf_samples, min_opacity=min_opacity,
-                                    max_depth_dist=max_depth_dist, use_median_depth=use_median_depth, seed=seed, device=dev,
-                                    details=True, image_height=image_height, image_width=image_width, outlier_nb=outlier_nb,
-                                    outlier_std=outlier_std, cluster_eps=cluster_eps, cluster_min_points=cluster_min_points,
-                                    cluster_keep=cluster_keep, cluster_min_size=cluster_min_size)
+    return stage_ms, lap
+
+
+def _clean_stage(vertices, faces, clean: dict, lap):
+    """(the mesh, the statistics of `mesh_ops.clean_mesh` or None) after a front end's extraction.  The stage runs only when
+    one of `keep_clusters`, `normals`, `simplify`, `smooth`, `fill_holes` was given: with none of them the soup is returned as
+    it always was.  Where it runs, a front end differs from `clean_mesh`'s own defaults on purpose: `keep_clusters=None`
+    (every cluster stays) and `normals=False` (two tensors) unless the caller says otherwise.  One more host read."""
+    if not clean.get("normals") and all(clean.get(k) is None for k in ("keep_clusters", "simplify", "smooth", "fill_holes")):
+        return (vertices, faces), None
+    from . import mesh_ops
+    *mesh, det = mesh_ops.clean_mesh(vertices, faces, weld=True, details=True, **{"keep_clusters": None, "normals": False, **clean})
+    lap("clean")
+    return tuple(mesh), det
+
+
+def _add_stages(det: dict, clean, outlier, cluster) -> dict:
+    """`det` with the statistics of the optional stages that ran, under `clean`, `outlier` and `cluster`."""
+    det.update({k: v for k, v in (("clean", clean), ("outlier", outlier), ("cluster", cluster)) if v is not None})
+    return det
+
+
+@torch.no_grad()
+def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, min_weight: float = 1.0, device="cuda",
+              details: bool = False, **options):
+    """A results directory to a triangle mesh, on the device: `(vertices (3T,3) float32, faces (T,3) int32)` in the world
+    frame, a triangle soup in the fixed order of `tsdf.TsdfVolume.extract`.
+
+    `**options` are those of `sample_surface` named in `_SAMPLE_OPTIONS` and those of `mesh_ops.clean_mesh` named in
+    `_CLEAN_OPTIONS`, passed on unchanged: the two functions give them their defaults and describe them, `_clean_stage` says
+    when the clean stage runs (with `normals=True` the return value is `(vertices, faces, normals)`).  Any other name is a
+    TypeError.  Here `outlier_nb` and `cluster_eps` filter the samples that name the TSDF blocks, so a block that only stray
+    samples at a depth discontinuity, or a floater's, would have named is never allocated; the clean stage removes the
+    floaters a fused LiDAR volume leaves there all the same, closes what a voxel no keyframe observed leaves open
+    (`fill_holes`), and takes out the terraces and the per-voxel jitter of a nearest-pixel fusion (`smooth`).
+
+    Pass 1 is `sample_surface` and `tsdf.allocate_blocks` around its cloud: blocks of 8^3 voxels of edge `voxel_size`,
+    truncation `trunc` (default 4 voxel_size).  Pass 2 renders every keyframe that contributed samples again (the full
+    allmap; the graph, the image size and the poses are those pass 1 read) and fuses it (`TsdfVolume.integrate`, nearest
+    pixel, weight 1 per observation); then the zero surface of the voxels seen at least `min_weight` times is extracted.
+    Host reads: those of `sample_surface`, one for the number of blocks, one for the number of triangles, one of the clean
+    stage.  `details=True` adds dict(blocks, volume_bytes, triangles, samples, frame_ids, stage_ms, volume: the TsdfVolume;
+    `clean`, `outlier`, `cluster`: the statistics of the optional stages that ran) and synchronises between the stages to
+    time them."""
+    from . import tsdf
+    sample, clean = _route_options("mesh_tsdf", options)
+    dev = _resolve_device("mesh_tsdf", device)
+    voxel_size = float(voxel_size)
+    trunc = 4.0 * voxel_size if trunc is None else float(trunc)
+    stage_ms, lap = _lap_timer(dev, details)
+    points, _, sampled, ctx = _sample_surface(graph_dir_or_yaml, dev, True, **sample)
     lap("sample")
-    outlier, cluster = det.get("outlier"), det.get("cluster")
     volume = tsdf.TsdfVolume(tsdf.allocate_blocks(points, voxel_size, trunc), voxel_size, trunc)
     lap("allocate")
-    path = Path(graph_dir_or_yaml)
-    graph_file = path / "graph.yaml" if path.is_dir() else path
-    graph = traj_io.read_graph(graph_file)
-    H, W = _image_size(graph_file.parent, image_height, image_width)
-    used = [u for u, kept in zip(frames_to_sample(graph, kf_interval), det["kept"]) if kept]
-    frames = {int(fr["id"]): fr for fr in graph["frames"]}
-    poses = [_pose44(frames[fid]["model_T_frame"]) for _, fid in used]
-    for i, fid, cam, allmap in _render_keyframes(graph_file.parent, graph, used, poses, H, W, dev):
-        volume.integrate(allmap, cam, graph["models"][used[i][0]]["world_T_model"], min_opacity=min_opacity,
-                         max_depth_dist=max_depth_dist, depth_ratio=1.0 if use_median_depth else 0.0)
+    graph = ctx["graph"]
+    used = [u for u, kept in zip(ctx["used"], ctx["kept"]) if kept]
+    poses = [p for p, kept in zip(ctx["poses"], ctx["kept"]) if kept]
+    for i, fid, cam, allmap in _render_keyframes(ctx["graph_dir"], graph, used, poses, *ctx["size"], dev):
+        volume.integrate(allmap, cam, graph["models"][used[i][0]]["world_T_model"], min_opacity=sample["min_opacity"],
+                         max_depth_dist=sample["max_depth_dist"], depth_ratio=1.0 if sample["use_median_depth"] else 0.0)
     lap("integrate")
     vertices, faces = volume.extract(min_weight=min_weight)
     lap("extract")
-    mesh, clean = (vertices, faces), None
-    if keep_clusters is not None or normals or simplify is not None or smooth is not None or fill_holes is not None:
-        from . import mesh_ops
-        *mesh, clean = mesh_ops.clean_mesh(vertices, faces, weld=True, keep_clusters=keep_clusters, min_triangles=min_triangles,
-                                           normals=normals, details=True, simplify=simplify, contraction=contraction,
-                                           regularisation=regularisation, smooth=smooth, smooth_method=smooth_method,
-                                           smooth_weights=smooth_weights, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                                           fix_boundary=fix_boundary, fill_holes=fill_holes, fill_max_size=fill_max_size)
-        mesh = tuple(mesh)
-        lap("clean")
+    mesh, cleaned = _clean_stage(vertices, faces, clean, lap)
     if details:
         det = {"blocks": int(volume.blocks.shape[0]), "volume_bytes": volume.nbytes, "triangles": int(faces.shape[0]),
                "samples": int(points.shape[0]), "frame_ids": [fid for _, fid in used], "stage_ms": stage_ms, "volume": volume}
-        if clean is not None:
-            det["clean"] = clean
-        if outlier is not None:
-            det["outlier"] = outlier
-        if cluster is not None:
-            det["cluster"] = cluster
-        return mesh + (det,)
+        return mesh + (_add_stages(det, cleaned, sampled.get("outlier"), sampled.get("cluster")),)
     return mesh
 
 
 @torch.no_grad()
 def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, screening: float = 4.0, iterations: int = 300,
-                 tol: float = 1e-4, min_density=None, min_density_quantile=None, density_sweeps: int = 2, kf_interval: int = -1,
-                 kf_samples: int = 5000, min_opacity: float = 0.5, max_depth_dist: float = 0.1, use_median_depth: bool = False,
-                 seed=None, device="cuda", details: bool = False, image_height=None, image_width=None, keep_clusters=None,
-                 min_triangles: int = 50, normals: bool = False, simplify: float = None, contraction: str = "average",
-                 regularisation: float = 1e-3, smooth: int = None, smooth_method: str = "taubin", smooth_weights: str = "inverse_distance",
-                 smooth_lambda: float = 0.5, smooth_mu: float = -0.53, fix_boundary: bool = False, fill_holes: int = None,
-                 fill_max_size: float = None, outlier_nb=None, outlier_std: float = 2.0,
-                 cluster_eps=None, cluster_min_points: int = 10, cluster_keep: int = 1, cluster_min_size: int = 0):
-    """The reference's `mesh_poisson` (scene/postprocessing.py) to its end, on the device: `sample_surface` (its options
-    unchanged: `kf_interval`, `kf_samples`, `min_opacity`, `max_depth_dist`, `use_median_depth`, `seed`, `outlier_nb`, `cluster_eps`, ...),
-    then `poisson.reconstruct` on the merged oriented cloud — blocks `margin` around the samples, the splat, the screened
-    solve, marching tetrahedra — the density trim, and the clean-up options of `mesh_tsdf`, passed on to
-    `mesh_ops.clean_mesh` unchanged (`normals=True` returns `(vertices, faces, normals)`).
+                 tol: float = 1e-4, min_density=None, min_density_quantile=None, density_sweeps: int = 2, device="cuda",
+                 details: bool = False, **options):
+    """The reference's `mesh_poisson` (scene/postprocessing.py) to its end, on the device: `sample_surface`, then
+    `poisson.reconstruct` on the merged oriented cloud — blocks `margin` around the samples, the splat, the screened solve,
+    marching tetrahedra — the density trim, and the clean stage of `mesh_tsdf`.  `**options` are those of `mesh_tsdf`: the
+    names in `_SAMPLE_OPTIONS` go to `sample_surface` and those in `_CLEAN_OPTIONS` to `mesh_ops.clean_mesh`, unchanged
+    (`normals=True` returns `(vertices, faces, normals)`); any other name is a TypeError.
 
     What it IS NOT: Open3D's octree solver.  It is a uniform band of `voxel_size` voxels with trilinear splats (see
     `poisson.py`); `voxel_size` takes the place of the reference's octree `depth`.  `min_density=t` trims by an absolute
@@ -411,39 +419,20 @@ def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, 
     and `density_sweeps` are judgements (`poisson.py` says why).
 
     Host reads: those of `sample_surface`, one for the blocks, one for the solve, one for the triangles.  `details=True` adds
-    dict(blocks, triangles, samples, solve, min_density, stage_ms, volume: the PoissonVolume) and synchronises between the
-    stages to time them."""
-    import time
-
+    dict(blocks, triangles, samples, solve, min_density, stage_ms, volume: the PoissonVolume; `clean`, `outlier`, `cluster` as
+    `mesh_tsdf` adds them) and synchronises between the stages to time them."""
     from . import poisson, tsdf
-    _check_outlier(outlier_nb, outlier_std)
-    _check_cluster(cluster_eps, cluster_min_points, cluster_keep, cluster_min_size)
+    sample, clean = _route_options("mesh_poisson", options)
     if min_density is not None and min_density_quantile is not None:
         raise ValueError("give min_density or min_density_quantile, not both")
     if min_density_quantile is not None and not (0.0 <= float(min_density_quantile) <= 1.0):
         raise ValueError("min_density_quantile must lie in [0, 1]")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("mesh_poisson runs on a ROCm device; there is no CPU fallback")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _resolve_device("mesh_poisson", device)
     voxel_size = float(voxel_size)
     margin = poisson.DEFAULT_MARGIN_VOXELS * voxel_size if margin is None else float(margin)
-    stage_ms, t0 = {}, time.perf_counter()
-
-    def lap(name):
-        nonlocal t0
-        if details:
-            torch.cuda.synchronize(dev)
-            stage_ms[name], t0 = (time.perf_counter() - t0) * 1e3, time.perf_counter()
-    points, cloud_normals, det = sample_surface(graph_dir_or_yaml, kf_interval=kf_interval, kf_samples=kf_samples, min_opacity=min_opacity,
-                                                max_depth_dist=max_depth_dist, use_median_depth=use_median_depth, seed=seed, device=dev,
-                                                details=True, image_height=image_height, image_width=image_width,
-                                                outlier_nb=outlier_nb, outlier_std=outlier_std, cluster_eps=cluster_eps,
-                                                cluster_min_points=cluster_min_points, cluster_keep=cluster_keep,
-                                                cluster_min_size=cluster_min_size)
+    stage_ms, lap = _lap_timer(dev, details)
+    points, cloud_normals, sampled, _ = _sample_surface(graph_dir_or_yaml, dev, True, **sample)
     lap("sample")
-    outlier, cluster = det.get("outlier"), det.get("cluster")
     volume = poisson.PoissonVolume(tsdf.allocate_blocks(points, voxel_size, margin), voxel_size)
     lap("allocate")
     volume.splat(points, cloud_normals)
@@ -457,24 +446,9 @@ def mesh_poisson(graph_dir_or_yaml, voxel_size: float, *, margin: float = None, 
         threshold = float(torch.quantile(seen[:: max(1, seen.numel() // (1 << 22))], float(min_density_quantile))) if seen.numel() else 0.0
     vertices, faces = volume.extract(min_density=threshold, density_sweeps=density_sweeps)
     lap("extract")
-    mesh, clean = (vertices, faces), None
-    if keep_clusters is not None or normals or simplify is not None or smooth is not None or fill_holes is not None:
-        from . import mesh_ops
-        *mesh, clean = mesh_ops.clean_mesh(vertices, faces, weld=True, keep_clusters=keep_clusters, min_triangles=min_triangles,
-                                           normals=normals, details=True, simplify=simplify, contraction=contraction,
-                                           regularisation=regularisation, smooth=smooth, smooth_method=smooth_method,
-                                           smooth_weights=smooth_weights, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                                           fix_boundary=fix_boundary, fill_holes=fill_holes, fill_max_size=fill_max_size)
-        mesh = tuple(mesh)
-        lap("clean")
+    mesh, cleaned = _clean_stage(vertices, faces, clean, lap)
     if details:
-        out = {"blocks": int(volume.blocks.shape[0]), "triangles": int(faces.shape[0]), "samples": int(points.shape[0]), "solve": solved,
-               "min_density": threshold, "frame_ids": det["frame_ids"], "stage_ms": stage_ms, "volume": volume}
-        if clean is not None:
-            out["clean"] = clean
-        if outlier is not None:
-            out["outlier"] = outlier
-        if cluster is not None:
-            out["cluster"] = cluster
-        return mesh + (out,)
+        det = {"blocks": int(volume.blocks.shape[0]), "triangles": int(faces.shape[0]), "samples": int(points.shape[0]), "solve": solved,
+               "min_density": threshold, "frame_ids": sampled["frame_ids"], "stage_ms": stage_ms, "volume": volume}
+        return mesh + (_add_stages(det, cleaned, sampled.get("outlier"), sampled.get("cluster")),)
     return mesh

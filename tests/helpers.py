@@ -3,7 +3,7 @@ the same seeded scene and compare."""
 import numpy as np
 import torch
 
-from splat_loam_amd import synth
+from splat_loam_amd import ply_io, synth, traj_io
 from splat_loam_amd.rasterizer import GaussianRasterizationSettings, rasterize_backward, rasterize_forward
 
 # Parity bar (BASELINE.json north_star): <= 1e-5 relative on rendered
@@ -59,3 +59,17 @@ def tangent(g, q):
     F.normalize's backward."""
     q = q / np.linalg.norm(q, axis=1, keepdims=True)
     return g - (g * q).sum(1, keepdims=True) * q
+
+
+def write_room(d, H=64, W=256):
+    """A results directory at the path `d`: one model, one keyframe of H x W, 6000 surfels on a shell of 2.4 - 2.6 m around
+    the sensor, facing it: a closed room."""
+    K = synth.spherical_K(H, W)
+    sc = synth.make_scene(6000, H, W, seed=77, range_lo=2.4, range_hi=2.6, scale_lo=0.06, scale_hi=0.15, opac_lo=0.6, max_tilt_deg=10.0)
+    ply_io.save_ply(d / "models/model_0.ply", sc["means"], np.log(sc["opac"] / (1 - sc["opac"])), np.log(sc["scales"]), sc["rots"])
+    model = {"id": 0, "world_T_model": np.eye(4), "filename": "models/model_0.ply", "frame_ids": [0]}
+    frame = {"id": 0, "timestamp": 0.0, "model_T_frame": synth.keyframe_poses(2)[1],
+             "projmatrix": [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])], "model_id": 0}
+    traj_io.write_graph(d / "graph.yaml", [model], [frame])
+    with open(d / "cfg.yaml", "w") as f:
+        f.write(f"preprocessing:\n  image_height: {H}\n  image_width: {W}\n")

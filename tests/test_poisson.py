@@ -11,7 +11,8 @@ import torch
 
 import poisson_ref as ref
 import tsdf_ref
-from splat_loam_amd import _abi, evaluation, mesh_ops, meshing, ply_io, poisson, synth, traj_io
+from helpers import write_room as _write_room
+from splat_loam_amd import _abi, evaluation, mesh_ops, meshing, ply_io, poisson
 from poisson_ref import ORIGIN, VS, bits, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -213,20 +214,7 @@ def test_two_runs_give_the_same_bits(device):
 
 
 # ---- 9. a results directory to a mesh ------------------------------------------------------------------------------------------
-H2, W2, K2, VS2, SEED = 64, 256, 4000, 0.1, 0x5EED
-
-
-def _write_room(d):
-    """One model, one keyframe: 6000 surfels on a shell of 2.4 - 2.6 m around the sensor, facing it: a closed room."""
-    K = synth.spherical_K(H2, W2)
-    sc = synth.make_scene(6000, H2, W2, seed=77, range_lo=2.4, range_hi=2.6, scale_lo=0.06, scale_hi=0.15, opac_lo=0.6, max_tilt_deg=10.0)
-    ply_io.save_ply(d / "models/model_0.ply", sc["means"], np.log(sc["opac"] / (1 - sc["opac"])), np.log(sc["scales"]), sc["rots"])
-    model = {"id": 0, "world_T_model": np.eye(4), "filename": "models/model_0.ply", "frame_ids": [0]}
-    frame = {"id": 0, "timestamp": 0.0, "model_T_frame": synth.keyframe_poses(2)[1],
-             "projmatrix": [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])], "model_id": 0}
-    traj_io.write_graph(d / "graph.yaml", [model], [frame])
-    with open(d / "cfg.yaml", "w") as f:
-        f.write(f"preprocessing:\n  image_height: {H2}\n  image_width: {W2}\n")
+K2, VS2, SEED = 4000, 0.1, 0x5EED
 
 
 def test_mesh_poisson_end_to_end(device, tmp_path):

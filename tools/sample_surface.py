@@ -29,6 +29,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
+import mesh_cli
 from splat_loam_amd import meshing, ply_io, synth, traj_io
 
 
@@ -128,36 +129,26 @@ def probe(out_file, kf_samples=5000, min_opacity=0.5, max_depth_dist=0.1):
     print(json.dumps(res))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("results_dir", nargs="?")
     ap.add_argument("out_ply", nargs="?")
-    ap.add_argument("--kf-interval", type=int, default=-1)
-    ap.add_argument("--kf-samples", type=int, default=5000)
-    ap.add_argument("--min-opacity", type=float, default=0.5)
-    ap.add_argument("--max-depth-dist", type=float, default=0.1)
-    ap.add_argument("--use-median-depth", action="store_true")
-    ap.add_argument("--outlier-nb", type=int, default=None, help="statistical outlier removal of the merged cloud: neighbours (1..32)")
-    ap.add_argument("--outlier-std", type=float, default=2.0, help="... and the threshold in standard deviations (with --outlier-nb)")
-    ap.add_argument("--cluster-eps", type=float, default=None, help="keep the largest DBSCAN cluster of the cloud: the radius, a few sample spacings")
-    ap.add_argument("--cluster-min-points", type=int, default=10, help="... and the neighbours, itself included, that make a point core (with --cluster-eps)")
-    ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--image-height", type=int, default=None)
-    ap.add_argument("--image-width", type=int, default=None)
-    ap.add_argument("--device", default="cuda")
+    mesh_cli.add_sample_arguments(ap)
+    mesh_cli.add_cloud_arguments(ap)
     ap.add_argument("--probe", action="store_true")
     ap.add_argument("--probe-out", default=os.path.join(ROOT, "profiles", "r13a_surface_samples.json"))
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
     if a.probe:
         probe(a.probe_out)
         return
     if not a.results_dir or not a.out_ply:
         ap.error("RESULTS_DIR and OUT.ply are required (or --probe)")
-    pts, nrm, det = meshing.sample_surface(a.results_dir, kf_interval=a.kf_interval, kf_samples=a.kf_samples,
-                                           min_opacity=a.min_opacity, max_depth_dist=a.max_depth_dist,
-                                           use_median_depth=a.use_median_depth, seed=a.seed, device=a.device, details=True,
-                                           image_height=a.image_height, image_width=a.image_width, outlier_nb=a.outlier_nb,
-                                           outlier_std=a.outlier_std, cluster_eps=a.cluster_eps, cluster_min_points=a.cluster_min_points)
+    pts, nrm, det = meshing.sample_surface(a.results_dir, device=a.device, details=True, **mesh_cli.sample_options(a))
     ply_io.save_point_cloud(a.out_ply, pts, nrm)
     empty = [f for f, kept in zip(det["frame_ids"], det["kept"]) if not kept]
     print(f"{pts.shape[0]} oriented points from {int(det['kept'].sum())} of {len(det['frame_ids'])} keyframes "
