@@ -760,6 +760,33 @@ int sls_mesh_distance(int V, const float *vertices, int F, const int32_t *faces,
                       size_t scratch_bytes, void *stream);
 int sls_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, void *stream);
 
+/* ---- first hits of rays on a mesh ---------------------------------------------------------------------------------------
+ * For every ray (origin o, direction d, need not be unit) the FIRST triangle it hits (include/sls_raycast_math.h): with
+ * hit(r, f) the header's watertight test of ray r against face f within [t_min, t_max], float32,
+ *   out_t[r] = the smallest t over the faces hit (the hit point is o + t d), +inf on a miss,
+ *   out_face[r] (optional) = the LOWEST face index attaining it, -1 on a miss,
+ *   out_uv[r] (Mr x 2, optional) = the barycentric weights of that face's second and third vertex, recomputed once from
+ *       (ray, face); 0, 0 on a miss,
+ * in the caller's ray order: the values of the header, bit for bit, for (ray, returned face).  Both sides of a face hit.
+ * No ray passes between two faces that share an edge or a vertex (the header says why).  The index is sls_mesh_distance's
+ * index of triangles, built ONCE by sls_mesh_rayindex_build and cast against any number of times — it is valid for the
+ * (V, vertices, F, faces) it was built from, which must be passed again unchanged; that is not checked.
+ * All pointers DEVICE; vertices (V x 3) row-major floats, faces (F x 3) int32, origins and directions (Mr x 3).
+ *   out_status (4 words): [F, faces with a vertex index outside [0, V), faces with a non-finite vertex, rays refused];
+ *       the build writes the first three and 0.  Such faces are never dereferenced out of range and never hit; when either
+ *       count is non-zero the other outputs are unspecified.  A refused ray (a non-finite component, or a direction whose
+ *       largest |component| is below 2^-100) misses.
+ *   index: sls_mesh_rayindex_bytes(V, F) bytes (0 for V < 1 or F < 1), 256-byte aligned.
+ * Mr == 0 succeeds and writes only the status (origins, directions and out_t may be null then).  Before anything is
+ * enqueued: SLS_E_ARG for V < 1, F < 1, Mr < 0, a null pointer other than the two optional ones, an index that is not
+ * 256-byte aligned, t_min NaN or negative, t_max NaN or below t_min; SLS_E_SCRATCH for too small an index. */
+size_t sls_mesh_rayindex_bytes(int V, int F);
+int sls_mesh_rayindex_build(int V, const float *vertices, int F, const int32_t *faces, void *index, size_t index_bytes,
+                            uint32_t *out_status, void *stream);
+int sls_mesh_raycast(int V, const float *vertices, int F, const int32_t *faces, const void *index, size_t index_bytes, int Mr,
+                     const float *origins, const float *directions, float t_min, float t_max, float *out_t, int32_t *out_face,
+                     float *out_uv, uint32_t *out_status, void *stream);
+
 /* ---- the k nearest neighbours, outlier removal ---------------------------------------------------------------------
  * sls_nn_query with k answers per query (include/sls_outlier_math.h): query q's list is the min(k, Mt) smallest keys
  * (bits(d2) << 32 | original target index) over ALL targets, ascending — nearer first, then the lower index; a target

@@ -505,6 +505,44 @@ int sls_error_colors(int M, const float *dist2, float truncation, uint8_t *out_r
     return launch_error_colors(M, dist2, truncation, out_rgb, (hipStream_t)stream);
 }
 
+size_t sls_mesh_rayindex_bytes(int V, int F) { return mesh_rayindex_bytes(V, F); }
+
+int sls_mesh_rayindex_build(int V, const float *vertices, int F, const int32_t *faces, void *index, size_t index_bytes,
+                            uint32_t *out_status, void *stream)
+{
+    SLS_REQUIRE(V >= 1, "V < 1: the mesh has no vertex");
+    SLS_REQUIRE(F >= 1, "F < 1: the mesh has no face");
+    SLS_REQUIRE(vertices && faces && index && out_status, "null pointer");
+    SLS_REQUIRE(((uintptr_t)index & 255u) == 0, "index not 256-byte aligned");
+    if (index_bytes < mesh_rayindex_bytes(V, F)) {
+        set_error("sls_mesh_rayindex_build: index too small: %zu < %zu", index_bytes, mesh_rayindex_bytes(V, F));
+        return SLS_E_SCRATCH;
+    }
+    return launch_mesh_rayindex_build(V, vertices, F, faces, index, out_status, (hipStream_t)stream);
+}
+
+int sls_mesh_raycast(int V, const float *vertices, int F, const int32_t *faces, const void *index, size_t index_bytes, int Mr,
+                     const float *origins, const float *directions, float t_min, float t_max, float *out_t, int32_t *out_face,
+                     float *out_uv, uint32_t *out_status, void *stream)
+{
+    SLS_REQUIRE(V >= 1, "V < 1: the mesh has no vertex");
+    SLS_REQUIRE(F >= 1, "F < 1: the mesh has no face");
+    SLS_REQUIRE(Mr >= 0, "negative Mr");
+    SLS_REQUIRE(vertices && faces && index && out_status && ((origins && directions && out_t) || Mr == 0), "null pointer");
+    SLS_REQUIRE(((uintptr_t)index & 255u) == 0, "index not 256-byte aligned");
+    SLS_REQUIRE(t_min >= 0.0f, "t_min is NaN or negative");
+    SLS_REQUIRE(t_max >= t_min, "t_max is NaN or below t_min");
+    if (index_bytes < mesh_rayindex_bytes(V, F)) {
+        set_error("sls_mesh_raycast: index too small: %zu < %zu", index_bytes, mesh_rayindex_bytes(V, F));
+        return SLS_E_SCRATCH;
+    }
+    RaycastLaunch a{};
+    a.V = V; a.vertices = vertices; a.F = F; a.faces = faces; a.index = index;
+    a.Mr = Mr; a.origins = origins; a.directions = directions; a.t_min = t_min; a.t_max = t_max;
+    a.out_t = out_t; a.out_face = out_face; a.out_uv = out_uv; a.out_status = out_status;
+    return launch_mesh_raycast(a, (hipStream_t)stream);
+}
+
 size_t sls_nn_k_scratch_bytes(int Mt, int Mq, int k) { return nn_k_scratch_bytes(Mt, Mq, k); }
 
 int sls_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,

@@ -15,7 +15,7 @@
 // the result is reproducible bit for bit by a CPU brute force.
 #include <float.h>
 
-#include "sls_geom.hpp"
+#include "sls_sweep.hpp"
 #include "../../include/sls_nn_math.h"
 #include "../../include/sls_meshdist_math.h"
 #include "../../include/sls_outlier_math.h"
@@ -25,8 +25,9 @@
 namespace sls {
 
 constexpr int kKnnBox = 256;
-constexpr int kKnnSub = 32;    // points per sub-box
-constexpr int kKnnSubs = kKnnBox / kKnnSub;     // 8 sub-boxes per box
+constexpr int kKnnSub = kSweepSub;              // points per sub-box
+constexpr int kKnnSubs = kSweepSubs;            // 8 sub-boxes per box
+static_assert(kKnnBox == kSweepBox, "the boxes of this file are the sweep's (sls_sweep.hpp)");
 
 __global__ void knn_init_bbox_kernel(uint32_t *bbox, uint32_t M, uint32_t M2)
 {
@@ -158,29 +159,9 @@ __global__ __launch_bounds__(256) void knn_gather_boxes_kernel(int M, const floa
 // scale, so there the argument holds up to that — the returned face is a nearest one within the header's own error, and
 // exact duplicates, equal to the bit, still resolve to the lower index wherever the 1e-5 slack covers that error.)
 // ---------------------------------------------------------------------------------------------------------------------
-// The sweep knows an index by its boxes alone; what an ITEM is (a point: float4, xyz + original index; a triangle: TriItem
-// below) matters to the stage, which copies items, and to the search, which reads them.
-template <class ItemT>
-struct SweepIndex {         // M items in curve order, boxes over runs of 256, sub-boxes over runs of 32
-    typedef ItemT Item;
-    int M, nboxes;
-    const Item *__restrict__ pts;
-    const float4 *__restrict__ boxes, *__restrict__ subboxes;
-    __device__ __forceinline__ int nsub() const { return (M + kKnnSub - 1) / kKnnSub; }
-};
 typedef SweepIndex<float4> KnnIndex;       // a cloud in curve order (knn_build)
 
-template <class Item>
-struct SweepLdsOf {         // wave-private: 2 816 bytes for points, 3 840 for triangles
-    Item run[kKnnSub];
-    uint32_t box[64], sub[64 * kKnnSubs];
-};
 typedef SweepLdsOf<float4> SweepLds;
-
-__device__ __forceinline__ float rl(float v, int k)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
-}
 
 __device__ __forceinline__ float box_gap2(const float4 amn, const float4 amx, const float4 bmn, const float4 bmx)
 {
@@ -210,14 +191,6 @@ __device__ __forceinline__ int sweep_chunk(int it, int c0, int nchunks)
     return (c0 < nchunks - 1 - c0) ? it : nchunks - 1 - it;
 }
 
-// Ballot compaction: the lanes with `keep` write v to dst in lane order; the count of them.
-__device__ __forceinline__ int wave_compact(bool keep, uint32_t v, uint32_t *dst)
-{
-    const uint64_t m = __ballot(keep);
-    if (keep) dst[__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = v;
-    return __builtin_popcountll(m);
-}
-
 // item `lane & 31` of run sb for the LDS stage; LOW: loaded by lanes 0..31 alone, the ones that stage it
 template <bool LOW, class Index, class Search>
 __device__ __forceinline__ typename Index::Item run_point(const Index &ix, int sb, const Search &s)
@@ -225,15 +198,6 @@ __device__ __forceinline__ typename Index::Item run_point(const Index &ix, int s
     const int r0 = sb * kKnnSub, i = r0 + ((int)threadIdx.x & (kKnnSub - 1));
     if (LOW && threadIdx.x >= kKnnSub) return typename Index::Item{};
     return i < ix.M ? ix.pts[i] : s.pad(ix.pts, r0);
-}
-
-// a run's 32 items -> LDS, for every lane to scan
-template <class Item>
-__device__ __forceinline__ void stage(SweepLdsOf<Item> &lds, const Item &p)
-{
-    __builtin_amdgcn_wave_barrier();
-    if (threadIdx.x < kKnnSub) lds.run[threadIdx.x] = p;
-    __syncthreads();
 }
 
 template <class Index, class Search>
@@ -851,33 +815,13 @@ int launch_nn_stats(int M, const float *dist2, float truncation, float threshold
 // A face with a vertex index outside [0, V) or a non-finite vertex is counted in the status words and indexed as three
 // points at the origin: nothing is read out of range, and the caller discards the outputs.
 // ---------------------------------------------------------------------------------------------------------------------
-struct TriItem { float4 a, b, c; };
-typedef SweepIndex<TriItem> TriIndex;
-
-// the face's vertices; false for an index outside [0, V) (*bad_index) or a non-finite coordinate
-__device__ __forceinline__ bool tri_load(int V, const float *__restrict__ vertices, const int32_t *__restrict__ faces, size_t f,
-                                         float4 &a, float4 &b, float4 &c, bool *bad_index)
-{
-    const int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-    a = b = c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    *bad_index = i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V;
-    if (*bad_index) return false;
-    const float4 ta = make_float4(vertices[3 * (size_t)i0], vertices[3 * (size_t)i0 + 1], vertices[3 * (size_t)i0 + 2], 0.0f);
-    const float4 tb = make_float4(vertices[3 * (size_t)i1], vertices[3 * (size_t)i1 + 1], vertices[3 * (size_t)i1 + 2], 0.0f);
-    const float4 tc = make_float4(vertices[3 * (size_t)i2], vertices[3 * (size_t)i2 + 1], vertices[3 * (size_t)i2 + 2], 0.0f);
-    auto finite = [](const float4 v) { return fabsf(v.x) <= FLT_MAX && fabsf(v.y) <= FLT_MAX && fabsf(v.z) <= FLT_MAX; };
-    if (!(finite(ta) && finite(tb) && finite(tc))) return false;
-    a = ta; b = tb; c = tc;
-    return true;
-}
-
-__global__ void tri_init_kernel(uint32_t *bbox, uint32_t *status, uint32_t F, uint32_t Mq)
+__global__ void tri_init_kernel(uint32_t *bbox, uint32_t *status, uint32_t F, uint32_t Mq, uint32_t word3)
 {
     if (threadIdx.x < 3) bbox[threadIdx.x] = 0xFFFFFFFFu;
     else if (threadIdx.x < 6) bbox[threadIdx.x] = 0u;
     else if (threadIdx.x == 6) bbox[6] = F;
     else if (threadIdx.x == 7) bbox[7] = Mq;
-    else if (threadIdx.x < 12) status[threadIdx.x - 8] = threadIdx.x == 8 ? F : (threadIdx.x == 11 ? 1u : 0u);
+    else if (threadIdx.x < 12) status[threadIdx.x - 8] = threadIdx.x == 8 ? F : (threadIdx.x == 11 ? word3 : 0u);
 }
 
 // the cube of the valid faces' vertices and the counts of the others (integer atomics: any order gives the same words)
@@ -1022,6 +966,30 @@ size_t mesh_distance_scratch_bytes(int V, int F, int Mq)
     return (V >= 1 && F >= 1 && Mq >= 0) ? mesh_distance_layout(F, Mq, nullptr, &items).total : 0;
 }
 
+// The index of a mesh's triangles, for launch_mesh_distance and for launch_mesh_rayindex_build (sls_raycast.hip) alike: the
+// status words [F, faces with a bad index, faces with a non-finite vertex, word3] and the cube of the valid faces; then,
+// unless counts_only, the centroids' codes, the sort, the triangles in curve order and their boxes and sub-boxes.
+// count2: the item count of a second sort that follows (bbox[7]).  *which: where the sorted (code, index) pairs ended up.
+int tri_index_build(int V, const float *vertices, int F, const int32_t *faces, const TriIndexBuild &b, uint32_t count2,
+                    uint32_t *out_status, uint32_t word3, bool counts_only, hipStream_t st, int *which)
+{
+    const int nb = (F + 255) / 256, key_bits = knn_key_bits(F), nboxes = (F + kKnnBox - 1) / kKnnBox;
+    hipLaunchKernelGGL(tri_init_kernel, dim3(1), dim3(64), 0, st, b.bbox, out_status, (uint32_t)F, count2, word3);
+    SLS_LAUNCH_CHECK("tri_init_kernel");
+    hipLaunchKernelGGL(tri_bbox_kernel, dim3(nb < 256 ? nb : 256), dim3(256), 0, st, V, vertices, F, faces, b.bbox, out_status);
+    SLS_LAUNCH_CHECK("tri_bbox_kernel");
+    if (counts_only) return SLS_OK;
+    hipLaunchKernelGGL(tri_code_kernel, dim3(nb), dim3(256), 0, st, V, vertices, F, faces, b.bbox, b.keys, b.vals, key_bits);
+    SLS_LAUNCH_CHECK("tri_code_kernel");
+    const int rc = radix_sort_pairs_u32(b.keys, b.vals, b.keys_tmp, b.vals_tmp, b.bbox + 6, (uint32_t)F, key_bits, b.sort, b.sort_bytes,
+                                        which, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tri_gather_boxes_kernel, dim3(nboxes), dim3(kKnnBox), 0, st, V, vertices, F, faces,
+                       *which ? b.vals_tmp : b.vals, b.items, b.boxes, b.subboxes);
+    SLS_LAUNCH_CHECK("tri_gather_boxes_kernel");
+    return SLS_OK;
+}
+
 int launch_mesh_distance(int V, const float *vertices, int F, const int32_t *faces, int Mq, const float *query_xyz,
                          float *out_dist2, int32_t *out_face, float *out_closest, uint32_t *out_status, void *scratch,
                          hipStream_t st)
@@ -1030,21 +998,13 @@ int launch_mesh_distance(int V, const float *vertices, int F, const int32_t *fac
     NnFront f;
     TriItem *items;
     const NnScratch &s = f.s = mesh_distance_layout(F, Mq, scratch, &items);
-    const int nb = (F + 255) / 256, key_bits = knn_key_bits(F), nboxes = (F + kKnnBox - 1) / kKnnBox;
-    hipLaunchKernelGGL(tri_init_kernel, dim3(1), dim3(64), 0, st, s.t.bbox, out_status, (uint32_t)F, (uint32_t)Mq);
-    SLS_LAUNCH_CHECK("tri_init_kernel");
-    hipLaunchKernelGGL(tri_bbox_kernel, dim3(nb < 256 ? nb : 256), dim3(256), 0, st, V, vertices, F, faces, s.t.bbox, out_status);
-    SLS_LAUNCH_CHECK("tri_bbox_kernel");
-    if (Mq == 0) return SLS_OK;                         // the status alone
-    hipLaunchKernelGGL(tri_code_kernel, dim3(nb), dim3(256), 0, st, V, vertices, F, faces, s.t.bbox, s.t.keys, s.t.vals, key_bits);
-    SLS_LAUNCH_CHECK("tri_code_kernel");
+    const int key_bits = knn_key_bits(F), nboxes = (F + kKnnBox - 1) / kKnnBox;
+    TriIndexBuild b{};
+    b.bbox = s.t.bbox; b.keys = s.t.keys; b.keys_tmp = s.t.keys_tmp; b.vals = s.t.vals; b.vals_tmp = s.t.vals_tmp;
+    b.items = items; b.boxes = s.t.boxes; b.subboxes = s.t.subboxes; b.sort = s.t.sort; b.sort_bytes = s.t.sort_bytes;
     int which = 0;
-    int rc = radix_sort_pairs_u32(s.t.keys, s.t.vals, s.t.keys_tmp, s.t.vals_tmp, s.t.bbox + 6, (uint32_t)F, key_bits, s.t.sort,
-                                  s.t.sort_bytes, &which, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tri_gather_boxes_kernel, dim3(nboxes), dim3(kKnnBox), 0, st, V, vertices, F, faces,
-                       which ? s.t.vals_tmp : s.t.vals, items, s.t.boxes, s.t.subboxes);
-    SLS_LAUNCH_CHECK("tri_gather_boxes_kernel");
+    int rc = tri_index_build(V, vertices, F, faces, b, (uint32_t)Mq, out_status, 1u, Mq == 0, st, &which);
+    if (rc || Mq == 0) return rc;                       // (Mq == 0: the status alone)
     f.tkeys = which ? s.t.keys_tmp : s.t.keys;
     hipLaunchKernelGGL(knn_morton_kernel, dim3((Mq + 255) / 256), dim3(256), 0, st, Mq, query_xyz, s.t.bbox, s.qkeys, s.qvals,
                        key_bits);

@@ -245,6 +245,28 @@ int launch_mesh_distance(int V, const float *vertices, int F, const int32_t *fac
                          float *out_dist2, int32_t *out_face, float *out_closest, uint32_t *out_status, void *scratch,
                          hipStream_t st);
 int launch_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, hipStream_t st);
+// the index of triangles behind it, which the ray caster shares (the body: sls_knn.hip; TriItem: sls_sweep.hpp).  The
+// caller lays the arrays out: F words each of keys / vals and their ping-pong copies, F items, 2 float4 per box of 256 and
+// per sub-box of 32, 8 words of bbox, the sorter's scratch for F items
+struct TriItem;
+struct TriIndexBuild {
+    uint32_t *bbox, *keys, *keys_tmp, *vals, *vals_tmp;
+    TriItem *items; float4 *boxes, *subboxes;
+    void *sort; size_t sort_bytes;
+};
+int tri_index_build(int V, const float *vertices, int F, const int32_t *faces, const TriIndexBuild &b, uint32_t count2,
+                    uint32_t *out_status, uint32_t word3, bool counts_only, hipStream_t st, int *which);
+// ---- sls_raycast.hip: first hits of rays against a mesh (the arguments are checked by the caller, sls_api.hip) -------
+size_t mesh_rayindex_bytes(int V, int F);
+int launch_mesh_rayindex_build(int V, const float *vertices, int F, const int32_t *faces, void *index, uint32_t *out_status,
+                               hipStream_t st);
+// Mr == 0: only the status is written.  out_face and out_uv may be null
+struct RaycastLaunch {
+    int V; const float *vertices; int F; const int32_t *faces; const void *index;
+    int Mr; const float *origins, *directions; float t_min, t_max;
+    float *out_t; int32_t *out_face; float *out_uv; uint32_t *out_status;
+};
+int launch_mesh_raycast(const RaycastLaunch &a, hipStream_t st);
 // ---- sls_icp.hip (the arguments are checked by the caller, sls_api.hip; init_pose12: host memory) ------------------
 size_t cloud_icp_scratch_bytes(int Ms, int Mt);
 int launch_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_xyz, const float *target_normals,

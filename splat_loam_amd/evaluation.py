@@ -21,6 +21,12 @@ and raises NotImplementedError for (eval_utils.py:93-94, 131-133) — per-vertex
 per-reference-point distances to the mesh, coloured by `error_colors` (sls_error_colors: green, yellow at half the
 truncation, red at or beyond it).  The defaults of both are off and change nothing.
 
+`cast_rays` is the other geometric query: the FIRST face a ray hits (sls_mesh_raycast: a second traversal of that same
+index of triangles, ray against box; include/sls_raycast_math.h: the watertight test of Woop, Benthin and Wald, so no
+ray passes between two faces that share an edge), `mesh_ray_index` the index built once for many casts, and
+`render_mesh` the range image of a mesh from a camera in the pixel convention of `renderer.depth_to_points`.  No BVH,
+no signed distance, rays cast in the caller's order; not compared against Open3D's `RaycastingScene.cast_rays`.
+
 Not done here: reading files (splat_loam_amd/ply_io.py: load_point_cloud, load_mesh; tools/eval_recon.py puts the two
 together).
 """
@@ -891,6 +897,163 @@ def error_colors(dist2: torch.Tensor, truncation: float) -> torch.Tensor:
         _abi.check(lib.sls_error_colors(M, dist2.data_ptr() if M else None, t, rgb.data_ptr() if M else None, st),
                    "sls_error_colors")
     return rgb
+
+
+class MeshRayIndex:
+    """What `mesh_ray_index` returns: the mesh as the native call reads it (`vertices` (V,3) float32, `faces` (F,3) int32,
+    contiguous device tensors) and the device buffer that holds the index of its triangles.  Valid for exactly these two
+    tensors' contents: cast against it, do not write to them."""
+    __slots__ = ("vertices", "faces", "buffer", "address", "nbytes", "status")
+
+    def __init__(self, vertices, faces, buffer, address, nbytes, status):
+        self.vertices, self.faces, self.buffer, self.address, self.nbytes, self.status = vertices, faces, buffer, address, nbytes, status
+
+
+def _ray_index_enqueue(lib, vertices, faces, st) -> MeshRayIndex:
+    """sls_mesh_rayindex_build without a host read; `status` (4,) int32 stays on the device."""
+    dev = vertices.device
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if V < 1 or F < 1:
+        raise ValueError("the mesh needs at least one vertex and one face")
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    buffer, address, nbytes = _scratch(lib.sls_mesh_rayindex_bytes(V, F), dev)
+    _abi.check(lib.sls_mesh_rayindex_build(V, vertices.data_ptr(), F, faces.data_ptr(), address, nbytes, status.data_ptr(), st),
+               "sls_mesh_rayindex_build")
+    return MeshRayIndex(vertices, faces, buffer, address, nbytes, status)
+
+
+def mesh_ray_index(vertices: torch.Tensor, faces: torch.Tensor) -> MeshRayIndex:
+    """The index of a mesh's triangles for `cast_rays(index=)` and `render_mesh(index=)`: built once (one native call,
+    sls_mesh_rayindex_build: the index `point_to_mesh` sweeps), cast against any number of times.  One host read (the
+    status words).  ValueError: a face with a vertex index outside the vertices or with a non-finite vertex; an empty
+    mesh."""
+    vertices, faces = _mesh(vertices, faces)
+    lib = _abi.lib()
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        index = _ray_index_enqueue(lib, vertices, faces, torch.cuda.current_stream(dev).cuda_stream)
+        _mesh_distance_status(index.status.cpu().tolist(), "mesh_ray_index")    # the one host read
+    return index
+
+
+def _check_t_range(t_min, t_max):
+    try:
+        lo, hi = ctypes.c_float(float(t_min)).value, ctypes.c_float(float(t_max)).value   # what the native call will see
+    except (TypeError, ValueError):
+        raise ValueError("t_min and t_max must be numbers") from None
+    if not lo >= 0.0:
+        raise ValueError("t_min must not be negative or NaN")
+    if not hi >= lo:
+        raise ValueError("t_max must not be below t_min or NaN")
+    return lo, hi
+
+
+def _use_index(index, vertices, faces) -> MeshRayIndex:
+    if not isinstance(index, MeshRayIndex):
+        raise TypeError("index must come from mesh_ray_index")
+    if index.vertices.shape != vertices.shape or index.faces.shape != faces.shape or index.vertices.device != vertices.device:
+        raise ValueError("the index was built for another mesh")
+    return index
+
+
+def _cast_enqueue(lib, index: MeshRayIndex, origins, directions, t_min: float, t_max: float, want_face: bool, want_uv: bool, st):
+    """sls_mesh_raycast without a host read: (t (M,), face (M,) | None, uv (M,2) | None, status (4,) int32)."""
+    dev = index.vertices.device
+    V, F, M = int(index.vertices.shape[0]), int(index.faces.shape[0]), int(origins.shape[0])
+    t = torch.empty((M,), dtype=torch.float32, device=dev)
+    face = torch.empty((M,), dtype=torch.int32, device=dev) if want_face else None
+    uv = torch.empty((M, 2), dtype=torch.float32, device=dev) if want_uv else None
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    _abi.check(lib.sls_mesh_raycast(V, index.vertices.data_ptr(), F, index.faces.data_ptr(), index.address, index.nbytes, M,
+                                    origins.data_ptr() if M else None, directions.data_ptr() if M else None, t_min, t_max,
+                                    t.data_ptr() if M else None, face.data_ptr() if (want_face and M) else None,
+                                    uv.data_ptr() if (want_uv and M) else None, status.data_ptr(), st), "sls_mesh_raycast")
+    return t, face, uv, status
+
+
+def cast_rays(origins: torch.Tensor, directions: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, t_min: float = 0.0,
+              t_max: float = math.inf, return_face: bool = True, return_uv: bool = False, index: MeshRayIndex = None):
+    """The first hit of every ray `origins[i] + t directions[i]` (both (M,3); a direction need not be unit) on the triangle
+    mesh within `t_min <= t <= t_max`: `t` (M,) float32, +inf on a miss; with `return_face` (the default) also `face` (M,)
+    int32, the lowest face index among hits of equal t bits, -1 on a miss; with `return_uv` also `uv` (M,2) float32, the
+    barycentric weights of that face's second and third vertex.  Returned as `t`, `(t, face)`, `(t, uv)` or
+    `(t, face, uv)`.  Both sides of a face hit.
+
+    The values are the bits of include/sls_raycast_math.h compiled for the host for (ray, returned face): the watertight
+    test of Woop, Benthin and Wald, under which no ray passes between two faces that share an edge or a vertex, and a
+    ray exactly through one hits every face that shares it.  A ray with a non-finite component or a zero direction (the
+    largest |component| below 2^-100) misses.  `index=mesh_ray_index(vertices, faces)` casts against an index built
+    before; without it the index is built by this call.  One host read (the status words), no float atomics: the same
+    input gives the same bits on every run.
+
+    It is not a BVH: the faces are indexed in the curve order of their centroids, in runs of 32 whose boxes bound all
+    three vertices, and 64 consecutive rays share one walk over the boxes — coherent rays (a range image) share most of
+    what they visit, incoherent ones list many boxes per wave and are slow, though exact.  Rays are cast in the caller's
+    order, not sorted.  There is no signed distance, and t on a sliver is as good as float32 edge functions make it
+    (DESIGN.md section 7).  Device tensors only.
+    ValueError: a face with a vertex index outside the vertices or with a non-finite vertex; an empty mesh; a bad range."""
+    origins, directions = _cloud(origins, "origins"), _cloud(directions, "directions")
+    vertices, faces = _mesh(vertices, faces)
+    if origins.shape != directions.shape:
+        raise ValueError("origins and directions must have the same shape")
+    if origins.device != vertices.device or directions.device != vertices.device:
+        raise ValueError("the rays and the mesh must live on the same device")
+    lo, hi = _check_t_range(t_min, t_max)
+    lib = _abi.lib()
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        index = _ray_index_enqueue(lib, vertices, faces, st) if index is None else _use_index(index, vertices, faces)
+        t, face, uv, status = _cast_enqueue(lib, index, origins, directions, lo, hi, bool(return_face), bool(return_uv), st)
+        _mesh_distance_status(status.cpu().tolist(), "cast_rays")               # the one host read
+    res = (t,) + ((face,) if return_face else ()) + ((uv,) if return_uv else ())
+    return res[0] if len(res) == 1 else res
+
+
+def _render_mesh_enqueue(lib, index: MeshRayIndex, col_half, row_half, cam_to_world, t_max: float, st):
+    """The range image of the indexed mesh without a host read.  col_half (W,2) / row_half (H,2): the half-pixel ray tables
+    (cos, sin of azimuth / elevation); cam_to_world: (4,4) float32 device tensor, sensor frame -> the mesh's frame.
+    (range (H,W), face (H,W) int32, normal (3,H,W) in the sensor frame, status (4,) int32)."""
+    W, H = int(col_half.shape[0]), int(row_half.shape[0])
+    ce, se = row_half[:, 0:1], row_half[:, 1:2]
+    rays = torch.stack([col_half[None, :, 0] * ce, col_half[None, :, 1] * ce, se.expand(H, W)], dim=-1).reshape(-1, 3)
+    R = cam_to_world[:3, :3]
+    directions = (rays @ R.T).contiguous()
+    origins = cam_to_world[:3, 3].expand(H * W, 3).contiguous()
+    t, face, _, status = _cast_enqueue(lib, index, origins, directions, 0.0, t_max, True, False, st)
+    hit = face >= 0
+    tri = index.vertices[index.faces[face.clamp(min=0).long()].long()]          # (HW, 3, 3)
+    n = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    n = torch.nn.functional.normalize(n, dim=1)
+    n = torch.where(((n * directions).sum(1, keepdim=True) > 0), -n, n)         # towards the sensor
+    n = torch.where(hit[:, None], n @ R, torch.zeros_like(n))                   # R^T n: back to the sensor frame
+    rng = torch.where(hit, t, torch.zeros_like(t))
+    return rng.view(H, W), face.view(H, W), n.T.reshape(3, H, W).contiguous(), status
+
+
+def render_mesh(vertices: torch.Tensor, faces: torch.Tensor, camera, t_max: float = math.inf, index: MeshRayIndex = None) -> dict:
+    """What a spherical sensor at `camera` (a `scene.Camera`: world_view_transform, projection_matrix, image size) sees of
+    the mesh: `{"range": (H,W) float32, "face": (H,W) int32, "normal": (3,H,W) float32}`.  The rays are the half-pixel rays
+    of the surface sampler and of `renderer.pixel_rays` — pixel (c, r) looks along image coordinate (c - 0.5, r - 0.5) —
+    built from `rasterizer.half_pixel_tables`, so `renderer.depth_to_points(camera, range[None])` puts every pixel back
+    on the face it hit.  `range` is the distance along the unit ray (0 on a miss, as in `surf_depth`), `face` the face
+    hit (-1), `normal` the unit geometric normal of that face in the SENSOR frame, turned towards the sensor (0).  One
+    `cast_rays` over H W rays (`index=`: against an index built before); one host read (the status words)."""
+    from .rasterizer import GaussianRasterizationSettings, get_camera, half_pixel_tables
+    vertices, faces = _mesh(vertices, faces)
+    _, hi = _check_t_range(0.0, t_max)
+    lib = _abi.lib()
+    dev = vertices.device
+    H, W = int(camera.image_height), int(camera.image_width)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        ce = get_camera(GaussianRasterizationSettings(H, W, 1.0, camera.world_view_transform, camera.projection_matrix), dev)
+        col_half, row_half = half_pixel_tables(ce, dev)
+        cam_to_world = torch.linalg.inv_ex(camera.world_view_transform.detach().to(dev, torch.float32).T).inverse
+        index = _ray_index_enqueue(lib, vertices, faces, st) if index is None else _use_index(index, vertices, faces)
+        rng, face, normal, status = _render_mesh_enqueue(lib, index, col_half, row_half, cam_to_world, hi, st)
+        _mesh_distance_status(status.cpu().tolist(), "render_mesh")             # the one host read
+    return {"range": rng, "face": face, "normal": normal}
 
 
 def _recon_metrics(reference, estimate, vertices, faces, exact: bool, error_map: bool, threshold, truncation_acc,

@@ -19,6 +19,7 @@ shares with `render()` (the maps, the back-projection) is pinned by goldens G1 /
 """
 from __future__ import annotations
 
+import math
 from pathlib import Path
 
 import numpy as np
@@ -399,6 +400,84 @@ def mesh_tsdf(graph_dir_or_yaml, voxel_size: float, trunc: float = None, *, min_
                "samples": int(points.shape[0]), "frame_ids": [fid for _, fid in used], "stage_ms": stage_ms, "volume": volume}
         return mesh + (_add_stages(det, cleaned, sampled.get("outlier"), sampled.get("cluster")),)
     return mesh
+
+
+# the options of `sample_surface` that `mesh_depth_check` takes: which keyframes, which of their pixels, which depth
+_DEPTH_CHECK_OPTIONS = ("kf_interval", "min_opacity", "max_depth_dist", "use_median_depth", "image_height", "image_width")
+
+
+@torch.no_grad()
+def mesh_depth_check(graph_dir_or_yaml, vertices: torch.Tensor, faces: torch.Tensor, *, truncation: float = 0.5, device="cuda", **options):
+    """Does a mesh agree, pixel by pixel, with what the map renders from its own keyframes?  A check that needs no reference
+    cloud: for every keyframe of the results graph (those `frames_to_sample` lists) the map is rendered as `sample_surface`
+    renders it, the sampler's validity rule is applied (`!(alpha < min_opacity) && !(dist > max_depth_dist)`), and the mesh
+    (world frame, e.g. `mesh_tsdf`'s) is rendered from the same pose by `evaluation.render_mesh`'s rays against an index
+    built once.  It catches what a cloud-free look cannot otherwise: surface the mesher extrapolated where nothing was
+    observed shows as valid pixels whose mesh range is off, and holes as valid pixels the mesh does not cover.
+
+    `**options`: `kf_interval`, `min_opacity`, `max_depth_dist`, `use_median_depth` (the map's depth is the median depth
+    instead of the expected one: depth_ratio 1 instead of 0), `image_height`, `image_width` — `sample_surface`'s, with its
+    defaults; any other name is a TypeError.  Returns dict(frame_ids, keyframes: per keyframe dict(valid: valid pixels,
+    covered: those of them the mesh covers, mean, median: of min(|range_mesh - depth_map|, truncation) over the covered
+    ones, None where there is none), and the same four over all keyframes' pixels together).  One host read, at the end:
+    the mesh's status words ride with the figures.  ValueError as `evaluation.cast_rays` raises it."""
+    from . import evaluation, traj_io
+    from .rasterizer import GaussianRasterizationSettings, _stream, get_camera, half_pixel_tables
+    for name in options:
+        if name not in _DEPTH_CHECK_OPTIONS:
+            raise TypeError(f"mesh_depth_check() got an unexpected keyword argument '{name}'")
+    defaults = sample_surface.__kwdefaults__
+    opt = {k: options.get(k, defaults[k]) for k in _DEPTH_CHECK_OPTIONS}
+    truncation = evaluation._check_truncation(truncation)
+    dev = _resolve_device("mesh_depth_check", device)
+    vertices, faces = evaluation._mesh(vertices, faces)
+    if vertices.device != dev:
+        raise ValueError(f"the mesh lives on {vertices.device}, not on {dev}")
+    path = Path(graph_dir_or_yaml)
+    graph_file = path / "graph.yaml" if path.is_dir() else path
+    graph_dir = graph_file.parent
+    graph = traj_io.read_graph(graph_file)
+    H, W = _image_size(graph_dir, opt["image_height"], opt["image_width"])
+    used = frames_to_sample(graph, opt["kf_interval"])
+    frames = {int(fr["id"]): fr for fr in graph["frames"]}
+    poses = [_pose44(frames[fid]["model_T_frame"]) for _, fid in used]
+    # sensor frame -> world, per keyframe: composed on the host in float64 from the view matrix the map is rendered with
+    Ms = [np.vstack([compose_cam_to_world(graph["models"][mi]["world_T_model"], np.linalg.inv(p).astype(np.float32)).reshape(3, 4),
+                     np.array([[0, 0, 0, 1]], np.float32)]) for (mi, _), p in zip(used, poses)]
+    Ms_dev = torch.from_numpy(np.ascontiguousarray(np.stack(Ms) if Ms else np.zeros((0, 4, 4), np.float32))).to(dev)
+    ratio = 1.0 if opt["use_median_depth"] else 0.0
+    lib = _abi.lib()
+    F = len(used)
+    stats = torch.zeros((F + 1, 4), dtype=torch.float64, device=dev)
+    residuals = torch.full((max(F, 1), H * W), float("nan"), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        index = evaluation._ray_index_enqueue(lib, vertices, faces, _stream(dev))
+        status = index.status
+        for i, fid, cam, allmap in _render_keyframes(graph_dir, graph, used, poses, H, W, dev):
+            ce = get_camera(GaussianRasterizationSettings(H, W, 1.0, cam.world_view_transform, cam.projection_matrix), dev)
+            col_half, row_half = half_pixel_tables(ce, dev)
+            rng, face, _, status = evaluation._render_mesh_enqueue(lib, index, col_half, row_half, Ms_dev[i], math.inf, _stream(dev))
+            alpha, dist = allmap[1], allmap[6]
+            valid = ~(alpha < opt["min_opacity"]) & ~(dist > opt["max_depth_dist"])
+            expected = torch.where(alpha > 0, allmap[0] / torch.where(alpha > 0, alpha, torch.ones_like(alpha)), allmap[0])
+            depth = expected * (1.0 - ratio) + allmap[5] * ratio
+            covered = valid & (face >= 0)
+            res = torch.where(covered, (rng - depth).abs().clamp(max=truncation), torch.full_like(rng, float("nan")))
+            residuals[i] = res.reshape(-1)
+            stats[i, 0], stats[i, 1] = valid.sum(), covered.sum()
+            stats[i, 2] = torch.nansum(res.double())
+            stats[i, 3] = torch.nanmedian(res)
+        stats[F, :3] = stats[:F, :3].sum(0)
+        stats[F, 3] = torch.nanmedian(residuals)
+        words = torch.cat([stats.reshape(-1), status.double()]).cpu().numpy()      # the one host read
+    evaluation._mesh_distance_status([int(w) for w in words[-4:]], "mesh_depth_check")
+    table = words[:-4].reshape(F + 1, 4)
+
+    def row(r):
+        n = int(r[1])
+        return {"valid": int(r[0]), "covered": n, "mean": float(r[2] / n) if n else None, "median": float(r[3]) if n else None}
+    return dict(row(table[F]), frame_ids=[fid for _, fid in used], keyframes=[dict(row(table[i]), frame_id=used[i][1]) for i in range(F)],
+                truncation=truncation)
 
 
 @torch.no_grad()
