@@ -787,6 +787,48 @@ int sls_mesh_raycast(int V, const float *vertices, int F, const int32_t *faces, 
                      const float *origins, const float *directions, float t_min, float t_max, float *out_t, int32_t *out_face,
                      float *out_uv, uint32_t *out_status, void *stream);
 
+/* ---- the signed distance to a mesh ---------------------------------------------------------------------------------------
+ * sls_mesh_distance with a SIGN (include/sls_signdist_math.h): |out_sdist| = sqrtf of the squared distance, out_face and
+ * out_closest are the bits sls_mesh_distance gives for the same input; the value is negative iff the query lies behind the
+ * angle-weighted pseudo-normal (Baerentzen and Aanaes 2005) of the feature of the returned face that the closest point
+ * lies on — out_feature (optional, one byte a query): 0 the face, 1-3 its edge AB, BC, CA, 4-6 its vertex a, b, c.  A point
+ * on the surface, or one whose feature has a zero row, gets the non-negative value.  The sign is correct for a closed,
+ * consistently oriented mesh and locally for an open oriented one; it is what the faces' orientation says, nothing is
+ * repaired.  It is not an inside / outside test by ray parity.
+ *
+ * sls_mesh_pseudonormals builds the three tables once for a mesh, nothing read back: out_face_normals (F x 3: the unit
+ * normals), out_edge_normals (F x 3 x 3: row 3 f + k is the sum of the unit normals of the faces sharing the undirected
+ * edge of corner k of face f, in ascending corner id), out_vertex_normals (V x 3: the sum of corner angle x unit normal
+ * over the corners at the vertex, in ascending corner id) — float64 sums, each component rounded once to float32; no
+ * float atomics: the same bytes on every run.
+ *   out_status (8 words): [faces with two equal indices or an index outside [0, V), those of them with an index outside,
+ *       faces with a non-finite vertex, zero-area faces, boundary edges (one owner), non-manifold edges (three or more),
+ *       edges with two owners that run the same way (inconsistent orientation), 1].  All of these faces have the zero
+ *       normal and are never dereferenced out of range.
+ *   scratch: sls_mesh_pseudonormals_scratch_bytes(V, F) bytes (0 for sizes out of range), 256-byte aligned.
+ * sls_mesh_signed_distance: the tables are those of the (V, vertices, F, faces) passed, which is not checked.
+ *   out_status (4 words): those of sls_mesh_distance.  scratch: sls_mesh_signed_distance_scratch_bytes(V, F, Mq).
+ *   Mq == 0 succeeds and writes only the status.
+ * sls_signed_stats: out_words (4 x uint64) = [n: the entries with |sd| < truncation, those of them with sd < 0, the bits of
+ *   the float64 sum of (double)sd over them in the fixed order of sls_nn_stats, M].  scratch: SLS_NN_STATS_SCRATCH_BYTES.
+ * sls_signed_error_colors: L = 255 for |sd| >= truncation, else (int)(|sd| / truncation * 256): sd >= 0 gives
+ *   (255, 255 - L, 255 - L), white to red; sd < 0 gives (255 - L, 255 - L, 255), white to blue; NaN (0, 0, 0).
+ * All pointers DEVICE.  Before anything is enqueued: SLS_E_ARG for sizes out of range, a null pointer other than the
+ * optional outputs, a scratch that is not 256-byte aligned, a NaN truncation (stats) or one that is not finite and > 0
+ * (colours); SLS_E_SCRATCH for too small a scratch. */
+size_t sls_mesh_pseudonormals_scratch_bytes(int V, int F);
+int sls_mesh_pseudonormals(int V, const float *vertices, int F, const int32_t *faces, float *out_face_normals,
+                           float *out_edge_normals, float *out_vertex_normals, uint32_t *out_status, void *scratch,
+                           size_t scratch_bytes, void *stream);
+size_t sls_mesh_signed_distance_scratch_bytes(int V, int F, int Mq);
+int sls_mesh_signed_distance(int V, const float *vertices, int F, const int32_t *faces, const float *face_normals,
+                             const float *edge_normals, const float *vertex_normals, int Mq, const float *query_xyz,
+                             float *out_sdist, int32_t *out_face, float *out_closest, uint8_t *out_feature, uint32_t *out_status,
+                             void *scratch, size_t scratch_bytes, void *stream);
+int sls_signed_stats(int M, const float *sdist, float truncation, uint64_t *out_words, void *scratch, size_t scratch_bytes,
+                     void *stream);
+int sls_signed_error_colors(int M, const float *sdist, float truncation, uint8_t *out_rgb, void *stream);
+
 /* ---- the k nearest neighbours, outlier removal ---------------------------------------------------------------------
  * sls_nn_query with k answers per query (include/sls_outlier_math.h): query q's list is the min(k, Mt) smallest keys
  * (bits(d2) << 32 | original target index) over ALL targets, ascending — nearer first, then the lower index; a target

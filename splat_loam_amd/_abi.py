@@ -182,6 +182,13 @@ _PROTOS = {
     "sls_mesh_rayindex_build": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP, _VP]),
     "sls_mesh_raycast": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, C.c_size_t, C.c_int, _VP, _VP, C.c_float, C.c_float, _VP, _VP,
                                    _VP, _VP, _VP]),
+    "sls_mesh_pseudonormals_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sls_mesh_pseudonormals": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "sls_mesh_signed_distance_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sls_mesh_signed_distance": (C.c_int, [C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                           C.c_size_t, _VP]),
+    "sls_signed_stats": (C.c_int, [C.c_int, _VP, C.c_float, _VP, _VP, C.c_size_t, _VP]),
+    "sls_signed_error_colors": (C.c_int, [C.c_int, _VP, C.c_float, _VP, _VP]),
     "sls_nn_k_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "sls_nn_query_k": (C.c_int, [C.c_int, _VP, C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "sls_outlier_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -543,6 +543,73 @@ int sls_mesh_raycast(int V, const float *vertices, int F, const int32_t *faces, 
     return launch_mesh_raycast(a, (hipStream_t)stream);
 }
 
+size_t sls_mesh_pseudonormals_scratch_bytes(int V, int F) { return mesh_pseudonormals_scratch_bytes(V, F); }
+
+int sls_mesh_pseudonormals(int V, const float *vertices, int F, const int32_t *faces, float *out_face_normals,
+                           float *out_edge_normals, float *out_vertex_normals, uint32_t *out_status, void *scratch,
+                           size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(V >= 1 && V <= SLS_MESH_MAX_VERTICES, "V < 1 or above SLS_MESH_MAX_VERTICES");
+    SLS_REQUIRE(F >= 1 && F <= SLS_MESH_MAX_TRIANGLES, "F < 1 or above SLS_MESH_MAX_TRIANGLES");
+    SLS_REQUIRE(vertices && faces && out_face_normals && out_edge_normals && out_vertex_normals && out_status && scratch,
+                "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < mesh_pseudonormals_scratch_bytes(V, F)) {
+        set_error("sls_mesh_pseudonormals: scratch too small: %zu < %zu", scratch_bytes, mesh_pseudonormals_scratch_bytes(V, F));
+        return SLS_E_SCRATCH;
+    }
+    return launch_mesh_pseudonormals(V, vertices, F, faces, out_face_normals, out_edge_normals, out_vertex_normals, out_status,
+                                     scratch, (hipStream_t)stream);
+}
+
+size_t sls_mesh_signed_distance_scratch_bytes(int V, int F, int Mq) { return mesh_signed_distance_scratch_bytes(V, F, Mq); }
+
+int sls_mesh_signed_distance(int V, const float *vertices, int F, const int32_t *faces, const float *face_normals,
+                             const float *edge_normals, const float *vertex_normals, int Mq, const float *query_xyz,
+                             float *out_sdist, int32_t *out_face, float *out_closest, uint8_t *out_feature, uint32_t *out_status,
+                             void *scratch, size_t scratch_bytes, void *stream)
+{
+    SLS_REQUIRE(V >= 1, "V < 1: the mesh has no vertex");
+    SLS_REQUIRE(F >= 1, "F < 1: the mesh has no face");
+    SLS_REQUIRE(Mq >= 0, "negative Mq");
+    SLS_REQUIRE(vertices && faces && face_normals && edge_normals && vertex_normals && out_status && scratch &&
+                ((query_xyz && out_sdist) || Mq == 0), "null pointer");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < mesh_signed_distance_scratch_bytes(V, F, Mq)) {
+        set_error("sls_mesh_signed_distance: scratch too small: %zu < %zu", scratch_bytes, mesh_signed_distance_scratch_bytes(V, F, Mq));
+        return SLS_E_SCRATCH;
+    }
+    SignedDistanceLaunch a{};
+    a.V = V; a.vertices = vertices; a.F = F; a.faces = faces;
+    a.face_n = face_normals; a.edge_n = edge_normals; a.vertex_n = vertex_normals;
+    a.Mq = Mq; a.query_xyz = query_xyz;
+    a.out_sdist = out_sdist; a.out_face = out_face; a.out_closest = out_closest; a.out_feature = out_feature;
+    a.out_status = out_status; a.scratch = scratch;
+    return launch_mesh_signed_distance(a, (hipStream_t)stream);
+}
+
+int sls_signed_stats(int M, const float *sdist, float truncation, uint64_t *out_words, void *scratch, size_t scratch_bytes,
+                     void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE((sdist || M == 0) && out_words && scratch, "null pointer");
+    SLS_REQUIRE(truncation == truncation, "NaN truncation");
+    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
+    if (scratch_bytes < (size_t)SLS_NN_STATS_SCRATCH_BYTES) {
+        set_error("sls_signed_stats: scratch too small: %zu < %d", scratch_bytes, SLS_NN_STATS_SCRATCH_BYTES);
+        return SLS_E_SCRATCH;
+    }
+    return launch_signed_stats(M, sdist, truncation, out_words, scratch, (hipStream_t)stream);
+}
+
+int sls_signed_error_colors(int M, const float *sdist, float truncation, uint8_t *out_rgb, void *stream)
+{
+    SLS_REQUIRE(M >= 0, "negative M");
+    SLS_REQUIRE((sdist && out_rgb) || M == 0, "null pointer");
+    SLS_REQUIRE(truncation > 0.0f && truncation <= 3.4028234e38f, "truncation must be finite and > 0");
+    return launch_signed_error_colors(M, sdist, truncation, out_rgb, (hipStream_t)stream);
+}
+
 size_t sls_nn_k_scratch_bytes(int Mt, int Mq, int k) { return nn_k_scratch_bytes(Mt, Mq, k); }
 
 int sls_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_xyz, int k, float *out_dist2, int32_t *out_index,

@@ -133,6 +133,18 @@ __device__ __forceinline__ void count_degenerate(int deg, uint32_t *degenerate, 
     }
 }
 
+// the first position of the n ascending keys that holds a key >= v (n where there is none): where vertex v's run of
+// sorted corners starts (sls_mesh.hip: the vertex normals; sls_signdist.hip: the vertex pseudo-normals)
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *__restrict__ keys, uint32_t n, uint32_t v)
+{
+    uint32_t lo = 0u, hi = n;                       // the position lies in [lo, hi]
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < v) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
+
 // the sorted directed pair (a, b) at position p as one word: a in the high half
 __device__ __forceinline__ uint64_t pair_key(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb, uint32_t p)
 {

@@ -267,6 +267,20 @@ struct RaycastLaunch {
     float *out_t; int32_t *out_face; float *out_uv; uint32_t *out_status;
 };
 int launch_mesh_raycast(const RaycastLaunch &a, hipStream_t st);
+// ---- sls_signdist.hip: the signed distance to a mesh (the arguments are checked by the caller, sls_api.hip) ---------
+size_t mesh_pseudonormals_scratch_bytes(int V, int F);
+int launch_mesh_pseudonormals(int V, const float *vertices, int F, const int32_t *faces, float *out_face_normals,
+                              float *out_edge_normals, float *out_vertex_normals, uint32_t *out_status, void *scratch, hipStream_t st);
+size_t mesh_signed_distance_scratch_bytes(int V, int F, int Mq);
+// Mq == 0: only the status is written.  out_face, out_closest and out_feature may be null
+struct SignedDistanceLaunch {
+    int V; const float *vertices; int F; const int32_t *faces; const float *face_n, *edge_n, *vertex_n;
+    int Mq; const float *query_xyz;
+    float *out_sdist; int32_t *out_face; float *out_closest; uint8_t *out_feature; uint32_t *out_status; void *scratch;
+};
+int launch_mesh_signed_distance(const SignedDistanceLaunch &a, hipStream_t st);
+int launch_signed_stats(int M, const float *sdist, float truncation, uint64_t *out_words, void *scratch, hipStream_t st);
+int launch_signed_error_colors(int M, const float *sdist, float truncation, uint8_t *out_rgb, hipStream_t st);
 // ---- sls_icp.hip (the arguments are checked by the caller, sls_api.hip; init_pose12: host memory) ------------------
 size_t cloud_icp_scratch_bytes(int Ms, int Mt);
 int launch_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_xyz, const float *target_normals,
@@ -336,6 +350,8 @@ int launch_mesh_filter(int V, const float *vertices, int T, const int32_t *faces
 size_t mesh_normals_scratch_bytes(int V, int T);
 int launch_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
                                hipStream_t st);
+// its sort of the 3 T corners by vertex (T >= 1; scratch: mesh_normals_scratch_bytes), which sls_signdist.hip shares
+int mesh_corner_sort(int V, int T, const int32_t *faces, void *scratch, const uint32_t **keys, const uint32_t **vals, hipStream_t st);
 // ---- sls_simplify.hip (the arguments are checked by the caller, sls_api.hip) ---------------------------------------
 size_t mesh_simplify_scratch_bytes(int V, int T);
 int launch_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces, double voxel_size, int contraction,

@@ -528,8 +528,8 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_normals_kernel(uint32_t V, 
     const size_t v = (size_t)blockIdx.x * kMeshThreads + threadIdx.x;
     if (v >= V) return;
     uint32_t lo = 0u, hi = n;                       // the first position with keys >= v lies in [lo, hi]
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
+    while (lo < hi) {                               // (lower_bound_u32, sls_geom.hpp, is this walk; calling it here changes
+        const uint32_t mid = lo + ((hi - lo) >> 1); // this kernel's instructions, so the kernel keeps its own text)
         if (keys[mid] < (uint32_t)v) lo = mid + 1u; else hi = mid;
     }
     float s[3] = { 0.0f, 0.0f, 0.0f }, nv[3];
@@ -552,13 +552,11 @@ size_t mesh_normals_scratch_bytes(int V, int T)
     return mesh_sizes_ok(V, T) ? mesh_sort_layout(3 * (size_t)T, nullptr).total : 0;
 }
 
-int launch_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
-                               hipStream_t st)
+// The 3 T corners sorted by vertex (T >= 1): *keys the vertex of every sorted position (V for a corner of a degenerate
+// triangle, behind every vertex), *vals its corner id 3 t + c, ascending within a vertex.  Both point into the scratch
+// (mesh_normals_scratch_bytes).  sls_signdist.hip sums its vertex pseudo-normals over the same runs.
+int mesh_corner_sort(int V, int T, const int32_t *faces, void *scratch, const uint32_t **keys, const uint32_t **vals, hipStream_t st)
 {
-    if (T == 0) {
-        SLS_HIP_CHECK(hipMemsetAsync(out_normals, 0, 3 * sizeof(float) * (size_t)V, st));
-        return SLS_OK;
-    }
     const MeshSortScratch s = mesh_sort_layout(3 * (size_t)T, scratch);
     const uint32_t n = 3u * (uint32_t)T;
     hipLaunchKernelGGL(mesh_hdr_kernel, dim3(1), dim3(64), 0, st, s.hdr, n);
@@ -569,8 +567,23 @@ int launch_mesh_vertex_normals(int V, const float *vertices, int T, const int32_
     const int rc = radix_sort_pairs_u32(s.keys, s.vals, s.keys_tmp, s.vals_tmp, s.hdr + MH_COUNT, n, sls_mesh_index_bits(V + 1), s.sort,
                                         s.sort_bytes, &which, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(mesh_normals_kernel, grid_for((size_t)V, kMeshThreads), dim3(kMeshThreads), 0, st, (uint32_t)V, n, vertices, faces,
-                       (const uint32_t *)(which ? s.keys_tmp : s.keys), (const uint32_t *)(which ? s.vals_tmp : s.vals), out_normals);
+    *keys = which ? s.keys_tmp : s.keys;
+    *vals = which ? s.vals_tmp : s.vals;
+    return SLS_OK;
+}
+
+int launch_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *faces, float *out_normals, void *scratch,
+                               hipStream_t st)
+{
+    if (T == 0) {
+        SLS_HIP_CHECK(hipMemsetAsync(out_normals, 0, 3 * sizeof(float) * (size_t)V, st));
+        return SLS_OK;
+    }
+    const uint32_t *keys = nullptr, *vals = nullptr;
+    const int rc = mesh_corner_sort(V, T, faces, scratch, &keys, &vals, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mesh_normals_kernel, grid_for((size_t)V, kMeshThreads), dim3(kMeshThreads), 0, st, (uint32_t)V, 3u * (uint32_t)T,
+                       vertices, faces, keys, vals, out_normals);
     SLS_LAUNCH_CHECK("mesh_normals_kernel");
     return SLS_OK;
 }

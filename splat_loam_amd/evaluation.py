@@ -14,7 +14,9 @@ Open3D is not a dependency: voxel_down_sample and sample_points_uniformly are re
 here, and pinned against NumPy restatements (tests/cloud_ref.py), not against Open3D itself.
 
 `point_to_mesh` is the exact distance of points to a triangle mesh (sls_mesh_distance: the same box sweep over an index
-of triangles, include/sls_meshdist_math.h) — unsigned, no BVH, not compared against Open3D's RaycastingScene.  With it
+of triangles, include/sls_meshdist_math.h) — unsigned, no BVH, not compared against Open3D's RaycastingScene;
+`signed_distance` gives it a sign from the mesh's angle-weighted pseudo-normals (`mesh_pseudonormals`,
+include/sls_signdist_math.h), and `evaluate_recon(signed=True)` reports the signed mean: bias, not only error.  With it
 `evaluate_recon(completeness="exact")` measures every reference point against the mesh itself, not against samples
 of it, and `error_map=True` returns where the mesh is wrong: the error map the reference's `evaluate_recon` announces
 and raises NotImplementedError for (eval_utils.py:93-94, 131-133) — per-vertex distances to the reference cloud and
@@ -25,7 +27,7 @@ truncation, red at or beyond it).  The defaults of both are off and change nothi
 index of triangles, ray against box; include/sls_raycast_math.h: the watertight test of Woop, Benthin and Wald, so no
 ray passes between two faces that share an edge), `mesh_ray_index` the index built once for many casts, and
 `render_mesh` the range image of a mesh from a camera in the pixel convention of `renderer.depth_to_points`.  No BVH,
-no signed distance, rays cast in the caller's order; not compared against Open3D's `RaycastingScene.cast_rays`.
+rays cast in the caller's order; not compared against Open3D's `RaycastingScene.cast_rays`.
 
 Not done here: reading files (splat_loam_amd/ply_io.py: load_point_cloud, load_mesh; tools/eval_recon.py puts the two
 together).
@@ -848,7 +850,7 @@ def point_to_mesh(points: torch.Tensor, vertices: torch.Tensor, faces: torch.Ten
     decided by float32 bits, then by the lower index.  One native call (sls_mesh_distance), one host read (the status
     words), no float atomics: the same input gives the same bits on every run.
 
-    It is not a signed distance (that needs pseudo-normals at edges and vertices) and there is no BVH: the faces are
+    The signed twin is `signed_distance`.  There is no BVH: the faces are
     indexed in the curve order of their centroids, in runs of 32 whose boxes bound all three vertices, so a few huge
     triangles among many small ones make their runs' boxes loose — that costs time, never exactness.  Device tensors
     only; the points must be finite (not checked; every access stays inside the buffers).
@@ -896,6 +898,157 @@ def error_colors(dist2: torch.Tensor, truncation: float) -> torch.Tensor:
         rgb = torch.empty((M, 3), dtype=torch.uint8, device=dist2.device)
         _abi.check(lib.sls_error_colors(M, dist2.data_ptr() if M else None, t, rgb.data_ptr() if M else None, st),
                    "sls_error_colors")
+    return rgb
+
+
+class MeshPseudoNormals:
+    """What `mesh_pseudonormals` returns: the mesh as the native call reads it (`vertices` (V,3) float32, `faces` (F,3)
+    int32, contiguous device tensors), the three tables of include/sls_signdist_math.h — `face_normals` (F,3) the unit
+    normals, `edge_normals` (F,3,3) the sum of the unit normals of the faces sharing the edge of every corner,
+    `vertex_normals` (V,3) the angle-weighted sum over the corners at every vertex, all float32 — and the device tensor
+    `status` (8,) int32.  Valid for exactly these two tensors' contents: do not write to them."""
+    __slots__ = ("vertices", "faces", "face_normals", "edge_normals", "vertex_normals", "status")
+
+    def __init__(self, vertices, faces, face_normals, edge_normals, vertex_normals, status):
+        self.vertices, self.faces, self.status = vertices, faces, status
+        self.face_normals, self.edge_normals, self.vertex_normals = face_normals, edge_normals, vertex_normals
+
+
+def _pseudonormals_enqueue(lib, vertices, faces, st) -> MeshPseudoNormals:
+    """sls_mesh_pseudonormals without a host read; `status` (8,) int32 stays on the device."""
+    dev = vertices.device
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if V < 1 or F < 1:
+        raise ValueError("the mesh needs at least one vertex and one face")
+    face_n = torch.empty((F, 3), dtype=torch.float32, device=dev)
+    edge_n = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+    vertex_n = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    status = torch.empty((8,), dtype=torch.int32, device=dev)
+    _, aligned, nbytes = scratch = _scratch(lib.sls_mesh_pseudonormals_scratch_bytes(V, F), dev)
+    _abi.check(lib.sls_mesh_pseudonormals(V, vertices.data_ptr(), F, faces.data_ptr(), face_n.data_ptr(), edge_n.data_ptr(),
+                                          vertex_n.data_ptr(), status.data_ptr(), aligned, nbytes, st), "sls_mesh_pseudonormals")
+    del scratch
+    return MeshPseudoNormals(vertices, faces, face_n, edge_n, vertex_n, status)
+
+
+def _pseudonormals_status(words, what: str) -> dict:
+    """The details of the eight status words; ValueError for the two kinds of face no distance is defined for."""
+    w = [int(x) & 0xFFFFFFFF for x in words[:8]]
+    if w[1]:
+        raise ValueError(f"{what}: {w[1]} faces have a vertex index outside the vertices")
+    if w[2]:
+        raise ValueError(f"{what}: {w[2]} faces have a vertex with a non-finite coordinate")
+    return {"degenerate_faces": w[0], "zero_area_faces": w[3], "boundary_edges": w[4], "nonmanifold_edges": w[5],
+            "inconsistent_edges": w[6]}
+
+
+def mesh_pseudonormals(vertices: torch.Tensor, faces: torch.Tensor, return_details: bool = False):
+    """The pseudo-normal tables of a mesh for `signed_distance(pseudonormals=)`: built once (one native call,
+    sls_mesh_pseudonormals: a thread per face, one stable sort of the corners by edge, the corner-by-vertex sort of
+    `mesh_ops.vertex_normals`, float64 sums in ascending corner id — no float atomics, the same bytes on every run), used
+    any number of times.  One host read (the status words).  With `return_details` also a dict of facts about the mesh,
+    none of them an error: `degenerate_faces` (two equal indices), `zero_area_faces`, `boundary_edges` (one owner),
+    `nonmanifold_edges` (three or more), `inconsistent_edges` (two owners that run the same way: a flipped face).
+    Nothing is repaired: a mesh with flipped faces gets the sign its faces say.
+    ValueError: a face with a vertex index outside the vertices or with a non-finite vertex; an empty mesh."""
+    vertices, faces = _mesh(vertices, faces)
+    lib = _abi.lib()
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        pn = _pseudonormals_enqueue(lib, vertices, faces, torch.cuda.current_stream(dev).cuda_stream)
+        details = _pseudonormals_status(pn.status.cpu().tolist(), "mesh_pseudonormals")      # the one host read
+    return (pn, details) if return_details else pn
+
+
+def _use_pseudonormals(pn, vertices, faces) -> MeshPseudoNormals:
+    if not isinstance(pn, MeshPseudoNormals):
+        raise TypeError("pseudonormals must come from mesh_pseudonormals")
+    if pn.vertices.shape != vertices.shape or pn.faces.shape != faces.shape or pn.vertices.device != vertices.device:
+        raise ValueError("the pseudo-normals were built for another mesh")
+    return pn
+
+
+def _signed_enqueue(lib, pn: MeshPseudoNormals, points, want_face: bool, want_closest: bool, want_feature: bool, st):
+    """sls_mesh_signed_distance without a host read: (sdist (M,), face (M,) | None, closest (M,3) | None, feature (M,) uint8
+    | None, status (4,) int32, scratch) — the scratch serves a following sls_signed_stats."""
+    dev = pn.vertices.device
+    V, F, M = int(pn.vertices.shape[0]), int(pn.faces.shape[0]), int(points.shape[0])
+    sdist = torch.empty((M,), dtype=torch.float32, device=dev)
+    face = torch.empty((M,), dtype=torch.int32, device=dev) if want_face else None
+    closest = torch.empty((M, 3), dtype=torch.float32, device=dev) if want_closest else None
+    feature = torch.empty((M,), dtype=torch.uint8, device=dev) if want_feature else None
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    scratch = _scratch(lib.sls_mesh_signed_distance_scratch_bytes(V, F, M), dev)
+    _abi.check(lib.sls_mesh_signed_distance(V, pn.vertices.data_ptr(), F, pn.faces.data_ptr(), pn.face_normals.data_ptr(),
+                                            pn.edge_normals.data_ptr(), pn.vertex_normals.data_ptr(), M,
+                                            points.data_ptr() if M else None, sdist.data_ptr() if M else None,
+                                            face.data_ptr() if (want_face and M) else None,
+                                            closest.data_ptr() if (want_closest and M) else None,
+                                            feature.data_ptr() if (want_feature and M) else None, status.data_ptr(), scratch[1],
+                                            scratch[2], st), "sls_mesh_signed_distance")
+    return sdist, face, closest, feature, status, scratch
+
+
+def signed_distance(points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, return_face: bool = False,
+                    return_closest: bool = False, return_feature: bool = False, pseudonormals: MeshPseudoNormals = None):
+    """The exact SIGNED distance of every row of `points` (M,3) to the triangle mesh: `sdist` (M,) float32, whose magnitude is
+    sqrt of `point_to_mesh`'s dist2, bit for bit, and which is negative iff the point lies BEHIND the mesh: behind the
+    angle-weighted pseudo-normal (Baerentzen and Aanaes 2005) of the part of the nearest face the closest point lies on —
+    the face, one of its edges, one of its vertices (include/sls_signdist_math.h).  With `return_face` also `face` (M,)
+    int32 and with `return_closest` `closest` (M,3), both `point_to_mesh`'s; with `return_feature` `feature` (M,) uint8:
+    0 the face, 1-3 its edge AB, BC, CA, 4-6 its vertex a, b, c.  Returned as `sdist` or a tuple in that order.
+
+    Positive means the point lies on the side the faces look to (counter-clockwise vertices seen from there).  The sign
+    is right for every closed, consistently oriented mesh and locally for an open oriented one, which the sign of the
+    nearest face's own normal is not: around a thin wedge that is wrong for one query in eight.  A point on the surface,
+    or on a feature whose faces cancel, gets the non-negative value.  `mesh_tsdf` and `mesh_poisson` emit oriented meshes
+    whose faces look to the observed, free-space side.
+
+    `pseudonormals=mesh_pseudonormals(vertices, faces)` uses tables built before; without it they are built by this call.
+    One host read either way (the two status tensors are read together), no float atomics: the same input gives the same
+    bits on every run.
+
+    It is not an inside / outside test by ray parity and no occupancy query, nothing repairs the orientation (a flipped
+    face gives the sign it says; `mesh_pseudonormals(return_details=True)` counts the evidence), it samples no volume,
+    and it is not compared against Open3D's `compute_signed_distance`, which signs by ray counting and is undefined on
+    the open meshes a LiDAR gives.  Device tensors only; the points must be finite.
+    ValueError: a face with a vertex index outside the vertices or with a non-finite vertex; an empty mesh."""
+    points = _cloud(points, "points")
+    vertices, faces = _mesh(vertices, faces)
+    if points.device != vertices.device:
+        raise ValueError("the points and the mesh must live on the same device")
+    lib = _abi.lib()
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        pn = _pseudonormals_enqueue(lib, vertices, faces, st) if pseudonormals is None else _use_pseudonormals(pseudonormals, vertices, faces)
+        sdist, face, closest, feature, status, _ = _signed_enqueue(lib, pn, points, bool(return_face), bool(return_closest),
+                                                                   bool(return_feature), st)
+        w = torch.cat([pn.status, status]).cpu().tolist()                      # the one host read
+    _pseudonormals_status(w[:8], "signed_distance")
+    _mesh_distance_status(w[8:12], "signed_distance")
+    res = (sdist,) + ((face,) if return_face else ()) + ((closest,) if return_closest else ()) + ((feature,) if return_feature else ())
+    return res[0] if len(res) == 1 else res
+
+
+def signed_error_colors(sdist: torch.Tensor, truncation: float) -> torch.Tensor:
+    """(M,3) uint8 RGB of signed distances (M,) at `truncation` metres (include/sls_signdist_math.h): L = 255 for
+    |sd| >= truncation, else int(|sd| / truncation * 256); positive (in front of the faces) (255, 255 - L, 255 - L), white
+    to red; negative (behind them) (255 - L, 255 - L, 255), white to blue; a NaN gives black.  One native call
+    (sls_signed_error_colors), no host read."""
+    if not isinstance(sdist, torch.Tensor) or not sdist.is_cuda:
+        raise RuntimeError("sdist must be a ROCm device tensor (libsls_hip.so); there is no CPU fallback")
+    if sdist.dim() != 1:
+        raise ValueError("sdist must be (M,)")
+    t = _check_truncation(truncation)
+    sdist = sdist.detach().float().contiguous()
+    M = int(sdist.shape[0])
+    lib = _abi.lib()
+    with torch.cuda.device(sdist.device):
+        st = torch.cuda.current_stream(sdist.device).cuda_stream
+        rgb = torch.empty((M, 3), dtype=torch.uint8, device=sdist.device)
+        _abi.check(lib.sls_signed_error_colors(M, sdist.data_ptr() if M else None, t, rgb.data_ptr() if M else None, st),
+                   "sls_signed_error_colors")
     return rgb
 
 
@@ -989,7 +1142,7 @@ def cast_rays(origins: torch.Tensor, directions: torch.Tensor, vertices: torch.T
     It is not a BVH: the faces are indexed in the curve order of their centroids, in runs of 32 whose boxes bound all
     three vertices, and 64 consecutive rays share one walk over the boxes — coherent rays (a range image) share most of
     what they visit, incoherent ones list many boxes per wave and are slow, though exact.  Rays are cast in the caller's
-    order, not sorted.  There is no signed distance, and t on a sliver is as good as float32 edge functions make it
+    order, not sorted.  t on a sliver is as good as float32 edge functions make it
     (DESIGN.md section 7).  Device tensors only.
     ValueError: a face with a vertex index outside the vertices or with a non-finite vertex; an empty mesh; a bad range."""
     origins, directions = _cloud(origins, "origins"), _cloud(directions, "directions")
@@ -1057,11 +1210,14 @@ def render_mesh(vertices: torch.Tensor, faces: torch.Tensor, camera, t_max: floa
 
 
 def _recon_metrics(reference, estimate, vertices, faces, exact: bool, error_map: bool, threshold, truncation_acc,
-                   truncation_com):
+                   truncation_com, signed: bool = False):
     """evaluate_recon's metric block where the completeness is exact or the error map is wanted: cloud_metrics' calls with
     sls_mesh_distance (reference points against the mesh, then the unchanged sls_nn_stats) and, for the map, one more
     sls_nn_query (the mesh's vertices against the reference cloud) and two sls_error_colors.  One host read: the eight
-    metric words and the four status words of sls_mesh_distance together.  (metrics, error map | None)"""
+    metric words and the four status words of sls_mesh_distance together.  With `signed` the reference points are measured
+    once more with the sign (sls_mesh_pseudonormals, sls_mesh_signed_distance, sls_signed_stats: the unsigned calls and
+    their bits stay as they are) and the four signed words and twelve more status words ride on that same read.
+    (metrics, error map | None, signed block | None)"""
     Mr, Me = int(reference.shape[0]), int(estimate.shape[0])
     lib = _abi.lib()
     dev = reference.device
@@ -1086,9 +1242,28 @@ def _recon_metrics(reference, estimate, vertices, faces, exact: bool, error_map:
             d_vert, _ = nearest(reference, vertices, return_index=False)
             emap = {"vertices": vertices, "vertex_dist2": d_vert, "vertex_colors": error_colors(d_vert, truncation_acc),
                     "points": reference, "point_dist2": d_mesh, "point_colors": error_colors(d_mesh, truncation_com)}
-        w = torch.cat([words, status.to(torch.int64)]).cpu().tolist()          # the one host read
+        read = [words, status.to(torch.int64)]
+        if signed:
+            t_com = _check_truncation(truncation_com)
+            pn = _pseudonormals_enqueue(lib, vertices, faces, st)
+            sdist, _, _, _, s_status, (_, s_aligned, s_nbytes) = _signed_enqueue(lib, pn, reference, False, False, False, st)
+            s_words = torch.empty((4,), dtype=torch.int64, device=dev)
+            _abi.check(lib.sls_signed_stats(Mr, sdist.data_ptr(), t_com, s_words.data_ptr(), s_aligned, s_nbytes, st),
+                       "sls_signed_stats")
+            if emap is not None:
+                emap["point_signed"] = sdist
+                emap["point_colors_signed"] = signed_error_colors(sdist, t_com)
+            read += [s_words, pn.status.to(torch.int64), s_status.to(torch.int64)]
+        w = torch.cat(read).cpu().tolist()                                     # the one host read
     _mesh_distance_status(w[8:12], "evaluate_recon")
-    return _metrics(w[:8], threshold, truncation_acc, truncation_com), emap
+    sblock = None
+    if signed:
+        details = _pseudonormals_status(w[16:24], "evaluate_recon")
+        _mesh_distance_status(w[24:28], "evaluate_recon")
+        n_s, behind = int(w[12]), int(w[13])
+        total = struct.unpack("<d", struct.pack("<q", w[14]))[0]
+        sblock = {"mean_m": total / n_s if n_s else math.nan, "share_behind": behind / n_s if n_s else math.nan, "n": n_s, **details}
+    return _metrics(w[:8], threshold, truncation_acc, truncation_com), emap, sblock
 
 
 ALIGN_MAX_POINTS = 200_000
@@ -1114,7 +1289,7 @@ def _align_vertices(reference: torch.Tensor, vertices: torch.Tensor, align) -> d
 def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces: torch.Tensor, down_sample_res: float = 0.02,
                    threshold: float = 0.2, truncation_acc: float = 0.5, truncation_com: float = 0.5,
                    crop_to_reference: bool = False, mesh_sample_point: int = 10_000_000, seed: int = 0, align=None,
-                   completeness: str = "sampled", error_map: bool = False) -> dict:
+                   completeness: str = "sampled", error_map: bool = False, signed: bool = False) -> dict:
     """The reference's `evaluate_recon` (utils/eval_utils.py:67-154) for a reference cloud and an estimated mesh already
     on the device, with its dictionary keys and units: sample `mesh_sample_point` points from the mesh, voxel-down-sample
     both clouds at `down_sample_res` (skipped where that is <= 0, as in the reference), then the metric block of
@@ -1149,11 +1324,26 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
     them, also with `crop_to_reference`), `vertex_dist2` (V,) their squared distances to the evaluated reference cloud
     (`nearest`), `vertex_colors` (V,3) uint8 = `error_colors(vertex_dist2, truncation_acc)`; `points` (the evaluated
     reference points), `point_dist2` their EXACT squared distances to the mesh, whatever `completeness` is, and
-    `point_colors` = `error_colors(point_dist2, truncation_com)`.  No further host read."""
+    `point_colors` = `error_colors(point_dist2, truncation_com)`.  No further host read.
+
+    `signed` (default False: nothing of what follows happens, the same calls, the same host reads, the same bits): True
+    measures the evaluated reference points against the mesh with `signed_distance` as well, whatever `completeness`
+    is, and adds the key "Signed": `mean_m`, the mean SIGNED distance over the points within `truncation_com` of the
+    mesh; `share_behind`, the fraction of them with a negative distance; `n`, their number; and the details of
+    `mesh_pseudonormals` (`degenerate_faces`, `zero_area_faces`, `boundary_edges`, `nonmanifold_edges`,
+    `inconsistent_edges`).  With `error_map=True` "ErrorMap" also gets `point_signed` (the signed distances) and
+    `point_colors_signed` = `signed_error_colors(point_signed, truncation_com)`.  No further host read: the new words
+    ride on the second one.  The unsigned search is not replaced, so the search runs twice.
+    What the sign means here: positive means the reference point lies on the side the faces look to.  For the output of
+    `mesh_tsdf` / `mesh_poisson` that is the observed, free-space side, so a POSITIVE mean says the mesh sits BEHIND the
+    true surface as the sensor saw it (a shrunk mesh), a negative one that it sits in front of it (an inflated one): bias
+    where the unsigned numbers only show error."""
     if completeness not in ("sampled", "exact"):
         raise ValueError('completeness must be "sampled" or "exact"')
     if not isinstance(error_map, bool):
         raise ValueError("error_map must be True or False")
+    if not isinstance(signed, bool):
+        raise ValueError("signed must be True or False")
     reference = _cloud(reference_points, "reference_points")
     vertices, faces = _mesh(vertices, faces)
     if reference.device != vertices.device:
@@ -1189,8 +1379,8 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
         if down:
             estimate = estimate[:_voxel_status(w[4:8], "evaluate_recon: the sampled mesh")]
             reference = reference[:_voxel_status(w[8:12], "evaluate_recon: the reference cloud")]
-    emap = None
-    if completeness == "sampled" and not error_map:
+    emap = sblock = None
+    if completeness == "sampled" and not error_map and not signed:
         m = cloud_metrics(reference, estimate, threshold=threshold, truncation_acc=truncation_acc,
                           truncation_com=truncation_com)                    # host read 2 of 2
     else:
@@ -1200,8 +1390,8 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
         if box is not None:                                                 # the faces the sampler keeps (closed box)
             inside = ((vertices >= box[:3]) & (vertices <= box[3:])).all(1)
             kept = faces[inside[faces.long()].all(1)].contiguous()          # (a host synchronisation: the boolean index)
-        m, emap = _recon_metrics(reference, estimate, vertices, kept, completeness == "exact", error_map, threshold,
-                                 truncation_acc, truncation_com)            # host read 2 of 2
+        m, emap, sblock = _recon_metrics(reference, estimate, vertices, kept, completeness == "exact", error_map, threshold,
+                                         truncation_acc, truncation_com, signed)   # host read 2 of 2
     out = {
         "MAE_accuracy (cm)": m["accuracy_m"] * 100, "MAE_completeness (cm)": m["completeness_m"] * 100,
         "Chamfer_L1 (cm)": m["chamfer_l1_m"] * 100, "Precision [Accuracy] (%)": m["precision"] * 100.0,
@@ -1213,4 +1403,6 @@ def evaluate_recon(reference_points: torch.Tensor, vertices: torch.Tensor, faces
         out["Alignment"] = alignment
     if emap is not None:
         out["ErrorMap"] = emap
+    if sblock is not None:
+        out["Signed"] = sblock
     return out

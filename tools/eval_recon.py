@@ -5,7 +5,7 @@ mesh, on the device (splat_loam_amd.evaluation.evaluate_recon), one JSON line wi
     python tools/eval_recon.py REFERENCE.ply MESH.ply [--down-sample-res 0.02] [--threshold 0.2] [--truncation-acc 0.5]
                                [--truncation-com 0.5] [--mesh-sample-point 10000000] [--seed 0] [--crop-to-reference]
                                [--align D [--align-iterations 30] [--align-method plane|point]]
-                               [--exact-completeness] [--error-map PREFIX]
+                               [--exact-completeness] [--error-map PREFIX] [--signed]
 
 REFERENCE.ply: binary little-endian PLY with `x y z` as float or double.  MESH.ply: binary little-endian PLY with a
 `vertex` element and one `face` element of triangles (`list uchar int vertex_indices`: what Open3D writes for a Poisson
@@ -19,7 +19,12 @@ reference_T_mesh), fitness, inlier_rmse, updates and the flags.  Without it noth
 nearest sample: the completeness then depends neither on --seed nor on --mesh-sample-point.  --error-map PREFIX writes
 PREFIX_accuracy.ply, the mesh with its vertices coloured by their distance to the reference cloud (red at
 --truncation-acc), and PREFIX_completeness.ply, the evaluated reference points coloured by their exact distance to the mesh
-(red at --truncation-com); green is good, yellow is half the truncation.  Without either nothing changes."""
+(red at --truncation-com); green is good, yellow is half the truncation.  Without either nothing changes.
+--signed adds "Signed": the mean SIGNED distance of the evaluated reference points to the mesh (evaluation.signed_distance;
+positive: the point lies in front of the faces — for a mesh of mesh_tsdf / mesh_poisson the observed side, so a positive
+mean says the mesh sits behind the true surface), the share of points behind the mesh, and the facts about the mesh the
+sign depends on; with --error-map also PREFIX_signed.ply, the reference points white on the surface, red in front of it,
+blue behind it.  Without it nothing changes."""
 import argparse
 import json
 import os
@@ -49,6 +54,7 @@ def main():
     ap.add_argument("--align-method", choices=("plane", "point"), default="plane")
     ap.add_argument("--exact-completeness", action="store_true")
     ap.add_argument("--error-map", default=None, metavar="PREFIX")
+    ap.add_argument("--signed", action="store_true")
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args()
     align = None
@@ -62,11 +68,14 @@ def main():
         reference, torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev), down_sample_res=a.down_sample_res,
         threshold=a.threshold, truncation_acc=a.truncation_acc, truncation_com=a.truncation_com,
         crop_to_reference=a.crop_to_reference, mesh_sample_point=a.mesh_sample_point, seed=a.seed, align=align,
-        completeness="exact" if a.exact_completeness else "sampled", error_map=a.error_map is not None)
+        completeness="exact" if a.exact_completeness else "sampled", error_map=a.error_map is not None,
+        signed=a.signed)
     if a.error_map is not None:
         em = res.pop("ErrorMap")
         ply_io.save_mesh(a.error_map + "_accuracy.ply", em["vertices"], faces, colors=em["vertex_colors"])
         ply_io.save_point_cloud(a.error_map + "_completeness.ply", em["points"], torch.zeros_like(em["points"]), em["point_colors"])
+        if a.signed:
+            ply_io.save_point_cloud(a.error_map + "_signed.ply", em["points"], torch.zeros_like(em["points"]), em["point_colors_signed"])
     if align is not None:
         al = res["Alignment"]
         al["target_T_source"] = al["target_T_source"][:3].reshape(-1).tolist()
