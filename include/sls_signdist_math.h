@@ -1,7 +1,7 @@
 /*
  * sls_signdist_math.h — the arithmetic of the SIGNED point-to-mesh distance (sls_mesh_pseudonormals,
  * sls_mesh_signed_distance, sls_signed_stats, sls_signed_error_colors), shared by the HIP kernels
- * (csrc/sls_signdist.hip) and by any CPU checker that wants to reproduce their results bit for bit
+ * (csrc/sls_signdist.hip, csrc/sls_metrics.hip) and by any CPU checker that wants to reproduce their results bit for bit
  * (tests/signdist_ref.py compiles this header for the host).
  *
  * The magnitude is the distance of include/sls_meshdist_math.h, untouched.  The SIGN is that of

@@ -448,6 +448,21 @@ int sls_knn_dist2_first(int M, int M_first, const float *xyz, float *out, void *
     return launch_knn(M, xyz, out, scratch, scratch_bytes, (hipStream_t)stream, M_first);
 }
 
+// What an entry point checks of the buffer it is lent — its scratch, or the ray casts' index: SLS_E_ARG unless it is
+// 256-byte aligned, then SLS_E_SCRATCH unless it holds `need` bytes.  who: the entry point's name, as SLS_REQUIRE prints it
+#define SLS_BUFFER_CHECK(who, what, ptr, have, need)                                                        \
+    do {                                                                                                    \
+        if (((uintptr_t)(ptr) & 255u) != 0) {                                                               \
+            set_error("%s: " what " not 256-byte aligned", who);                                            \
+            return SLS_E_ARG;                                                                               \
+        }                                                                                                   \
+        if ((have) < (size_t)(need)) {                                                                      \
+            set_error("%s: " what " too small: %zu < %zu", who, (size_t)(have), (size_t)(need));            \
+            return SLS_E_SCRATCH;                                                                           \
+        }                                                                                                   \
+    } while (0)
+#define SLS_SCRATCH(need) SLS_BUFFER_CHECK(__func__, "scratch", scratch, scratch_bytes, need)
+
 size_t sls_nn_scratch_bytes(int Mt, int Mq) { return nn_scratch_bytes(Mt, Mq); }
 
 int sls_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
@@ -457,11 +472,7 @@ int sls_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz
     SLS_REQUIRE(Mq >= 0, "negative Mq");
     if (Mq == 0) return SLS_OK;
     SLS_REQUIRE(target_xyz && query_xyz && out_dist2 && scratch, "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < nn_scratch_bytes(Mt, Mq)) {
-        set_error("sls_nn_query: scratch too small: %zu < %zu", scratch_bytes, nn_scratch_bytes(Mt, Mq));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(nn_scratch_bytes(Mt, Mq));
     return launch_nn_query(Mt, target_xyz, Mq, query_xyz, out_dist2, out_index, scratch, (hipStream_t)stream);
 }
 
@@ -471,11 +482,7 @@ int sls_nn_stats(int M, const float *dist2, float truncation, float threshold, i
     SLS_REQUIRE(M >= 0, "negative M");
     SLS_REQUIRE((dist2 || M == 0) && out_stats && scratch, "null pointer");
     SLS_REQUIRE(truncation == truncation && threshold == threshold, "NaN truncation or threshold");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < (size_t)SLS_NN_STATS_SCRATCH_BYTES) {
-        set_error("sls_nn_stats: scratch too small: %zu < %d", scratch_bytes, SLS_NN_STATS_SCRATCH_BYTES);
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(SLS_NN_STATS_SCRATCH_BYTES);
     return launch_nn_stats(M, dist2, truncation, threshold, include_truncated, out_stats, scratch, (hipStream_t)stream);
 }
 
@@ -488,11 +495,7 @@ int sls_mesh_distance(int V, const float *vertices, int F, const int32_t *faces,
     SLS_REQUIRE(F >= 1, "F < 1: the mesh has no face");
     SLS_REQUIRE(Mq >= 0, "negative Mq");
     SLS_REQUIRE(vertices && faces && out_status && scratch && ((query_xyz && out_dist2) || Mq == 0), "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < mesh_distance_scratch_bytes(V, F, Mq)) {
-        set_error("sls_mesh_distance: scratch too small: %zu < %zu", scratch_bytes, mesh_distance_scratch_bytes(V, F, Mq));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(mesh_distance_scratch_bytes(V, F, Mq));
     return launch_mesh_distance(V, vertices, F, faces, Mq, query_xyz, out_dist2, out_face, out_closest, out_status, scratch,
                                 (hipStream_t)stream);
 }
@@ -513,11 +516,7 @@ int sls_mesh_rayindex_build(int V, const float *vertices, int F, const int32_t *
     SLS_REQUIRE(V >= 1, "V < 1: the mesh has no vertex");
     SLS_REQUIRE(F >= 1, "F < 1: the mesh has no face");
     SLS_REQUIRE(vertices && faces && index && out_status, "null pointer");
-    SLS_REQUIRE(((uintptr_t)index & 255u) == 0, "index not 256-byte aligned");
-    if (index_bytes < mesh_rayindex_bytes(V, F)) {
-        set_error("sls_mesh_rayindex_build: index too small: %zu < %zu", index_bytes, mesh_rayindex_bytes(V, F));
-        return SLS_E_SCRATCH;
-    }
+    SLS_BUFFER_CHECK(__func__, "index", index, index_bytes, mesh_rayindex_bytes(V, F));
     return launch_mesh_rayindex_build(V, vertices, F, faces, index, out_status, (hipStream_t)stream);
 }
 
@@ -529,13 +528,10 @@ int sls_mesh_raycast(int V, const float *vertices, int F, const int32_t *faces, 
     SLS_REQUIRE(F >= 1, "F < 1: the mesh has no face");
     SLS_REQUIRE(Mr >= 0, "negative Mr");
     SLS_REQUIRE(vertices && faces && index && out_status && ((origins && directions && out_t) || Mr == 0), "null pointer");
-    SLS_REQUIRE(((uintptr_t)index & 255u) == 0, "index not 256-byte aligned");
-    SLS_REQUIRE(t_min >= 0.0f, "t_min is NaN or negative");
+    SLS_REQUIRE(((uintptr_t)index & 255u) == 0, "index not 256-byte aligned");   // (in its place before the range tests;
+    SLS_REQUIRE(t_min >= 0.0f, "t_min is NaN or negative");                      // SLS_BUFFER_CHECK repeats it, then the size)
     SLS_REQUIRE(t_max >= t_min, "t_max is NaN or below t_min");
-    if (index_bytes < mesh_rayindex_bytes(V, F)) {
-        set_error("sls_mesh_raycast: index too small: %zu < %zu", index_bytes, mesh_rayindex_bytes(V, F));
-        return SLS_E_SCRATCH;
-    }
+    SLS_BUFFER_CHECK(__func__, "index", index, index_bytes, mesh_rayindex_bytes(V, F));
     RaycastLaunch a{};
     a.V = V; a.vertices = vertices; a.F = F; a.faces = faces; a.index = index;
     a.Mr = Mr; a.origins = origins; a.directions = directions; a.t_min = t_min; a.t_max = t_max;
@@ -553,11 +549,7 @@ int sls_mesh_pseudonormals(int V, const float *vertices, int F, const int32_t *f
     SLS_REQUIRE(F >= 1 && F <= SLS_MESH_MAX_TRIANGLES, "F < 1 or above SLS_MESH_MAX_TRIANGLES");
     SLS_REQUIRE(vertices && faces && out_face_normals && out_edge_normals && out_vertex_normals && out_status && scratch,
                 "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < mesh_pseudonormals_scratch_bytes(V, F)) {
-        set_error("sls_mesh_pseudonormals: scratch too small: %zu < %zu", scratch_bytes, mesh_pseudonormals_scratch_bytes(V, F));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(mesh_pseudonormals_scratch_bytes(V, F));
     return launch_mesh_pseudonormals(V, vertices, F, faces, out_face_normals, out_edge_normals, out_vertex_normals, out_status,
                                      scratch, (hipStream_t)stream);
 }
@@ -574,11 +566,7 @@ int sls_mesh_signed_distance(int V, const float *vertices, int F, const int32_t 
     SLS_REQUIRE(Mq >= 0, "negative Mq");
     SLS_REQUIRE(vertices && faces && face_normals && edge_normals && vertex_normals && out_status && scratch &&
                 ((query_xyz && out_sdist) || Mq == 0), "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < mesh_signed_distance_scratch_bytes(V, F, Mq)) {
-        set_error("sls_mesh_signed_distance: scratch too small: %zu < %zu", scratch_bytes, mesh_signed_distance_scratch_bytes(V, F, Mq));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(mesh_signed_distance_scratch_bytes(V, F, Mq));
     SignedDistanceLaunch a{};
     a.V = V; a.vertices = vertices; a.F = F; a.faces = faces;
     a.face_n = face_normals; a.edge_n = edge_normals; a.vertex_n = vertex_normals;
@@ -594,11 +582,7 @@ int sls_signed_stats(int M, const float *sdist, float truncation, uint64_t *out_
     SLS_REQUIRE(M >= 0, "negative M");
     SLS_REQUIRE((sdist || M == 0) && out_words && scratch, "null pointer");
     SLS_REQUIRE(truncation == truncation, "NaN truncation");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < (size_t)SLS_NN_STATS_SCRATCH_BYTES) {
-        set_error("sls_signed_stats: scratch too small: %zu < %d", scratch_bytes, SLS_NN_STATS_SCRATCH_BYTES);
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(SLS_NN_STATS_SCRATCH_BYTES);
     return launch_signed_stats(M, sdist, truncation, out_words, scratch, (hipStream_t)stream);
 }
 
@@ -620,11 +604,7 @@ int sls_nn_query_k(int Mt, const float *target_xyz, int Mq, const float *query_x
     SLS_REQUIRE(k >= 1 && k <= SLS_NN_K_MAX, "k outside [1, SLS_NN_K_MAX]");
     if (Mq == 0) return SLS_OK;
     SLS_REQUIRE(target_xyz && query_xyz && scratch, "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < nn_k_scratch_bytes(Mt, Mq, k)) {
-        set_error("sls_nn_query_k: scratch too small: %zu < %zu", scratch_bytes, nn_k_scratch_bytes(Mt, Mq, k));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(nn_k_scratch_bytes(Mt, Mq, k));
     return launch_nn_query_k(Mt, target_xyz, Mq, query_xyz, k, SLS_NN_K_MAX, out_dist2, out_index, out_mean, nullptr, scratch, (hipStream_t)stream);
 }
 
@@ -641,11 +621,7 @@ static int outlier_check(const char *who, int M, const float *xyz, const float *
     }
     if (!(xyz && out_status && scratch)) { set_error("%s: null pointer", who); return SLS_E_ARG; }
     if (out_normals && !normals) { set_error("%s: out_normals without normals", who); return SLS_E_ARG; }
-    if (((uintptr_t)scratch & 255u) != 0) { set_error("%s: scratch not 256-byte aligned", who); return SLS_E_ARG; }
-    if (scratch_bytes < outlier_scratch_bytes(M, k)) {
-        set_error("%s: scratch too small: %zu < %zu", who, scratch_bytes, outlier_scratch_bytes(M, k));
-        return SLS_E_SCRATCH;
-    }
+    SLS_BUFFER_CHECK(who, "scratch", scratch, scratch_bytes, outlier_scratch_bytes(M, k));
     *done = false;
     return SLS_OK;
 }
@@ -693,11 +669,7 @@ int sls_cloud_dbscan(int M, const float *xyz, float eps, int min_points, int32_t
     SLS_REQUIRE(out_status, "null pointer");
     if (M > 0) {
         SLS_REQUIRE(xyz && out_labels && out_counts && scratch, "null pointer");
-        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-        if (scratch_bytes < cloud_dbscan_scratch_bytes(M)) {
-            set_error("sls_cloud_dbscan: scratch too small: %zu < %zu", scratch_bytes, cloud_dbscan_scratch_bytes(M));
-            return SLS_E_SCRATCH;
-        }
+        SLS_SCRATCH(cloud_dbscan_scratch_bytes(M));
     }
     return launch_cloud_dbscan(M, xyz, eps, min_points, out_labels, out_counts, out_status, scratch, (hipStream_t)stream);
 }
@@ -711,11 +683,7 @@ int sls_cloud_select(int M, const float *xyz, const float *normals, const int32_
     if (M > 0) {
         SLS_REQUIRE(xyz && labels && counts && cluster_status && scratch, "null pointer");
         SLS_REQUIRE(!(out_normals && !normals), "out_normals without normals");
-        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-        if (scratch_bytes < cloud_select_scratch_bytes(M)) {
-            set_error("sls_cloud_select: scratch too small: %zu < %zu", scratch_bytes, cloud_select_scratch_bytes(M));
-            return SLS_E_SCRATCH;
-        }
+        SLS_SCRATCH(cloud_select_scratch_bytes(M));
     }
     return launch_cloud_select(M, xyz, normals, labels, counts, cluster_status, keep, min_cluster_points, out_xyz, out_normals,
                                out_index, out_status, scratch, (hipStream_t)stream);
@@ -731,11 +699,7 @@ int sls_cloud_normals(int M, const float *xyz, int k, float radius, const float 
     SLS_REQUIRE(radius > 0.0f, "radius is not a number > 0 (+inf: the k nearest at any distance)");
     if (M == 0) return SLS_OK;
     SLS_REQUIRE(xyz && viewpoint3 && out_normals && scratch, "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < cloud_normals_scratch_bytes(M, k)) {
-        set_error("sls_cloud_normals: scratch too small: %zu < %zu", scratch_bytes, cloud_normals_scratch_bytes(M, k));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(cloud_normals_scratch_bytes(M, k));
     return launch_cloud_normals(M, xyz, k, radius, viewpoint3, out_normals, out_count, out_eigenvalues, scratch,
                                 (hipStream_t)stream);
 }
@@ -762,11 +726,7 @@ int sls_ground_segment(int M, const float *xyz, const SlsGroundParams *prm, uint
     SLS_REQUIRE(prm->num_min_pts >= 3, "num_min_pts < 3");
     if (M > 0) {
         SLS_REQUIRE(xyz && out_label && scratch, "null pointer (xyz, out_label, scratch)");
-        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-        if (scratch_bytes < ground_scratch_bytes(M)) {
-            set_error("sls_ground_segment: scratch too small: %zu < %zu", scratch_bytes, ground_scratch_bytes(M));
-            return SLS_E_SCRATCH;
-        }
+        SLS_SCRATCH(ground_scratch_bytes(M));
     }
     return launch_ground_segment(M, xyz, *prm, out_label, out_bin, out_planes, out_info, out_status, scratch, (hipStream_t)stream);
 }
@@ -789,11 +749,7 @@ int sls_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_x
     SLS_REQUIRE(prm->iterations >= 0 && prm->iterations <= SLS_ICP_MAX_ITERATIONS, "iterations outside [0, 1000]");
     SLS_REQUIRE(prm->min_inliers >= 0, "negative min_inliers");
     for (int k = 0; k < 12; ++k) SLS_REQUIRE(fabs(init_pose12[k]) <= DBL_MAX, "init_pose12 holds a value that is not finite");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < cloud_icp_scratch_bytes(Ms, Mt)) {
-        set_error("sls_cloud_icp: scratch too small: %zu < %zu", scratch_bytes, cloud_icp_scratch_bytes(Ms, Mt));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(cloud_icp_scratch_bytes(Ms, Mt));
     return launch_cloud_icp(Ms, source_xyz, Mt, target_xyz, target_normals, *prm, init_pose12, out_status, out_system, out_index,
                             out_dist2, scratch, (hipStream_t)stream);
 }
@@ -810,11 +766,7 @@ int sls_voxel_downsample(int M, const float *xyz, double voxel_size, float *out_
         return SLS_OK;
     }
     SLS_REQUIRE(xyz && out_xyz && out_status && scratch, "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < voxel_scratch_bytes(M)) {
-        set_error("sls_voxel_downsample: scratch too small: %zu < %zu", scratch_bytes, voxel_scratch_bytes(M));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(voxel_scratch_bytes(M));
     return launch_voxel_downsample(M, xyz, voxel_size, out_xyz, out_count, out_status, scratch, (hipStream_t)stream);
 }
 
@@ -831,11 +783,7 @@ int sls_mesh_sample(int V, const float *vertices, int F, const int32_t *faces, c
         return SLS_OK;
     }
     SLS_REQUIRE((vertices || V == 0) && (faces || F == 0) && out_xyz && out_status && scratch, "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < mesh_sample_scratch_bytes(V, F, n_samples)) {
-        set_error("sls_mesh_sample: scratch too small: %zu < %zu", scratch_bytes, mesh_sample_scratch_bytes(V, F, n_samples));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(mesh_sample_scratch_bytes(V, F, n_samples));
     return launch_mesh_sample(V, vertices, F, faces, crop_box, n_samples, seed, out_xyz, out_face, out_status, scratch,
                               (hipStream_t)stream);
 }
@@ -864,11 +812,7 @@ int sls_tsdf_blocks(int M, const float *xyz, double voxel_size, double trunc, co
         return SLS_OK;
     }
     SLS_REQUIRE(xyz && (out_blocks || capacity == 0) && out_status && scratch, "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < tsdf_blocks_scratch_bytes(M)) {
-        set_error("sls_tsdf_blocks: scratch too small: %zu < %zu", scratch_bytes, tsdf_blocks_scratch_bytes(M));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(tsdf_blocks_scratch_bytes(M));
     return launch_tsdf_blocks(M, xyz, voxel_size, trunc, origin3, capacity, out_blocks, out_status, scratch, (hipStream_t)stream);
 }
 
@@ -931,11 +875,7 @@ int sls_poisson_splat(int M, const float *xyz, const float *normals, int B, cons
         return SLS_OK;
     }
     SLS_REQUIRE(xyz && normals && out_status && scratch && (B == 0 || (blocks && out_field)), "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < poisson_splat_scratch_bytes(M, B)) {
-        set_error("sls_poisson_splat: scratch too small: %zu < %zu", scratch_bytes, poisson_splat_scratch_bytes(M, B));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(poisson_splat_scratch_bytes(M, B));
     return launch_poisson_splat(M, xyz, normals, B, blocks, voxel_size, origin3, out_field, out_status, scratch, (hipStream_t)stream);
 }
 
@@ -949,11 +889,7 @@ int sls_poisson_solve(int B, const int32_t *blocks, const float *field, double a
     SLS_REQUIRE(out_status, "null pointer (out_status)");
     if (B > 0) {
         SLS_REQUIRE(blocks && field && out_chi && scratch, "null pointer");
-        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-        if (scratch_bytes < poisson_solve_scratch_bytes(B)) {
-            set_error("sls_poisson_solve: scratch too small: %zu < %zu", scratch_bytes, poisson_solve_scratch_bytes(B));
-            return SLS_E_SCRATCH;
-        }
+        SLS_SCRATCH(poisson_solve_scratch_bytes(B));
     }
     return launch_poisson_solve(B, blocks, field, alpha, iterations, tol, out_chi, out_status, scratch, (hipStream_t)stream);
 }
@@ -965,11 +901,7 @@ int sls_poisson_density(int B, const int32_t *blocks, const float *field, int sw
     SLS_REQUIRE(sweeps >= 0 && sweeps <= SLS_POISSON_MAX_SWEEPS, "sweeps outside [0, 64]");
     if (B == 0) return SLS_OK;
     SLS_REQUIRE(blocks && field && out_density && scratch, "null pointer");
-    SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");
-    if (scratch_bytes < poisson_density_scratch_bytes(B)) {
-        set_error("sls_poisson_density: scratch too small: %zu < %zu", scratch_bytes, poisson_density_scratch_bytes(B));
-        return SLS_E_SCRATCH;
-    }
+    SLS_SCRATCH(poisson_density_scratch_bytes(B));
     return launch_poisson_density(B, blocks, field, sweeps, out_density, scratch, (hipStream_t)stream);
 }
 
@@ -993,22 +925,13 @@ static int mesh_empty_status(uint32_t *out_status, int zeros, int has_value, uin
     return SLS_OK;
 }
 
-#define SLS_MESH_SCRATCH(name, need)                                                        \
-    do {                                                                                    \
-        SLS_REQUIRE(((uintptr_t)scratch & 255u) == 0, "scratch not 256-byte aligned");      \
-        if (scratch_bytes < (need)) {                                                       \
-            set_error(name ": scratch too small: %zu < %zu", scratch_bytes, (size_t)(need)); \
-            return SLS_E_SCRATCH;                                                           \
-        }                                                                                   \
-    } while (0)
-
 int sls_mesh_weld(int n_rows, const float *soup, float *out_vertices, int32_t *out_index, uint32_t *out_status, void *scratch,
                   size_t scratch_bytes, void *stream)
 {
     SLS_REQUIRE(n_rows >= 0 && (int64_t)n_rows <= 3 * (int64_t)SLS_MESH_MAX_TRIANGLES, "n_rows negative or above 3 SLS_MESH_MAX_TRIANGLES");
     if (n_rows == 0) return mesh_empty_status(out_status, 3, 0, 0u, (hipStream_t)stream);
     SLS_REQUIRE(soup && out_vertices && out_index && out_status && scratch, "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_weld", mesh_weld_scratch_bytes(n_rows));
+    SLS_SCRATCH(mesh_weld_scratch_bytes(n_rows));
     return launch_mesh_weld(n_rows, soup, out_vertices, out_index, out_status, scratch, (hipStream_t)stream);
 }
 
@@ -1019,7 +942,7 @@ int sls_mesh_clusters(int T, const int32_t *faces, int V, int32_t *out_labels, i
     SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
     if (T == 0) return mesh_empty_status(out_status, 5, 0, 0u, (hipStream_t)stream);
     SLS_REQUIRE(faces && out_labels && out_counts && out_status && scratch, "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_clusters", mesh_clusters_scratch_bytes(T));
+    SLS_SCRATCH(mesh_clusters_scratch_bytes(T));
     return launch_mesh_clusters(T, faces, V, out_labels, out_counts, out_status, scratch, (hipStream_t)stream);
 }
 
@@ -1033,7 +956,7 @@ int sls_mesh_filter(int V, const float *vertices, int T, const int32_t *faces, c
     if (V == 0 || T == 0) return mesh_empty_status(out_status, 2, 1, min_triangles > 0 ? (uint32_t)min_triangles : 0u, (hipStream_t)stream);
     SLS_REQUIRE(vertices && faces && labels && counts && cluster_status && out_vertices && out_faces && out_status && scratch,
                 "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_filter", mesh_filter_scratch_bytes(V, T));
+    SLS_SCRATCH(mesh_filter_scratch_bytes(V, T));
     return launch_mesh_filter(V, vertices, T, faces, labels, counts, cluster_status, keep_clusters, min_triangles, out_vertices,
                               out_faces, out_vmap, out_status, scratch, (hipStream_t)stream);
 }
@@ -1045,7 +968,7 @@ int sls_mesh_vertex_normals(int V, const float *vertices, int T, const int32_t *
     SLS_REQUIRE(V >= 0 && V <= SLS_MESH_MAX_VERTICES, "V negative or above SLS_MESH_MAX_VERTICES");
     if (V == 0) return SLS_OK;
     SLS_REQUIRE(out_normals && (T == 0 || (vertices && faces && scratch)), "null pointer");
-    if (T > 0) SLS_MESH_SCRATCH("sls_mesh_vertex_normals", mesh_normals_scratch_bytes(V, T));
+    if (T > 0) SLS_SCRATCH(mesh_normals_scratch_bytes(V, T));
     return launch_mesh_vertex_normals(V, vertices, T, faces, out_normals, scratch, (hipStream_t)stream);
 }
 
@@ -1063,7 +986,7 @@ int sls_mesh_simplify(int V, const float *vertices, int T, const int32_t *faces,
         return mesh_empty_status(out_status, 7, 0, 0u, (hipStream_t)stream);
     }
     SLS_REQUIRE(vertices && faces && out_vertices && out_faces && out_status && scratch, "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_simplify", mesh_simplify_scratch_bytes(V, T));
+    SLS_SCRATCH(mesh_simplify_scratch_bytes(V, T));
     return launch_mesh_simplify(V, vertices, T, faces, voxel_size, contraction, regularisation, out_vertices, out_faces, out_vmap,
                                 out_status, scratch, (hipStream_t)stream);
 }
@@ -1080,7 +1003,7 @@ int sls_mesh_adjacency(int V, int T, const int32_t *faces, int32_t *out_offsets,
         return mesh_empty_status(out_status, 7, 0, 0u, (hipStream_t)stream);
     }
     SLS_REQUIRE(faces && out_offsets && out_neighbours && out_boundary && out_status && scratch, "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_adjacency", mesh_adjacency_scratch_bytes(V, T));
+    SLS_SCRATCH(mesh_adjacency_scratch_bytes(V, T));
     return launch_mesh_adjacency(V, T, faces, out_offsets, out_neighbours, out_boundary, out_status, scratch, (hipStream_t)stream);
 }
 
@@ -1103,7 +1026,7 @@ int sls_mesh_smooth(int V, const float *vertices, int T, const int32_t *faces, i
         return mesh_empty_status(out_status, 7, 0, 0u, (hipStream_t)stream);
     }
     SLS_REQUIRE(vertices && faces && out_vertices && out_status && scratch, "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_smooth", mesh_smooth_scratch_bytes(V, T));
+    SLS_SCRATCH(mesh_smooth_scratch_bytes(V, T));
     return launch_mesh_smooth(V, vertices, T, faces, method, weights, iterations, lambda, mu, fix_boundary, out_vertices, out_status,
                               scratch, (hipStream_t)stream);
 }
@@ -1116,7 +1039,7 @@ int sls_mesh_boundary_loops(int V, int T, const int32_t *faces, const uint32_t *
     if (V == 0 || T == 0)                           // no half-edge
         return launch_mesh_fill_empty(V, nullptr, T, nullptr, in_counts, 0, nullptr, 0, nullptr, out_status, (hipStream_t)stream);
     SLS_REQUIRE(faces && out_halfedges && out_loop && out_loop_edges && out_status && scratch, "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_boundary_loops", mesh_fill_scratch_bytes(V, T));
+    SLS_SCRATCH(mesh_fill_scratch_bytes(V, T));
     return launch_mesh_boundary_loops(V, T, faces, in_counts, out_halfedges, out_loop, out_loop_edges, out_status, scratch,
                                       (hipStream_t)stream);
 }
@@ -1139,7 +1062,7 @@ int sls_mesh_fill_holes(int V, const float *vertices, int T, const int32_t *face
                                       (hipStream_t)stream);
     }
     SLS_REQUIRE(vertices && faces && out_vertices && out_faces && out_status && scratch, "null pointer");
-    SLS_MESH_SCRATCH("sls_mesh_fill_holes", mesh_fill_scratch_bytes(V, T));
+    SLS_SCRATCH(mesh_fill_scratch_bytes(V, T));
     return launch_mesh_fill_holes(V, vertices, T, faces, in_counts, max_edges, max_size, cap_vertices, out_vertices, cap_triangles,
                                   out_faces, out_status, scratch, (hipStream_t)stream);
 }

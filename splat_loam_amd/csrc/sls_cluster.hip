@@ -4,7 +4,8 @@
 //   sls_cloud_select   the K largest clusters and those above a floor kept — the rule of sls_mesh_filter — as an ordered
 //                      compaction of the cloud, normals travelling along.
 // One native call each, nothing read back inside it.  sls_cloud_dbscan:
-//   1. the index of the cloud's self-query and the COUNT search (sls_knn.hip: cluster_index_count) -> core[i], parent[i] = i;
+//   1. the index of the cloud's self-query (knn_build, sls_knn.hip) and the COUNT search (cluster_index_count) -> core[i],
+//      parent[i] = i;
 //   2. the UNITE search over the core points (cluster_unite): the lock-free union-find of sls_unionfind.hpp, parent by
 //      original index, so a root is its component's lowest core whatever the order of the threads;
 //   3. cluster_flatten: root[i] of every core (a launch of its own: parent is only read), SLS_CLUSTER_NONE elsewhere, and
@@ -17,8 +18,9 @@
 // Steps 3 and 5 number the components as sls_mesh.hip numbers its clusters of triangles, and sls_cloud_select keeps the
 // largest as sls_mesh_filter does: uf_root and uf_kth_largest (sls_unionfind.hpp) serve both.  The compaction's rows are
 // written by Chunks::write_rows (sls_scan.hpp), as sls_outlier.hip's.
-#include "sls_launch.hpp"
+#include "sls_sweep.hpp"
 #include "sls_unionfind.hpp"
+#include "../../include/sls_nn_math.h"
 #include "../../include/sls_cluster_math.h"
 
 namespace sls {
@@ -27,11 +29,177 @@ constexpr int kCluThreads = 256;
 using CluChunks = Chunks<kCluThreads, 4>;
 enum { CH_CORES = 0, CH_BORDERS = 1, CH_NOISE = 2, CH_NMIN = 3, CH_WORDS = 4 };
 
-// (in sls_knn.hip: the searches share the sweep)
-int cluster_index_count(int M, const float *xyz, float r2, int min_points, uint32_t *core, uint32_t *parent, void *scratch,
-                        hipStream_t st);
-int cluster_unite(int M, float r2, uint32_t *parent, void *scratch, hipStream_t st);
-int cluster_border(int M, float r2, uint32_t *root, void *scratch, hipStream_t st);
+// ---------------------------------------------------------------------------------------------------------------------
+// The three searches (the stages between them follow).  All three are the cloud's SELF-query at the constant radius r2 —
+// the own box first, then the sweep (self_search, sls_sweep.hpp), as knn_query_kernel does, but a point is its own
+// neighbour: no lane leaves itself out.
+//   count   CountSearch: the neighbours within r2, the bound r2 until the lane's count reaches min_points and after that
+//           a value nothing passes, so a wave whose lanes are all core lists nothing more.  A count rests on the sweep
+//           showing every target once; a saturated lane may be shown more for another lane's sake, which only raises a
+//           count that is read as `>= min_points`.
+//   unite   UniteSearch, core lanes alone: uf_unite(own index, target's index) for the core targets of LOWER index within
+//           r2 — each pair joined once.  parent is indexed by ORIGINAL index, so a root is its component's lowest core.
+//   border  BorderSearch, non-core lanes alone: the lowest root among the core targets within r2.
+// The core flag rides in the staged item: cluster_mark_kernel, between count and unite, sets the top bit of pts[].w (an
+// original index is below 2^31).  The pad of a short last run is a far point: d2 = +inf passes no radius.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kClusterCoreBit = 0x80000000u;
+
+__device__ __forceinline__ float4 cluster_pad() { return make_float4(1.0e30f, 1.0e30f, 1.0e30f, 0.0f); }
+
+struct CountSearch {
+    const float4 me;
+    const float r2;
+    const int min_points;
+    int count;
+    __device__ __forceinline__ float bound() const { return sls_cluster_count_bound(count, min_points, r2); }
+    __device__ __forceinline__ float4 pad(const float4 *, int) const { return cluster_pad(); }
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
+#pragma unroll 8
+        for (int k = 0; k < kSweepSub; ++k) {
+            const float4 p = s_run[k];
+            count += sls_cluster_near(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), r2);
+        }
+    }
+};
+
+struct UniteSearch {
+    const float4 me;
+    const float r2;
+    const bool active;              // a core lane: the others are shown the runs and do nothing
+    const uint32_t mine;            // the lane's original index
+    uint32_t *parent;
+    __device__ __forceinline__ float bound() const { return r2; }
+    __device__ __forceinline__ float4 pad(const float4 *, int) const { return cluster_pad(); }
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
+        for (int k = 0; k < kSweepSub; ++k) {
+            const float4 p = s_run[k];
+            const uint32_t w = __float_as_uint(p.w);        // a core target of lower index: w - bit < mine
+            if (active && sls_cluster_near(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), r2) && w >= kClusterCoreBit &&
+                (w ^ kClusterCoreBit) < mine)
+                uf_unite(parent, mine, w ^ kClusterCoreBit);
+        }
+    }
+};
+
+struct BorderSearch {
+    const float4 me;
+    const float r2;
+    const bool active;
+    const uint32_t *__restrict__ root;
+    uint32_t best;
+    __device__ __forceinline__ float bound() const { return r2; }
+    __device__ __forceinline__ float4 pad(const float4 *, int) const { return cluster_pad(); }
+    __device__ __forceinline__ void scan(const float4 *s_run)
+    {
+        for (int k = 0; k < kSweepSub; ++k) {
+            const float4 p = s_run[k];
+            const uint32_t w = __float_as_uint(p.w);
+            if (active && sls_cluster_near(sls_nn_dist2(me.x, me.y, me.z, p.x, p.y, p.z), r2) && w >= kClusterCoreBit)
+                best = min(best, root[w ^ kClusterCoreBit]);
+        }
+    }
+};
+
+// core[i] = 1 / 0 and parent[i] = i, both by original index
+__global__ __launch_bounds__(64) void cluster_count_kernel(int M, int nboxes, const float4 *__restrict__ pts,
+                                                           const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                           float r2, int min_points, uint32_t *__restrict__ core,
+                                                           uint32_t *__restrict__ parent)
+{
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { M, nboxes, pts, boxes, subboxes };
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    const bool live = q < M;
+    const float4 me = pts[live ? q : M - 1];
+    CountSearch s = { me, r2, min_points, 0 };
+    self_search(ix, live, me, s, lds);
+    if (live) {
+        const uint32_t i = __float_as_uint(me.w);
+        core[i] = (uint32_t)sls_cluster_core(s.count, min_points);
+        parent[i] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void cluster_mark_kernel(int M, float4 *__restrict__ pts, const uint32_t *__restrict__ core)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const uint32_t i = __float_as_uint(pts[j].w);
+    if (core[i]) pts[j].w = __uint_as_float(i | kClusterCoreBit);
+}
+
+__global__ __launch_bounds__(64) void cluster_unite_kernel(int M, int nboxes, const float4 *__restrict__ pts,
+                                                           const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                           float r2, uint32_t *parent)
+{
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { M, nboxes, pts, boxes, subboxes };
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    const float4 me = pts[q < M ? q : M - 1];
+    const bool live = q < M && __float_as_uint(me.w) >= kClusterCoreBit;
+    if (!__ballot(live)) return;                        // a wave without a core point joins nothing
+    UniteSearch s = { me, r2, live, __float_as_uint(me.w) & ~kClusterCoreBit, parent };
+    self_search(ix, live, me, s, lds);
+}
+
+// root[i] of the non-core points: the lowest root among their core neighbours, SLS_CLUSTER_NONE without one (the cores'
+// entries, written by the flatten pass before this launch, are only read)
+__global__ __launch_bounds__(64) void cluster_border_kernel(int M, int nboxes, const float4 *__restrict__ pts,
+                                                            const float4 *__restrict__ boxes, const float4 *__restrict__ subboxes,
+                                                            float r2, uint32_t *root)
+{
+    __shared__ SweepLds lds;
+    const KnnIndex ix = { M, nboxes, pts, boxes, subboxes };
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    const float4 me = pts[q < M ? q : M - 1];
+    const bool live = q < M && __float_as_uint(me.w) < kClusterCoreBit;
+    if (!__ballot(live)) return;                        // a wave of core points has no border to find
+    BorderSearch s = { me, r2, live, root, SLS_CLUSTER_NONE };
+    self_search(ix, live, me, s, lds);
+    if (live) root[__float_as_uint(me.w)] = s.best;
+}
+
+// The cloud's index in `scratch` (knn_scratch_bytes(M), 256-byte aligned), the count and the mark; then, after the
+// caller's own stages, the other two searches over the same index.  core, parent, root: [M] words by original index.
+static int cluster_index_count(int M, const float *xyz, float r2, int min_points, uint32_t *core, uint32_t *parent, void *scratch,
+                               hipStream_t st)
+{
+    const KnnScratch s = knn_layout(M, scratch, M);
+    int which = 0;
+    const int rc = knn_build(M, xyz, s, knn_key_bits(M), 0u, st, &which);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cluster_count_kernel, dim3((M + 63) / 64), dim3(64), 0, st, M, (M + kSweepBox - 1) / kSweepBox,
+                       (const float4 *)s.pts, (const float4 *)s.boxes, (const float4 *)s.subboxes, r2, min_points, core, parent);
+    SLS_LAUNCH_CHECK("cluster_count_kernel");
+    hipLaunchKernelGGL(cluster_mark_kernel, dim3((M + 255) / 256), dim3(256), 0, st, M, s.pts, (const uint32_t *)core);
+    SLS_LAUNCH_CHECK("cluster_mark_kernel");
+    return SLS_OK;
+}
+
+static int cluster_unite(int M, float r2, uint32_t *parent, void *scratch, hipStream_t st)
+{
+    const KnnScratch s = knn_layout(M, scratch, M);
+    hipLaunchKernelGGL(cluster_unite_kernel, dim3((M + 63) / 64), dim3(64), 0, st, M, (M + kSweepBox - 1) / kSweepBox,
+                       (const float4 *)s.pts, (const float4 *)s.boxes, (const float4 *)s.subboxes, r2, parent);
+    SLS_LAUNCH_CHECK("cluster_unite_kernel");
+    return SLS_OK;
+}
+
+static int cluster_border(int M, float r2, uint32_t *root, void *scratch, hipStream_t st)
+{
+    const KnnScratch s = knn_layout(M, scratch, M);
+    hipLaunchKernelGGL(cluster_border_kernel, dim3((M + 63) / 64), dim3(64), 0, st, M, (M + kSweepBox - 1) / kSweepBox,
+                       (const float4 *)s.pts, (const float4 *)s.boxes, (const float4 *)s.subboxes, r2, root);
+    SLS_LAUNCH_CHECK("cluster_border_kernel");
+    return SLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the stages between the searches
+// ---------------------------------------------------------------------------------------------------------------------
 
 __global__ void cluster_status0_kernel(uint32_t *status, int words, uint32_t n_min)
 {

@@ -216,8 +216,6 @@ size_t nn_scratch_bytes(int Mt, int Mq);
 // (both: the arguments are checked by the caller, sls_api.hip — sizes, pointers, scratch size and alignment)
 int launch_nn_query(int Mt, const float *target_xyz, int Mq, const float *query_xyz, float *out_dist2, int32_t *out_index,
                     void *scratch, hipStream_t st);
-int launch_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
-                    void *scratch, hipStream_t st);
 // the k nearest (sls_knn.hip).  Every output may be null; out_last_key: the k-th key of every query's list.  k_max: the
 // caller's own limit, SLS_NN_K_MAX everywhere but in sls_normals.hip (SLS_NORMALS_NN_MAX = 2 * SLS_NN_K_MAX).  Beyond
 // SLS_NN_K_MAX the list is found in two passes: out_mean must be null and out_last_key [Mq] must be given — it carries the
@@ -238,14 +236,52 @@ struct NnIndexRef {
 int nn_index_target(int Mt, const float *target_xyz, int Mq, void *scratch, hipStream_t st, NnIndexRef *ref);
 int nn_index_query(int Mt, int Mq, const float *query_xyz, const NnIndexRef &ref, float *out_dist2, int32_t *out_index, void *scratch,
                    hipStream_t st);
-// the nearest triangle of a mesh (sls_knn.hip: the same sweep over an index of triangles) and the error colours; the
-// arguments are checked by the caller, sls_api.hip.  Mq == 0: only the status is written
+// The host side of the point index, for the files that build one of their own or sort queries along its curve
+// (sls_meshdist.hip, sls_cluster.hip).  The scratch of an index (every array 256-byte aligned) ...
+struct KnnScratch {
+    uint32_t *bbox;
+    uint32_t *keys, *keys_tmp;
+    uint32_t *vals, *vals_tmp;
+    float4 *pts, *boxes, *subboxes;
+    void *sort;
+    size_t sort_bytes, total;
+};
+// ... and of a two-cloud query: the target's index (its sorter scratch sized for the larger cloud), then the queries' buffers
+struct NnScratch {
+    KnnScratch t;
+    uint32_t *qkeys, *qkeys_tmp, *qvals, *qvals_tmp;
+    float4 *qpts;
+    size_t total;
+};
+// what a two-cloud launcher holds before its query kernel
+struct NnFront {
+    NnScratch s;
+    const uint32_t *tkeys, *qkeys;      // the sorted codes of the targets and of the queries
+    const float4 *qpts;
+};
+KnnScratch knn_layout(int M, void *base, int sort_items);       // sort_items: what the sorter's scratch, the last piece, is sized for
+NnScratch nn_layout(int Mt, int Mq, void *base);
+int knn_key_bits(int M);                                        // small clouds are sorted on 21 code bits, the others on 30
+// bounding cube, Hilbert codes, sort, points in curve order, boxes and sub-boxes.  M2: the item count of a second sort that
+// follows (bbox[7]).  *which: where the sorted (code, index) pairs ended up
+int knn_build(int M, const float *xyz, const KnnScratch &s, int key_bits, uint32_t M2, hipStream_t st, int *which);
+// the queries' codes in the cube of an index (a point outside is clamped to the border cells) and the identity ...
+int nn_query_codes(int Mq, const float *query_xyz, const uint32_t *bbox, uint32_t *qkeys, uint32_t *qvals, int key_bits, hipStream_t st);
+// ... and behind codes that are in f->s.qkeys / qvals: the sort (Mt decides the key bits) and the gather in curve order
+int nn_front_sorted_queries(int Mt, int Mq, const float *query_xyz, hipStream_t st, NnFront *f);
+// ---- sls_metrics.hip: the sums and the colours of an array of distances, unsigned or signed (checked by sls_api.hip) --
+int launch_nn_stats(int M, const float *dist2, float truncation, float threshold, int include_truncated, uint64_t *out_stats,
+                    void *scratch, hipStream_t st);
+int launch_signed_stats(int M, const float *sdist, float truncation, uint64_t *out_words, void *scratch, hipStream_t st);
+int launch_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, hipStream_t st);
+int launch_signed_error_colors(int M, const float *sdist, float truncation, uint8_t *out_rgb, hipStream_t st);
+// ---- sls_meshdist.hip: the nearest triangle of a mesh, the same sweep over an index of triangles (the arguments are
+// checked by the caller, sls_api.hip).  Mq == 0: only the status is written
 size_t mesh_distance_scratch_bytes(int V, int F, int Mq);
 int launch_mesh_distance(int V, const float *vertices, int F, const int32_t *faces, int Mq, const float *query_xyz,
                          float *out_dist2, int32_t *out_face, float *out_closest, uint32_t *out_status, void *scratch,
                          hipStream_t st);
-int launch_error_colors(int M, const float *dist2, float truncation, uint8_t *out_rgb, hipStream_t st);
-// the index of triangles behind it, which the ray caster shares (the body: sls_knn.hip; TriItem: sls_sweep.hpp).  The
+// the index of triangles behind it, which the ray caster shares (TriItem: sls_sweep.hpp).  The
 // caller lays the arrays out: F words each of keys / vals and their ping-pong copies, F items, 2 float4 per box of 256 and
 // per sub-box of 32, 8 words of bbox, the sorter's scratch for F items
 struct TriItem;
@@ -279,8 +315,6 @@ struct SignedDistanceLaunch {
     float *out_sdist; int32_t *out_face; float *out_closest; uint8_t *out_feature; uint32_t *out_status; void *scratch;
 };
 int launch_mesh_signed_distance(const SignedDistanceLaunch &a, hipStream_t st);
-int launch_signed_stats(int M, const float *sdist, float truncation, uint64_t *out_words, void *scratch, hipStream_t st);
-int launch_signed_error_colors(int M, const float *sdist, float truncation, uint8_t *out_rgb, hipStream_t st);
 // ---- sls_icp.hip (the arguments are checked by the caller, sls_api.hip; init_pose12: host memory) ------------------
 size_t cloud_icp_scratch_bytes(int Ms, int Mt);
 int launch_cloud_icp(int Ms, const float *source_xyz, int Mt, const float *target_xyz, const float *target_normals,

@@ -1,6 +1,6 @@
 // sls_raycast.hip — sls_mesh_rayindex_build / sls_mesh_raycast: for every ray the FIRST triangle of a mesh it hits — the
 // parameter t, the face and its barycentric weights as include/sls_raycast_math.h defines them, the lowest face index
-// among hits of equal t bits.  The index is the one sls_mesh_distance sweeps (tri_index_build, sls_knn.hip): triangles in
+// among hits of equal t bits.  The index is the one sls_mesh_distance sweeps (tri_index_build, sls_meshdist.hip): triangles in
 // the curve order of their centroids, boxes over runs of 256 and sub-boxes over runs of 32 that bound all three
 // vertices.  It is built once and cast against many times (one range image per keyframe).
 //

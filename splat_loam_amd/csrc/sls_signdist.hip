@@ -1,6 +1,6 @@
 // sls_signdist.hip — the SIGNED distance of points to a triangle mesh: the pseudo-normal tables of a mesh
-// (sls_mesh_pseudonormals), the sign of sls_mesh_distance's result from them (sls_mesh_signed_distance), and the signed
-// twins of sls_nn_stats and sls_error_colors (sls_signed_stats, sls_signed_error_colors).  include/sls_signdist_math.h
+// (sls_mesh_pseudonormals) and the sign of sls_mesh_distance's result from them (sls_mesh_signed_distance); the signed
+// twins of sls_nn_stats and sls_error_colors live with them in sls_metrics.hip.  include/sls_signdist_math.h
 // states every rule; tests/signdist_ref.py compiles it for the host.  Built EXACT (-ffp-contract=off): the bits of the
 // tables are part of the contract.
 //
@@ -251,106 +251,6 @@ int launch_mesh_signed_distance(const SignedDistanceLaunch &a, hipStream_t st)
                        a.face_n, a.edge_n, a.vertex_n, a.Mq, a.query_xyz, (const float *)s.d2, (const int32_t *)face, a.out_sdist,
                        a.out_feature);
     SLS_LAUNCH_CHECK("sd_sign_kernel");
-    return SLS_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// sls_signed_stats: n, the negative ones and the float64 sum over the entries within the truncation, in the FIXED order of
-// sls_nn_stats (sls_knn.hip): block b of a grid that depends on M alone sums its entries b*256 + t, + grid*256, ... per
-// thread, the 64 lanes by the xor butterfly, the 4 waves in order; one block then adds the partials the same way.  A
-// kernel pair of its own: the two kernels of sls_nn_stats stay as they are.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int kSdStatsMaxBlocks = SLS_NN_STATS_SCRATCH_BYTES / 32;     // 32 bytes per partial: n, negative, sum, pad
-
-struct SdPartial { unsigned long long n, neg; double sum; };
-
-__device__ __forceinline__ SdPartial sd_block_sum(SdPartial v)
-{   // valid in thread 0
-    __shared__ unsigned long long s_n[4], s_b[4];
-    __shared__ double s_s[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v.n += __shfl_xor(v.n, off, 64);
-        v.neg += __shfl_xor(v.neg, off, 64);
-        v.sum += __shfl_xor(v.sum, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { s_n[threadIdx.x >> 6] = v.n; s_b[threadIdx.x >> 6] = v.neg; s_s[threadIdx.x >> 6] = v.sum; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < 4; ++w) { v.n += s_n[w]; v.neg += s_b[w]; v.sum += s_s[w]; }
-    return v;
-}
-
-__global__ __launch_bounds__(256) void sd_stats_partial_kernel(int M, const float *__restrict__ sdist, float truncation,
-                                                               unsigned long long *__restrict__ partials)
-{
-    SdPartial v = { 0ull, 0ull, 0.0 };
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)M; i += (size_t)gridDim.x * 256) {
-        const float sd = sdist[i];
-        if (sls_sd_stats_term(sd, truncation)) {
-            v.n += 1ull;
-            v.neg += sd < 0.0f ? 1ull : 0ull;
-            v.sum += (double)sd;
-        }
-    }
-    v = sd_block_sum(v);
-    if (threadIdx.x == 0) {
-        partials[4 * blockIdx.x] = v.n;
-        partials[4 * blockIdx.x + 1] = v.neg;
-        partials[4 * blockIdx.x + 2] = (unsigned long long)__double_as_longlong(v.sum);
-    }
-}
-
-__global__ __launch_bounds__(256) void sd_stats_final_kernel(int M, int nblocks, const unsigned long long *__restrict__ partials,
-                                                             unsigned long long *__restrict__ out)
-{
-    SdPartial v = { 0ull, 0ull, 0.0 };
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        v.n += partials[4 * b];
-        v.neg += partials[4 * b + 1];
-        v.sum += __longlong_as_double((long long)partials[4 * b + 2]);
-    }
-    v = sd_block_sum(v);
-    if (threadIdx.x == 0) {
-        out[0] = v.n;
-        out[1] = v.neg;
-        out[2] = (unsigned long long)__double_as_longlong(v.sum);
-        out[3] = (unsigned long long)M;
-    }
-}
-
-int launch_signed_stats(int M, const float *sdist, float truncation, uint64_t *out_words, void *scratch, hipStream_t st)
-{
-    int nblocks = (M + 255) / 256;
-    if (nblocks > kSdStatsMaxBlocks) nblocks = kSdStatsMaxBlocks;
-    unsigned long long *partials = (unsigned long long *)scratch;
-    if (nblocks > 0) {
-        hipLaunchKernelGGL(sd_stats_partial_kernel, dim3(nblocks), dim3(256), 0, st, M, sdist, truncation, partials);
-        SLS_LAUNCH_CHECK("sd_stats_partial_kernel");
-    }
-    hipLaunchKernelGGL(sd_stats_final_kernel, dim3(1), dim3(256), 0, st, M, nblocks, (const unsigned long long *)partials,
-                       (unsigned long long *)out_words);
-    SLS_LAUNCH_CHECK("sd_stats_final_kernel");
-    return SLS_OK;
-}
-
-__global__ __launch_bounds__(256) void sd_colors_kernel(int M, const float *__restrict__ sdist, float truncation,
-                                                        uint8_t *__restrict__ out_rgb)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)M) return;
-    uint8_t rgb[3];
-    sls_signed_error_color(sdist[i], truncation, rgb);
-    out_rgb[3 * i] = rgb[0];
-    out_rgb[3 * i + 1] = rgb[1];
-    out_rgb[3 * i + 2] = rgb[2];
-}
-
-int launch_signed_error_colors(int M, const float *sdist, float truncation, uint8_t *out_rgb, hipStream_t st)
-{
-    if (M == 0) return SLS_OK;
-    hipLaunchKernelGGL(sd_colors_kernel, dim3((M + 255) / 256), dim3(256), 0, st, M, sdist, truncation, out_rgb);
-    SLS_LAUNCH_CHECK("sd_colors_kernel");
     return SLS_OK;
 }
 

@@ -1,5 +1,5 @@
 // sls_unionfind.hpp — the lock-free union-find shared by sls_mesh.hip (clusters of triangles), sls_fill.hip (chains of
-// boundary half-edges) and sls_knn.hip (the cores of a cloud): agent-scope integer atomics, no waiting.  The larger root
+// boundary half-edges) and sls_cluster.hip (the cores of a cloud): agent-scope integer atomics, no waiting.  The larger root
 // is always linked under the smaller, so the root of a component is its lowest element whatever the order of the threads.
 // Behind it what sls_mesh.hip and sls_cluster.hip share once nothing writes parent any more: uf_root, the walk of their
 // flatten kernels, and uf_kth_largest, the k-th largest component count of their "keep the K largest" rule.

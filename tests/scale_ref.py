@@ -56,11 +56,11 @@ SOURCES = (
     ("splat_loam_amd/csrc/sls_tsdf.hip", "using TsdfChunks = Chunks<kTsdfThreads, 4>;", "test_tsdf_blocks_sort_tail"),
     ("include/sls_tsdf_math.h", "#define SLS_TSDF_BLOCK_VOXELS 512", "test_tsdf_blocks_sort_tail"),
     ("include/sls_tsdf_math.h", "#define SLS_TSDF_POINT_KEYS 27", "test_tsdf_blocks_sort_tail"),
-    ("splat_loam_amd/csrc/sls_knn.hip", "constexpr int kKnnBox = 256;", "test_nearest_k_*"),
-    ("splat_loam_amd/csrc/sls_knn.hip", "const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;", "test_nearest_k_*"),
-    ("splat_loam_amd/csrc/sls_knn.hip", "constexpr int kNnStatsMaxBlocks = SLS_NN_STATS_SCRATCH_BYTES / 32;", "test_nearest_and_metrics_*"),
+    ("splat_loam_amd/csrc/sls_sweep.hpp", "constexpr int kSweepBox = 256;", "test_nearest_k_*"),
+    ("splat_loam_amd/csrc/sls_sweep.hpp", "const int nchunks = (nboxes + 63) / 64, c0 = start_box / 64;", "test_nearest_k_*"),
+    ("splat_loam_amd/csrc/sls_metrics.hip", "constexpr int kNnStatsMaxBlocks = SLS_NN_STATS_SCRATCH_BYTES / 32;", "test_nearest_and_metrics_*"),
     ("include/sls_abi.h", "#define SLS_NN_STATS_SCRATCH_BYTES 32768", "test_nearest_and_metrics_*"),
-    ("splat_loam_amd/csrc/sls_knn.hip", "int nblocks = (M + 255) / 256;", "test_nearest_and_metrics_*"),
+    ("splat_loam_amd/csrc/sls_metrics.hip", "int nblocks = (M + 255) / 256;", "test_nearest_and_metrics_*"),
     ("include/sls_smooth_math.h", "#define SLS_SMOOTH_LONG 64", "test_fans_smooth_long_rows_stride"),
     ("include/sls_fill_math.h", "#define SLS_FILL_LONG 64", "test_fans_fill_long_loops_stride"),
 )

@@ -11,6 +11,7 @@ import tempfile
 import numpy as np
 
 import meshdist_ref
+import nn_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _f = np.float32
@@ -205,6 +206,14 @@ def stats(sd, truncation):
     with np.errstate(invalid="ignore"):
         m = np.abs(sd) < _f(truncation)
     return int(m.sum()), int((sd[m] < 0).sum()), float(sd[m].astype(np.float64).sum())
+
+
+def stats_device_order(sd, truncation):
+    """stats with the sum in the device's order (nn_ref.device_sum): the first three words of sls_signed_stats, bit for bit"""
+    sd = np.asarray(sd, _f)
+    with np.errstate(invalid="ignore"):
+        m = np.abs(sd) < _f(truncation)
+    return stats(sd, truncation)[:2] + (nn_ref.device_sum(np.where(m, sd.astype(np.float64), 0.0)),)
 
 
 # ---- the float64 restatement -----------------------------------------------------------------------------------------

@@ -121,6 +121,47 @@ def test_evaluation_refuses_cpu_tensors():
         evaluation.nearest(a.numpy(), b)
 
 
+def _order_terms(M):
+    """the float64 terms (0.0 where an entry does not count) of the three sums the device tests pin at size M"""
+    import signdist_ref
+    d2, sd = nn_ref.stats_order_dist2(M), nn_ref.stats_order_signed(M)
+    out = []
+    for inc in (False, True):
+        d, counted = nn_ref._stats_terms(d2, 0.5, inc)
+        out.append(np.where(counted, d.astype(np.float64), 0.0))
+    out.append(np.where(np.abs(sd) < np.float32(0.5), sd.astype(np.float64), 0.0))
+    assert signdist_ref.stats_device_order(sd, 0.5)[2] == nn_ref.device_sum(out[2])
+    return out
+
+
+@pytest.mark.parametrize("M", nn_ref.STATS_ORDER_SIZES)
+def test_restated_device_sum_is_a_sum(M):
+    """nn_ref.device_sum, the order the device tests pin bit for bit, on those tests' own terms against the exactly
+    rounded sum (math.fsum), to 1e-12 of the sum: every term passes through fewer than 30 additions (2 strided, 6 + 3 in
+    the block, 4 + 6 + 3 in the final block), so the two differ by less than 30 * 2^-53 of the sum of magnitudes, which
+    is the sum itself for the distances and, asserted, at most 10 times its magnitude for the signed terms: 3.4e-14."""
+    import math
+    assert nn_ref.device_sum(np.zeros(0)) == 0.0
+    for v in _order_terms(M):
+        exact = math.fsum(v)
+        assert math.fsum(np.abs(v)) <= 10.0 * abs(exact)
+        assert abs(nn_ref.device_sum(v) - exact) <= 1e-12 * abs(exact)
+
+
+@pytest.mark.parametrize("M", [m for m in nn_ref.STATS_ORDER_SIZES if m > 1])
+def test_order_tests_data_tells_orders_apart(M):
+    """What makes the device tests a pin of the ORDER: on their own terms (nn_ref.STATS_ORDER_SEEDS) the documented order
+    gives other bits than NumPy's sum, than a left-to-right sum, than the documented order with its butterfly run upwards
+    (offsets 1 .. 32) and, from three waves on, than the waves added 3 .. 0."""
+    for v in _order_terms(M):
+        want = nn_ref.device_sum(v)
+        assert want != float(v.sum())
+        assert want != float(np.cumsum(v)[-1])
+        assert want != nn_ref.device_sum(v, butterfly=nn_ref.BUTTERFLY[::-1])
+        if M > 128:
+            assert want != nn_ref.device_sum(v, waves=nn_ref.WAVES[::-1])
+
+
 def test_restatement_lowest_index_and_metrics():
     """The restatement itself: ties go to the lowest index; the metric block on a case worked by hand."""
     target = np.array([[1, 0, 0], [-1, 0, 0], [1, 0, 0], [0, 3, 0]], np.float32)

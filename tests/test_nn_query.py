@@ -181,6 +181,20 @@ def test_nn_stats(device, M):
         assert nn_stats(device, d2, float(trunc), float(thr), inc)[4] == bits      # the same bits on a second run
 
 
+@pytest.mark.parametrize("M", nn_ref.STATS_ORDER_SIZES)
+def test_nn_stats_sum_is_the_documented_order(device, M):
+    """Word 2 bit for bit: the float64 sum is taken in the order nn_ref.device_sum restates, on terms spread over
+    eighteen decades, seeded so that other orders give other bits (tests/test_nn_host.py shows that on this very data).  280 800 entries:
+    1024 blocks whose first 18 656 threads take a second entry, and a final block whose threads read four partials each."""
+    d2 = nn_ref.stats_order_dist2(M)
+    for inc in (0, 1):
+        n, below, s, m, bits = nn_stats(device, d2, 0.5, 0.2, inc)
+        rn, rbelow, rs, rm = nn_ref.stats_device_order(d2, 0.5, 0.2, bool(inc))
+        print(f"M={M} include_truncated={inc}: n {n} sum {s!r} (restated {rs!r}, NumPy's order {nn_ref.stats(d2, 0.5, 0.2, bool(inc))[2]!r})")
+        assert (n, below, m) == (rn, rbelow, rm) and 0 < n <= M
+        assert int(bits) == int(np.array([rs], np.float64).view(np.int64)[0])
+
+
 @functools.lru_cache(maxsize=None)
 def two_clouds():
     """Two lattice clouds of one surface region, each with points beyond both truncations."""

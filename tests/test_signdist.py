@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import meshdist_ref
+import nn_ref
 import signdist_ref as R
 from splat_loam_amd import _abi, evaluation
 
@@ -145,6 +146,18 @@ def test_signed_stats(device, M):
     assert (n, neg, m) == (wn, wneg, M)
     assert abs(total - wtotal) <= 1e-12 * max(1.0, float(np.abs(sd[np.isfinite(sd)]).sum()))
     assert _signed_stats(device, t, 0.5) == (n, neg, total, m)
+
+
+@pytest.mark.parametrize("M", nn_ref.STATS_ORDER_SIZES)
+def test_signed_stats_sum_is_the_documented_order(device, M):
+    """Word 2 bit for bit: the float64 sum is taken in the order of sls_nn_stats (nn_ref.device_sum), on terms spread over
+    thirty decades, seeded so that other orders give other bits (tests/test_nn_host.py shows that on this very data)."""
+    sd = nn_ref.stats_order_signed(M)
+    n, neg, total, m = _signed_stats(device, tt(sd, device), 0.5)
+    wn, wneg, wtotal = R.stats_device_order(sd, 0.5)
+    print(f"M={M}: n {n} negative {neg} sum {total!r} (restated {wtotal!r}, NumPy's order {R.stats(sd, 0.5)[2]!r})")
+    assert (n, neg, m) == (wn, wneg, M) and 0 < n <= M
+    assert struct.pack("<d", total) == struct.pack("<d", wtotal)
 
 
 def test_signed_colours_are_the_headers(device):
